@@ -12,12 +12,18 @@ and exit code 2, never a silently different measurement.  Rank 0 prints ONE JSON
             Triangulation::UnitSphere(recursions=9), N = 1 048 576 panels (SURVEY.md section 8d config 3),
             k=3, theta=0.5, ncrit=64, all panels POTENTIAL (first-kind operator, int G)
   value     matvecs/s of the whole job (K matvecs / max-over-ranks wall time)
+
+A plain run sets up, warms up, times the K steps, writes the result of the last step if --dump-outputs DIR is given
+(DIR/y.npy, float64, original panel order), and prints the line.  Everything below is measured or checked only with
+--full; a --full run times its steps with HIP events around the near-field kernel, as the roofline needs.
   roofline  the HBM-bound P2P kernel (near_spmv): algorithmic bytes per launch / mean launch duration
             measured with HIP events on the launch stream during the timed steps
   cpu_baseline  the oracle ("port" of the reference's OpenMP path, faithful structure, the reference's compiler flags)
             timed on this box's host cores in a child process (tools/cpu_baseline.py): a quarter-size sample of the
             same geometry first, then the workload itself when the sample says it fits --cpu-budget seconds
             (`extrapolated` says which of the two `value` is)
+  accuracy  the full-vector parity with the cpu_baseline's result and the Direct-sum gate on a seeded row sample; for
+            N > 1 also the per-rank breakdown and the check that every rank holds the same result
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6      # MI355X FP64 vector peak (AMD datasheet); the guide lists no FP64 figure
+DUMP_BYTES = 64 << 20        # --dump-outputs writes at most this much
 
 
 def parse():
@@ -43,8 +50,15 @@ def parse():
     ap.add_argument("--p", type=int, default=10)
     ap.add_argument("--theta", type=float, default=0.5)
     ap.add_argument("--ncrit", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-accuracy", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: roofline and per-stage figures, the CPU baseline, the parity and accuracy "
+                         "checks (N > 1: per-rank breakdown, replica check); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the result vector of the last step to DIR/y.npy (float64; above "
+                         "%d MB a seeded sample: y_sample.npy and its indices y_sample_index.npy)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-accuracy", action="store_true",
+                    help="no Direct-sum check: neither --full's accuracy gate nor, for N > 1, the preflight's")
     ap.add_argument("--cpu-budget", type=float, default=150.0,
                     help="seconds of host time the cpu_baseline leg may spend on the full workload (else: quarter-size sample, "
                          "extrapolated); the full N = 1M Laplace workload takes ~45 s on a 128-core host, Stokes config 4 ~100 s")
@@ -119,6 +133,22 @@ def gate_rows(np, n, nrows=GATE_ROWS):
     """The target rows of the accuracy gate: `nrows` panels drawn with a fixed seed over the WHOLE vector (BASELINE.md 3.5;
     the reference forms its error over all bodies, tests/scaling.cpp:56-74 -- a seeded sample of them is what O(N^2) allows)."""
     return np.sort(np.random.default_rng(GATE_SEED).choice(n, size=min(nrows, n), replace=False)).astype(np.int32)
+
+
+DUMP_SEED = 6464
+
+
+def dump_outputs(np, d, y):
+    """--dump-outputs: the result vector of the last timed step, float64, original panel order.  A vector larger than
+    DUMP_BYTES is written as a seeded sample of its entries (the same entries for the same arguments) beside their indices."""
+    os.makedirs(d, exist_ok=True)
+    y = y.cpu().numpy()
+    if y.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(d, "y.npy"), y)
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(y), size=DUMP_BYTES // 16, replace=False))
+    np.save(os.path.join(d, "y_sample.npy"), y[idx])
+    np.save(os.path.join(d, "y_sample_index.npy"), idx.astype(np.float64))
 
 
 def direct_check(args, np, v, x, y, stokes, bc, nrows=GATE_ROWS, y_oracle=None):
@@ -215,6 +245,86 @@ def preflight(args, fb, make_op, x, v, stokes, bc, rank, world, dev):
     return op_plain, info
 
 
+def kernel_figures(args, st, st_near, n, dof, world, stokes, traction):
+    """--full: the roofline of the near-field kernel over the timed steps (st_near: the plan's stats after them, events
+    around that kernel only), the M2L figures and the per-stage breakdown of the instrumented pass (st)."""
+    # ---- roofline of the P2P kernel on this rank's shard (SURVEY.md section 8d "Algorithmic bytes, P2P") ----
+    rows = st["owned_row_end"] - st["owned_row_begin"]
+    # Stokes: the 3x3 block of a panel pair is symmetric and is streamed as 6 values (DESIGN.md section 4), not the 9 of SURVEY 8d
+    hybrid = st["near_recomputed_pairs"] > 0
+    # a hybrid plan streams only the blocks it stores (near_bytes); the recomputed pairs cost arithmetic, stated beside the bytes
+    p2p_bytes = (st["near_bytes"] if hybrid else st["near_nnz"] * 8 * (6 if stokes else 1)) + n * 8 * dof + rows * 8 * dof
+    near_ms = st_near["ms_near"]                              # measured live over the timed region, on the launch stream
+    p2p_gbs = p2p_bytes / (near_ms * 1e-3) / 1e9 if near_ms > 0 else 0.0
+    traffic = None
+    try:                                                     # PMC traffic comes from a separate rocprofv3 --pmc pass
+        prof = json.load(open(os.path.join(ROOT, "profiles", "pmc_near_spmv_stokes.json" if stokes else "pmc_near_spmv.json")))
+        import hashlib
+        sha = hashlib.sha256(open(os.path.join(ROOT, "fmm-bem-relaxed_amd", "csrc", "kernels_near.hip"), "rb").read()).hexdigest()
+        # a figure measured on another build of the near-field kernels is stale: report none rather than that
+        # ... and so is one measured on another configuration of the near field (the committed passes are the streamed plans of
+        # the laplace and stokes_rbc workloads: tools/round_profile.sh, tools/stokes_profile.sh)
+        if (prof.get("n_panels") == n and prof.get("n_gpus") == world and prof.get("kernels_near_sha256") == sha and not hybrid
+                and not traction and not args.matrix_free):
+            traffic = prof.get("hbm_bytes_per_launch")
+    except Exception:
+        pass
+    P = args.p
+    n_exp = (7 if traction else 4) if stokes else 1                              # live expansions per box
+    # reference operation count: the double sum of LaplaceSpherical::M2L, 4 FMAs = 8 flop per complex multiply-add ...
+    m2l_ref_flops = n_exp * st["m2l_pairs_owned"] * 8.0 * (P * (P + 1) // 2) * P * P
+    # ... and what the kernel executes: rotation / axial translation / rotation (csrc/m2l_rot.hpp), per pair and expansion
+    rot_fma = 4 * sum(n * n + n + 1 for n in range(1, P)) + sum((P - k) ** 2 * (2 if k else 1) for k in range(P))
+    rot_mul = 4 * 2 * sum(P - m for m in range(1, P)) + 2 * (P * P - 1)        # z rotations (2 mul + 2 FMA per coefficient), powers of rho
+    rot_fma += 4 * 2 * sum(P - m for m in range(1, P))
+    rot_on = st["m2l_kernel"] == 1                           # which kernel the plan launched (fmmbem_stats), not a guess from the environment
+    # the double-sum kernels (p > 12, FMMBEM_M2L_ROT=0) execute 280 of the reference's 400 real FMAs per output and source at
+    # p = 10 (real radial table x complex phase, kernels_m2l.hip header): 0.70 of the reference's count
+    m2l_flops = n_exp * st["m2l_pairs_owned"] * (2.0 * rot_fma + rot_mul) if rot_on else 0.70 * m2l_ref_flops
+    m2l_tflops = m2l_flops / (st["ms_m2l"] * 1e-3) / 1e12 if st["ms_m2l"] > 0 else 0.0
+
+    if args.matrix_free:
+        # SURVEY.md section 8(d): a matrix-free P2P has no meaningful HBM figure; report FP64 flop/s with its count,
+        # (3 rsqrt + 20 flop) * K per far panel pair (Laplace; the few near-regime pairs cost more and are not counted)
+        kq = 4 if stokes else 3
+        mf_flops = st["near_nnz"] * kq * 23.0 * (4 if stokes else 1)
+        # What bounds it is FP64 instruction issue, and of that the reciprocal square roots cost most per instruction: measured on
+        # this part (tools/microbench/rsq64.hip, profiles/r04m_rsq64_issue_rate.txt) v_rsq_f64 issues 9.09e12 lane-operations/s
+        # against 33.4e12 for v_fma_f64.  Ceiling = per quadrature point one v_rsq_f64 and ~16 other FP64 instructions (the
+        # difference vector, r^2, the Newton step, the accumulation; kernels_near.hip mf_far) at those rates; `frac` = ceiling time
+        # / launch time.  The FMA-peak view of SURVEY 8(d) is kept beside it, labelled: it is not the bound.
+        RSQ_RATE, FMA_RATE, OTHER = 9.09e12, 33.4e12, 16
+        points = st["near_nnz"] * kq
+        ceil_ms = points * (1.0 / RSQ_RATE + OTHER / FMA_RATE) * 1e3
+        mf = {"kernel": "mf_sweep (P2P recomputed)", "bound": "fp64 instruction issue (v_rsq_f64 at 0.27 of the FMA rate, measured)",
+              "achieved": points / (near_ms * 1e-3) / 1e12, "peak": points / (ceil_ms * 1e-3) / 1e12, "unit": "T quadrature points/s",
+              "frac": ceil_ms / near_ms, "traffic": None, "panel_pairs": st["near_nnz"], "launch_ms": near_ms, "ceiling_ms": ceil_ms,
+              "fma_peak_view": {"algorithmic_flops_per_launch": mf_flops, "tflops": mf_flops / (near_ms * 1e-3) / 1e12,
+                                "frac_of_fma_peak_not_the_bound": mf_flops / (near_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS}}
+    return {
+        "roofline": mf if args.matrix_free else
+                    {"kernel": "near_spmv (P2P)", "bound": "hbm", "achieved": p2p_gbs, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": p2p_gbs / HBM_PEAK_GBS, "traffic": traffic,
+                     "algorithmic_bytes_per_launch": p2p_bytes, "launch_ms": near_ms,
+                     "timed_launches": st_near["timed_executes"],
+                     **({"near_stream_fraction": args.near_stream_fraction, "streamed_bytes": st["near_bytes"],
+                         "recomputed_pairs": st["near_recomputed_pairs"], "recomputed_quadrature_points": st["near_recomputed_pairs"] * (4 if stokes else 3),
+                         "listed_near_regime_pairs": st["near_side_entries"],
+                         "note": "hybrid near field: launch_ms spans the streaming kernel and the recompute kernel running side by side; "
+                                 "`achieved` counts the streamed bytes only, so it falls short of the HBM rate of the streaming kernel itself "
+                                 "when the recompute kernel is the longer of the two"} if hybrid else {})},
+        "roofline_m2l": {"kernel": {1: "m2l_rot", 2: "m2l (double sum)", 3: "m2l_small (double sum, lanes = sources)"}.get(st["m2l_kernel"], "?"), "bound": "fp64 vector FMA", "achieved": m2l_tflops,
+                         "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": m2l_tflops / FP64_PEAK_TFLOPS,
+                         "executed_flops_per_launch": m2l_flops, "launch_ms": st["ms_m2l"],
+                         "reference_flops_per_launch": m2l_ref_flops,
+                         "reference_equivalent_tflops": m2l_ref_flops / (st["ms_m2l"] * 1e-3) / 1e12 if st["ms_m2l"] > 0 else 0.0},
+        "stage_ms": {k[3:]: st[k] for k in ("ms_total", "ms_gather", "ms_near", "ms_scatter", "ms_p2m", "ms_m2m",
+                                            "ms_mh", "ms_m2l", "ms_l2l", "ms_l2p")},
+        "stage_ms_note": "a second pass of %d matvecs with HIP events around every stage, outside the timed region (the events "
+                         "themselves lengthen such a matvec; `ms_per_step` is the un-instrumented figure)" % min(args.steps, 10),
+    }
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): start the N ranks as CHILD processes
     through torch.distributed.run, one per GPU, and hand back the launcher's exit code.  Called before this process has
@@ -238,6 +348,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     one_process = args.one_process and args.gpus > 1
     if one_process:
@@ -376,10 +488,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # HIP events around the near-field kernel only (the roofline kernel), no added syncs: events around every stage put a
+    # --full: HIP events around the near-field kernel only (the roofline kernel), no added syncs: events around every stage put a
     # packet between every two kernels and cost 85 us per matvec (profiles/r03b_p10_timeline.md); the per-stage breakdown
     # (`stage_ms`) comes from a second, fully instrumented pass OUTSIDE the timed region
-    plan.set_timing(2)
+    if args.full:
+        plan.set_timing(2)
     stage(rank, "timed region: %d steps" % args.steps)
     try:
         fence()
@@ -392,18 +505,22 @@ def main():
         if world == 1:
             raise
         die(rank, world, "timed region raised: %r" % (e,))
-    st_near = plan.stats()
-    plan.set_timing(1)
-    for _ in range(min(args.steps, 10)):
-        step()
-    fence()
-    st = plan.stats()                                        # every stage bracketed: the breakdown, not the throughput
-    plan.set_timing(False)
+    if rank == 0 and args.dump_outputs:                       # y is replicated on every rank
+        dump_outputs(np, args.dump_outputs, y)
+    st = st_near = plan.stats()
+    if args.full:
+        plan.set_timing(1)
+        for _ in range(min(args.steps, 10)):
+            step()
+        fence()
+        st = plan.stats()                                    # every stage bracketed: the breakdown, not the throughput
+        plan.set_timing(False)
     per_rank, replicas_equal = None, None
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if world > 1 and args.full:
         # OUTSIDE the timed region: a few more steps with the collectives bracketed by device syncs, so that a SCALE line
         # explains itself -- per rank: kernel stage times of its shard, seconds spent in collectives, bytes received
         op.profile, op.collective_s, c0 = True, 0.0, op.calls
@@ -433,59 +550,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the P2P kernel on this rank's shard (SURVEY.md section 8d "Algorithmic bytes, P2P") ----
-    rows = st["owned_row_end"] - st["owned_row_begin"]
-    # Stokes: the 3x3 block of a panel pair is symmetric and is streamed as 6 values, not the 9 of SURVEY 8d
-    hybrid = st["near_recomputed_pairs"] > 0
-    # a hybrid plan streams only the blocks it stores (near_bytes); the recomputed pairs cost arithmetic, stated beside the bytes
-    p2p_bytes = (st["near_bytes"] if hybrid else st["near_nnz"] * 8 * (6 if stokes else 1)) + n * 8 * dof + rows * 8 * dof
-    near_ms = st_near["ms_near"]                              # measured live over the timed region, on the launch stream
-    p2p_gbs = p2p_bytes / (near_ms * 1e-3) / 1e9 if near_ms > 0 else 0.0
-    traffic = None
-    try:                                                     # PMC traffic comes from a separate rocprofv3 --pmc pass
-        prof = json.load(open(os.path.join(ROOT, "profiles", "pmc_near_spmv_stokes.json" if stokes else "pmc_near_spmv.json")))
-        import hashlib
-        sha = hashlib.sha256(open(os.path.join(ROOT, "fmm-bem-relaxed_amd", "csrc", "kernels_near.hip"), "rb").read()).hexdigest()
-        # a figure measured on another build of the near-field kernels is stale: report none rather than that
-        # ... and so is one measured on another configuration of the near field (the committed passes are the streamed plans of
-        # the laplace and stokes_rbc workloads: tools/round_profile.sh, tools/stokes_profile.sh)
-        if (prof.get("n_panels") == n and prof.get("n_gpus") == world and prof.get("kernels_near_sha256") == sha and not hybrid
-                and not traction and not args.matrix_free):
-            traffic = prof.get("hbm_bytes_per_launch")
-    except Exception:
-        pass
     P = args.p
-    n_exp = (7 if traction else 4) if stokes else 1                              # live expansions per box
-    # reference operation count: the double sum of LaplaceSpherical::M2L, 4 FMAs = 8 flop per complex multiply-add ...
-    m2l_ref_flops = n_exp * st["m2l_pairs_owned"] * 8.0 * (P * (P + 1) // 2) * P * P
-    # ... and what the kernel executes: rotation / axial translation / rotation (csrc/m2l_rot.hpp), per pair and expansion
-    rot_fma = 4 * sum(n * n + n + 1 for n in range(1, P)) + sum((P - k) ** 2 * (2 if k else 1) for k in range(P))
-    rot_mul = 4 * 2 * sum(P - m for m in range(1, P)) + 2 * (P * P - 1)        # z rotations (2 mul + 2 FMA per coefficient), powers of rho
-    rot_fma += 4 * 2 * sum(P - m for m in range(1, P))
-    rot_on = st["m2l_kernel"] == 1                           # which kernel the plan launched (fmmbem_stats), not a guess from the environment
-    # the double-sum kernels (p > 12, FMMBEM_M2L_ROT=0) execute 280 of the reference's 400 real FMAs per output and source at
-    # p = 10 (real radial table x complex phase, kernels_m2l.hip header): 0.70 of the reference's count
-    m2l_flops = n_exp * st["m2l_pairs_owned"] * (2.0 * rot_fma + rot_mul) if rot_on else 0.70 * m2l_ref_flops
-    m2l_tflops = m2l_flops / (st["ms_m2l"] * 1e-3) / 1e12 if st["ms_m2l"] > 0 else 0.0
-
-    if args.matrix_free:
-        # a matrix-free P2P has no meaningful HBM figure; report FP64 flop/s with its count,
-        # (3 rsqrt + 20 flop) * K per far panel pair (Laplace; the few near-regime pairs cost more and are not counted)
-        kq = 4 if stokes else 3
-        mf_flops = st["near_nnz"] * kq * 23.0 * (4 if stokes else 1)
-        # What bounds it is FP64 instruction issue, and of that the reciprocal square roots cost most per instruction: measured on
-        # this part (tools/microbench/rsq64.hip, profiles/r04m_rsq64_issue_rate.txt) v_rsq_f64 issues 9.09e12 lane-operations/s
-        # against 33.4e12 for v_fma_f64.  Ceiling = per quadrature point one v_rsq_f64 and ~16 other FP64 instructions (the
-        # difference vector, r^2, the Newton step, the accumulation; kernels_near.hip mf_far) at those rates; `frac` = ceiling time
-        # / launch time.  The FMA-peak view of SURVEY 8(d) is kept beside it, labelled: it is not the bound.
-        RSQ_RATE, FMA_RATE, OTHER = 9.09e12, 33.4e12, 16
-        points = st["near_nnz"] * kq
-        ceil_ms = points * (1.0 / RSQ_RATE + OTHER / FMA_RATE) * 1e3
-        mf = {"kernel": "mf_sweep (P2P recomputed)", "bound": "fp64 instruction issue (v_rsq_f64 at 0.27 of the FMA rate, measured)",
-              "achieved": points / (near_ms * 1e-3) / 1e12, "peak": points / (ceil_ms * 1e-3) / 1e12, "unit": "T quadrature points/s",
-              "frac": ceil_ms / near_ms, "traffic": None, "panel_pairs": st["near_nnz"], "launch_ms": near_ms, "ceiling_ms": ceil_ms,
-              "fma_peak_view": {"algorithmic_flops_per_launch": mf_flops, "tflops": mf_flops / (near_ms * 1e-3) / 1e12,
-                                "frac_of_fma_peak_not_the_bound": mf_flops / (near_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS}}
     out = {
         "metric": (("FMM matvecs/s (StokesBEM red blood cell, %s) + achieved HBM GB/s on P2P" % ("TRACTION targets: double layer" if traction else "velocity BC")) if stokes else
                    "FMM matvecs/s (LaplaceBEM sphere N=1e6 p=10) + achieved HBM GB/s on P2P"),
@@ -511,37 +576,22 @@ def main():
                    # generators produce -- FMMOptions.reference_l2l selects the reference's list where they differ)
                    "l2l_rule": "complete", "l2l_reference_omitted": st["l2l_reference_omitted"],
                    "near_stream_fraction": args.near_stream_fraction},
-        "roofline": mf if args.matrix_free else
-                    {"kernel": "near_spmv (P2P)", "bound": "hbm", "achieved": p2p_gbs, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": p2p_gbs / HBM_PEAK_GBS, "traffic": traffic,
-                     "algorithmic_bytes_per_launch": p2p_bytes, "launch_ms": near_ms,
-                     "timed_launches": st_near["timed_executes"],
-                     **({"near_stream_fraction": args.near_stream_fraction, "streamed_bytes": st["near_bytes"],
-                         "recomputed_pairs": st["near_recomputed_pairs"], "recomputed_quadrature_points": st["near_recomputed_pairs"] * (4 if stokes else 3),
-                         "listed_near_regime_pairs": st["near_side_entries"],
-                         "note": "hybrid near field: launch_ms spans the streaming kernel and the recompute kernel running side by side; "
-                                 "`achieved` counts the streamed bytes only, so it falls short of the HBM rate of the streaming kernel itself "
-                                 "when the recompute kernel is the longer of the two"} if hybrid else {})},
-        "roofline_m2l": {"kernel": {1: "m2l_rot", 2: "m2l (double sum)", 3: "m2l_small (double sum, lanes = sources)"}.get(st["m2l_kernel"], "?"), "bound": "fp64 vector FMA", "achieved": m2l_tflops,
-                         "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": m2l_tflops / FP64_PEAK_TFLOPS,
-                         "executed_flops_per_launch": m2l_flops, "launch_ms": st["ms_m2l"],
-                         "reference_flops_per_launch": m2l_ref_flops,
-                         "reference_equivalent_tflops": m2l_ref_flops / (st["ms_m2l"] * 1e-3) / 1e12 if st["ms_m2l"] > 0 else 0.0},
-        "stage_ms": {k[3:]: st[k] for k in ("ms_total", "ms_gather", "ms_near", "ms_scatter", "ms_p2m", "ms_m2m",
-                                            "ms_mh", "ms_m2l", "ms_l2l", "ms_l2p")},
-        "stage_ms_note": "a second pass of %d matvecs with HIP events around every stage, outside the timed region (the events "
-                         "themselves lengthen such a matvec; `ms_per_step` is the un-instrumented figure)" % min(args.steps, 10),
-        "per_rank": per_rank, "replicas_equal": replicas_equal, "preflight": pre,
+    }
+    if args.full:
+        out.update(kernel_figures(args, st, st_near, n, dof, world, stokes, traction))
+        out.update(per_rank=per_rank, replicas_equal=replicas_equal)
+    out.update({
+        "preflight": pre,
         "one_process": ({"devices": op.devices, "transport": "hipMemcpyPeerAsync ordered by events (no collective library)"} if one_process else None),
         "collectives": None if world == 1 else {"upward": ("all-to-all of the multipoles each shard reads" if op.plan.exchange_mode == 2 else "all-gather of multipoles") if op.split else "none (upward pass repeated)",
                                                 "result": op.y_collective},
         "plan_build_s": build_s, "near_assemble_s": st["build_assemble_ms"] * 1e-3,
         "host_lists_s": st["build_host_ms"] * 1e-3,
-    }
+    })
 
-    # The oracle is only ever touched in this CPU leg of the bench (rank 0): as the checker of the result just
+    # The oracle is only ever touched in this CPU leg of the bench (rank 0, --full): as the checker of the result just
     # computed (Direct sum on a row sample) and as the timed CPU baseline -- never inside the timed region.
-    cpu_leg = world == 1 and not args.no_cpu_baseline
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
     y_oracle = None
     if cpu_leg and traction:
         # the oracle restates the reference, whose far field for this operator is wrong: there is no CPU FMM to time
@@ -560,9 +610,9 @@ def main():
         yg = y.cpu().numpy()
         out["parity_vs_oracle_full"] = float(np.linalg.norm(yg - y_oracle) / np.linalg.norm(y_oracle))
         out["parity_vs_oracle_full_max_abs_over_max"] = float(np.abs(yg - y_oracle).max() / np.abs(y_oracle).max())
-    else:
+    elif args.full:
         out["parity_vs_oracle_full"] = None
-    if not args.no_accuracy:                                  # rank 0, any N (the result is replicated); independent of the baseline switch
+    if args.full and not args.no_accuracy:                    # rank 0, any N (the result is replicated); independent of the baseline switch
         g_d, o_d, nr, rowdist = direct_check(args, np, v, x, y, stokes, bc, y_oracle=y_oracle)
         gate = 1e-6
         out["rel_l2_vs_direct_sample"] = g_d

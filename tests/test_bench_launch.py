@@ -48,7 +48,7 @@ def test_bare_gpus_2_starts_two_ranks_itself():
 
 @pytest.mark.gpu
 def test_bare_gpus_2_runs_the_sharded_path_on_one_card():
-    r, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--recursions", "6", "--no-cpu-baseline"],
+    r, lines = _run(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--recursions", "6", "--no-cpu-baseline"],
                     {"FMMBEM_BENCH_BACKEND": "gloo"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, r.stdout
@@ -65,8 +65,29 @@ def test_bare_gpus_2_runs_the_sharded_path_on_one_card():
 def test_one_process_form_over_a_device_list():
     """`--gpus 2 --one-process`: one plan over two list entries (the one GPU named twice here) inside this process -- the same line
     format, n_gpus = 2, the result checked against the Direct sum as ever."""
-    r, lines = _run(["--gpus", "2", "--one-process", "--steps", "2", "--warmup", "1", "--recursions", "6", "--no-cpu-baseline"], timeout=900)
+    r, lines = _run(["--gpus", "2", "--one-process", "--full", "--steps", "2", "--warmup", "1", "--recursions", "6", "--no-cpu-baseline"], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = lines[-1]
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["one_process"]["devices"] == [0, 0]
     assert out["rel_l2_vs_direct_sample"] < 1e-5
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain one-GPU run: the headline keys, none of --full's figures, and --dump-outputs writes the last step's y (float64,
+    one value per panel); a second run with the same arguments writes the same vector (seeded inputs, bitwise repeatable matvec)."""
+    import numpy as np
+    ys = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--recursions", "5", "--dump-outputs", str(d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1, r.stdout
+        out = lines[0]
+        assert out["steps"] == 3 and out["unit"] == "matvecs/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+        assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-6 * 1e3
+        assert not {"roofline", "stage_ms", "cpu_baseline", "accuracy_gate", "parity_vs_oracle_full"} & set(out)
+        y = np.load(d / "y.npy")
+        assert y.dtype == np.float64 and y.shape == (out["config"]["n_panels"],) and np.all(np.isfinite(y))
+        ys.append(y)
+    assert np.array_equal(ys[0], ys[1])
