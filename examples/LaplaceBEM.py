@@ -6,6 +6,10 @@ same report lines (timing, potential at the exterior point (3,3,3) :346-369, rel
 :372).  All matvecs run in libfmmbem_hip.so; this file is host glue.
 
     python examples/LaplaceBEM.py -recursions 6 -p 12 -theta 0.5
+
+-field N (not a flag of the reference): after the solve, the same representation formula on N points of the sphere of radius 3
+through a plan over those target points (FMM_plan(K, panels, targets=...), the reference's FMM_plan(K, sources, targets, opts)),
+one more report line with its largest error against the exact exterior solution 1/|x|.
 """
 import math
 import os
@@ -64,12 +68,39 @@ def exterior_potential(v, bc_flip, k, density, point):
     return float(kern @ density)
 
 
+def exterior_direct(v, g_density, dgdn_density, point, k=3):
+    """The driver's representation formula at one exterior point by Direct sums (:346-369): (sum G x - sum dG/dn c) / 4 pi"""
+    return (exterior_potential(v, True, k, g_density, point) - exterior_potential(v, False, k, dgdn_density, point)) / 4 / math.pi
+
+
+def exterior_fmm(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None):
+    """The same formula at many points: two executes over the target points, one with their flags POTENTIAL (G), one with
+    them switched (dG/dn) -- the FMM in place of the two Direct sums"""
+    m = len(points)
+    K = fb_.LaplaceSphericalBEM(p, k)
+    g = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.zeros(m, dtype=np.uint8))
+    d = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.ones(m, dtype=np.uint8))
+    out = (g.execute(g_density) - d.execute(dgdn_density)) / 4 / math.pi
+    g.close()
+    d.close()
+    return out
+
+
+def sphere_points(m, radius):
+    """m points spread over a sphere (golden-angle spiral)"""
+    i = np.arange(m) + 0.5
+    z = 1 - 2 * i / m
+    r = np.sqrt(1 - z * z)
+    phi = math.pi * (3 - math.sqrt(5)) * i
+    return radius * np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+
+
 def main(argv):
     print("\nLaplaceBEM on a sphere")
     if len(argv) == 1:
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
-    second_kind, mesh = False, None
+    second_kind, mesh, field = False, None, 0
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -110,6 +141,8 @@ def main(argv):
             print_help_and_exit()
         elif a == "-mesh":
             i += 1; mesh = argv[i]
+        elif a == "-field":
+            i += 1; field = int(argv[i])
         else:
             print('[W]: Unknown command line arg: "%s"' % a)
             print_help_and_exit()
@@ -182,6 +215,11 @@ def main(argv):
     print("external phi: %.5g, exact: %.5g, error: %.4e" % (outside, exact, abs(outside - exact) / abs(exact)))
     e = float(((xs - 1.0) ** 2).sum())
     print("relative error: %.3e" % math.sqrt(e / n))
+    if field > 0:
+        pts = sphere_points(field, 3.0)
+        phi = exterior_fmm(fb, v, xs, np.ones(n), pts, p, k, opts)
+        err = np.abs(phi - 1.0 / 3.0) / (1.0 / 3.0)
+        print("field: %d points at r = 3, max error: %.4e, rms error: %.4e" % (field, float(err.max()), float(np.sqrt((err ** 2).mean()))))
     return it, res, math.sqrt(e / n), abs(outside - exact) / abs(exact)
 
 

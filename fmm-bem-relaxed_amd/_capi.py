@@ -46,6 +46,17 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TargetInfo(C.Structure):
+    """fmmbem_target_info"""
+    _fields_ = ([(n, C.c_int64) for n in (
+        "n_panels", "n_targets", "n_target_points", "n_source_boxes", "n_source_leaves", "n_source_levels",
+        "n_target_boxes", "n_target_leaves", "n_target_levels")] +
+        [("tree_coder_levels", C.c_int32), ("reserved", C.c_int32)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class SolverOpts(C.Structure):
     """fmmbem_solver_options"""
     _fields_ = [("residual", C.c_double), ("max_iters", C.c_int32), ("restart", C.c_int32), ("max_p", C.c_int32),
@@ -87,6 +98,7 @@ SYMBOLS = (
     "fmmbem_mesh_read_vert_face", "fmmbem_mesh_write_vert_face", "fmmbem_quadrature", "fmmbem_status_string", "fmmbem_last_error",
     "fmmbem_version", "fmmbem_plan_create_like", "fmmbem_host_register", "fmmbem_host_unregister", "fmmbem_solver_options_default", "fmmbem_gmres_device", "fmmbem_gmres",
     "fmmbem_ops_create", "fmmbem_ops_destroy", "fmmbem_ops_slots", "fmmbem_ops_p2m", "fmmbem_ops_m2m", "fmmbem_ops_m2l", "fmmbem_ops_l2l", "fmmbem_ops_l2p",
+    "fmmbem_plan_create_targets", "fmmbem_plan_target_info", "fmmbem_plan_get_target_boxes", "fmmbem_plan_get_target_perm",
 )
 
 
@@ -152,6 +164,10 @@ def lib():
     L.fmmbem_solver_options_default.restype = None
     L.fmmbem_gmres_device.argtypes = [vp, C.POINTER(SolverOpts), vp, vp, C.POINTER(Preconditioner), C.POINTER(SolverLog), vp]
     L.fmmbem_plan_create_like.argtypes = [vp, vp, C.POINTER(vp)]
+    L.fmmbem_plan_create_targets.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.fmmbem_plan_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
+    L.fmmbem_plan_get_target_boxes.argtypes = [vp] * 8
+    L.fmmbem_plan_get_target_perm.argtypes = [vp, vp, vp]
     L.fmmbem_gmres.argtypes = [vp, C.POINTER(SolverOpts), vp, vp, C.POINTER(Preconditioner), C.POINTER(SolverLog)]
     L.fmmbem_ops_create.argtypes = [C.POINTER(Options), C.POINTER(vp)]
     L.fmmbem_ops_destroy.argtypes = [vp]

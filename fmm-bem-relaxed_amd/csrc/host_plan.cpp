@@ -2,6 +2,7 @@
 #include "host_plan.hpp"
 
 #include <algorithm>
+#include <memory>
 #include <array>
 #include <atomic>
 #include <cmath>
@@ -522,6 +523,74 @@ bool build_tree(HostPlan& hp, unsigned L, const std::vector<double>& cen, double
   tmark("perm + geometry");
   return true;
 }
+
+// Dual tree traversal (EvalInteractionLazySparse.hpp:68-110, :239-252) of source tree S against target tree T (one tree for the
+// operator: S and T are the same plan).  The two trees must share one lattice (root cube and coder width): the DefaultMAC then
+// sees the same box geometry whichever tree a box comes from.  Pairs are (S box, T box) in the traversal's generation order.
+// keep_lr = false: EvalLocalSparse.hpp:34-86, the same traversal with accepted multipoles dropped (:120-127).
+void dual_walk(const HostPlan& S, const HostPlan& T, double theta, bool keep_lr, std::vector<int>& p2p_src, std::vector<int>& p2p_tgt,
+               std::vector<int>& lr_src, std::vector<int>& lr_tgt) {
+  auto accept = [&](int s, int t) {     // DefaultMAC, radius = side/2
+    const double dx = S.box_center[3 * s] - T.box_center[3 * t], dy = S.box_center[3 * s + 1] - T.box_center[3 * t + 1],
+                 dz = S.box_center[3 * s + 2] - T.box_center[3 * t + 2];
+    const double rhs = (S.box_side[s] / 2.0 + T.box_side[t] / 2.0) / theta;
+    return dx * dx + dy * dy + dz * dz > rhs * rhs;
+  };
+  // The reference walks a FIFO (EvalInteractionLazySparse.hpp:68-110): pairs are taken in the order they were queued, so the
+  // queue is a sequence of GENERATIONS -- the children of generation g, in order, are generation g + 1 -- and the lists come out
+  // generation by generation, pair by pair.  A generation's pairs are independent: cut into contiguous chunks for a few
+  // threads, each chunk's output (next generation, P2P pairs, M2L pairs) appended in chunk order, the lists are the serial
+  // ones entry for entry (tests/test_capi_host.py, test_random_meshes.py compare them with the oracle's).
+  typedef std::pair<int, int> Pair;
+  std::vector<Pair> cur, next;
+  cur.emplace_back(0, 0);
+  struct Out { std::vector<Pair> next, p2p, lr; };
+  auto walk = [&](const Pair* first, const Pair* last, Out& out) {
+    for (const Pair* it = first; it != last; ++it) {
+      const int s = it->first, t = it->second;
+      bool split_source;
+      if (S.box_leaf[s]) {
+        if (T.box_leaf[t]) { out.p2p.emplace_back(s, t); continue; }
+        split_source = false;
+      } else if (T.box_leaf[t]) {
+        split_source = true;
+      } else {
+        split_source = S.box_side[s] > T.box_side[t];        // ties split the target side (:98-108)
+      }
+      const HostPlan& O = split_source ? S : T;
+      const int open = split_source ? s : t;
+      for (int c = O.box_child_begin[open]; c < O.box_child_end[open]; ++c) {
+        const int ns = split_source ? c : s, nt = split_source ? t : c;
+        if (accept(ns, nt)) { if (keep_lr) out.lr.emplace_back(ns, nt); }
+        else out.next.emplace_back(ns, nt);
+      }
+    }
+  };
+  const int max_threads = (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
+  std::vector<Out> outs;
+  while (!cur.empty()) {
+    const int nt = cur.size() < 8192 ? 1 : std::min<int>(max_threads, (int)(cur.size() / 4096));
+    outs.assign(nt, Out{});
+    if (nt == 1) walk(cur.data(), cur.data() + cur.size(), outs[0]);
+    else {
+      host_parallel(nt, [&](int k) { walk(cur.data() + cur.size() * k / nt, cur.data() + cur.size() * (k + 1) / nt, outs[k]); });
+    }
+    // the shares' finds, concatenated in share order (= the serial walk's order): sizes first, then every share copies its own
+    std::vector<size_t> on(nt + 1, 0), op(nt + 1, p2p_src.size()), ol(nt + 1, lr_src.size());
+    for (int k = 0; k < nt; ++k) { on[k + 1] = on[k] + outs[k].next.size(); op[k + 1] = op[k] + outs[k].p2p.size(); ol[k + 1] = ol[k] + outs[k].lr.size(); }
+    next.resize(on[nt]);
+    p2p_src.resize(op[nt]); p2p_tgt.resize(op[nt]);
+    lr_src.resize(ol[nt]); lr_tgt.resize(ol[nt]);
+    auto place = [&](int k) {
+      const Out& o_ = outs[k];
+      std::copy(o_.next.begin(), o_.next.end(), next.begin() + on[k]);
+      for (size_t i = 0; i < o_.p2p.size(); ++i) { p2p_src[op[k] + i] = o_.p2p[i].first; p2p_tgt[op[k] + i] = o_.p2p[i].second; }
+      for (size_t i = 0; i < o_.lr.size(); ++i) { lr_src[ol[k] + i] = o_.lr[i].first; lr_tgt[ol[k] + i] = o_.lr[i].second; }
+    };
+    if (nt == 1) place(0); else host_parallel(nt, place);
+    cur.swap(next);
+  }
+}
 }  // namespace
 
 void alloc_panels(PanelSoA& P, int64_t n, int nq) {
@@ -608,76 +677,30 @@ std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double
   }
   mark("tree + box geometry");
   // ---- dual tree traversal (EvalInteractionLazySparse.hpp:68-110, :239-252) ----
-  auto accept = [&](int s, int t) {     // DefaultMAC, radius = side/2
-    const double dx = box_center[3 * s] - box_center[3 * t], dy = box_center[3 * s + 1] - box_center[3 * t + 1],
-                 dz = box_center[3 * s + 2] - box_center[3 * t + 2];
-    const double rhs = (box_side[s] / 2.0 + box_side[t] / 2.0) / o.theta;
-    return dx * dx + dy * dy + dz * dz > rhs * rhs;
-  };
-  {
-    // The reference walks a FIFO (EvalInteractionLazySparse.hpp:68-110): pairs are taken in the order they were queued, so the
-    // queue is a sequence of GENERATIONS -- the children of generation g, in order, are generation g + 1 -- and the lists come out
-    // generation by generation, pair by pair.  A generation's pairs are independent: cut into contiguous chunks for a few
-    // threads, each chunk's output (next generation, P2P pairs, M2L pairs) appended in chunk order, the lists are the serial
-    // ones entry for entry (tests/test_capi_host.py, test_random_meshes.py compare them with the oracle's).
-    // evaluator: 0 = EvalInteractionLazySparse; 1 = EvalLocalSparse.hpp:34-86, the same traversal with accepted
-    // multipoles dropped (:120-127); 2 = EvalDiagonalSparse.hpp:33-49, every leaf with itself in box order
-    typedef std::pair<int, int> Pair;
-    std::vector<Pair> cur, next;
-    if (opt.evaluator == 2) {
-      for (int b = 0; b < nboxes; ++b)
-        if (box_leaf[b]) { p2p_src.push_back(b); p2p_tgt.push_back(b); }
-    } else {
-      cur.emplace_back(0, 0);
-    }
-    struct Out { std::vector<Pair> next, p2p, lr; };
-    auto walk = [&](const Pair* first, const Pair* last, Out& out) {
-      for (const Pair* it = first; it != last; ++it) {
-        const int s = it->first, t = it->second;
-        bool split_source;
-        if (box_leaf[s]) {
-          if (box_leaf[t]) { out.p2p.emplace_back(s, t); continue; }
-          split_source = false;
-        } else if (box_leaf[t]) {
-          split_source = true;
-        } else {
-          split_source = box_side[s] > box_side[t];        // ties split the target side (:98-108)
-        }
-        const int open = split_source ? s : t;
-        for (int c = box_child_begin[open]; c < box_child_end[open]; ++c) {
-          const int ns = split_source ? c : s, nt = split_source ? t : c;
-          if (accept(ns, nt)) { if (opt.evaluator == 0) out.lr.emplace_back(ns, nt); }
-          else out.next.emplace_back(ns, nt);
-        }
-      }
-    };
-    const int max_threads = (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
-    std::vector<Out> outs;
-    while (!cur.empty()) {
-      const int nt = cur.size() < 8192 ? 1 : std::min<int>(max_threads, (int)(cur.size() / 4096));
-      outs.assign(nt, Out{});
-      if (nt == 1) walk(cur.data(), cur.data() + cur.size(), outs[0]);
-      else {
-        host_parallel(nt, [&](int k) { walk(cur.data() + cur.size() * k / nt, cur.data() + cur.size() * (k + 1) / nt, outs[k]); });
-      }
-      // the shares' finds, concatenated in share order (= the serial walk's order): sizes first, then every share copies its own
-      std::vector<size_t> on(nt + 1, 0), op(nt + 1, p2p_src.size()), ol(nt + 1, lr_src.size());
-      for (int k = 0; k < nt; ++k) { on[k + 1] = on[k] + outs[k].next.size(); op[k + 1] = op[k] + outs[k].p2p.size(); ol[k + 1] = ol[k] + outs[k].lr.size(); }
-      next.resize(on[nt]);
-      p2p_src.resize(op[nt]); p2p_tgt.resize(op[nt]);
-      lr_src.resize(ol[nt]); lr_tgt.resize(ol[nt]);
-      auto place = [&](int k) {
-        const Out& o_ = outs[k];
-        std::copy(o_.next.begin(), o_.next.end(), next.begin() + on[k]);
-        for (size_t i = 0; i < o_.p2p.size(); ++i) { p2p_src[op[k] + i] = o_.p2p[i].first; p2p_tgt[op[k] + i] = o_.p2p[i].second; }
-        for (size_t i = 0; i < o_.lr.size(); ++i) { lr_src[ol[k] + i] = o_.lr[i].first; lr_tgt[ol[k] + i] = o_.lr[i].second; }
-      };
-      if (nt == 1) place(0); else host_parallel(nt, place);
-      cur.swap(next);
-    }
+  if (opt.evaluator == 2) {          // EvalDiagonalSparse.hpp:33-49: every leaf with itself in box order
+    for (int b = 0; b < nboxes; ++b)
+      if (box_leaf[b]) { p2p_src.push_back(b); p2p_tgt.push_back(b); }
+  } else {
+    dual_walk(*this, *this, o.theta, opt.evaluator == 0, p2p_src, p2p_tgt, lr_src, lr_tgt);
   }
 
   mark("traversal");
+  return finish(vertices, bc);
+}
+
+// Everything after the traversal: leaves, near lists, need/has, the L2L rule, the shard, the operator lists, the M2L CSR and its
+// classes, the panels.  Dual plans (n_src > 0, build_targets) own the target leaves -- the bodies from row n_src on -- and fill
+// their panels themselves.
+std::string HostPlan::finish(const double* vertices, const uint8_t* bc) {
+  const HostOptions& o = opt;
+  const bool trace = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
+  auto t_last = std::chrono::steady_clock::now();
+  auto mark = [&](const char* what) {
+    if (!trace) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "host_plan %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  };
   // ---- leaves in tree order ----
   box_leaf_index.assign(nboxes, -1);
   for (int b = 0; b < nboxes; ++b)
@@ -760,7 +783,13 @@ std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double
   std::vector<int64_t> shard_rb;                         // first row of every shard, then n
   {
     std::vector<int> cut;
-    partition_leaves(*this, o.shard_world, cut);
+    if (n_src > 0) {                                     // dual plan: the target leaves, all of them
+      int first = nl;
+      for (int l = 0; l < nl; ++l) if (box_body_begin[leaf_box[l]] >= n_src) { first = l; break; }
+      cut = {first, nl};
+    } else {
+      partition_leaves(*this, o.shard_world, cut);
+    }
     if (o.shard_world > 1) {
       std::vector<int64_t> rb(o.shard_world + 1, n);
       for (int r = 0; r < o.shard_world; ++r) rb[r] = cut[r] < nl ? box_body_begin[leaf_box[cut[r]]] : n;
@@ -944,7 +973,7 @@ std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double
   // ---- panels in tree order, SoA (LaplaceSphericalBEM.hpp:64-97) ----
   PanelSoA& P = panels;
   const int nq = rule.n;
-  if (o.panels_on_device) return {};                  // (the flags were set above, ahead of the hand-over)
+  if (o.panels_on_device || n_src > 0) return {};                  // (the flags were set above, ahead of the hand-over)
   alloc_panels(P, n, nq);
   // independent per panel: cut into ranges for a few host threads (half of this function's time at N = 1M when serial)
   const int nthreads = n < (1 << 16) ? 1 : (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
@@ -962,6 +991,164 @@ std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double
   }
   for (int t = 0; t < nthreads; ++t) { has_bc[0] = has_bc[0] || seen_bc[t][0]; has_bc[1] = has_bc[1] || seen_bc[t][1]; }
   mark("panels SoA");
+  return {};
+}
+
+std::string HostPlan::build_targets(const HostOptions& o, int64_t n_panels, const double* vertices, int64_t n_tg, const double* points,
+                                    const uint8_t* target_bc) {
+  opt = o;
+  if (n_panels <= 0 || !vertices) return "no panels";
+  if (n_tg <= 0 || !points) return "no targets";
+  if (n_panels + n_tg > (int64_t(1) << 31) - 1) return "too many panels and targets";
+  if (!quad_rule(o.quad_k, rule)) return "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)";
+  if (o.p_max < 1 || o.p_max > kPmax) return "p_max out of range";
+  if (!(o.theta > 0)) return "theta must be positive";
+  if (o.shard_world != 1 || o.shard_rank != 0) return "bad shard";
+  for (int64_t k = 0; k < 3 * n_tg; ++k)
+    if (!std::isfinite(points[k])) return "target point not finite";
+  n_targets = n_tg;
+  // ---- coincident targets (same point, same flag) are one body: the tree could not separate them ----
+  std::vector<uint32_t> order((size_t)n_tg);
+  for (int64_t k = 0; k < n_tg; ++k) order[(size_t)k] = (uint32_t)k;
+  auto flag_of = [&](int64_t k) -> uint8_t { return target_bc && target_bc[k] ? 1 : 0; };
+  auto less = [&](uint32_t a, uint32_t b) {
+    for (int c = 0; c < 3; ++c) {
+      const double x = points[3 * (size_t)a + c], y = points[3 * (size_t)b + c];
+      if (x != y) return x < y;
+    }
+    if (flag_of(a) != flag_of(b)) return flag_of(a) < flag_of(b);
+    return a < b;
+  };
+  std::sort(order.begin(), order.end(), less);
+  auto same = [&](uint32_t a, uint32_t b) {
+    return points[3 * (size_t)a] == points[3 * (size_t)b] && points[3 * (size_t)a + 1] == points[3 * (size_t)b + 1] &&
+           points[3 * (size_t)a + 2] == points[3 * (size_t)b + 2] && flag_of(a) == flag_of(b);
+  };
+  std::vector<uint32_t> rep((size_t)n_tg);              // given target -> first given target of its point
+  for (size_t i = 0; i < order.size();) {
+    size_t j = i + 1;
+    while (j < order.size() && same(order[i], order[j])) ++j;
+    for (size_t k = i; k < j; ++k) rep[order[k]] = order[i];
+    i = j;
+  }
+  // distinct points numbered in the order they were first given (no duplicates: the identity)
+  target_point.assign((size_t)n_tg, 0);
+  std::vector<double> cen_t;
+  std::vector<uint8_t> flag_t;
+  cen_t.reserve(3 * (size_t)n_tg);
+  for (int64_t k = 0; k < n_tg; ++k) {
+    if (rep[(size_t)k] == (uint32_t)k) {
+      target_point[(size_t)k] = (uint32_t)flag_t.size();
+      for (int c = 0; c < 3; ++c) cen_t.push_back(points[3 * (size_t)k + c]);
+      flag_t.push_back(flag_of(k));
+    } else {
+      target_point[(size_t)k] = target_point[rep[(size_t)k]];
+    }
+  }
+  const int64_t n_tp = (int64_t)flag_t.size();
+  // ---- panel centroids; ONE root cube over the centroids and the targets (the rule of build: inflated by 1 + 1e-6) ----
+  std::vector<double> cen_s(3 * (size_t)n_panels);
+  double lo[3], hi[3];
+  for (int64_t i = 0; i < n_panels; ++i)
+    for (int k = 0; k < 3; ++k) {
+      const double c = (vertices[9 * i + k] + vertices[9 * i + 3 + k] + vertices[9 * i + 6 + k]) / 3;
+      cen_s[3 * i + k] = c;
+      if (i == 0) lo[k] = hi[k] = c;
+      else { lo[k] = std::min(lo[k], c); hi[k] = std::max(hi[k], c); }
+    }
+  for (int64_t i = 0; i < n_tp; ++i)
+    for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], cen_t[3 * i + k]); hi[k] = std::max(hi[k], cen_t[3 * i + k]); }
+  const double ext = std::max({std::fabs(hi[0] - lo[0]), std::fabs(hi[1] - lo[1]), std::fabs(hi[2] - lo[2])});
+  for (int k = 0; k < 3; ++k) {
+    hi[k] = std::max(hi[k], lo[k] + ext * (1 + 1e-6));
+    pmin[k] = lo[k];
+  }
+  // ---- the two trees, one coder for both: 21 levels for both if either needs them ----
+  std::unique_ptr<HostPlan> S(new HostPlan), T(new HostPlan);
+  S->n = n_panels; T->n = n_tp;
+  for (int k = 0; k < 3; ++k) S->pmin[k] = T->pmin[k] = pmin[k];
+  tree_levels_max = 10;
+  if (!build_tree<uint32_t>(*S, 10, cen_s, hi, o.ncrit) || !build_tree<uint32_t>(*T, 10, cen_t, hi, o.ncrit)) {
+    tree_levels_max = 21;
+    S.reset(new HostPlan); T.reset(new HostPlan);
+    S->n = n_panels; T->n = n_tp;
+    for (int k = 0; k < 3; ++k) S->pmin[k] = T->pmin[k] = pmin[k];
+    if (!build_tree<uint64_t>(*S, 21, cen_s, hi, o.ncrit) || !build_tree<uint64_t>(*T, 21, cen_t, hi, o.ncrit))
+      return "octree deeper than 21 levels (coincident panel centroids?)";
+  }
+  for (int k = 0; k < 3; ++k) cell[k] = S->cell[k];
+  // ---- the traversal, source tree against target tree (local box ids) ----
+  std::vector<int> ps, pt, ls, lt;
+  dual_walk(*S, *T, o.theta, true, ps, pt, ls, lt);
+  // ---- the merged box numbering: level by level, the source boxes of a level, then the target boxes ----
+  src_nlevels = S->nlevels; tgt_nlevels = T->nlevels;
+  nlevels = std::max(S->nlevels, T->nlevels);
+  nboxes = S->nboxes + T->nboxes;
+  src_box.assign(S->nboxes, 0); tgt_box.assign(T->nboxes, 0);
+  level_off.assign(1, 0);
+  {
+    int u = 0;
+    for (int l = 0; l < nlevels; ++l) {
+      if (l < S->nlevels) for (int b = S->level_off[l]; b < S->level_off[l + 1]; ++b) src_box[b] = u++;
+      if (l < T->nlevels) for (int b = T->level_off[l]; b < T->level_off[l + 1]; ++b) tgt_box[b] = u++;
+      level_off.push_back(u);
+    }
+  }
+  box_key.assign(nboxes, 0); box_level.assign(nboxes, 0); box_parent.assign(nboxes, 0);
+  box_child_begin.assign(nboxes, 0); box_child_end.assign(nboxes, 0); box_leaf.assign(nboxes, 0);
+  box_body_begin.assign(nboxes, 0); box_body_end.assign(nboxes, 0);
+  box_center.assign(3 * (size_t)nboxes, 0.0); box_side.assign(nboxes, 0.0); box_icoord.assign(3 * (size_t)nboxes, 0);
+  auto merge = [&](const HostPlan& X, const std::vector<int>& map, int64_t body0) {
+    for (int b = 0; b < X.nboxes; ++b) {
+      const int u = map[b];
+      box_key[u] = X.box_key[b];
+      box_level[u] = X.box_level[b];
+      box_parent[u] = b == 0 ? u : map[X.box_parent[b]];       // a root is its own parent
+      if (X.box_child_end[b] > X.box_child_begin[b]) {          // the children of a box are consecutive on the next level either way
+        box_child_begin[u] = map[X.box_child_begin[b]];
+        box_child_end[u] = box_child_begin[u] + (X.box_child_end[b] - X.box_child_begin[b]);
+      }
+      box_leaf[u] = X.box_leaf[b];
+      box_body_begin[u] = (int)(X.box_body_begin[b] + body0);
+      box_body_end[u] = (int)(X.box_body_end[b] + body0);
+      for (int k = 0; k < 3; ++k) { box_center[3 * u + k] = X.box_center[3 * b + k]; box_icoord[3 * u + k] = X.box_icoord[3 * b + k]; }
+      box_side[u] = X.box_side[b];
+    }
+  };
+  merge(*S, src_box, 0);
+  merge(*T, tgt_box, n_panels);
+  src_nleaves = tgt_nleaves = 0;
+  for (int b = 0; b < S->nboxes; ++b) src_nleaves += S->box_leaf[b];
+  for (int b = 0; b < T->nboxes; ++b) tgt_nleaves += T->box_leaf[b];
+  n_src = n_panels;
+  n = n_panels + n_tp;
+  perm.resize((size_t)n);
+  std::copy(S->perm.begin(), S->perm.end(), perm.begin());
+  std::copy(T->perm.begin(), T->perm.end(), perm.begin() + n_panels);
+  p2p_src.resize(ps.size()); p2p_tgt.resize(ps.size());
+  for (size_t i = 0; i < ps.size(); ++i) { p2p_src[i] = src_box[ps[i]]; p2p_tgt[i] = tgt_box[pt[i]]; }
+  lr_src.resize(ls.size()); lr_tgt.resize(ls.size());
+  for (size_t i = 0; i < ls.size(); ++i) { lr_src[i] = src_box[ls[i]]; lr_tgt[i] = tgt_box[lt[i]]; }
+  S.reset(); T.reset();
+  const std::string err = finish(vertices, nullptr);
+  if (!err.empty()) return err;
+  // ---- bodies: the panels in source-tree order, then the target points as panels of no extent (centre = the point) ----
+  PanelSoA& P = panels;
+  const int nq = rule.n;
+  alloc_panels(P, n, nq);
+  has_bc[0] = has_bc[1] = false;
+  for (int64_t i = 0; i < n_panels; ++i) fill_panel(P, n, i, vertices + 9 * (size_t)perm[i], rule, 0);
+  for (int64_t i = n_panels; i < n; ++i) {
+    const size_t t = perm[i];
+    const double x = cen_t[3 * t], y = cen_t[3 * t + 1], z = cen_t[3 * t + 2];
+    P.cx[i] = x; P.cy[i] = y; P.cz[i] = z;
+    P.nx[i] = P.ny[i] = P.nz[i] = 0.0;
+    P.area[i] = 0.0;
+    for (int q = 0; q < nq; ++q) { P.quad[((size_t)q * 3) * n + i] = x; P.quad[((size_t)q * 3 + 1) * n + i] = y; P.quad[((size_t)q * 3 + 2) * n + i] = z; }
+    for (int v = 0; v < 3; ++v) { P.vert[(size_t)(3 * v) * n + i] = x; P.vert[(size_t)(3 * v + 1) * n + i] = y; P.vert[(size_t)(3 * v + 2) * n + i] = z; }
+    P.bc[i] = flag_t[t];
+    has_bc[flag_t[t]] = true;
+  }
   return {};
 }
 

@@ -172,8 +172,24 @@ struct HostPlan {
   PanelSoA panels;                        // tree order
   bool has_bc[2] = {false, false};
 
+  // ---- dual plans (build_targets): source panels against target points of their own ----
+  // One plan over two trees on ONE lattice (common root cube, one coder width): the source tree of the panels and the target tree
+  // of the distinct target points.  Their boxes are merged level by level -- level l holds the source boxes of level l, then the
+  // target boxes -- so that every list above (BFS order, parents first, box_icoord differences) holds as it is; bodies [0, n_src)
+  // are the panels in source-tree order, [n_src, n) the distinct target points in target-tree order (perm: their index among the
+  // distinct points).  The plan owns the target leaves only.
+  int64_t n_src = 0;                      // > 0: a dual plan
+  int64_t n_targets = 0;                  // targets as given; coincident ones (same point, same flag) are one body
+  std::vector<uint32_t> target_point;     // given target -> distinct point
+  std::vector<int> src_box, tgt_box;      // box of the source / target tree (its own BFS numbering) -> box of this plan
+  int src_nlevels = 0, tgt_nlevels = 0, src_nleaves = 0, tgt_nleaves = 0;
+
   // Builds everything above. Returns an empty string on success, else the error text.
   std::string build(const HostOptions& o, int64_t n_panels, const double* vertices, const uint8_t* bc);
+  // The dual plan of n_panels source panels and n_targets points (xyz), flags target_bc (or all POTENTIAL)
+  std::string build_targets(const HostOptions& o, int64_t n_panels, const double* vertices, int64_t n_targets, const double* points,
+                            const uint8_t* target_bc);
+  std::string finish(const double* vertices, const uint8_t* bc);      // build's steps after the traversal
   int nleaves() const { return (int)leaf_box.size(); }
 };
 

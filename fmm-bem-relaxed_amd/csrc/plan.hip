@@ -240,6 +240,17 @@ struct fmmbem_plan {
   double *stage_x = nullptr, *stage_y = nullptr;               // device staging for host-pointer execute
   fmmbem::SolverWs* solver_ws = nullptr;                       // workspace of fmmbem_gmres* on this plan (krylov.hip), kept between solves
   hipStream_t own_stream = nullptr;
+  // Dual plans (fmmbem_plan_create_targets): hp holds the source tree and the target tree as one plan (HostPlan::build_targets);
+  // x has hp.n_src entries, y hp.n_targets.  Every source feeds both expansions (the TARGET's flag picks the kernel): P2M runs once
+  // per live slot with the flags of all sources set to that slot's (bc_all[slot]) and that slot's moment table.
+  bool targets = false;
+  bool zero_target_rows = false;                               // some target leaf has no near pair
+  const uint8_t* bc_all[2] = {nullptr, nullptr};
+  const double2* p2m_tab_slot[2] = {nullptr, nullptr};
+  const uint32_t* d_target_point = nullptr;                    // given target -> distinct point (only when some coincide)
+  double* y_points = nullptr;                                  // the result per distinct point (only when some coincide)
+  double* stage_y_targets = nullptr;                           // device staging of y for host-pointer execute
+  int p2m_targets(int p, hipStream_t s);
 
   template <class T, class A>
   int upload(const std::vector<T, A>& v, const T** out) {
@@ -317,6 +328,12 @@ __global__ void expand_csr_targets_kernel(const int* __restrict__ ptr, int nboxe
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= nboxes) return;
   for (int i = ptr[b]; i < ptr[b + 1]; ++i) tgt[i] = b;
+}
+
+// a target plan whose targets coincide: y[k] = y_points[point[k]] over the targets as given
+__global__ void expand_targets_kernel(const uint32_t* __restrict__ point, const double* __restrict__ yp, double* __restrict__ y, int64_t n) {
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k < n) y[k] = yp[point[k]];
 }
 
 int fmmbem_plan::to_device(int part) {
@@ -950,6 +967,12 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
     HIP_TRY(hipMemcpy(dbc, bc_tree, (size_t)hp.n, hipMemcpyHostToDevice));
     d.bc = dbc;
   }
+  for (int f = 0; targets && f < 2; ++f) {
+    uint8_t* all = nullptr;
+    TRY(alloc((size_t)hp.n, &all, false));
+    HIP_TRY(hipMemset(all, f, (size_t)hp.n));
+    bc_all[f] = all;
+  }
   if (near_total_doubles) TRY(alloc((size_t)near_total_doubles, &d.near_val, false));
   if (sym_total_doubles) TRY(alloc((size_t)sym_total_doubles, &d.near_sym, false));
   if (hybrid) {
@@ -1022,12 +1045,19 @@ int fmmbem_plan::to_device_bc_end() {
     }
     const bool want = !stokes || d.stokes_velocity_targets;
     if (want && !(e && std::atoi(e) == 0) && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
-      double2* tab = nullptr;
-      TRY(alloc(count, &tab, true));
-      HIP_TRY(hipDeviceSynchronize());                 // the zero-fill ran on the NULL stream
-      HIP_TRY(launch_p2m_table(d, tab, own_stream));
-      HIP_TRY(hipStreamSynchronize(own_stream));
-      d.p2m_tab = tab;
+      for (int f = 0; f < 2; ++f) {                    // (a dual plan: the table of every live slot, all sources; else one table)
+        if (targets && !has_bc[f]) continue;
+        DevicePlan dt = d;
+        if (targets) dt.bc = bc_all[f];
+        double2* tab = nullptr;
+        TRY(alloc(count, &tab, true));
+        HIP_TRY(hipDeviceSynchronize());               // the zero-fill ran on the NULL stream
+        HIP_TRY(launch_p2m_table(dt, tab, own_stream));
+        HIP_TRY(hipStreamSynchronize(own_stream));
+        p2m_tab_slot[f] = tab;
+        if (!targets) break;
+      }
+      d.p2m_tab = p2m_tab_slot[0] ? p2m_tab_slot[0] : p2m_tab_slot[1];
     }
   }
   mark("p2m table");
@@ -1154,13 +1184,29 @@ int fmmbem_plan::l2l_pass(int p, hipStream_t s) {
   return FMMBEM_OK;
 }
 
+// P2M of a dual plan: once per live slot, every source panel taken with that slot's flag (the moments of G, or of dG/dn with the
+// panel's normal) and that slot's table; the same kernels as a plan whose panels all carry the flag
+int fmmbem_plan::p2m_targets(int p, hipStream_t s) {
+  for (int f = 0; f < 2; ++f) {
+    if (!has_bc[f]) continue;
+    DevicePlan dp = d;
+    dp.bc = bc_all[f];
+    dp.n_act = 1; dp.act[0] = f;
+    if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
+    HIP_TRY(launch_p2m(dp, p, s));
+  }
+  return FMMBEM_OK;
+}
+
 int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, int phase, double* xbuf) {
+  if (!on_device && targets) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
   if (!on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   if ((phase < 2 && !d_x) || (phase != 1 && !d_y)) return fail(FMMBEM_ERR_INVALID, "null vector");
   if (split_upward && phase == 0 && !near_only)
     return fail(FMMBEM_ERR_UNSUPPORTED, "plan shards the upward pass: use fmmbem_plan_upward_device / _downward_device");
   if (phase != 0 && (!split_upward || (!xbuf && phase != 3))) return fail(FMMBEM_ERR_INVALID, "split execute needs shard_upward and an exchange buffer");
+  if (targets && (phase != 0 || result_slices)) return fail(FMMBEM_ERR_UNSUPPORTED, "a target plan runs whole executes only");
   DEVICE_SCOPE(opts.device);
   const int tm = timing;
   const int64_t ring = ev_count % kRing;
@@ -1208,7 +1254,11 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   };
   if (phase < 2) {
     HIP_TRY(begin(0, s));
-    HIP_TRY(launch_gather_x(d, d_x, s));
+    if (targets) {                                     // x: the source panels only (the target rows of x_tree stay 0)
+      DevicePlan dg = d;
+      dg.n = hp.n_src;
+      HIP_TRY(launch_gather_x(dg, d_x, s));
+    } else HIP_TRY(launch_gather_x(d, d_x, s));
     HIP_TRY(end(0, s));
   }
   if (phase == 1) {                                    // upward half: my leaves, my boxes, pack what the others need
@@ -1228,6 +1278,10 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   }
   auto near_field = [&](hipStream_t ns) -> int {
     HIP_TRY(begin(1, ns));
+    // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
+    // only added to by L2P -- they start from zero
+    if (targets && zero_target_rows)
+      HIP_TRY(hipMemsetAsync(d.yt + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), ns));
     if (hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
     else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
     HIP_TRY(end(1, ns));
@@ -1241,6 +1295,13 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     if (result_slices) {
       HIP_TRY(hipMemcpyAsync(d_y, d.yt + d.row_begin * d.dof, sizeof(double) * (size_t)(d.row_end - d.row_begin) * d.dof,
                              hipMemcpyDeviceToDevice, ns));
+    } else if (targets) {                              // the target rows -> distinct points -> the targets as given
+      HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : d_y, ns));
+      if (d_target_point) {
+        const int64_t nt = hp.n_targets;
+        hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ns, d_target_point, y_points, d_y, nt);
+        HIP_TRY(hipGetLastError());
+      }
     } else {
       if (hp.opt.shard_world > 1) HIP_TRY(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)hp.n * d.dof, ns));
       HIP_TRY(launch_scatter_y(d, d_y, ns));
@@ -1261,7 +1322,8 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   if (!near_only) {
     if (phase == 0) {
       HIP_TRY(begin(3, s));
-      if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
+      if (targets) TRY(p2m_targets(p, s));
+      else if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
       HIP_TRY(end(3, s));
       HIP_TRY(begin(4, s));
       TRY(m2m_pass(p, false, s));
@@ -1763,9 +1825,129 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   return FMMBEM_OK;
 }
 
+// ---- plans over separate targets (include/fmmbem.h fmmbem_plan_create_targets) ----
+// FMM_plan(K, sources, targets, opts) of the reference (include/FMM_plan.hpp:45-55): y_i = sum_j K(t_i, s_j) x_j at target POINTS,
+// the target's flag picking G or dG/dn.  One host plan over both trees (HostPlan::build_targets), then the single plan's device
+// path: the near rows are the target points (the same entry functions, so a target on a panel's centroid gets that row's bits),
+// the far field runs P2M/M2M on the source boxes, M2L from source to target boxes, L2L/L2P on the target boxes.
+static int target_plan_only(const fmmbem_plan* plan, const char* what) {
+  if (plan && plan->targets)
+    return fail(FMMBEM_ERR_UNSUPPORTED, std::string(what) + ": not on a plan over separate targets (fmmbem_plan_create_targets)");
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, const double* vertices, const uint8_t* bc,
+                               size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
+  (void)bc;       // the sources' flags do not enter: the target's flag picks the kernel (kernel/LaplaceSphericalBEM.hpp:273-297)
+  if (!opts || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
+  if (!target_points || n_targets == 0) return fail(FMMBEM_ERR_INVALID, "no targets");
+  if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: Laplace only (Stokes velocity at points is not implemented)");
+  if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "unknown kernel id");
+  if (opts->shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: shard_world > 1 is not implemented");
+  if (opts->n_devices > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: a device list is not implemented");
+  if (opts->evaluator != FMMBEM_EVAL_FMM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: the FMM evaluator only");
+  if (!opts->sparse_local) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: the assembled near field only (sparse_local = 1)");
+  if (opts->l2l_rule != FMMBEM_L2L_COMPLETE) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: l2l_rule COMPLETE only");
+  if (n_panels + n_targets > (size_t)INT32_MAX) return fail(FMMBEM_ERR_INVALID, "too many panels and targets");
+  if (!opts->host_only) (void)order_tables();
+  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan);
+  if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
+  pl->opts = *opts;
+  pl->opts.near_stream_fraction = 1.0;                 // the hybrid near field is taken as 1 here
+  pl->opts.shard_rank = 0; pl->opts.shard_world = 1; pl->opts.n_devices = 0;
+  pl->targets = true;
+  HostOptions ho;
+  ho.p_max = opts->p_max; ho.quad_k = opts->quad_k; ho.theta = opts->theta; ho.ncrit = opts->ncrit;
+  const double t0 = now_ms();
+  std::string err;
+  try {
+    err = pl->hp.build_targets(ho, (int64_t)n_panels, vertices, (int64_t)n_targets, target_points, target_bc);
+  } catch (const std::bad_alloc&) {
+    return fail(FMMBEM_ERR_ALLOC, "host allocation failed while building the plan");
+  }
+  if (!err.empty()) return fail(err.find("octree") != std::string::npos ? FMMBEM_ERR_TREE : FMMBEM_ERR_INVALID, err);
+  pl->build_host_ms = now_ms() - t0;
+  pl->has_bc[0] = pl->hp.has_bc[0]; pl->has_bc[1] = pl->hp.has_bc[1];
+  if (!opts->host_only) {
+    try {
+      TRY(pl->to_device(0));
+      DEVICE_SCOPE(opts->device);
+      pl->alloc_list = &pl->allocs;
+      const HostPlan& h = pl->hp;
+      for (int l = h.leaf_begin; l < h.leaf_end; ++l) pl->zero_target_rows = pl->zero_target_rows || h.near_ncols[l] == 0;
+      bool coincide = false;
+      for (size_t k = 0; k < h.target_point.size() && !coincide; ++k) coincide = h.target_point[k] != (uint32_t)k;
+      if (coincide) {
+        TRY(pl->upload(h.target_point, &pl->d_target_point));
+        TRY(pl->alloc((size_t)(h.n - h.n_src), &pl->y_points, true));
+      }
+      TRY(pl->alloc((size_t)n_targets, &pl->stage_y_targets, true));
+      HIP_TRY(hipDeviceSynchronize());
+    } catch (const std::bad_alloc&) {
+      return fail(FMMBEM_ERR_ALLOC, "host allocation failed while tabulating operators");
+    }
+    pl->hp.panels.vert.clear(); pl->hp.panels.vert.shrink_to_fit();
+  }
+  *out = pl.release();
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_target_info(const fmmbem_plan* plan, fmmbem_target_info* o) {
+  if (!plan || !o) return fail(FMMBEM_ERR_INVALID, "null argument");
+  if (!plan->targets) return fail(FMMBEM_ERR_INVALID, "not a plan over separate targets");
+  const HostPlan& h = plan->hp;
+  std::memset(o, 0, sizeof(*o));
+  o->n_panels = h.n_src;
+  o->n_targets = h.n_targets;
+  o->n_target_points = h.n - h.n_src;
+  o->n_source_boxes = (int64_t)h.src_box.size(); o->n_source_leaves = h.src_nleaves; o->n_source_levels = h.src_nlevels;
+  o->n_target_boxes = (int64_t)h.tgt_box.size(); o->n_target_leaves = h.tgt_nleaves; o->n_target_levels = h.tgt_nlevels;
+  o->tree_coder_levels = h.tree_levels_max;
+  return FMMBEM_OK;
+}
+
+// the boxes of one tree of a dual plan, in that tree's own BFS numbering; bodies counted from 0 in that tree
+static void dual_boxes(const HostPlan& h, bool tgt, double* center, double* side, int32_t* level, int32_t* is_leaf, int32_t* parent,
+                       int32_t* body_begin, int32_t* body_end) {
+  const std::vector<int>& map = tgt ? h.tgt_box : h.src_box;
+  std::vector<int> local((size_t)h.nboxes, -1);
+  for (size_t b = 0; b < map.size(); ++b) local[(size_t)map[b]] = (int)b;
+  const int64_t body0 = tgt ? h.n_src : 0;
+  for (size_t b = 0; b < map.size(); ++b) {
+    const int u = map[b];
+    if (center) std::memcpy(center + 3 * b, &h.box_center[3 * (size_t)u], sizeof(double) * 3);
+    if (side) side[b] = h.box_side[u];
+    if (level) level[b] = h.box_level[u];
+    if (is_leaf) is_leaf[b] = h.box_leaf[u];
+    if (parent) parent[b] = b == 0 ? 0 : local[(size_t)h.box_parent[u]];
+    if (body_begin) body_begin[b] = (int32_t)(h.box_body_begin[u] - body0);
+    if (body_end) body_end[b] = (int32_t)(h.box_body_end[u] - body0);
+  }
+}
+
+int fmmbem_plan_get_target_boxes(const fmmbem_plan* plan, double* center, double* side, int32_t* level, int32_t* is_leaf,
+                                 int32_t* parent, int32_t* body_begin, int32_t* body_end) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!plan->targets) return fail(FMMBEM_ERR_INVALID, "not a plan over separate targets");
+  dual_boxes(plan->hp, true, center, side, level, is_leaf, parent, body_begin, body_end);
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_get_target_perm(const fmmbem_plan* plan, uint32_t* tree_to_point, uint32_t* target_to_point) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!plan->targets) return fail(FMMBEM_ERR_INVALID, "not a plan over separate targets");
+  const HostPlan& h = plan->hp;
+  if (tree_to_point) std::memcpy(tree_to_point, h.perm.data() + h.n_src, sizeof(uint32_t) * (size_t)(h.n - h.n_src));
+  if (target_to_point) std::memcpy(target_to_point, h.target_point.data(), sizeof(uint32_t) * h.target_point.size());
+  return FMMBEM_OK;
+}
+
 int fmmbem_plan_create_like(const fmmbem_plan* base, const uint8_t* bc, fmmbem_plan** out) {
   if (!base || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
   *out = nullptr;
+  TRY(target_plan_only(base, "fmmbem_plan_create_like"));
   if (!base->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "fmmbem_plan_create_like: the base plan was built host-only");
   if (base->multi) return multi_like(*base, bc, out);
   return fmmbem_plan::like(*base, bc, out);
@@ -1793,6 +1975,7 @@ static int64_t active_slots(const fmmbem_plan* plan) {
 }
 
 int fmmbem_plan_exchange_doubles(const fmmbem_plan* plan, int p, size_t* per_shard) {
+  TRY(target_plan_only(plan, "fmmbem_plan_exchange_doubles"));
   if (!plan || !per_shard) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
@@ -1806,6 +1989,7 @@ int fmmbem_plan_exchange_doubles(const fmmbem_plan* plan, int p, size_t* per_sha
 }
 
 int fmmbem_plan_exchange_counts(const fmmbem_plan* plan, int p, int64_t* send_doubles, int64_t* recv_doubles) {
+  TRY(target_plan_only(plan, "fmmbem_plan_exchange_counts"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan || !send_doubles || !recv_doubles) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
@@ -1823,24 +2007,28 @@ int fmmbem_plan_exchange_counts(const fmmbem_plan* plan, int p, int64_t* send_do
 }
 
 int fmmbem_plan_upward_device(fmmbem_plan* plan, int p, const double* d_x, double* d_send, void* stream) {
+  TRY(target_plan_only(plan, "fmmbem_plan_upward_device"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   return plan->run(p, d_x, nullptr, static_cast<hipStream_t>(stream), false, 1, d_send);
 }
 
 int fmmbem_plan_downward_device(fmmbem_plan* plan, int p, const double* d_recv, double* d_y, void* stream) {
+  TRY(target_plan_only(plan, "fmmbem_plan_downward_device"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   return plan->run(p, nullptr, d_y, static_cast<hipStream_t>(stream), false, 2, const_cast<double*>(d_recv));
 }
 
 int fmmbem_plan_near_split_device(fmmbem_plan* plan, double* d_y, void* stream) {
+  TRY(target_plan_only(plan, "fmmbem_plan_near_split_device"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   return plan->run(plan->last_p > 0 ? plan->last_p : 1, nullptr, d_y, static_cast<hipStream_t>(stream), false, 3, nullptr);
 }
 
 int fmmbem_plan_shard_rows(const fmmbem_plan* plan, int64_t* cut) {
+  TRY(target_plan_only(plan, "fmmbem_plan_shard_rows"));
   if (!plan || !cut) return fail(FMMBEM_ERR_INVALID, "null argument");
   const HostPlan& h = plan->hp;
   std::vector<int> leaf_cut;
@@ -1851,6 +2039,7 @@ int fmmbem_plan_shard_rows(const fmmbem_plan* plan, int64_t* cut) {
 }
 
 int fmmbem_plan_set_result_slices(fmmbem_plan* plan, int enabled) {
+  TRY(target_plan_only(plan, "fmmbem_plan_set_result_slices"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   plan->result_slices = enabled != 0;
@@ -1858,6 +2047,7 @@ int fmmbem_plan_set_result_slices(fmmbem_plan* plan, int enabled) {
 }
 
 int fmmbem_plan_assemble_slices_device(fmmbem_plan* plan, const double* d_slices, size_t chunk_doubles, double* d_y, void* stream) {
+  TRY(target_plan_only(plan, "fmmbem_plan_assemble_slices_device"));
   if (!plan || !d_slices || !d_y) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   const int world = plan->hp.opt.shard_world;
@@ -1882,17 +2072,22 @@ int fmmbem_plan_near_device(fmmbem_plan* plan, const double* d_x, double* d_y, v
 
 int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!plan->on_device && plan->targets) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   if (!x || !y) return fail(FMMBEM_ERR_INVALID, "null vector");
   if (plan->result_slices)         // the owned rows in tree order at the head of y are only meaningful to the device-side all-gather
     return fail(FMMBEM_ERR_INVALID, "plan delivers result slices (fmmbem_plan_set_result_slices): use the device entry points");
   DEVICE_SCOPE(plan->opts.device);
   const size_t bytes = sizeof(double) * (size_t)plan->hp.n * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);
+  // a target plan: x over the panels, y over the targets
+  const size_t bytes_x = plan->targets ? sizeof(double) * (size_t)plan->hp.n_src : bytes;
+  const size_t bytes_y = plan->targets ? sizeof(double) * (size_t)plan->hp.n_targets : bytes;
+  double* sy = plan->targets ? plan->stage_y_targets : plan->stage_y;
   hipStream_t s = plan->own_stream;
-  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, bytes, hipMemcpyHostToDevice, s));
-  const int rc = plan->multi ? multi_execute_device(plan, p, plan->stage_x, plan->stage_y, s) : plan->run(p, plan->stage_x, plan->stage_y, s, false);
+  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, bytes_x, hipMemcpyHostToDevice, s));
+  const int rc = plan->multi ? multi_execute_device(plan, p, plan->stage_x, sy, s) : plan->run(p, plan->stage_x, sy, s, false);
   if (rc != FMMBEM_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(y, plan->stage_y, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(y, sy, bytes_y, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return FMMBEM_OK;
 }
@@ -1974,6 +2169,12 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
   o->expansions_active = (plan->has_bc[0] ? 1 : 0) | (plan->has_bc[1] ? 2 : 0);
   o->last_p = plan->last_p;
   o->build_host_ms = plan->build_host_ms; o->build_assemble_ms = plan->build_assemble_ms;
+  if (plan->targets) {                                 // the source tree's figures (the target tree's: fmmbem_plan_target_info)
+    o->n_panels = h.n_src;
+    o->n_boxes = (int64_t)h.src_box.size(); o->n_leaves = h.src_nleaves; o->n_levels = h.src_nlevels;
+    o->owned_leaf_begin = 0; o->owned_leaf_end = h.tgt_nleaves;
+    o->owned_row_begin = 0; o->owned_row_end = h.n - h.n_src;
+  }
   if (plan->on_device && plan->ev_count > 0) {
     // mean stage times over the recorded executes (waits for the recorded events)
     constexpr int NS = fmmbem_plan::kStages, NR = fmmbem_plan::kRing;
@@ -2013,7 +2214,7 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
 
 int fmmbem_plan_get_perm(const fmmbem_plan* plan, uint32_t* out) {
   if (!plan || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
-  std::memcpy(out, plan->hp.perm.data(), sizeof(uint32_t) * (size_t)plan->hp.n);
+  std::memcpy(out, plan->hp.perm.data(), sizeof(uint32_t) * (size_t)(plan->targets ? plan->hp.n_src : plan->hp.n));
   return FMMBEM_OK;
 }
 
@@ -2021,6 +2222,7 @@ int fmmbem_plan_get_boxes(const fmmbem_plan* plan, double* center, double* side,
                           int32_t* parent, int32_t* body_begin, int32_t* body_end) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   const HostPlan& h = plan->hp;
+  if (plan->targets) { dual_boxes(h, false, center, side, level, is_leaf, parent, body_begin, body_end); return FMMBEM_OK; }
   for (int b = 0; b < h.nboxes; ++b) {
     if (center) std::memcpy(center + 3 * b, &h.box_center[3 * b], sizeof(double) * 3);
     if (side) side[b] = h.box_side[b];
@@ -2037,20 +2239,29 @@ int fmmbem_plan_get_pairs(const fmmbem_plan* plan, int which, int32_t* out, int6
   if (!plan || !n) return fail(FMMBEM_ERR_INVALID, "null argument");
   const HostPlan& h = plan->hp;
   std::vector<int32_t> flat;
+  // a target plan: the boxes of a pair in their own tree's numbering (source box, target box), as fmmbem_plan_get_boxes /
+  // fmmbem_plan_get_target_boxes number them
+  std::vector<int> loc;
+  if (plan->targets) {
+    loc.assign((size_t)h.nboxes, -1);
+    for (size_t b = 0; b < h.src_box.size(); ++b) loc[(size_t)h.src_box[b]] = (int)b;
+    for (size_t b = 0; b < h.tgt_box.size(); ++b) loc[(size_t)h.tgt_box[b]] = (int)b;
+  }
+  auto L = [&](int b) { return loc.empty() ? b : loc[(size_t)b]; };
   switch (which) {
-    case 0: for (size_t i = 0; i < h.p2p_src.size(); ++i) { flat.push_back(h.p2p_src[i]); flat.push_back(h.p2p_tgt[i]); } break;
-    case 1: for (size_t i = 0; i < h.lr_src.size(); ++i) { flat.push_back(h.lr_src[i]); flat.push_back(h.lr_tgt[i]); } break;
+    case 0: for (size_t i = 0; i < h.p2p_src.size(); ++i) { flat.push_back(L(h.p2p_src[i])); flat.push_back(L(h.p2p_tgt[i])); } break;
+    case 1: for (size_t i = 0; i < h.lr_src.size(); ++i) { flat.push_back(L(h.lr_src[i])); flat.push_back(L(h.lr_tgt[i])); } break;
     case 2:
       for (int par : h.m2m_parents)
-        for (int c = h.box_child_begin[par]; c < h.box_child_end[par]; ++c) { flat.push_back(c); flat.push_back(par); }
+        for (int c = h.box_child_begin[par]; c < h.box_child_end[par]; ++c) { flat.push_back(L(c)); flat.push_back(L(par)); }
       break;
-    case 3: for (int c : h.l2l_children) { flat.push_back(h.box_parent[c]); flat.push_back(c); } break;
+    case 3: for (int c : h.l2l_children) { flat.push_back(L(h.box_parent[c])); flat.push_back(L(c)); } break;
     case 4:
       if (h.rot_alias) {
         for (int b = 0; b < h.nboxes; ++b)
-          for (int i = h.m2l_ptr[b]; i < h.m2l_ptr[b + 1]; ++i) { flat.push_back(h.m2l_src[i]); flat.push_back(b); }
+          for (int i = h.m2l_ptr[b]; i < h.m2l_ptr[b + 1]; ++i) { flat.push_back(L(h.m2l_src[i])); flat.push_back(L(b)); }
       } else
-        for (size_t i = 0; i < h.rot_src.size(); ++i) { flat.push_back(h.rot_src[i]); flat.push_back(h.rot_tgt[i]); }
+        for (size_t i = 0; i < h.rot_src.size(); ++i) { flat.push_back(L(h.rot_src[i])); flat.push_back(L(h.rot_tgt[i])); }
       break;
     case 5: for (size_t i = 0; i + 1 < h.rot_item_ptr.size(); ++i) { flat.push_back(h.rot_item_ptr[i]); flat.push_back(h.rot_item_ptr[i + 1]); } break;
     case 6: for (size_t i = 0; i + 1 < h.rot_item_ptr_long.size(); ++i) { flat.push_back(h.rot_item_ptr_long[i]); flat.push_back(h.rot_item_ptr_long[i + 1]); } break;
@@ -2062,6 +2273,7 @@ int fmmbem_plan_get_pairs(const fmmbem_plan* plan, int which, int32_t* out, int6
 }
 
 int fmmbem_plan_get_near_row(const fmmbem_plan* plan, int64_t row, uint32_t* cols, double* vals, int64_t* n) {
+  TRY(target_plan_only(plan, "fmmbem_plan_get_near_row"));
   if (!plan || !n) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (plan->multi) {
     const MultiDevice& m = *plan->multi;
@@ -2141,6 +2353,7 @@ int fmmbem_plan_get_near_row(const fmmbem_plan* plan, int64_t row, uint32_t* col
 }
 
 int fmmbem_plan_get_diagonal(const fmmbem_plan* plan, double* out) {
+  TRY(target_plan_only(plan, "fmmbem_plan_get_diagonal"));
   if (!plan || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (plan->multi) {                                   // every shard returns its own rows and zeros elsewhere
     const MultiDevice& m = *plan->multi;
@@ -2186,6 +2399,7 @@ int fmmbem_plan_get_diagonal(const fmmbem_plan* plan, double* out) {
 }
 
 int fmmbem_plan_get_expansions(const fmmbem_plan* plan, int which, int p, double* out) {
+  TRY(target_plan_only(plan, "fmmbem_plan_get_expansions"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "expansions live on the device");
@@ -2298,6 +2512,7 @@ int fmmbem_version(void) { return FMMBEM_VERSION; }
 // what the solver of krylov.hip needs to know about a plan; it reaches the matvec through the public entry point
 int fmmbem::plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, int* p_max, fmmbem::SolverWs*** slot) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  TRY(target_plan_only(plan, "fmmbem_gmres"));
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   if (!plan->multi && (plan->result_slices || plan->hp.opt.shard_world > 1))
     return fail(FMMBEM_ERR_UNSUPPORTED, "fmmbem_gmres runs on a whole operator; shards are driven by the caller's collectives (distributed.py)");

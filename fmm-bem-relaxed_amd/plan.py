@@ -290,10 +290,14 @@ class FMM_plan:
     panels: (N, 3, 3) triangle vertices (the arguments of Panel(p0, p1, p2)); bc: N boundary flags.
     p_max: largest order later set through kernel().set_p (defaults to K.P, or 16 if the caller
     intends to relax p upward).
+
+    targets: the reference's FMM_plan(K, sources, targets, opts) (include/FMM_plan.hpp:45-55) -- (M, 3) points, or (M, 3, 3)
+    triangles standing for their centroids; target_bc: M flags (default POTENTIAL).  execute then returns the M values
+    y_i = sum_j K(t_i, s_j) x_j, the target's flag picking G or dG/dn (fmmbem_plan_create_targets; Laplace only).
     """
 
     def __init__(self, K, panels, opts=None, bc=None, p_max=None, device=0, shard=(0, 1), host_only=False,
-                 shard_upward=False, devices=None, replicate_upward=False):
+                 shard_upward=False, devices=None, replicate_upward=False, targets=None, target_bc=None):
         opts = opts if opts is not None else FMMOptions()
         # executor/make_executor.hpp:24-60: lazy_evaluation wins, then local_evaluation, then block_diagonal; the
         # non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones
@@ -350,7 +354,28 @@ class FMM_plan:
                 raise ValueError("bc must have one flag per panel")
             bcp = bc.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        _capi.check(_capi.lib().fmmbem_plan_create(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), bcp, C.byref(h)))
+        self.n_targets = None
+        if targets is None:
+            if target_bc is not None:
+                raise ValueError("target_bc without targets")
+            _capi.check(_capi.lib().fmmbem_plan_create(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), bcp, C.byref(h)))
+        else:
+            t = np.asarray(targets, dtype=np.float64)
+            if t.ndim == 3 and t.shape[1:] == (3, 3):
+                t = (t[:, 0] + t[:, 1] + t[:, 2]) / 3          # a Panel target: its centre (LaplaceSphericalBEM.hpp:64-97)
+            if t.ndim != 2 or t.shape[1] != 3:
+                raise ValueError("targets must be (M, 3) points or (M, 3, 3) triangles")
+            t = np.ascontiguousarray(t)
+            tbcp = None
+            if target_bc is not None:
+                target_bc = np.ascontiguousarray(target_bc, dtype=np.uint8)
+                if target_bc.shape != (t.shape[0],):
+                    raise ValueError("target_bc must have one flag per target")
+                tbcp = target_bc.ctypes.data_as(C.c_void_p)
+            self._targets = (t, target_bc)                 # kept alive with the plan
+            _capi.check(_capi.lib().fmmbem_plan_create_targets(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), bcp, t.shape[0],
+                                                               t.ctypes.data_as(C.c_void_p), tbcp, C.byref(h)))
+            self.n_targets = t.shape[0]
         self._h = h
 
     def like(self, bc, K=None):
@@ -386,7 +411,7 @@ class FMM_plan:
         want = (self.n,) if self.dof == 1 else (self.n, self.dof)
         if x.shape != want:
             raise ValueError("charges must have shape %r" % (want,))
-        y = np.empty(want)
+        y = np.empty(want if self.n_targets is None else (self.n_targets,))
         _capi.check(_capi.lib().fmmbem_plan_execute(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
                                                     y.ctypes.data_as(C.c_void_p)))
         return y
@@ -449,7 +474,7 @@ class FMM_plan:
         if x.device.index != self.device:
             raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
         if out is None:
-            out = torch.empty_like(x)
+            out = torch.empty_like(x) if self.n_targets is None else x.new_empty(self.n_targets)
         self.execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
@@ -481,6 +506,30 @@ class FMM_plan:
         _capi.check(_capi.lib().fmmbem_plan_get_boxes(self._h, *[d[k].ctypes.data_as(C.c_void_p) for k in
                                                                  ("center", "side", "level", "leaf", "parent", "bb", "be")]))
         return d
+
+    def target_info(self):
+        """A plan over separate targets: counts of both trees (fmmbem_plan_target_info)."""
+        s = _capi.TargetInfo()
+        _capi.check(_capi.lib().fmmbem_plan_target_info(self._h, C.byref(s)))
+        return s.as_dict()
+
+    def target_boxes(self):
+        """The target tree's boxes, as boxes() gives the source tree's."""
+        nb = self.target_info()["n_target_boxes"]
+        d = dict(center=np.empty((nb, 3)), side=np.empty(nb))
+        for k in ("level", "leaf", "parent", "bb", "be"):
+            d[k] = np.empty(nb, dtype=np.int32)
+        _capi.check(_capi.lib().fmmbem_plan_get_target_boxes(self._h, *[d[k].ctypes.data_as(C.c_void_p) for k in
+                                                                        ("center", "side", "level", "leaf", "parent", "bb", "be")]))
+        return d
+
+    def target_perm(self):
+        """(target-tree position -> distinct point, given target -> distinct point)"""
+        info = self.target_info()
+        tree = np.empty(info["n_target_points"], dtype=np.uint32)
+        given = np.empty(info["n_targets"], dtype=np.uint32)
+        _capi.check(_capi.lib().fmmbem_plan_get_target_perm(self._h, tree.ctypes.data_as(C.c_void_p), given.ctypes.data_as(C.c_void_p)))
+        return tree, given
 
     def pairs(self, which):
         idx = {"p2p": 0, "m2l": 1, "m2m": 2, "l2l": 3, "m2l_work": 4, "m2l_items": 5, "m2l_items_long": 6}[which]

@@ -169,6 +169,35 @@ int fmmbem_plan_create(const fmmbem_options *opts, size_t n_panels, const double
  * instead of 0.28 s at N = 1M.  fmmbem_plan_create does the same on its own when it is handed the vertices and options of a live
  * plan (recognised by two 64-bit hashes of the vertex bytes; FMMBEM_PLAN_SHARE=0 disables that). */
 int fmmbem_plan_create_like(const fmmbem_plan *base, const uint8_t *bc, fmmbem_plan **out);
+/* FMM_plan(const Kernel&, const std::vector<source_type>&, const std::vector<target_type>&, FMMOptions&)  (FMM_plan.hpp:45-55):
+ * a plan whose targets are POINTS of their own.  An execute computes y_i = sum_j K(t_i, s_j) x_j, K of
+ * LaplaceSphericalBEM::operator() (kernel/LaplaceSphericalBEM.hpp:273-297): the target's flag picks the integral of G or of
+ * dG/dn over the source panel (its normal), whatever the panels' flags -- what Direct::matvec(K, panels, x, targets) computes
+ * (the exterior potential of the drivers, examples/LaplaceBEM.cpp:346-369).  target_points: n_targets x 3; target_bc: n_targets
+ * flags or NULL (all POTENTIAL); bc (the panels' flags) does not enter and may be NULL.  Coincident targets are legal.
+ * x of fmmbem_plan_execute / _execute_device has n_panels entries, y n_targets, both in the caller's order.
+ * Laplace, the FMM evaluator, sparse_local = 1, shard_world = 1, one device and l2l_rule COMPLETE only (FMMBEM_ERR_UNSUPPORTED
+ * otherwise); near_stream_fraction is taken as 1.  fmmbem_plan_set_timing, _stats (the SOURCE tree's figures), _get_perm (the
+ * panels' permutation), _get_boxes (the source tree), _get_pairs (source box, target box: each in its own tree's numbering),
+ * _set_graphs and _destroy take the handle; the calls of whole operators (GMRES, create_like, the sharded and slice calls,
+ * near_split, get_near_row, get_diagonal, get_expansions) return FMMBEM_ERR_UNSUPPORTED and leave it usable. */
+int fmmbem_plan_create_targets(const fmmbem_options *opts, size_t n_panels, const double *vertices, const uint8_t *bc,
+                               size_t n_targets, const double *target_points, const uint8_t *target_bc, fmmbem_plan **out);
+typedef struct {
+  int64_t n_panels, n_targets;
+  int64_t n_target_points;          /* distinct (point, flag) pairs: the bodies of the target tree                      */
+  int64_t n_source_boxes, n_source_leaves, n_source_levels;
+  int64_t n_target_boxes, n_target_leaves, n_target_levels;
+  int32_t tree_coder_levels;        /* 10 or 21, the same for both trees                                                */
+  int32_t reserved;
+} fmmbem_target_info;
+int fmmbem_plan_target_info(const fmmbem_plan *plan, fmmbem_target_info *out);
+/* The target tree's boxes in its BFS order (as fmmbem_plan_get_boxes; bodies = target-tree positions of the distinct points) */
+int fmmbem_plan_get_target_boxes(const fmmbem_plan *plan, double *center, double *side, int32_t *level, int32_t *is_leaf,
+                                 int32_t *parent, int32_t *body_begin, int32_t *body_end);
+/* tree_to_point: n_target_points, target-tree position -> distinct point; target_to_point: n_targets, given target -> distinct
+ * point.  Either may be NULL. */
+int fmmbem_plan_get_target_perm(const fmmbem_plan *plan, uint32_t *tree_to_point, uint32_t *target_to_point);
 void fmmbem_plan_destroy(fmmbem_plan *plan);
 
 /* ---- the hot path ----------------------------------------------------------------------- */

@@ -518,6 +518,22 @@ class PlanAdapter {
     K.device = device;
     create(p_max > 0 ? p_max : K.p());
   }
+  // FMM_plan(K, sources, targets, opts) of include/FMM_plan.hpp:45-55: execute(charges) returns targets.size() results,
+  // result i = sum_j K(targets[i], sources[j]) charges[j] -- a target's centre and BC are what count (G or dG/dn over the source
+  // panel, kernel/LaplaceSphericalBEM.hpp:273-297), the same sum as Direct::matvec(K, sources..., charges..., targets...).
+  // Laplace only (Stokes throws Error(FMMBEM_ERR_UNSUPPORTED)); the near field is always assembled (fmmbem_plan_create_targets).
+  PlanAdapter(const kernel_type& k, const std::vector<source_type>& source, const std::vector<target_type>& targets, FMMOptions& opts,
+              int p_max = 0, int device = 0)
+      : K(k), opts_(opts), sources_(source), n_(source.size()), device_(device), has_targets_(true) {
+    K.device = device;
+    points_.reserve(3 * targets.size());
+    target_bc_.reserve(targets.size());
+    for (const target_type& t : targets) {
+      for (int c = 0; c < 3; ++c) points_.push_back(t.center[c]);
+      target_bc_.push_back(t.BC == target_type::BC1);
+    }
+    create(p_max > 0 ? p_max : K.p());
+  }
   ~PlanAdapter() { fmmbem_plan_destroy(plan_); }
   PlanAdapter(const PlanAdapter&) = delete;
   PlanAdapter& operator=(const PlanAdapter&) = delete;
@@ -528,7 +544,7 @@ class PlanAdapter {
 
   std::vector<result_type> execute(const std::vector<charge_type>& charges) {
     if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
-    std::vector<result_type> results(charges.size());
+    std::vector<result_type> results(has_targets_ ? target_bc_.size() : charges.size());
     if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as set_p does
     check(fmmbem_plan_execute(plan_, K.p(), KernelBinding<Kernel>::in(charges), KernelBinding<Kernel>::out(results)));
     return results;
@@ -576,7 +592,12 @@ class PlanAdapter {
     o.near_stream_fraction = opts_.near_stream_fraction;
     sparse_ = o.sparse_local != 0;
     fmmbem_plan* fresh = nullptr;
-    check(fmmbem_plan_create(&o, n_, v.data(), bc.data(), &fresh));
+    if (has_targets_) {
+      o.sparse_local = 1;                                    // a target plan assembles its near field (the same sums)
+      check(fmmbem_plan_create_targets(&o, n_, v.data(), bc.data(), target_bc_.size(), points_.data(), target_bc_.data(), &fresh));
+    } else {
+      check(fmmbem_plan_create(&o, n_, v.data(), bc.data(), &fresh));
+    }
     if (plan_) fmmbem_plan_destroy(plan_);
     plan_ = fresh;
     p_max_ = p_max;
@@ -587,7 +608,7 @@ class PlanAdapter {
     std::vector<uint32_t> perm(n_);
     check(fmmbem_plan_get_perm(plan_, perm.data()));
     std::vector<double> diag;
-    if (sparse_ && std::is_same<charge_type, double>::value) {
+    if (sparse_ && !has_targets_ && std::is_same<charge_type, double>::value) {
       diag.resize(n_);
       check(fmmbem_plan_get_diagonal(plan_, diag.data()));
     }
@@ -604,6 +625,9 @@ class PlanAdapter {
   size_t n_;
   int device_ = 0, p_max_ = 0;
   bool sparse_ = false;
+  bool has_targets_ = false;
+  std::vector<double> points_;                              // the targets' centres, n_targets x 3
+  std::vector<uint8_t> target_bc_;
   fmmbem_plan* plan_ = nullptr;
 };
 
