@@ -99,6 +99,7 @@ SYMBOLS = (
     "fmmbem_version", "fmmbem_plan_create_like", "fmmbem_host_register", "fmmbem_host_unregister", "fmmbem_solver_options_default", "fmmbem_gmres_device", "fmmbem_gmres",
     "fmmbem_ops_create", "fmmbem_ops_destroy", "fmmbem_ops_slots", "fmmbem_ops_p2m", "fmmbem_ops_m2m", "fmmbem_ops_m2l", "fmmbem_ops_l2l", "fmmbem_ops_l2p",
     "fmmbem_plan_create_targets", "fmmbem_plan_target_info", "fmmbem_plan_get_target_boxes", "fmmbem_plan_get_target_perm",
+    "fmmbem_plan_execute_batch", "fmmbem_plan_execute_batch_device", "fmmbem_plan_batch_width",
 )
 
 
@@ -127,6 +128,9 @@ def lib():
     L.fmmbem_plan_execute.argtypes = [vp, i32, vp, vp]
     L.fmmbem_plan_execute_device.argtypes = [vp, i32, vp, vp, vp]
     L.fmmbem_plan_near_device.argtypes = [vp, vp, vp, vp]
+    L.fmmbem_plan_execute_batch.argtypes = [vp, i32, i32, vp, C.c_size_t, vp, C.c_size_t]
+    L.fmmbem_plan_execute_batch_device.argtypes = [vp, i32, i32, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.fmmbem_plan_batch_width.argtypes = [vp, C.POINTER(i32)]
     L.fmmbem_plan_near_split_device.argtypes = [vp, vp, vp]
     L.fmmbem_plan_exchange_doubles.argtypes = [vp, i32, C.POINTER(C.c_size_t)]
     L.fmmbem_plan_exchange_counts.argtypes = [vp, i32, vp, vp]

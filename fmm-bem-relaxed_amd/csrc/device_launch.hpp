@@ -59,5 +59,21 @@ hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);
 
+// ---- batched execute (fmmbem_plan_execute_batch): one pass over the near matrix / the P2M tables for nv vectors ----
+constexpr int kBatchMax = 8;                           // most vectors of one pass
+struct BatchVecs {                                     // per vector of the pass: tree-order x and y, its multipole set
+  double* xt[kBatchMax];
+  double* yt[kBatchMax];
+  double2* M[kBatchMax];
+  int nv;                                              // vectors of this pass; the kernels may also run slots nv .. width-1 (scratch)
+  int width;                                           // slots allocated: 2, 4 or 8
+};
+// the pipelined one-unknown SpMV (near_spmv_pipe_kernel) for nv vectors: bit for bit nv calls of launch_near_spmv; plans where
+// launch_near_spmv takes that kernel only (batch_near_ok)
+bool batch_near_ok(const DevicePlan& d);
+hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s);
+// P2M for nv vectors: the streaming kernel once where launch_p2m streams (one live slot, p >= 8), else launch_p2m per vector
+hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s);
+
 
 }  // namespace fmmbem

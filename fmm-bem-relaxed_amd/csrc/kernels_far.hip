@@ -686,6 +686,85 @@ __global__ __launch_bounds__(4 * kWave) void p2m_stream_kernel(DevicePlan d, con
   }
 }
 
+// p2m_stream_kernel for NV charge vectors (fmmbem_plan_execute_batch): every table entry is loaded once and feeds the moments of
+// all NV vectors; each vector's moments are summed in panel order with the single kernel's FMAs, so each multipole set is bit
+// for bit what p2m_stream_kernel writes for that vector.  The charges come through the scalar cache as there.
+template <int NV>
+__global__ __launch_bounds__(4 * kWave) void p2m_stream_multi_kernel(DevicePlan d, const int P, BatchVecs bv) {
+  constexpr int U = kP2MStream;
+  const int S = P * (P + 1) / 2, SM = d.s_max, TS = d.p2m_stride;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const double2* __restrict__ tab = d.p2m_tab - (size_t)d.p2m_tab_row0 * TS;
+  const ConstInt* leaf_of = as_const_space<ConstInt>(d.p2m_leaf);
+  const ConstInt* box_of = as_const_space<ConstInt>(d.leaf_box);
+  const ConstInt* row0_of = as_const_space<ConstInt>(d.leaf_row0);
+  const ConstInt* nrows_of = as_const_space<ConstInt>(d.leaf_nrows);
+  const int slot = d.act[0], stride = gridDim.x * 4, n = d.n_p2m;
+  int tslot[2], st0[2], st1[2];                        // as p2m_stream_kernel
+  {
+    const int nb = d.p2m_packed ? P * (P - 1) / 2 : S, items = d.p2m_packed ? nb + (P + 1) / 2 : S;
+    for (int it = 0; it < 2; ++it) {
+      const int item = lane + it * kWave;
+      tslot[it] = -1; st0[it] = 0; st1[it] = -2;
+      if (item >= items) continue;
+      if (!d.p2m_packed) { tslot[it] = item; st0[it] = item; }
+      else if (item < nb) {
+        int cn = 1;
+        while (cn * (cn + 1) / 2 <= item) ++cn;
+        tslot[it] = item; st0[it] = item + cn + 1;
+      } else {
+        const int k = item - nb;
+        tslot[it] = d.p2m_real_off + k;
+        st0[it] = (2 * k) * (2 * k + 1) / 2;
+        st1[it] = 2 * k + 1 < P ? (2 * k + 1) * (2 * k + 2) / 2 : -1;
+      }
+    }
+  }
+  int li = blockIdx.x * 4 + wv;
+  if (li >= n) return;
+  int leaf = leaf_of[li];
+  int box = box_of[leaf], row0 = row0_of[leaf], nrows = nrows_of[leaf];
+  for (; li < n; li += stride) {
+    const int nl = li + stride < n ? li + stride : li;
+    const int nleaf = leaf_of[nl];
+    const int nbox = box_of[nleaf], nrow0 = row0_of[nleaf], nnrows = nrows_of[nleaf];
+    for (int it = 0; it < 2; ++it) {
+      if (tslot[it] < 0) break;
+      double2 m[NV];
+#pragma unroll
+      for (int v = 0; v < NV; ++v) m[v] = double2{0, 0};
+      for (int r = 0; r < nrows; r += U) {
+        tvec2 t[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          t[u] = tvec2{0, 0};
+          if (r + u < nrows) t[u] = __builtin_nontemporal_load(reinterpret_cast<const tvec2*>(tab + (size_t)((int64_t)row0 + r + u) * TS + tslot[it]));
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          const ConstDouble* xt = as_const_space<ConstDouble>(bv.xt[v]);
+          double x[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) x[u] = r + u < nrows ? xt[(int64_t)row0 + r + u] : 0.0;
+#pragma unroll
+          for (int u = 0; u < U; ++u) { m[v].x = fma(x[u], t[u].x, m[v].x); m[v].y = fma(x[u], t[u].y, m[v].y); }
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        double2* Mb = bv.M[v] + ((size_t)box * d.nslots + slot) * SM;
+        if (st1[it] == -2) Mb[st0[it]] = m[v];
+        else {
+          Mb[st0[it]] = double2{m[v].x, 0.0};
+          if (st1[it] >= 0) Mb[st1[it]] = double2{m[v].y, 0.0};
+        }
+      }
+    }
+    leaf = nleaf; box = nbox; row0 = nrow0; nrows = nnrows;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // M2M, one tree level per launch.  A workgroup = kShiftWaves wavefronts takes one parent box; wavefront w
 // translates child w (children are the <= 8 occupied octants) with the precomputed sparse operator
@@ -1164,6 +1243,33 @@ hipError_t launch_p2m(const DevicePlan& d, int p, hipStream_t s) {
     if (d.act[a] == 0) hipLaunchKernelGGL((p2m_kernel<0>), g, b, 0, s, d, p, 0, 0);
     else hipLaunchKernelGGL((p2m_kernel<1>), g, b, 0, s, d, p, 0, 1);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s) {
+  if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
+  if (b.nv < 1 || b.nv > b.width || b.width > kBatchMax) return hipErrorInvalidValue;
+  if (d.n_p2m <= 0) return hipSuccess;
+  if (p < 1 || p > kPmaxDev) return hipErrorInvalidValue;
+  const char* se = std::getenv("FMMBEM_P2M_STREAM");
+  const bool stream_off = se && std::atoi(se) == 0;
+  // exactly the case in which launch_p2m takes p2m_stream_kernel; elsewhere its own choice, once per vector
+  if (b.nv == 1 || !d.p2m_tab || d.n_act != 1 || p * (p + 1) / 2 <= kWave / 2 || stream_off) {
+    for (int j = 0; j < b.nv; ++j) {
+      DevicePlan dj = d;
+      dj.xt = b.xt[j]; dj.M = b.M[j];
+      if (hipError_t e = launch_p2m(dj, p, s); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  // the kernel for 2, 4 or 8 vectors; slots nv .. of a short pass are the batch's scratch and their moments are never read
+  const int nv = b.nv <= 2 ? 2 : b.nv <= 4 ? 4 : 8;
+  if (nv > b.width) return hipErrorInvalidValue;
+  const int nb = (d.n_p2m + 3) / 4;
+  const dim3 g(nb < 256 * 8 ? nb : 256 * 8), t(4 * kWave);
+  if (nv == 2) hipLaunchKernelGGL(p2m_stream_multi_kernel<2>, g, t, 0, s, d, p, b);
+  else if (nv == 4) hipLaunchKernelGGL(p2m_stream_multi_kernel<4>, g, t, 0, s, d, p, b);
+  else hipLaunchKernelGGL(p2m_stream_multi_kernel<8>, g, t, 0, s, d, p, b);
   return hipGetLastError();
 }
 

@@ -1279,6 +1279,174 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_pipe_k
   spmv_pipe_run<kRows, kVecs>(d, xs_all, part, blockIdx.x, gridDim.x, d.near_rec ? d.near_nitems_stream : d.near_nitems);
 }
 
+// ---------------------------------------------------------------------------------------------
+// near_spmv for NV vectors in one pass over the matrix (fmmbem_plan_execute_batch): the items, records, run descriptors and
+// pipelining of spmv_pipe_run, with every nontemporal 16-byte matrix load feeding the FMAs of all NV vectors.  Each vector's
+// row sums are formed exactly as near_spmv_pipe_kernel forms them -- chunks of kSpmvPipeChunk columns with a later chunk added
+// into y; the colsplit segments and the fixed sum of their parts; lane l taking the 16-byte column vectors v0 + l + 64 j in
+// increasing j; fma(v.x, x.x, fma(v.y, x.y, acc)); wave_sum -- so every result is bit for bit the single kernel's.
+// LDS: xs_all [2][NV][kSpmvPipeChunk] doubles (one vector's chunk contiguous: the lanes read it as the single kernel does, free
+// of bank conflicts), then runbuf [2][2][max_runs] ints; part [NV][kSpmvWaves][kColRows].  16 KiB of x per vector: NV = 2, 4, 8
+// leave 4, 2, 1 workgroups per CU, so the loads in flight come from kRows x kVecs per wavefront (launch_near_spmv_multi).
+// ---------------------------------------------------------------------------------------------
+constexpr int batch_occ(int nv) { return nv <= 2 ? 4 : nv <= 4 ? 2 : 1; }
+
+template <int kRows, int kVecs, int NV>
+__global__ __launch_bounds__(kSpmvWaves * kWave, batch_occ(NV)) void near_spmv_pipe_multi_kernel(DevicePlan d, BatchVecs bv) {
+  extern __shared__ double xs_all[];
+  __shared__ double part[NV][kSpmvWaves][kColRows];
+  constexpr int XB = NV * kSpmvPipeChunk;             // doubles of one x buffer (all vectors)
+  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * XB);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int mr = d.max_runs, nitems = d.near_nitems, tid = threadIdx.x;
+  const int step = gridDim.x;
+  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(d.near_recs));
+
+  int item = blockIdx.x;
+  if (item >= nitems) return;
+  NearItem it = load_item(recs + item);
+  NearItem nx = load_item(recs + (item + step < nitems ? item + step : nitems - 1));
+  for (int i = tid; i < it.nruns; i += blockDim.x) { runbuf[i] = d.near_run_row0[it.run_begin + i]; runbuf[mr + i] = d.near_run_off[it.run_begin + i]; }
+  for (int i = tid; i < nx.nruns; i += blockDim.x) { runbuf[2 * mr + i] = d.near_run_row0[nx.run_begin + i]; runbuf[3 * mr + i] = d.near_run_off[nx.run_begin + i]; }
+  __syncthreads();
+  {
+    const Runs runs{runbuf, runbuf + mr, it.nruns};
+    const int cw = it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk;
+    for (int c = tid; c < cw; c += blockDim.x) {
+      const bool in = c < it.ncols;
+      const int row = in ? column_to_row(runs, c) : 0;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) xs_all[v * kSpmvPipeChunk + c] = in ? bv.xt[v][row] : 0.0;
+    }
+  }
+  __syncthreads();
+  int xb = 0, rb = 0;
+  for (;; item += step) {
+    const bool more = item + step < nitems;
+    const int i2 = item + 2 * step;
+    const NearItem nn = load_item(recs + (i2 < nitems ? i2 : nitems - 1));
+    // ---- set-up of the following items, in flight while this item's rows stream ----
+    double px[NV][kSpmvPre];
+    int pr0 = 0, pr1 = 0;
+    const bool prun = i2 < nitems && tid < nn.nruns;
+    if (more) {
+      const Runs nruns{runbuf + (rb ^ 1) * 2 * mr, runbuf + (rb ^ 1) * 2 * mr + mr, nx.nruns};
+      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
+#pragma unroll
+      for (int u = 0; u < kSpmvPre; ++u) {
+        const int c = tid + u * (kSpmvWaves * kWave);
+        const bool in = c < ncw && c < nx.ncols;
+        const int row = in ? column_to_row(nruns, c) : 0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) px[v][u] = in ? bv.xt[v][row] : 0.0;
+      }
+      if (prun) { pr0 = d.near_run_row0[nn.run_begin + tid]; pr1 = d.near_run_off[nn.run_begin + tid]; }
+    }
+    // ---- this item ----
+    const int nrows = it.nrows, ncols = it.ncols, stride = it.stride;
+    const bool colsplit = it.colsplit != 0;
+    const double* blk = d.near_val + it.val_off;
+    double* xs = xs_all + xb * XB;
+    const Runs runs{runbuf + rb * 2 * mr, runbuf + rb * 2 * mr + mr, it.nruns};
+    for (int c0 = 0; c0 < stride; c0 += kSpmvPipeChunk) {
+      const int cw = stride - c0 < kSpmvPipeChunk ? stride - c0 : kSpmvPipeChunk;
+      if (c0) {                                       // further chunks of a wide leaf: staged in place
+        __syncthreads();
+        for (int c = tid; c < cw; c += blockDim.x) {
+          const bool in = c0 + c < ncols;
+          const int row = in ? column_to_row(runs, c0 + c) : 0;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) xs[v * kSpmvPipeChunk + c] = in ? bv.xt[v][row] : 0.0;
+        }
+        __syncthreads();
+      }
+      const int nvec = cw >> 1;
+      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
+      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
+      const int rstep = colsplit ? 1 : kSpmvWaves;
+      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
+        const dvec2* row[kRows];
+        double acc[NV][kRows];
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int ri = r + i * rstep;
+          row[i] = reinterpret_cast<const dvec2*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
+#pragma unroll
+          for (int v = 0; v < NV; ++v) acc[v][i] = 0;
+        }
+        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
+          dvec2 a[kRows][kVecs];
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            const bool ok = cc < v1;
+#pragma unroll
+            for (int i = 0; i < kRows; ++i) a[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : dvec2{0, 0};
+          }
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            if (cc < v1) {
+#pragma unroll
+              for (int v = 0; v < NV; ++v) {
+                const dvec2 x2 = reinterpret_cast<const dvec2*>(xs + v * kSpmvPipeChunk)[cc];
+#pragma unroll
+                for (int i = 0; i < kRows; ++i) acc[v][i] = fma(a[i][u].x, x2.x, fma(a[i][u].y, x2.y, acc[v][i]));
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int i = 0; i < kRows; ++i) acc[v][i] = wave_sum(acc[v][i]);
+        if (lane == 0) {
+#pragma unroll
+          for (int i = 0; i < kRows; ++i) {
+            const int ri = r + i * rstep;
+            if (ri < nrows) {
+#pragma unroll
+              for (int v = 0; v < NV; ++v) {
+                double* yt = bv.yt[v] + it.yrow;
+                if (colsplit) part[v][wave][ri] = acc[v][i];
+                else yt[ri] = c0 ? yt[ri] + acc[v][i] : acc[v][i];
+              }
+            }
+          }
+        }
+      }
+      if (colsplit) {
+        __syncthreads();
+        if (tid < nrows) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            double* yt = bv.yt[v] + it.yrow;
+            const double sum = ((part[v][0][tid] + part[v][1][tid]) + part[v][2][tid]) + part[v][3][tid];
+            yt[tid] = c0 ? yt[tid] + sum : sum;
+          }
+        }
+      }
+    }
+    if (!more) break;
+    // ---- hand over: next item's x and the item after's runs into the halves nobody reads now ----
+    {
+      double* xn = xs_all + (xb ^ 1) * XB;
+      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
+#pragma unroll
+      for (int u = 0; u < kSpmvPre; ++u) {
+        const int c = tid + u * (kSpmvWaves * kWave);
+        if (c < ncw) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) xn[v * kSpmvPipeChunk + c] = px[v][u];
+        }
+      }
+    }
+    if (prun) { runbuf[rb * 2 * mr + tid] = pr0; runbuf[rb * 2 * mr + mr + tid] = pr1; }
+    __syncthreads();
+    it = nx; nx = nn; xb ^= 1; rb ^= 1;
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -2115,6 +2283,42 @@ hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s) {
   } else {
     hipLaunchKernelGGL((near_spmv_kernel<2, 4>), g, b, lds, s, d);
   }
+  return hipGetLastError();
+}
+
+bool batch_near_ok(const DevicePlan& d) { return !d.near_rec && d.dof == 1 && d.max_runs <= kSpmvWaves * kWave; }
+
+// One pass over the matrix for b.nv vectors; a pass of one vector is launch_near_spmv itself.  The kernel is instantiated for 2,
+// 4 and 8 vectors; a pass of 3 runs the 4-vector kernel, the fourth slot being scratch of the batch buffers.
+// Shape (rows x 16-byte loads in flight per wavefront; FMMBEM_BATCH_SHAPE 0 / 1 / 2 = 2x4 / 2x8 / 4x4 for sweeps), N = 1M,
+// tools/batch_time.py (profiles/r06b_batch_time.txt), ms per 4-vector pass: 2x4 1.46, 2x8 1.50, 4x4 1.60; 2 vectors 2x4 0.80;
+// 8 vectors 2x4 3.8.  The 4-vector pass is issue-bound at two workgroups per CU (2.8 TB/s effective), yet the cheapest per vector.
+hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s) {
+  if (!batch_near_ok(d) || b.nv < 1 || b.nv > b.width || b.width > kBatchMax) return hipErrorInvalidValue;
+  if (b.nv == 1) {
+    DevicePlan d1 = d;
+    d1.xt = b.xt[0]; d1.yt = b.yt[0];
+    return launch_near_spmv(d1, s);
+  }
+  if (d.near_nitems <= 0) return hipSuccess;
+  const int nv = b.nv <= 2 ? 2 : b.nv <= 4 ? 4 : 8;
+  if (nv > b.width) return hipErrorInvalidValue;
+  static const int shape = [] { const char* e = std::getenv("FMMBEM_BATCH_SHAPE"); return e ? std::atoi(e) : 0; }();
+  const size_t lds = 2 * (size_t)nv * kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
+  const dim3 g(std::min(d.near_nitems, 256 * (nv == 2 ? batch_occ(2) : nv == 4 ? batch_occ(4) : batch_occ(8)))), t(kSpmvWaves * kWave);
+#define BATCH_NEAR(R, V, NV)                                                                                                         \
+  {                                                                                                                                  \
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(near_spmv_pipe_multi_kernel<R, V, NV>),        \
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                     \
+    if (attr != hipSuccess) return attr;                                                                                             \
+    hipLaunchKernelGGL((near_spmv_pipe_multi_kernel<R, V, NV>), g, t, lds, s, d, b);                                                 \
+  }
+#define BATCH_SHAPES(NV) \
+  if (shape == 1) BATCH_NEAR(2, 8, NV) else if (shape == 2) BATCH_NEAR(4, 4, NV) else BATCH_NEAR(2, 4, NV)
+  if (nv == 2) BATCH_NEAR(2, 4, 2)                    // 2x8 and 4x4 spill at the 128 VGPRs of four workgroups per CU
+  else if (nv == 4) BATCH_SHAPES(4) else BATCH_SHAPES(8)
+#undef BATCH_SHAPES
+#undef BATCH_NEAR
   return hipGetLastError();
 }
 

@@ -289,6 +289,20 @@ struct fmmbem_plan {
   static int like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc, fmmbem_plan** out);
   // phase 0: whole matvec; 1: upward half (gather, P2M, M2M of owned boxes, pack -> xbuf); 2: the rest (xbuf = gathered)
   int run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, int phase = 0, double* xbuf = nullptr);
+  // Batched execute (fmmbem_plan_execute_batch).  Per vector of a pass: tree-order x and y, one multipole set, and a copy of d
+  // pointing at them in device memory (the double-sum M2L reads the plan from there); allocated at the first batch call, kept
+  // until destroy.  L, Mh and the target plans' y_points are shared: the vectors run the far field one after another.
+  struct BatchBufs {
+    int width = 0;                                             // 0: not allocated
+    double* xt[kBatchMax] = {};
+    double* yt[kBatchMax] = {};
+    double2* M[kBatchMax] = {};
+    DevicePlan* dev[kBatchMax] = {};
+  };
+  BatchBufs bat;
+  int batch_width() const;                                     // > 1: the fast path (one near-field pass for several vectors)
+  int batch_alloc(hipStream_t s);
+  int run_batch(int p, int k, const double* x, size_t ldx, double* y, size_t ldy, hipStream_t s, bool host);
   ~fmmbem_plan() {
     if (solver_ws) fmmbem::solver_ws_destroy(solver_ws);
     if (on_device) {
@@ -1357,6 +1371,151 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   return FMMBEM_OK;
 }
 
+// ======================================= batched execute =======================================
+// Vectors per near-field pass on the fast path (FMMBEM_BATCH_NV = 2, 4 or 8 for sweeps).  ms per vector at N = 1M, k = 4 / 8,
+// p = 10 and 2 (tools/batch_time.py, profiles/r06b_batch_time.txt): 2 -> 1.24, 0.59; 4 -> 1.16, 0.56; 8 -> 1.29, 0.67.
+static int batch_nv() {
+  static const int nv = [] {
+    const char* e = std::getenv("FMMBEM_BATCH_NV");
+    const int v = e ? std::atoi(e) : 4;
+    return v == 2 || v == 8 ? v : 4;
+  }();
+  return nv;
+}
+
+// the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch)
+int fmmbem_plan::batch_width() const {
+  const bool fast = on_device && !multi && opts.kernel != FMMBEM_KERNEL_STOKES_BEM && opts.sparse_local && !hybrid &&
+                    hp.opt.shard_world <= 1 && !split_upward && !result_slices && batch_near_ok(d);
+  return !fast ? 1 : bat.width ? bat.width : batch_nv();
+}
+
+// all or nothing: a failed allocation leaves the plan as it was (FMMBEM_ERR_ALLOC; single executes are unaffected)
+int fmmbem_plan::batch_alloc(hipStream_t s) {
+  if (bat.width) return FMMBEM_OK;
+  const int w = batch_nv();
+  const size_t nt = (size_t)hp.n * d.dof, nm = (size_t)hp.nboxes * d.nslots * d.s_max;
+  BatchBufs b;
+  std::vector<void*> got;
+  auto get = [&](size_t bytes, auto** out) -> bool {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(bytes, 1)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    got.push_back(q);
+    *out = static_cast<std::remove_pointer_t<decltype(out)>>(q);
+    return true;
+  };
+  bool ok = true;
+  for (int j = 0; j < w && ok; ++j)
+    ok = get(nt * sizeof(double), &b.xt[j]) && get(nt * sizeof(double), &b.yt[j]) && get(nm * sizeof(double2), &b.M[j]) &&
+         get(sizeof(DevicePlan), &b.dev[j]);
+  for (int j = 0; j < w && ok; ++j) {
+    // zero as the plan's own x_tree, y_tree and M (a target plan's x rows of the targets stay 0); on `s`, ahead of the batch
+    ok = hipMemsetAsync(b.xt[j], 0, nt * sizeof(double), s) == hipSuccess && hipMemsetAsync(b.yt[j], 0, nt * sizeof(double), s) == hipSuccess &&
+         hipMemsetAsync(b.M[j], 0, nm * sizeof(double2), s) == hipSuccess;
+    DevicePlan dj = d;
+    dj.xt = b.xt[j]; dj.yt = b.yt[j]; dj.M = b.M[j];
+    ok = ok && hipMemcpy(b.dev[j], &dj, sizeof(DevicePlan), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipStreamSynchronize(s);
+    for (void* q : got) (void)hipFree(q);
+    (void)hipGetLastError();
+    return fail(FMMBEM_ERR_ALLOC, "batch buffers: device allocation failed");
+  }
+  for (void* q : got) allocs.push_back(q);           // this plan's alone, freed at destroy
+  b.width = w;
+  bat = b;
+  return FMMBEM_OK;
+}
+
+// The fast path: per pass of up to bat.width vectors the gathers, ONE near-field pass and one P2M pass (launch_near_spmv_multi,
+// launch_p2m_multi), then M2M .. L2P and the delivery once per vector, with the launchers of run() on d pointing at that
+// vector's buffers.  The same kernels in the same order per vector as run(): the same bits.  host: x and y are host pointers,
+// staged through stage_x / stage_y(_targets) one vector at a time, in stream order.  With stage timing on, each pass records
+// its near-field and P2M passes (fmmbem_plan_stats ms_near, ms_p2m: means per pass).
+int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y, size_t ldy, hipStream_t s, bool host) {
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  DEVICE_SCOPE(opts.device);
+  TRY(batch_alloc(s));
+  const int w = bat.width;
+  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n);
+  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n);
+  double* sy = targets ? stage_y_targets : stage_y;
+  BatchVecs bv{};
+  bv.width = w;
+  for (int j = 0; j < w; ++j) { bv.xt[j] = bat.xt[j]; bv.yt[j] = bat.yt[j]; bv.M[j] = bat.M[j]; }
+  // m2m_pass / l2l_pass and the M2L launchers read the plan's d / d_dev: pointed at vector j's buffers while its far field is
+  // issued (the launches take d by value), restored after
+  struct View {
+    fmmbem_plan& pl;
+    const DevicePlan keep;
+    const DevicePlan* keep_dev;
+    View(fmmbem_plan& q, int j) : pl(q), keep(q.d), keep_dev(q.d_dev) {
+      pl.d.xt = pl.bat.xt[j]; pl.d.yt = pl.bat.yt[j]; pl.d.M = pl.bat.M[j]; pl.d_dev = pl.bat.dev[j];
+    }
+    ~View() { pl.d = keep; pl.d_dev = keep_dev; }
+  };
+  for (int j0 = 0; j0 < k; j0 += w) {
+    const int nv = std::min(w, k - j0);
+    bv.nv = nv;
+    for (int j = 0; j < nv; ++j) {
+      const double* xj = x + (size_t)(j0 + j) * ldx;
+      if (host) { HIP_TRY(hipMemcpyAsync(stage_x, xj, bytes_x, hipMemcpyHostToDevice, s)); xj = stage_x; }
+      DevicePlan dg = d;
+      dg.xt = bat.xt[j];
+      if (targets) dg.n = hp.n_src;                  // the target rows of x_tree stay 0
+      HIP_TRY(launch_gather_x(dg, xj, s));
+      if (targets && zero_target_rows)
+        HIP_TRY(hipMemsetAsync(bat.yt[j] + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), s));
+    }
+    // stage timing on: a pass is one record of the ring with two stages, its near-field pass (1) and its P2M (3)
+    hipEvent_t* set = timing ? &ev[(size_t)(ev_count % kRing) * 2 * kStages] : nullptr;
+    if (set) HIP_TRY(hipEventRecord(set[2 * 1], s));
+    HIP_TRY(launch_near_spmv_multi(d, bv, s));
+    if (set) { HIP_TRY(hipEventRecord(set[2 * 1 + 1], s)); HIP_TRY(hipEventRecord(set[2 * 3], s)); }
+    if (targets) {                                     // as p2m_targets: once per live slot
+      for (int f = 0; f < 2; ++f) {
+        if (!has_bc[f]) continue;
+        DevicePlan dp = d;
+        dp.bc = bc_all[f];
+        dp.n_act = 1; dp.act[0] = f;
+        if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
+        HIP_TRY(launch_p2m_multi(dp, bv, p, s));
+      }
+    } else HIP_TRY(launch_p2m_multi(d, bv, p, s));
+    if (set) {
+      HIP_TRY(hipEventRecord(set[2 * 3 + 1], s));
+      ev_mask[ev_count % kRing] = (1u << 1) | (1u << 3);
+      ++ev_count;
+    }
+    for (int j = 0; j < nv; ++j) {
+      double* yj = host ? sy : y + (size_t)(j0 + j) * ldy;
+      {
+        View view(*this, j);
+        TRY(m2m_pass(p, false, s));
+        const bool rot = use_rot(p);
+        if (!rot) HIP_TRY(launch_mh_prep(d, p, s));
+        if (rot) HIP_TRY(launch_m2l_rot(d, d_dev, p, s));
+        else HIP_TRY(launch_m2l(d, d_dev, p, s));
+        TRY(l2l_pass(p, s));
+        HIP_TRY(launch_l2p(d, p, d.yt, s));
+        if (targets) {
+          HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : yj, s));
+          if (d_target_point) {
+            const int64_t nt = hp.n_targets;
+            hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, y_points, yj, nt);
+            HIP_TRY(hipGetLastError());
+          }
+        } else HIP_TRY(launch_scatter_y(d, yj, s));
+      }
+      if (host) HIP_TRY(hipMemcpyAsync(y + (size_t)(j0 + j) * ldy, sy, bytes_y, hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (host) HIP_TRY(hipStreamSynchronize(s));
+  last_p = p;
+  return FMMBEM_OK;
+}
+
 // ============================================ C ABI ============================================
 extern "C" {
 
@@ -1445,6 +1604,7 @@ int fmmbem_plan::like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc,
   pl->own_stream = nullptr; pl->hyb = HybridStreams{}; pl->d.ys = nullptr; pl->d.xt4 = nullptr;
   pl->asm_ev[0] = pl->asm_ev[1] = nullptr;
   pl->d_dev = nullptr; pl->stage_x = pl->stage_y = nullptr; pl->solver_ws = nullptr; pl->d_cut = nullptr;
+  pl->bat = BatchBufs{};
   pl->multi.reset();
   pl->result_slices = false; pl->pending_mask = 0; pl->pending_near = false;
   pl->timing = 0; pl->last_p = 0; pl->ev_count = 0;
@@ -2089,6 +2249,64 @@ int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   if (rc != FMMBEM_OK) return rc;
   HIP_TRY(hipMemcpyAsync(y, sy, bytes_y, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
+// ---- batched execute (include/fmmbem.h) ----
+static int batch_args(const fmmbem_plan* plan, int k, const void* x, size_t ldx, const void* y, size_t ldy) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (k < 1) return fail(FMMBEM_ERR_INVALID, "batch of k < 1 vectors");
+  if (!x || !y) return fail(FMMBEM_ERR_INVALID, "null vector");
+  const size_t dof = plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
+  const size_t nx = plan->targets ? (size_t)plan->hp.n_src : (size_t)plan->hp.n * dof;
+  const size_t ny = plan->targets ? (size_t)plan->hp.n_targets : (size_t)plan->hp.n * dof;
+  if (ldx < nx || ldy < ny) return fail(FMMBEM_ERR_INVALID, "leading dimension shorter than a vector");
+  return FMMBEM_OK;
+}
+
+// batches never capture or replay graphs: off for the call (on the shards of a device list too), restored after
+struct GraphsOff {
+  fmmbem_plan* pl;
+  bool own;
+  std::vector<bool> shard;
+  explicit GraphsOff(fmmbem_plan* p) : pl(p), own(p->use_graphs) {
+    pl->use_graphs = false;
+    if (pl->multi) for (auto& sh : pl->multi->shards) { shard.push_back(sh->use_graphs); sh->use_graphs = false; }
+  }
+  ~GraphsOff() {
+    pl->use_graphs = own;
+    if (pl->multi) for (size_t r = 0; r < shard.size(); ++r) pl->multi->shards[r]->use_graphs = shard[r];
+  }
+};
+
+static int batch_execute(fmmbem_plan* plan, int p, int k, const double* x, size_t ldx, double* y, size_t ldy, hipStream_t s, bool host) {
+  GraphsOff off(plan);
+  if (plan->batch_width() > 1) return plan->run_batch(p, k, x, ldx, y, ldy, s, host);
+  for (int j = 0; j < k; ++j) {                        // vector by vector: exactly the single entry points
+    const double* xj = x + (size_t)j * ldx;
+    double* yj = y + (size_t)j * ldy;
+    TRY(host ? fmmbem_plan_execute(plan, p, xj, yj) : fmmbem_plan_execute_device(plan, p, xj, yj, s));
+  }
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_execute_batch(fmmbem_plan* plan, int p, int k, const double* x, size_t ldx, double* y, size_t ldy) {
+  TRY(batch_args(plan, k, x, ldx, y, ldy));
+  if (!plan->on_device && plan->targets) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+  if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
+  if (plan->result_slices)
+    return fail(FMMBEM_ERR_INVALID, "plan delivers result slices (fmmbem_plan_set_result_slices): use the device entry points");
+  return batch_execute(plan, p, k, x, ldx, y, ldy, plan->own_stream, true);
+}
+
+int fmmbem_plan_execute_batch_device(fmmbem_plan* plan, int p, int k, const double* d_x, size_t ldx, double* d_y, size_t ldy, void* stream) {
+  TRY(batch_args(plan, k, d_x, ldx, d_y, ldy));
+  return batch_execute(plan, p, k, d_x, ldx, d_y, ldy, static_cast<hipStream_t>(stream), false);
+}
+
+int fmmbem_plan_batch_width(const fmmbem_plan* plan, int* width) {
+  if (!plan || !width) return fail(FMMBEM_ERR_INVALID, "null argument");
+  *width = plan->batch_width();
   return FMMBEM_OK;
 }
 

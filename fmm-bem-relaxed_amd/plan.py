@@ -478,6 +478,51 @@ class FMM_plan:
         self.execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
+    # ---- batched execute: k vectors, one near-field pass per batch_width() of them (fmmbem_plan_execute_batch) ----
+    def execute_batch(self, charges):
+        """(k, n) charges -- (k, n, 3) for Stokes -> (k, m) results ((k, m, 3)), m = n or the number of targets, at the
+        kernel's current p.  Each row is bit for bit what execute gives for that row.  numpy in, numpy out (host)."""
+        x = np.ascontiguousarray(charges, dtype=np.float64)
+        want = (self.n,) if self.dof == 1 else (self.n, self.dof)
+        if x.ndim != 1 + len(want) or x.shape[1:] != want or x.shape[0] < 1:
+            raise ValueError("charges must have shape (k,) + %r with k >= 1" % (want,))
+        k = x.shape[0]
+        y = np.empty((k,) + (want if self.n_targets is None else (self.n_targets,)))
+        ldx = self.n * self.dof
+        ldy = ldx if self.n_targets is None else self.n_targets
+        _capi.check(_capi.lib().fmmbem_plan_execute_batch(self._h, self._K.P, k, x.ctypes.data_as(C.c_void_p), ldx,
+                                                          y.ctypes.data_as(C.c_void_p), ldy))
+        return y
+
+    def execute_batch_device(self, k, x_ptr, ldx, y_ptr, ldy, stream=0, p=None):
+        _capi.check(_capi.lib().fmmbem_plan_execute_batch_device(self._h, self._K.P if p is None else int(p), int(k), C.c_void_p(x_ptr),
+                                                                 int(ldx), C.c_void_p(y_ptr), int(ldy), C.c_void_p(stream)))
+
+    def execute_batch_torch(self, x, out=None, p=None):
+        """x: contiguous float64 CUDA tensor (k, n * dof), ORIGINAL panel order. Returns (k, m * dof) (m: n or the number of
+        targets). Runs on torch's current stream."""
+        import torch
+        if (x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.dim() != 2 or x.shape[0] < 1
+                or x.shape[1] != self.n * self.dof):
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (k, n * dof)")
+        if x.device.index != self.device:
+            raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
+        m = self.n * self.dof if self.n_targets is None else self.n_targets
+        if out is None:
+            out = x.new_empty((x.shape[0], m))
+        elif (out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (x.shape[0], m)
+              or out.device != x.device):
+            raise ValueError("out must be a contiguous float64 tensor of shape (k, %d) on x's device" % m)
+        self.execute_batch_device(x.shape[0], x.data_ptr(), x.shape[1], out.data_ptr(), m,
+                                  torch.cuda.current_stream(x.device).cuda_stream, p)
+        return out
+
+    def batch_width(self):
+        """Vectors one near-field pass of execute_batch serves on this plan (1: the batch runs vector by vector)."""
+        w = C.c_int(0)
+        _capi.check(_capi.lib().fmmbem_plan_batch_width(self._h, C.byref(w)))
+        return w.value
+
     # ---- introspection ----
     def set_timing(self, on=True):
         """True / 1: HIP events around every stage; 2: around the near-field kernel only (an event record costs ~5 us of

@@ -222,6 +222,31 @@ int fmmbem_plan_execute_device(fmmbem_plan *plan, int p, const double *d_x, doub
  * DEVICE pointers, asynchronous. */
 int fmmbem_plan_near_device(fmmbem_plan *plan, const double *d_x, double *d_y, void *stream);
 
+/* Batched execute: k vectors on one plan at order p, each result bit for bit what fmmbem_plan_execute(_device) gives for that
+ * vector.  Vector j is x + j*ldx (n_panels x dof doubles, caller's panel order), result j is y + j*ldy (n_panels x dof doubles,
+ * or n_targets for a target plan); the doubles between vectors are neither read nor written.  k < 1, a null pointer or a
+ * leading dimension shorter than the vector give FMMBEM_ERR_INVALID; everything else is refused as execute refuses it (a
+ * host-only plan FMMBEM_ERR_NO_DEVICE, a host-only target plan FMMBEM_ERR_UNSUPPORTED, the host form with result slices
+ * FMMBEM_ERR_INVALID).  Any k: the call works through it in passes of at most fmmbem_plan_batch_width vectors.
+ * Fast path -- Laplace plans, assembled (sparse_local = 1), not hybrid (a plan whose near_stream_fraction < 1 fell back to the
+ * streamed matrix counts as not hybrid), one device, shard_world = 1, no result slices; single, create_like and target plans;
+ * the FMM, LOCAL and BLOCK_DIAGONAL evaluators: one pass over the near-field matrix serves every vector of the pass (and one
+ * pass over the P2M tables, where a single execute streams them: one live slot, p >= 8); M2M, M2L, L2L, L2P, the gather and
+ * the delivery run once per vector.  Every other plan (Stokes, hybrid, matrix-free, device lists, shard_world > 1, result
+ * slices) runs the k vectors one after another inside the call.
+ * Batch buffers (per vector of a pass: x and y in tree order, one multipole set) are allocated on the plan's device at the
+ * first batch call and kept until destroy; if that fails the call returns FMMBEM_ERR_ALLOC and single executes still work.
+ * Batches never capture or replay graphs, whatever fmmbem_plan_set_graphs says.  With stage timing on, a fast-path pass records
+ * its near-field and P2M passes only (fmmbem_plan_stats: ms_near, ms_p2m per pass); a batch run vector by vector records as
+ * its single executes do.
+ * The host form takes HOST pointers and returns when y is written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_batch(fmmbem_plan *plan, int p, int k, const double *x, size_t ldx, double *y, size_t ldy);
+int fmmbem_plan_execute_batch_device(fmmbem_plan *plan, int p, int k, const double *d_x, size_t ldx,
+                                     double *d_y, size_t ldy, void *stream);
+/* Vectors one pass of the near field serves on this plan: > 1 on the fast path above, 1 where the batch runs vector by vector
+ * (also on a host-only plan). */
+int fmmbem_plan_batch_width(const fmmbem_plan *plan, int *width);
+
 /* Toggle per-stage HIP-event timing.  While enabled every execute records HIP events around each
  * kernel on the stream it runs on (no synchronisation is added); fmmbem_plan_stats() waits for the
  * recorded events and reports the mean stage times of up to the last 64 executes.  Enabling resets

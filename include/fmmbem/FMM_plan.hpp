@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -547,6 +548,23 @@ class PlanAdapter {
     std::vector<result_type> results(has_targets_ ? target_bc_.size() : charges.size());
     if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as set_p does
     check(fmmbem_plan_execute(plan_, K.p(), KernelBinding<Kernel>::in(charges), KernelBinding<Kernel>::out(results)));
+    return results;
+  }
+  // Several charge vectors at the kernel's current p (fmmbem_plan_execute_batch): results[j] is bit for bit execute(charges[j]).
+  // Not in the reference: one near-field pass serves several vectors where the plan allows it (fmmbem_plan_batch_width).
+  std::vector<std::vector<result_type>> execute_batch(const std::vector<std::vector<charge_type>>& charges) {
+    if (charges.empty()) throw Error(FMMBEM_ERR_INVALID, "execute_batch of no vectors");
+    for (const auto& c : charges)
+      if (c.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges[j].size() != number of panels");
+    constexpr size_t dof = sizeof(charge_type) / sizeof(double);
+    const size_t k = charges.size(), m = has_targets_ ? target_bc_.size() : n_;
+    const size_t ldx = n_ * dof, ldy = m * (has_targets_ ? 1 : dof);
+    std::vector<double> x(k * ldx), y(k * ldy);
+    for (size_t j = 0; j < k; ++j) std::memcpy(x.data() + j * ldx, KernelBinding<Kernel>::in(charges[j]), ldx * sizeof(double));
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    check(fmmbem_plan_execute_batch(plan_, K.p(), (int)k, x.data(), ldx, y.data(), ldy));
+    std::vector<std::vector<result_type>> results(k, std::vector<result_type>(m));
+    for (size_t j = 0; j < k; ++j) std::memcpy(KernelBinding<Kernel>::out(results[j]), y.data() + j * ldy, ldy * sizeof(double));
     return results;
   }
   // preconditioner-style operator()(x, y) (examples/BEM/Preconditioner.hpp:11-15)
