@@ -15,6 +15,14 @@
  * the CALLER of the path, the reference's own GMRES.hpp compiled unmodified
  * around this oracle's matvec (ref_gmres_driver.cpp -> _ref/ref_gmres,
  * fixtures tests/golden/gmres_ref_r*.json).
+ *
+ * TARGET PLANS (targets.c): the reference declares FMM_plan(K, sources, targets, opts) and never builds it, so nothing of the
+ * reference can pin them.  targets.c is a second derivation of the product's documented contract from this oracle's own
+ * pieces (orc_tree_build twice over one root cube, orc_dual_walk between the trees, every source in every live slot, the
+ * complete L2L rule, L2P at the point, orc_eval_G / orc_eval_dGdn by the target's flag); its lists are checked against the
+ * product's entry for entry (tests/test_target_plan_oracle_host.py) and its matvec against the GPU row by row
+ * (tests/test_gpu_target_plan_oracle.py).  With targets at the centroids and one flag it IS the single oracle with the
+ * complete L2L rule (to 1e-13, tested).
  */
 #ifndef FMM_ORACLE_H
 #define FMM_ORACLE_H
@@ -58,6 +66,18 @@ typedef struct {
 } orc_box;
 
 typedef struct { int first, second; } orc_pair;
+
+/* one octree on its own (tree.c orc_tree_build): the single plan's tree, or either tree of a target plan */
+typedef struct {
+  int n;                   /* bodies                                           */
+  double pmin[3], cell[3];
+  unsigned levels;         /* bits per dimension of the coder: 10 or 21        */
+  int nboxes, nlevels;
+  orc_box *boxes;          /* BFS order                                        */
+  uint32_t *perm;          /* tree index -> body index                         */
+  uint64_t *code;
+  int *level_offset;       /* nlevels+1 entries                                */
+} orc_tree;
 
 typedef struct orc_ctx {
   /* inputs */
@@ -117,6 +137,11 @@ void orc_semi_analytical(double *G, double *dGdn, const double y0[3], const doub
                          const double y2[3], const double x[3], int same);
 
 /* ---- tree.c ---- */
+int  orc_tree_build(orc_tree *t, int n, const double *pts, const double pmin[3], const double mx[3], unsigned levels,
+                    unsigned ncrit);
+void orc_tree_free(orc_tree *t);
+void orc_dual_walk(const orc_tree *S, const orc_tree *T, double theta, int keep_lr, orc_pair **p2p, int *n_p2p,
+                   orc_pair **lr, int *n_lr);
 enum { ORC_EVAL_FMM = 0, ORC_EVAL_LOCAL = 1, ORC_EVAL_BLOCK_DIAGONAL = 2 };
 orc_ctx *orc_create_eval(int n, const double *verts, const uint8_t *bc, int K, double theta, unsigned ncrit, int evaluator);
 orc_ctx *orc_create(int n, const double *verts, const uint8_t *bc, int K, double theta,
@@ -162,6 +187,42 @@ int orc_single_p2m(int kernel, int P, int K, double mu, int n, const double *ver
                    const double center[3], cplx *M);
 int orc_single_l2p(int kernel, int P, int K, double mu, const cplx *L, const double center[3], int n, const double *verts,
                    const uint8_t *bc, double *result);
+
+/* ---- targets.c: an FMM over separate target points (NOT a reference path: the reference declares FMM_plan(K, sources,
+ * targets, opts), include/FMM_plan.hpp:45-55, and never builds it).  y_i = sum_j K(t_i, s_j) x_j, the target's flag picking
+ * G or dG/dn.  Two trees on one root cube, the dual walk of tree.c between them, every source in every live expansion slot,
+ * the complete L2L rule on the target tree. ---- */
+typedef struct orc_tctx {
+  int n;                   /* source panels                                    */
+  int nt;                  /* targets as given                                 */
+  int np;                  /* distinct targets (point, flag), first-occurrence order */
+  int K, nq;
+  double qw[ORC_MAXK];
+  double theta;
+  unsigned ncrit;
+  orc_panel *panels;       /* ORIGINAL order; bc unused                        */
+  double *quad;
+  double *pts;             /* np x 3                                           */
+  uint8_t *flag;           /* np                                               */
+  uint32_t *point_of;      /* nt: given target -> distinct target              */
+  double pmin[3];
+  orc_tree S, T;           /* source tree (panel centroids), target tree (distinct points) */
+  orc_pair *p2p; int n_p2p;        /* (S leaf, T leaf), walk order             */
+  orc_pair *lr;  int n_lr;         /* (S box, T box), walk order               */
+  orc_pair *m2m; int n_m2m;        /* (S child, S parent), post-order          */
+  orc_pair *l2l; int n_l2l;        /* (T parent, T child), BFS order           */
+  int *p2m; int n_p2m;             /* S leaves that need a multipole           */
+  char *hasL;                      /* per T box                                */
+  int live[2];                     /* slot 0 (G) / 1 (dG/dn) read by some target */
+  int *lr_ptr, *lr_src;            /* M2L grouped by T box                     */
+  int *near_ptr, *near_src;        /* per T box: its P2P source leaves, ascending body range */
+} orc_tctx;
+
+orc_tctx *orc_target_create(int n, const double *verts, int nt, const double *pts, const uint8_t *flags, int K, double theta,
+                            unsigned ncrit);
+void orc_target_destroy(orc_tctx *c);
+int  orc_target_matvec(const orc_tctx *c, int P, const double *x, double *y);
+void orc_target_direct(const orc_tctx *c, const double *x, double *y);
 
 #define ORC_FLAG_FAITHFUL 1   /* both expansions, serial SpMV/M2M/L2L like the reference */
 #define ORC_FLAG_TARGET_RANGE 2

@@ -94,6 +94,17 @@ def lib():
         L.orc_stokes_get_expansions.argtypes = [vp, i32, i32, vp]
         L.orc_stokes_entries.argtypes = [vp, i32, vp, vp, vp]
         L.orc_red_blood_cell_map.argtypes = [C.c_long, vp]
+        L.orc_target_create.restype = vp
+        L.orc_target_create.argtypes = [i32, vp, i32, vp, vp, i32, dbl, C.c_uint]
+        L.orc_target_destroy.argtypes = [vp]
+        L.orc_target_matvec.argtypes = [vp, i32, vp, vp]
+        L.orc_target_matvec.restype = i32
+        L.orc_target_direct.argtypes = [vp, vp, vp]
+        L.orc_target_info.argtypes = [vp, vp]
+        L.orc_target_boxes.argtypes = [vp, i32] + [vp] * 7
+        L.orc_target_pairs.argtypes = [vp, i32, vp]
+        L.orc_target_pairs.restype = i32
+        L.orc_target_perm.argtypes = [vp] * 6
         _LIB = L
     return _LIB
 
@@ -424,3 +435,102 @@ class StokesOracle(Oracle):
         out = np.empty((len(ti), 3, 3))
         lib().orc_stokes_entries(self._h, len(ti), _p(ti), _p(sj), _p(out))
         return out
+
+
+TARGET_INFO_NAMES = ("n_panels", "n_targets", "n_target_points", "n_source_boxes", "n_source_leaves", "n_source_levels",
+                     "n_target_boxes", "n_target_leaves", "n_target_levels", "tree_coder_levels", "p2p_pairs", "m2l_pairs",
+                     "m2m_ops", "l2l_ops", "p2m_leaves", "live_slots")
+
+
+class TargetOracle:
+    """An FMM over separate target points on the CPU (oracle/targets.c): y_i = sum_j K(t_i, s_j) x_j at the points t_i, the
+    target's flag (0 G, 1 dG/dn) picking the kernel.  The reference declares this plan (include/FMM_plan.hpp:45-55) and never
+    builds it: the rules restated are the product's documented contract, derived from the oracle's own tree, walk and
+    operators -- two trees on one root cube, every source in every live slot, the complete L2L rule."""
+
+    def __init__(self, vertices, points, target_bc=None, K=3, theta=0.5, ncrit=64):
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 9)
+        t = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        self.n, self.n_targets = v.shape[0], t.shape[0]
+        fl = None if target_bc is None else np.ascontiguousarray(target_bc, dtype=np.uint8)
+        if fl is not None and fl.shape != (self.n_targets,):
+            raise ValueError("target_bc must have one flag per target")
+        self._h = lib().orc_target_create(self.n, _p(v), self.n_targets, _p(t), None if fl is None else _p(fl), K, theta, ncrit)
+        if not self._h:
+            raise ValueError("orc_target_create failed (bad quadrature key, empty input or a point not finite)")
+
+    def close(self):
+        if self._h:
+            lib().orc_target_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(16, dtype=np.int64)
+        lib().orc_target_info(self._h, _p(out))
+        return dict(zip(TARGET_INFO_NAMES, out.tolist()))
+
+    def boxes(self, tree="source"):
+        """one tree's boxes in its own BFS numbering, bodies counted from 0 in that tree (as FMM_plan.boxes / target_boxes)"""
+        info = self.info()
+        nb = info["n_target_boxes" if tree == "target" else "n_source_boxes"]
+        d = dict(center=np.empty((nb, 3)), side=np.empty(nb))
+        for k in ("level", "leaf", "parent", "bb", "be"):
+            d[k] = np.empty(nb, dtype=np.int32)
+        lib().orc_target_boxes(self._h, 1 if tree == "target" else 0,
+                               *[_p(d[k]) for k in ("center", "side", "level", "leaf", "parent", "bb", "be")])
+        return d
+
+    def pairs(self, which):
+        """p2p (source leaf, target leaf) and m2l (source box, target box) in walk order; m2m (child, parent) on the source
+        tree; l2l (parent, child) on the target tree"""
+        idx = {"p2p": 0, "m2l": 1, "m2m": 2, "l2l": 3}[which]
+        n = lib().orc_target_pairs(self._h, idx, None)
+        out = np.empty((n, 2), dtype=np.int32)
+        lib().orc_target_pairs(self._h, idx, _p(out))
+        return out
+
+    def perm(self):
+        """source-tree position -> panel"""
+        out = np.empty(self.n, dtype=np.uint32)
+        lib().orc_target_perm(self._h, _p(out), None, None, None, None)
+        return out
+
+    def target_perm(self):
+        """(target-tree position -> distinct target, given target -> distinct target), as FMM_plan.target_perm"""
+        info = self.info()
+        tree = np.empty(info["n_target_points"], dtype=np.uint32)
+        given = np.empty(self.n_targets, dtype=np.uint32)
+        lib().orc_target_perm(self._h, None, _p(tree), _p(given), None, None)
+        return tree, given
+
+    def target_points(self):
+        """(distinct target points (m, 3), their flags)"""
+        m = self.info()["n_target_points"]
+        pts, fl = np.empty((m, 3)), np.empty(m, dtype=np.uint8)
+        lib().orc_target_perm(self._h, None, None, None, _p(pts), _p(fl))
+        return pts, fl
+
+    def matvec(self, x, p):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.n,):
+            raise ValueError("x must have one value per panel")
+        y = np.empty(self.n_targets)
+        rc = lib().orc_target_matvec(self._h, p, _p(x), _p(y))
+        if rc:
+            raise RuntimeError("orc_target_matvec rc=%d" % rc)
+        return y
+
+    def direct(self, x):
+        """sum_j K(t_i, s_j) x_j over every panel at the exact points, given order"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.n,):
+            raise ValueError("x must have one value per panel")
+        y = np.empty(self.n_targets)
+        lib().orc_target_direct(self._h, _p(x), _p(y))
+        return y

@@ -49,7 +49,7 @@ typedef struct { uint64_t code; uint32_t idx; } code_pair;
 #define PUSH(v, x) do { if ((v).n == (v).cap) { (v).cap = (v).cap ? 2*(v).cap : 1024; \
       (v).d = realloc((v).d, (v).cap*sizeof(*(v).d)); } (v).d[(v).n++] = (x); } while (0)
 
-static void box_geometry(orc_ctx *c, orc_box *b) {
+static void box_geometry(const orc_tree *c, orc_box *b) {
   /* Box::center(), Octree.hpp:350-355, through MortonCoder::cell (:109-113) and
      box_data::get_mc_lower_bound (:243-248); Box::side_length (:334-336) */
   const unsigned L = c->levels;
@@ -68,10 +68,10 @@ static void box_geometry(orc_ctx *c, orc_box *b) {
 }
 
 /* include/FMMOptions.hpp:21-31 (DefaultMAC); radius = side/2 (Octree.hpp:340-342) */
-static int mac(const orc_ctx *c, const orc_box *b1, const orc_box *b2) {
+static int mac(double theta, const orc_box *b1, const orc_box *b2) {
   double d[3] = { b1->center[0]-b2->center[0], b1->center[1]-b2->center[1], b1->center[2]-b2->center[2] };
   double r0 = d[0]*d[0] + d[1]*d[1] + d[2]*d[2];
-  double rhs = (b1->side/2.0 + b2->side/2.0) / c->theta;
+  double rhs = (b1->side/2.0 + b2->side/2.0) / theta;
   return r0 > rhs*rhs;
 }
 
@@ -112,6 +112,119 @@ static void propagate_local(orc_ctx *c, int b, char *initL, char *l2pset, int_ve
   }
 }
 
+/* The octree of n points pts[3*i..3*i+2] in the cube [pmin, mx] with a coder of `levels` bits per dimension: construct_tree,
+ * include/tree/Octree.hpp:617-692 (incremental stable bucket sort, BFS box order), and the box geometry.  Returns -1 (nothing
+ * kept) when a box on the coder's last level still holds more than ncrit points and `levels` is not DEEP_LEVELS: the caller
+ * rebuilds with DEEP_LEVELS.  At DEEP_LEVELS such a box becomes a leaf (reported on stderr). */
+int orc_tree_build(orc_tree *t, int n, const double *pts, const double pmin[3], const double mx[3], unsigned levels, unsigned ncrit) {
+  memset(t, 0, sizeof *t);
+  t->n = n; t->levels = levels;
+  const unsigned L = levels;
+  for (int k = 0; k < 3; ++k) {
+    t->pmin[k] = pmin[k];
+    t->cell[k] = (mx[k] - pmin[k]) / ldexp(1.0, (int)L);     /* MortonCoder ctor, :95-99 */
+  }
+  code_pair *codes = malloc(sizeof(code_pair)*(size_t)n), *tmp = malloc(sizeof(code_pair)*(size_t)n);
+  VEC(orc_box) boxes = {0};
+  int_vec level_offset = {0};
+
+  /* ---- codes: MortonCoder::code, :118-129 ---- */
+  for (int i = 0; i < n; ++i) {
+    uint64_t s[3];
+    for (int k = 0; k < 3; ++k) {
+      double v = pts[3*(size_t)i + k];
+      v -= t->pmin[k]; v /= t->cell[k];
+      s[k] = (uint64_t)(uint32_t)v;
+    }
+    codes[i].code = interleave(s[0], s[1], s[2]); codes[i].idx = (uint32_t)i;
+  }
+
+  orc_box root; memset(&root, 0, sizeof root);
+  root.key = 1; root.parent = 0; root.cb = 0; root.ce = (uint32_t)n; root.level = 0; root.bb = 0; root.be = (uint32_t)n;
+  PUSH(boxes, root);
+  PUSH(level_offset, 0);
+  int maxlevel = 0;
+  for (size_t k = 0; k != boxes.n; ++k) {
+    orc_box bk = boxes.d[k];
+    if (bk.ce - bk.cb <= ncrit) { boxes.d[k].leaf = 1; continue; }       /* :641-644 */
+    if (bk.level >= (int)L) {                                            /* 32-bit key limit, :85-92 */
+      if (L != DEEP_LEVELS) {                                            /* not a reference rule: see DEEP_LEVELS */
+        free(codes); free(tmp); free(boxes.d); free(level_offset.d);
+        memset(t, 0, sizeof *t);
+        return -1;
+      }
+      fprintf(stderr, "oracle: octree deeper than %u levels\n", L);
+      boxes.d[k].leaf = 1; continue;
+    }
+    unsigned shift = 3*(L - (unsigned)bk.level - 1);                    /* :649 */
+    size_t cnt[9] = {0};
+    for (uint32_t i = bk.cb; i < bk.ce; ++i) cnt[((codes[i].code >> shift) & 7) + 1]++;
+    for (int b = 0; b < 8; ++b) cnt[b+1] += cnt[b];
+    size_t pos[8]; for (int b = 0; b < 8; ++b) pos[b] = cnt[b];
+    for (uint32_t i = bk.cb; i < bk.ce; ++i) tmp[bk.cb + pos[(codes[i].code >> shift) & 7]++] = codes[i];   /* stable */
+    memcpy(codes + bk.cb, tmp + bk.cb, sizeof(code_pair)*(bk.ce - bk.cb));
+    uint32_t first_child = (uint32_t)boxes.n, nchild = 0;
+    for (int ch = 0; ch < 8; ++ch) {                                     /* :661-681 */
+      uint32_t bch = bk.cb + (uint32_t)cnt[ch], ech = bk.cb + (uint32_t)cnt[ch+1];
+      if (ech - bch > 0) {
+        orc_box nb; memset(&nb, 0, sizeof nb);
+        nb.key = (bk.key << 3) | (uint64_t)ch; nb.parent = (uint32_t)k;
+        nb.cb = bch; nb.ce = ech; nb.bb = bch; nb.be = ech;
+        nb.level = key_level(nb.key);
+        if (nb.level > maxlevel) { maxlevel = nb.level; PUSH(level_offset, (int)boxes.n); }
+        PUSH(boxes, nb);
+        ++nchild;
+      }
+    }
+    boxes.d[k].cb = first_child; boxes.d[k].ce = first_child + nchild;
+  }
+  PUSH(level_offset, (int)boxes.n);                                       /* :684 */
+  t->nboxes = (int)boxes.n; t->boxes = boxes.d;
+  t->nlevels = (int)level_offset.n - 1; t->level_offset = level_offset.d;
+  t->perm = malloc(sizeof(uint32_t)*(size_t)n); t->code = malloc(sizeof(uint64_t)*(size_t)n);
+  for (int i = 0; i < n; ++i) { t->perm[i] = codes[i].idx; t->code[i] = codes[i].code; }    /* :687-691 */
+  free(codes); free(tmp);
+  for (int b = 0; b < t->nboxes; ++b) box_geometry(t, &t->boxes[b]);
+  return 0;
+}
+
+void orc_tree_free(orc_tree *t) {
+  free(t->boxes); free(t->perm); free(t->code); free(t->level_offset);
+  memset(t, 0, sizeof *t);
+}
+
+/* Dual tree traversal, EvalInteractionLazySparse.hpp:68-110, interact :239-252, of source tree S against target tree T (the
+ * single plan passes its one tree twice).  Both trees must lie on one lattice (same root cube and coder).  Pairs are
+ * (S box, T box) in FIFO order; the root pair is not MAC-tested.  keep_lr = 0: EvalLocalSparse.hpp:120-127, accepted pairs
+ * are dropped. */
+void orc_dual_walk(const orc_tree *S, const orc_tree *T, double theta, int keep_lr, orc_pair **p2p_out, int *n_p2p,
+                   orc_pair **lr_out, int *n_lr) {
+  pair_vec q = {0}, p2p = {0}, lr = {0};
+  size_t head = 0;
+  orc_pair rr = {0, 0};
+  PUSH(q, rr);
+  while (head < q.n) {
+    orc_pair pr = q.d[head++];
+    const orc_box *b1 = &S->boxes[pr.first], *b2 = &T->boxes[pr.second];
+    int split_first;
+    if (b1->leaf) {
+      if (b2->leaf) { PUSH(p2p, pr); continue; }
+      split_first = 0;
+    } else if (b2->leaf) split_first = 1;
+    else split_first = (b1->side > b2->side);                          /* ties split b2, :98-108 */
+    const orc_box *sp = split_first ? b1 : b2;
+    for (uint32_t ch = sp->cb; ch < sp->ce; ++ch) {
+      orc_pair np = split_first ? (orc_pair){ (int)ch, pr.second } : (orc_pair){ pr.first, (int)ch };
+      if (mac(theta, &S->boxes[np.first], &T->boxes[np.second])) { if (keep_lr) PUSH(lr, np); } else PUSH(q, np);
+    }
+    if (head > (1u << 20) && head*2 > q.n) {       /* compact the FIFO */
+      memmove(q.d, q.d + head, sizeof(orc_pair)*(q.n - head)); q.n -= head; head = 0;
+    }
+  }
+  free(q.d);
+  *p2p_out = p2p.d; *n_p2p = (int)p2p.n; *lr_out = lr.d; *n_lr = (int)lr.n;
+}
+
 orc_ctx *orc_create(int n, const double *verts, const uint8_t *bc, int K, double theta, unsigned ncrit) {
   return orc_create_eval(n, verts, bc, K, theta, ncrit, ORC_EVAL_FMM);
 }
@@ -144,98 +257,25 @@ orc_ctx *orc_create_eval(int n, const double *verts, const uint8_t *bc, int K, d
     mx[k] = fmax(mx[k], a);
     c->pmin[k] = mn[k];
   }
-  c->levels = LEVELS;
-  code_pair *codes = malloc(sizeof(code_pair)*(size_t)n), *tmp = malloc(sizeof(code_pair)*(size_t)n);
-  VEC(orc_box) boxes = {0};
-  int_vec level_offset = {0};
-rebuild:;
-  const unsigned L = c->levels;
-  for (int k = 0; k < 3; ++k) c->cell[k] = (mx[k] - mn[k]) / ldexp(1.0, (int)L);     /* MortonCoder ctor, :95-99 */
-
-  /* ---- codes: MortonCoder::code, :118-129 ---- */
-  for (int i = 0; i < n; ++i) {
-    uint64_t s[3];
-    for (int k = 0; k < 3; ++k) {
-      double v = c->panels[i].c[k];
-      v -= c->pmin[k]; v /= c->cell[k];
-      s[k] = (uint64_t)(uint32_t)v;
-    }
-    codes[i].code = interleave(s[0], s[1], s[2]); codes[i].idx = (uint32_t)i;
-  }
-
-  /* ---- construct_tree: Octree.hpp:617-692 (incremental stable bucket sort, BFS box order) ---- */
-  boxes.n = 0; level_offset.n = 0;
-  orc_box root; memset(&root, 0, sizeof root);
-  root.key = 1; root.parent = 0; root.cb = 0; root.ce = (uint32_t)n; root.level = 0; root.bb = 0; root.be = (uint32_t)n;
-  PUSH(boxes, root);
-  PUSH(level_offset, 0);
-  int maxlevel = 0;
-  for (size_t k = 0; k != boxes.n; ++k) {
-    orc_box bk = boxes.d[k];
-    if (bk.ce - bk.cb <= ncrit) { boxes.d[k].leaf = 1; continue; }       /* :641-644 */
-    if (bk.level >= (int)L) {                                            /* 32-bit key limit, :85-92 */
-      if (L == LEVELS) { c->levels = DEEP_LEVELS; goto rebuild; }        /* not a reference rule: see DEEP_LEVELS */
-      fprintf(stderr, "oracle: octree deeper than %u levels\n", L);
-      boxes.d[k].leaf = 1; continue;
-    }
-    unsigned shift = 3*(L - (unsigned)bk.level - 1);                    /* :649 */
-    size_t cnt[9] = {0};
-    for (uint32_t i = bk.cb; i < bk.ce; ++i) cnt[((codes[i].code >> shift) & 7) + 1]++;
-    for (int b = 0; b < 8; ++b) cnt[b+1] += cnt[b];
-    size_t pos[8]; for (int b = 0; b < 8; ++b) pos[b] = cnt[b];
-    for (uint32_t i = bk.cb; i < bk.ce; ++i) tmp[bk.cb + pos[(codes[i].code >> shift) & 7]++] = codes[i];   /* stable */
-    memcpy(codes + bk.cb, tmp + bk.cb, sizeof(code_pair)*(bk.ce - bk.cb));
-    uint32_t first_child = (uint32_t)boxes.n, nchild = 0;
-    for (int ch = 0; ch < 8; ++ch) {                                     /* :661-681 */
-      uint32_t bch = bk.cb + (uint32_t)cnt[ch], ech = bk.cb + (uint32_t)cnt[ch+1];
-      if (ech - bch > 0) {
-        orc_box nb; memset(&nb, 0, sizeof nb);
-        nb.key = (bk.key << 3) | (uint64_t)ch; nb.parent = (uint32_t)k;
-        nb.cb = bch; nb.ce = ech; nb.bb = bch; nb.be = ech;
-        nb.level = key_level(nb.key);
-        if (nb.level > maxlevel) { maxlevel = nb.level; PUSH(level_offset, (int)boxes.n); }
-        PUSH(boxes, nb);
-        ++nchild;
-      }
-    }
-    boxes.d[k].cb = first_child; boxes.d[k].ce = first_child + nchild;
-  }
-  PUSH(level_offset, (int)boxes.n);                                       /* :684 */
-  c->nboxes = (int)boxes.n; c->boxes = boxes.d;
-  c->nlevels = (int)level_offset.n - 1; c->level_offset = level_offset.d;
-  c->perm = malloc(sizeof(uint32_t)*(size_t)n); c->code = malloc(sizeof(uint64_t)*(size_t)n);
-  for (int i = 0; i < n; ++i) { c->perm[i] = codes[i].idx; c->code[i] = codes[i].code; }    /* :687-691 */
-  free(codes); free(tmp);
-  for (int b = 0; b < c->nboxes; ++b) box_geometry(c, &c->boxes[b]);
+  double *cen = malloc(sizeof(double)*3*(size_t)n);
+  for (int i = 0; i < n; ++i) for (int k = 0; k < 3; ++k) cen[3*i + k] = c->panels[i].c[k];
+  orc_tree tr;
+  if (orc_tree_build(&tr, n, cen, c->pmin, mx, LEVELS, ncrit))
+    orc_tree_build(&tr, n, cen, c->pmin, mx, DEEP_LEVELS, ncrit);     /* not a reference rule: see DEEP_LEVELS */
+  free(cen);
+  memcpy(c->cell, tr.cell, sizeof c->cell);
+  c->levels = tr.levels; c->nboxes = tr.nboxes; c->boxes = tr.boxes; c->nlevels = tr.nlevels;
+  c->level_offset = tr.level_offset; c->perm = tr.perm; c->code = tr.code;
 
   /* ---- dual tree traversal: EvalInteractionLazySparse.hpp:68-110, interact :239-252 ---- */
-  pair_vec q = {0}, p2p = {0}, lr = {0};
-  size_t head = 0;
-  orc_pair rr = {0, 0};
   if (evaluator == ORC_EVAL_BLOCK_DIAGONAL) {
+    pair_vec p2p = {0};
     for (int b = 0; b < c->nboxes; ++b)
       if (c->boxes[b].leaf) { orc_pair pr = {b, b}; PUSH(p2p, pr); }
-  } else PUSH(q, rr);
-  while (head < q.n) {
-    orc_pair pr = q.d[head++];
-    const orc_box *b1 = &c->boxes[pr.first], *b2 = &c->boxes[pr.second];
-    int split_first;
-    if (b1->leaf) {
-      if (b2->leaf) { PUSH(p2p, pr); continue; }
-      split_first = 0;
-    } else if (b2->leaf) split_first = 1;
-    else split_first = (b1->side > b2->side);                          /* ties split b2, :98-108 */
-    const orc_box *sp = split_first ? b1 : b2;
-    for (uint32_t ch = sp->cb; ch < sp->ce; ++ch) {
-      orc_pair np = split_first ? (orc_pair){ (int)ch, pr.second } : (orc_pair){ pr.first, (int)ch };
-      if (mac(c, &c->boxes[np.first], &c->boxes[np.second])) { if (evaluator == ORC_EVAL_FMM) PUSH(lr, np); } else PUSH(q, np);
-    }
-    if (head > (1u << 20) && head*2 > q.n) {       /* compact the FIFO */
-      memmove(q.d, q.d + head, sizeof(orc_pair)*(q.n - head)); q.n -= head; head = 0;
-    }
+    c->p2p = p2p.d; c->n_p2p = (int)p2p.n; c->lr = NULL; c->n_lr = 0;
+  } else {
+    orc_dual_walk(&tr, &tr, c->theta, evaluator == ORC_EVAL_FMM, &c->p2p, &c->n_p2p, &c->lr, &c->n_lr);
   }
-  free(q.d);
-  c->p2p = p2p.d; c->n_p2p = (int)p2p.n; c->lr = lr.d; c->n_lr = (int)lr.n;
 
   /* ---- resolve_LR_interactions: :225-237 ---- */
   char *initM = calloc((size_t)c->nboxes, 1), *initL = calloc((size_t)c->nboxes, 1), *l2pset = calloc((size_t)c->nboxes, 1);
