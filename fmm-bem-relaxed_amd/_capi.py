@@ -100,6 +100,7 @@ SYMBOLS = (
     "fmmbem_ops_create", "fmmbem_ops_destroy", "fmmbem_ops_slots", "fmmbem_ops_p2m", "fmmbem_ops_m2m", "fmmbem_ops_m2l", "fmmbem_ops_l2l", "fmmbem_ops_l2p",
     "fmmbem_plan_create_targets", "fmmbem_plan_target_info", "fmmbem_plan_get_target_boxes", "fmmbem_plan_get_target_perm",
     "fmmbem_plan_execute_batch", "fmmbem_plan_execute_batch_device", "fmmbem_plan_batch_width",
+    "fmmbem_gmres_batch_device", "fmmbem_gmres_batch",
 )
 
 
@@ -173,6 +174,10 @@ def lib():
     L.fmmbem_plan_get_target_boxes.argtypes = [vp] * 8
     L.fmmbem_plan_get_target_perm.argtypes = [vp, vp, vp]
     L.fmmbem_gmres.argtypes = [vp, C.POINTER(SolverOpts), vp, vp, C.POINTER(Preconditioner), C.POINTER(SolverLog)]
+    L.fmmbem_gmres_batch_device.argtypes = [vp, C.POINTER(SolverOpts), i32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(Preconditioner),
+                                            C.POINTER(SolverLog), vp]
+    L.fmmbem_gmres_batch.argtypes = [vp, C.POINTER(SolverOpts), i32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(Preconditioner),
+                                     C.POINTER(SolverLog)]
     L.fmmbem_ops_create.argtypes = [C.POINTER(Options), C.POINTER(vp)]
     L.fmmbem_ops_destroy.argtypes = [vp]
     L.fmmbem_ops_destroy.restype = None

@@ -24,6 +24,7 @@ struct SolverWs;
 // (freed with the plan through solver_ws_destroy)
 int plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, int* p_max, SolverWs*** slot);
 void solver_ws_destroy(SolverWs* ws);
+size_t plan_unknowns(const fmmbem_plan* plan);      // plan.hip: doubles of one x vector (any plan, host-only ones included)
 }
 
 namespace {
@@ -104,6 +105,72 @@ __global__ __launch_bounds__(kThreads) void mgs_step_kernel(int64_t n, double* _
   }
 }
 
+// The sweep of mgs_step_kernel on its vector path, statement for statement, as a function: the multi-system kernel below runs
+// it once per system (whose vectors always start on 16-byte boundaries).  mgs_step_kernel itself stays as it is -- wrapping it
+// round this function moves its instructions -- so the two must be kept in step; tests/test_gpu_gmres_batch.py holds them to
+// the same bits.
+__device__ __forceinline__ void mgs_step_body(int64_t n, double* __restrict__ w, const double* __restrict__ v_prev,
+                                              const double* __restrict__ part_prev, const double* __restrict__ v_dot,
+                                              double* __restrict__ part_out) {
+  __shared__ double wsum[kThreads / 64];
+  const double hp = v_prev ? block_total(part_prev, wsum) : 0.0;
+  double acc = 0;
+  // the slots of this row no workgroup of this grid writes are part of every total: zero them here, every call (a scratch
+  // reused after a call with a larger n would otherwise add stale partial sums)
+  if (blockIdx.x == 0)
+    for (int k = gridDim.x + threadIdx.x; k < kBlocks; k += kThreads) part_out[k] = 0.0;
+  // four consecutive elements per thread and step, as two 16-byte vectors per array: all loads of a step are in flight before
+  // the first FMA
+  const int64_t n4 = n >> 2;
+  typedef double dv2 __attribute__((ext_vector_type(2)));
+  dv2* w2 = reinterpret_cast<dv2*>(w);
+  const dv2* p2 = reinterpret_cast<const dv2*>(v_prev);
+  const dv2* d2 = reinterpret_cast<const dv2*>(v_dot);
+  for (int64_t q = blockIdx.x * (int64_t)kThreads + threadIdx.x; q < n4; q += (int64_t)gridDim.x * kThreads) {
+    dv2 wa = w2[2 * q], wb = w2[2 * q + 1];
+    dv2 pa = {0, 0}, pb = {0, 0}, da, db;
+    if (v_prev) { pa = p2[2 * q]; pb = p2[2 * q + 1]; }
+    if (v_dot) { da = d2[2 * q]; db = d2[2 * q + 1]; }
+    if (v_prev) {
+      wa.x = fma(-hp, pa.x, wa.x); wa.y = fma(-hp, pa.y, wa.y); wb.x = fma(-hp, pb.x, wb.x); wb.y = fma(-hp, pb.y, wb.y);
+      w2[2 * q] = wa; w2[2 * q + 1] = wb;
+    }
+    if (!v_dot) { da = wa; db = wb; }
+    acc = fma(wa.x, da.x, acc); acc = fma(wa.y, da.y, acc); acc = fma(wb.x, db.x, acc); acc = fma(wb.y, db.y, acc);
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {   // n mod 4 leftovers
+    double wi = w[i];
+    if (v_prev) { wi = fma(-hp, v_prev[i], wi); w[i] = wi; }
+    acc = fma(wi, v_dot ? v_dot[i] : wi, acc);
+  }
+  acc = wave_sum64(acc);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0;
+    for (int k = 0; k < kThreads / 64; ++k) s += wsum[k];
+    part_out[blockIdx.x] = s;
+  }
+}
+
+// The systems of one multi-system launch (fmmbem_gmres_batch): blockIdx.y picks a workspace slot from a table passed by value
+constexpr int kSysPerLaunch = 64;
+struct SysTable {
+  int count;
+  int slot[kSysPerLaunch];
+};
+
+// mgs_step_kernel for several systems at once: system blockIdx.y works on its own w, its own column of V and its own rows of
+// partial sums, all `slot` strides from the bases; the x dimension, and with it every sum, is the single kernel's
+__global__ __launch_bounds__(kThreads) void mgs_step_multi_kernel(int64_t n, double* __restrict__ w, const double* __restrict__ v_prev,
+                                                                   const double* __restrict__ part_prev, const double* __restrict__ v_dot,
+                                                                   double* __restrict__ part_out, int64_t ld, int64_t part_stride, SysTable t) {
+  const int64_t j = t.slot[blockIdx.y];
+  mgs_step_body(n, w + j * ld, v_prev ? v_prev + j * ld : nullptr, part_prev ? part_prev + j * part_stride : nullptr,
+                v_dot ? v_dot + j * ld : nullptr, part_out + j * part_stride);
+}
+
 // x += a z
 __global__ __launch_bounds__(kThreads) void mgs_axpy_kernel(int64_t n, double* __restrict__ x, double a, const double* __restrict__ z) {
   for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) x[i] = fma(a, z[i], x[i]);
@@ -124,11 +191,41 @@ __global__ __launch_bounds__(kThreads) void mgs_scale_kernel(int64_t n, const do
   for (int64_t i = (n2 << 1) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v_next[i] = w[i] * inv;
 }
 
+// mgs_scale_kernel as a function, for the multi-system kernel (see mgs_step_body)
+__device__ __forceinline__ void mgs_scale_body(int64_t n, const double* __restrict__ w, const double* __restrict__ part_norm,
+                                               double* __restrict__ v_next) {
+  __shared__ double wsum[kThreads / 64];
+  const double inv = 1.0 / sqrt(block_total(part_norm, wsum));
+  typedef double dv2 __attribute__((ext_vector_type(2)));
+  const int64_t n2 = n >> 1;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n2; q += (int64_t)gridDim.x * blockDim.x) {
+    dv2 v = reinterpret_cast<const dv2*>(w)[q];
+    v.x *= inv; v.y *= inv;
+    reinterpret_cast<dv2*>(v_next)[q] = v;
+  }
+  for (int64_t i = (n2 << 1) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v_next[i] = w[i] * inv;
+}
+
+__global__ __launch_bounds__(kThreads) void mgs_scale_multi_kernel(int64_t n, const double* __restrict__ w, const double* __restrict__ part_norm,
+                                                                    double* __restrict__ v_next, int64_t ld, int64_t part_stride, SysTable t) {
+  const int64_t j = t.slot[blockIdx.y];
+  mgs_scale_body(n, w + j * ld, part_norm + j * part_stride, v_next + j * ld);
+}
+
 // h[k] = total of the k-th row of partial sums, k <= ncols; the last one is |w|^2 -> |w|
 __global__ __launch_bounds__(kThreads) void mgs_finish_kernel(const double* __restrict__ partial, int ncols, double* __restrict__ h) {
   __shared__ double wsum[kThreads / 64];
   const double t = block_total(partial + (size_t)blockIdx.x * kBlocks, wsum);
   if (threadIdx.x == 0) h[blockIdx.x] = (int)blockIdx.x == ncols ? sqrt(t) : t;
+}
+
+// the same for several systems: the columns land one after the other in launch order (ncols + 1 doubles each), so that all of
+// them cross to the host in one copy
+__global__ __launch_bounds__(kThreads) void mgs_finish_multi_kernel(const double* __restrict__ partial, int ncols, double* __restrict__ h,
+                                                                     int64_t part_stride, SysTable t) {
+  __shared__ double wsum[kThreads / 64];
+  const double v = block_total(partial + t.slot[blockIdx.y] * part_stride + (size_t)blockIdx.x * kBlocks, wsum);
+  if (threadIdx.x == 0) h[(size_t)blockIdx.y * (ncols + 1) + blockIdx.x] = (int)blockIdx.x == ncols ? sqrt(v) : v;
 }
 
 }  // namespace
@@ -193,6 +290,15 @@ __global__ __launch_bounds__(kThreads) void scale_kernel(int64_t n, const double
     out[i] = r ? r[i] * in[i] : a * in[i];
 }
 
+// out = r .* in for every system of the table, `slot` strides of ld from the bases: the diagonal preconditioner of
+// fmmbem_gmres_batch in one launch
+__global__ __launch_bounds__(kThreads) void scale_multi_kernel(int64_t n, const double* __restrict__ in, const double* __restrict__ r,
+                                                                double* __restrict__ out, int64_t ld, SysTable t) {
+  const int64_t off = t.slot[blockIdx.y] * ld;
+  for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+    out[off + i] = r[i] * in[off + i];
+}
+
 // x += sum_j y[j] * (r .* B_j), j ascending as the reference's loop (GMRES.hpp:237-241 with M = identity or diagonal;
 // FGMRES :368-371 with B = Z): the basis is read once, x once
 __global__ __launch_bounds__(kThreads) void update_x_kernel(int64_t n, double* __restrict__ x, const double* __restrict__ B, int64_t ldb, int ncols,
@@ -212,7 +318,21 @@ __global__ __launch_bounds__(kThreads) void update_x_kernel(int64_t n, double* _
 
 namespace fmmbem {
 
+// Workspace of fmmbem_gmres_batch: `cap` systems side by side.  Column c of system j is at ((c * cap) + j) * ld of V (and Z), w
+// and z of system j at j * ld: column c of all systems is equally spaced, so one batched execute takes it as it lies.
+// Separate from the single solver's buffers: neither solver frees or resizes what the other one holds.
+struct BatchWs {
+  int cap = 0;
+  int64_t n = 0, ld = 0;
+  int vcols = 0, zcols = 0, hcap = 0;
+  double *V = nullptr, *Z = nullptr, *w = nullptr, *z = nullptr, *d_h = nullptr, *d_scratch = nullptr, *d_y = nullptr;
+  double *d_xb = nullptr, *d_recip = nullptr;       // staging of the host-pointer entry point
+  size_t xb_doubles = 0;
+  double* h_pin = nullptr;                          // pinned, 2 * cap * hcap: the Hessenberg columns, then the y coefficients
+};
+
 struct SolverWs {
+  BatchWs batch;
   int device = 0;
   int64_t n = 0, ld = 0;
   int vcols = 0, zcols = 0, hcap = 0;
@@ -229,6 +349,10 @@ void solver_ws_destroy(SolverWs* ws) {
   for (double* p : {ws->V, ws->Z, ws->w, ws->z, ws->d_h, ws->d_scratch, ws->d_y, ws->d_xb, ws->d_recip})
     if (p) (void)hipFree(p);
   if (ws->h_pin) (void)hipHostFree(ws->h_pin);
+  const BatchWs& b = ws->batch;
+  for (double* p : {b.V, b.Z, b.w, b.z, b.d_h, b.d_scratch, b.d_y, b.d_xb, b.d_recip})
+    if (p) (void)hipFree(p);
+  if (b.h_pin) (void)hipHostFree(b.h_pin);
   (void)hipSetDevice(prev);
   delete ws;
 }
@@ -320,13 +444,17 @@ int sweep_grid(int64_t n) {
 }
 
 // |w| (after w += a v when v) -> host; one synchronisation
-int axpy_norm(SolverWs* ws, double* w, double a, const double* v, hipStream_t s, double* out) {
-  hipLaunchKernelGGL(axpy_norm_kernel, dim3(sweep_grid(ws->n)), dim3(kThreads), 0, s, ws->n, w, a, v, ws->d_scratch);
-  hipLaunchKernelGGL(mgs_finish_kernel, dim3(1), dim3(kThreads), 0, s, ws->d_scratch, 0, ws->d_h);      // ncols = 0: row 0 is a norm
-  KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double), hipMemcpyDeviceToHost, s));
+int axpy_norm(int64_t n, double* w, double a, const double* v, double* d_scratch, double* d_h, double* h_pin, hipStream_t s, double* out) {
+  hipLaunchKernelGGL(axpy_norm_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, w, a, v, d_scratch);
+  hipLaunchKernelGGL(mgs_finish_kernel, dim3(1), dim3(kThreads), 0, s, d_scratch, 0, d_h);      // ncols = 0: row 0 is a norm
+  KRY_HIP(hipMemcpyAsync(h_pin, d_h, sizeof(double), hipMemcpyDeviceToHost, s));
   KRY_HIP(hipStreamSynchronize(s));
-  *out = ws->h_pin[0];
+  *out = h_pin[0];
   return FMMBEM_OK;
+}
+
+int axpy_norm(SolverWs* ws, double* w, double a, const double* v, hipStream_t s, double* out) {
+  return axpy_norm(ws->n, w, a, v, ws->d_scratch, ws->d_h, ws->h_pin, s, out);
 }
 
 // SolverOptions::predict_p (SolverOptions.hpp:25-38), the (unsigned) cast of the reference kept as far as it matters: a
@@ -366,6 +494,57 @@ void plane_rotation(double dx, double dy, double* cs, double* sn) {             
 int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const double* d_b, const fmmbem_preconditioner* M,
           fmmbem_solver_log* log, hipStream_t s, int depth);
 
+// what a solve refuses before it touches anything, the single solver and the batched one alike
+int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem_preconditioner* M, int depth, int* device, int64_t* n,
+                int* plan_pmax, SolverWs*** slot) {
+  KRY_TRY(fmmbem::plan_solver_info(plan, device, n, plan_pmax, slot));
+  if (depth > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "fmmbem_gmres: a preconditioner's inner solve cannot itself be preconditioned by a plan");
+  if (so.restart < 1 || so.max_iters < 0 || so.max_p < 1 || !(so.residual > 0.0))
+    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: restart >= 1, max_iters >= 0, max_p >= 1, residual > 0 required");
+  const int kind = M ? M->kind : FMMBEM_PC_IDENTITY;
+  if (kind == FMMBEM_PC_DIAGONAL && !M->reciprocals) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: diagonal preconditioner without reciprocals");
+  if (kind == FMMBEM_PC_INNER_PLAN) {
+    if (!M->inner_plan || M->inner_plan == plan) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner needs a plan of its own");
+    int dv = 0, pm = 0; int64_t nn = 0; SolverWs** sl = nullptr;
+    KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
+    if (dv != *device || nn != *n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
+  }
+  if (kind < 0 || kind > FMMBEM_PC_INNER_PLAN) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: unknown preconditioner kind");
+  return FMMBEM_OK;
+}
+
+// The host side of one system: the (R+1) x R Hessenberg matrix, the Givens rotations and the rotated right-hand side
+struct Arnoldi {
+  int R = 0;
+  std::vector<double> H, cs, sn, sv;
+  explicit Arnoldi(int restart) : R(restart), H((size_t)(restart + 1) * restart, 0.0), cs(restart, 0.0), sn(restart, 0.0), sv(restart + 1, 0.0) {}
+  double& Hm(int r, int c) { return H[(size_t)r * R + c]; }
+  // column i arrives (h: i + 2 numbers): the earlier rotations, the new one, the right-hand side (GMRES.hpp:108-117, :214-218)
+  void column(int i, const double* h) {
+    for (int k = 0; k <= i + 1; ++k) Hm(k, i) = h[k];
+    for (int k = 0; k < i; ++k) {          // PlaneRotation, :108-117
+      const double t = cs[k] * Hm(k, i) + sn[k] * Hm(k + 1, i);
+      Hm(k + 1, i) = -sn[k] * Hm(k, i) + cs[k] * Hm(k + 1, i);
+      Hm(k, i) = t;
+    }
+    plane_rotation(Hm(i, i), Hm(i + 1, i), &cs[i], &sn[i]);
+    {
+      const double t = cs[i] * Hm(i, i) + sn[i] * Hm(i + 1, i);
+      Hm(i + 1, i) = -sn[i] * Hm(i, i) + cs[i] * Hm(i + 1, i);
+      Hm(i, i) = t;
+    }
+    sv[i + 1] = -sn[i] * sv[i];
+    sv[i] = cs[i] * sv[i];
+  }
+  // solve the upper triangular system in place (:228-234): sv[0..i] become the coefficients y
+  void back_substitute(int i) {
+    for (int j = i; j >= 0; --j) {
+      sv[j] /= Hm(j, j);
+      for (int k = j - 1; k >= 0; --k) sv[k] -= Hm(k, j) * sv[j];
+    }
+  }
+};
+
 // z = M(v): returns in *z either v itself (identity) or ws->z / the given buffer
 int apply_pc(SolverWs* ws, const fmmbem_preconditioner* M, const double* v, double* zbuf, const double** z, hipStream_t s, int depth) {
   const int kind = M ? M->kind : FMMBEM_PC_IDENTITY;
@@ -387,19 +566,8 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const
   int device = 0, plan_pmax = 0;
   int64_t n = 0;
   SolverWs** slot = nullptr;
-  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &plan_pmax, &slot));
-  if (depth > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "fmmbem_gmres: a preconditioner's inner solve cannot itself be preconditioned by a plan");
-  if (so.restart < 1 || so.max_iters < 0 || so.max_p < 1 || !(so.residual > 0.0))
-    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: restart >= 1, max_iters >= 0, max_p >= 1, residual > 0 required");
+  KRY_TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
   const int kind = M ? M->kind : FMMBEM_PC_IDENTITY;
-  if (kind == FMMBEM_PC_DIAGONAL && !M->reciprocals) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: diagonal preconditioner without reciprocals");
-  if (kind == FMMBEM_PC_INNER_PLAN) {
-    if (!M->inner_plan || M->inner_plan == plan) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner needs a plan of its own");
-    int dv = 0, pm = 0; int64_t nn = 0; SolverWs** sl = nullptr;
-    KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
-    if (dv != device || nn != n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
-  }
-  if (kind < 0 || kind > FMMBEM_PC_INNER_PLAN) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: unknown preconditioner kind");
   const int R = so.restart;
   // the inner loop runs while i + 1 < R and i + 1 <= max_iters (GMRES.hpp:221): at most min(R, max_iters + 1) columns
   const int most = (int)std::min<int64_t>(R, (int64_t)so.max_iters + 1);
@@ -407,8 +575,8 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const
   KRY_TRY(ensure_ws(slot, device, n, most + 1, so.flexible ? most : 0, &ws));
   const int64_t ld = ws->ld;
   const int grid = sweep_grid(n);
-  std::vector<double> H((size_t)(R + 1) * R, 0.0), cs(R, 0.0), sn(R, 0.0), sv(R + 1, 0.0);
-  auto Hm = [&](int r, int c) -> double& { return H[(size_t)r * R + c]; };
+  Arnoldi ar(R);
+  std::vector<double>& sv = ar.sv;
   if (log) { log->iterations = 0; log->residual = 0.0; }
 
   // scale residual by |b| (GMRES.hpp:162)
@@ -438,29 +606,12 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const
       KRY_TRY(fmmbem_mgs_column_device(n, ws->w, ws->V, ld, i + 1, ws->d_h, ws->V + (int64_t)(i + 1) * ld, ws->d_scratch, s));
       KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, s));
       KRY_HIP(hipStreamSynchronize(s));
-      for (int k = 0; k <= i + 1; ++k) Hm(k, i) = ws->h_pin[k];
-      for (int k = 0; k < i; ++k) {          // PlaneRotation, :108-117
-        const double t = cs[k] * Hm(k, i) + sn[k] * Hm(k + 1, i);
-        Hm(k + 1, i) = -sn[k] * Hm(k, i) + cs[k] * Hm(k + 1, i);
-        Hm(k, i) = t;
-      }
-      plane_rotation(Hm(i, i), Hm(i + 1, i), &cs[i], &sn[i]);
-      {
-        const double t = cs[i] * Hm(i, i) + sn[i] * Hm(i + 1, i);
-        Hm(i + 1, i) = -sn[i] * Hm(i, i) + cs[i] * Hm(i + 1, i);
-        Hm(i, i) = t;
-      }
-      sv[i + 1] = -sn[i] * sv[i];
-      sv[i] = cs[i] * sv[i];
+      ar.column(i, ws->h_pin);
       resid = sv[i + 1] / normb;
       if (log && log->p && log->resid && iter <= log->capacity) { log->p[iter - 1] = cur_p; log->resid[iter - 1] = std::fabs(resid); }
       if (std::fabs(resid) < so.residual) break;
     } while (i + 1 < R && i + 1 <= so.max_iters && std::fabs(resid) > so.residual);
-    // solve the upper triangular system in place (:228-234)
-    for (int j = i; j >= 0; --j) {
-      sv[j] /= Hm(j, j);
-      for (int k = j - 1; k >= 0; --k) sv[k] -= Hm(k, j) * sv[j];
-    }
+    ar.back_substitute(i);
     // update the solution (:237-241; FGMRES :368-371)
     if (kind == FMMBEM_PC_INNER_PLAN && !so.flexible) {
       for (int j = 0; j <= i; ++j) {         // x += y_j M(V_j): the inner solve again, column by column, as the reference
@@ -471,7 +622,8 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const
     } else {
       for (int j = 0; j <= i; ++j) ws->h_pin[j] = sv[j];
       KRY_HIP(hipMemcpyAsync(ws->d_y, ws->h_pin, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, d_x, so.flexible ? ws->Z : ws->V, ld, i + 1, ws->d_y,
+      // FGMRES with the identity: Z_j = V_j was never copied (apply_pc hands V_j back), the update reads V
+      hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, d_x, (so.flexible && kind != FMMBEM_PC_IDENTITY) ? ws->Z : ws->V, ld, i + 1, ws->d_y,
                          (!so.flexible && kind == FMMBEM_PC_DIAGONAL) ? M->reciprocals : (const double*)nullptr);
       KRY_HIP(hipStreamSynchronize(s));      // h_pin is reused by the next cycle
     }
@@ -479,6 +631,290 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const
   KRY_HIP(hipStreamSynchronize(s));
   if (log) { log->iterations = iter; log->residual = std::fabs(resid); }
   return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres: a launch failed");
+}
+
+
+// ================================================================================================================
+// fmmbem_gmres_batch: k independent solves of the loop above on one plan, advanced in lockstep.  Every system keeps its own
+// Krylov space, Hessenberg matrix, rotations, residual estimate and order; restart length and max_iters are common, so the
+// systems still running share the column index i and the iteration count.  Per iteration: the matvecs of the systems that ask
+// for the same order are one fmmbem_plan_execute_batch_device, the Arnoldi columns of all of them one chain of i + 3 launches
+// with the system as the grid's second dimension, and their Hessenberg columns cross to the host in one copy behind one
+// synchronisation.  Each system runs the operations of solve() on its own data in solve()'s order: same bits.
+// ================================================================================================================
+void reset_batch(fmmbem::BatchWs* b) {
+  for (double** p : {&b->w, &b->z, &b->V, &b->Z, &b->d_h, &b->d_y, &b->d_scratch}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  if (b->h_pin) (void)hipHostFree(b->h_pin);
+  b->h_pin = nullptr;
+  b->n = b->ld = 0;
+  b->cap = b->vcols = b->zcols = b->hcap = 0;
+}
+
+int grow_batch(fmmbem::BatchWs* b, int64_t n, int k, int vcols, int zcols) {
+  const int64_t ld = (n + 1) & ~int64_t(1);                      // even stride: every vector of every system on a 16-byte boundary
+  if (b->n != n || b->cap < k) {
+    reset_batch(b);
+    KRY_TRY(grow(&b->w, (size_t)ld * k));
+    KRY_TRY(grow(&b->z, (size_t)ld * k));
+    b->n = n; b->ld = ld; b->cap = k;
+  }
+  const size_t col = (size_t)ld * b->cap;
+  if (b->vcols < vcols) { b->vcols = 0; KRY_TRY(grow(&b->V, col * vcols)); b->vcols = vcols; }
+  if (b->zcols < zcols) { b->zcols = 0; KRY_TRY(grow(&b->Z, col * zcols)); b->zcols = zcols; }
+  if (b->hcap < vcols + 1) {
+    const int hcap = vcols + 1;
+    b->hcap = 0;
+    KRY_TRY(grow(&b->d_h, (size_t)hcap * b->cap));
+    KRY_TRY(grow(&b->d_y, (size_t)hcap * b->cap));
+    KRY_TRY(grow(&b->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap) * b->cap));
+    if (b->h_pin) (void)hipHostFree(b->h_pin);
+    b->h_pin = nullptr;
+    KRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_pin), sizeof(double) * 2 * (size_t)hcap * b->cap, hipHostMallocDefault));
+    b->hcap = hcap;
+  }
+  return FMMBEM_OK;
+}
+
+// as ensure_ws: a failed allocation leaves the batched workspace empty (the next batched solve allocates from scratch) and does
+// not touch the single solver's
+int ensure_batch(SolverWs** slot, int device, int64_t n, int k, int vcols, int zcols, fmmbem::BatchWs** out) {
+  if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
+  fmmbem::BatchWs* b = &(*slot)->batch;
+  const int rc = grow_batch(b, n, k, vcols, zcols);
+  if (rc != FMMBEM_OK) { reset_batch(b); return rc; }
+  *out = b;
+  return FMMBEM_OK;
+}
+
+struct BatchSystem {
+  double* x;
+  const double* b;
+  fmmbem_solver_log* log;
+  Arnoldi ar;
+  double normb = 0, resid = 0;
+  int cur_p = 0;
+  BatchSystem(double* x_, const double* b_, fmmbem_solver_log* log_, int R) : x(x_), b(b_), log(log_), ar(R) {}
+};
+
+struct MatvecJob { int p; const double* x; double* y; };
+
+// y = A x for every job, the jobs of one order through fmmbem_plan_execute_batch_device: as many vectors per call as lie
+// equally spaced in x and in y (all of a group when it is one column of the workspace and no system between them has left)
+int batch_matvecs(fmmbem_plan* plan, int64_t n, const std::vector<MatvecJob>& jobs, hipStream_t s) {
+  std::vector<char> done(jobs.size(), 0);
+  for (size_t a = 0; a < jobs.size(); ++a) {
+    if (done[a]) continue;
+    std::vector<size_t> g;                                         // the jobs at this order, in system order
+    for (size_t c = a; c < jobs.size(); ++c)
+      if (!done[c] && jobs[c].p == jobs[a].p) { g.push_back(c); done[c] = 1; }
+    for (size_t f = 0; f < g.size();) {
+      size_t cnt = 1;
+      ptrdiff_t dx = n, dy = n;
+      if (f + 1 < g.size()) {
+        dx = jobs[g[f + 1]].x - jobs[g[f]].x;
+        dy = jobs[g[f + 1]].y - jobs[g[f]].y;
+        if (dx >= n && dy >= n) {
+          cnt = 2;
+          while (f + cnt < g.size() && jobs[g[f + cnt]].x - jobs[g[f + cnt - 1]].x == dx && jobs[g[f + cnt]].y - jobs[g[f + cnt - 1]].y == dy) ++cnt;
+        } else {
+          dx = dy = n;
+        }
+      }
+      KRY_TRY(fmmbem_plan_execute_batch_device(plan, jobs[a].p, (int)cnt, jobs[g[f]].x, (size_t)dx, jobs[g[f]].y, (size_t)dy, s));
+      f += cnt;
+    }
+  }
+  return FMMBEM_OK;
+}
+
+int solve_batch(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
+                const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth);
+
+struct BatchSolver {
+  fmmbem_plan* plan;
+  const fmmbem_solver_options& so;
+  const fmmbem_preconditioner* M;
+  hipStream_t s;
+  int depth, kind, plan_pmax;
+  int64_t n, ld;
+  fmmbem::BatchWs* ws;
+  std::vector<BatchSystem> sys;
+
+  double* wv(int j) const { return ws->w + (int64_t)j * ld; }
+  double* zv(int j) const { return ws->z + (int64_t)j * ld; }
+  double* Vc(int c, int j) const { return ws->V + ((int64_t)c * ws->cap + j) * ld; }
+  double* Zc(int c, int j) const { return ws->Z + ((int64_t)c * ws->cap + j) * ld; }
+  double* scratch(int j) const { return ws->d_scratch + (size_t)j * fmmbem_mgs_scratch_doubles(ws->hcap); }
+
+  // a launch per kSysPerLaunch systems: f(table, first position of the table in `act`)
+  template <class F> void for_tables(const std::vector<int>& act, F f) const {
+    for (size_t a = 0; a < act.size(); a += kSysPerLaunch) {
+      SysTable t;
+      t.count = (int)std::min<size_t>(kSysPerLaunch, act.size() - a);
+      for (int q = 0; q < kSysPerLaunch; ++q) t.slot[q] = q < t.count ? act[a + q] : 0;
+      f(t, a);
+    }
+  }
+
+  int norm(int j, double* w, double a, const double* v, double* out) const {
+    return axpy_norm(n, w, a, v, scratch(j), ws->d_h, ws->h_pin, s, out);
+  }
+
+  // z_j = M(column c of system j) for the systems of act -> zs; one launch (diagonal) or one batched inner solve
+  int apply_pc(const std::vector<int>& act, int c, bool keep, std::vector<const double*>* zs) const {
+    zs->clear();
+    if (kind == FMMBEM_PC_IDENTITY) {
+      for (int j : act) zs->push_back(Vc(c, j));
+      return FMMBEM_OK;
+    }
+    double* out = keep ? Zc(c, 0) : ws->z;                          // system j: j * ld further on, either way
+    for (int j : act) zs->push_back(out + (int64_t)j * ld);
+    if (kind == FMMBEM_PC_DIAGONAL) {
+      for_tables(act, [&](const SysTable& t, size_t) {
+        hipLaunchKernelGGL(scale_multi_kernel, dim3(sweep_grid(n), t.count), dim3(kThreads), 0, s, n, Vc(c, 0), M->reciprocals, out, ld, t);
+      });
+      return FMMBEM_OK;
+    }
+    // LocalPC.hpp:35-41: fill(y, 0); GMRES(plan, y, x, options) -- for all systems of act in one batched solve on the inner plan
+    std::vector<double*> y;
+    std::vector<const double*> v;
+    for (int j : act) {
+      y.push_back(out + (int64_t)j * ld);
+      v.push_back(Vc(c, j));
+    }
+    // one memset from the first to the last system of act: a system in between that has left has finished with its z
+    KRY_HIP(hipMemsetAsync(y.front(), 0, sizeof(double) * (size_t)((int64_t)(act.back() - act.front()) * ld + n), s));
+    return solve_batch(M->inner_plan, M->inner, (int)act.size(), y.data(), v.data(), nullptr, nullptr, s, depth + 1);
+  }
+
+  // the Arnoldi column of every system of act: fmmbem_mgs_column_device with the system as the grid's second dimension; the
+  // columns land in d_h in the order of act, ncols + 1 doubles each
+  void mgs_columns(const std::vector<int>& act, int ncols) const {
+    const int64_t want = (n / 4 + kThreads - 1) / kThreads + 1;
+    const int grid = (int)(want < kBlocks ? want : kBlocks);        // as fmmbem_mgs_column_device: the partial sums depend on it
+    const int64_t ps = fmmbem_mgs_scratch_doubles(ws->hcap);
+    double* sc = ws->d_scratch;
+    for_tables(act, [&](const SysTable& t, size_t first) {
+      for (int c = 0; c <= ncols; ++c)
+        hipLaunchKernelGGL(mgs_step_multi_kernel, dim3(grid, t.count), dim3(kThreads), 0, s, n, ws->w, c ? Vc(c - 1, 0) : (const double*)nullptr,
+                           c ? sc + (size_t)(c - 1) * kBlocks : (const double*)nullptr, c < ncols ? Vc(c, 0) : (const double*)nullptr,
+                           sc + (size_t)c * kBlocks, ld, ps, t);
+      hipLaunchKernelGGL(mgs_scale_multi_kernel, dim3(grid, t.count), dim3(kThreads), 0, s, n, ws->w, sc + (size_t)ncols * kBlocks, Vc(ncols, 0), ld, ps, t);
+      hipLaunchKernelGGL(mgs_finish_multi_kernel, dim3(ncols + 1, t.count), dim3(kThreads), 0, s, sc, ncols, ws->d_h + first * (size_t)(ncols + 1), ps, t);
+    });
+  }
+
+  // back substitution and x += ... of system j after column i (GMRES.hpp:228-241; FGMRES :368-371)
+  int update(int j, int i) {
+    BatchSystem& S = sys[j];
+    S.ar.back_substitute(i);
+    const int grid = sweep_grid(n);
+    if (kind == FMMBEM_PC_INNER_PLAN && !so.flexible) {
+      const std::vector<int> one(1, j);
+      std::vector<const double*> z;
+      for (int c = 0; c <= i; ++c) {           // x += y_c M(V_c): the inner solve again, column by column, as the reference
+        KRY_TRY(apply_pc(one, c, false, &z));
+        hipLaunchKernelGGL(mgs_axpy_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, S.ar.sv[c], z[0]);
+      }
+      return FMMBEM_OK;
+    }
+    // this system's slice of the pinned y area: rewritten at the earliest one synchronised iteration later
+    double* hy = ws->h_pin + (size_t)ws->hcap * (ws->cap + j);
+    double* dy = ws->d_y + (size_t)ws->hcap * j;
+    for (int c = 0; c <= i; ++c) hy[c] = S.ar.sv[c];
+    KRY_HIP(hipMemcpyAsync(dy, hy, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, (so.flexible && kind != FMMBEM_PC_IDENTITY) ? Zc(0, j) : Vc(0, j), ld * ws->cap, i + 1, dy,
+                       (!so.flexible && kind == FMMBEM_PC_DIAGONAL) ? M->reciprocals : (const double*)nullptr);
+    return FMMBEM_OK;
+  }
+
+  int run() {
+    const int R = so.restart;
+    const int k = (int)sys.size();
+    std::vector<int> live;
+    for (int j = 0; j < k; ++j) {
+      BatchSystem& S = sys[j];
+      if (S.log) { S.log->iterations = 0; S.log->residual = 0.0; }
+      KRY_TRY(norm(j, const_cast<double*>(S.b), 0.0, nullptr, &S.normb));      // scale residual by |b| (GMRES.hpp:162)
+      if (S.normb == 0.0) continue;            // b = 0: x = x0 is returned, as the single solver
+      S.cur_p = std::min(so.initial_p > 0 ? so.initial_p : so.max_p, plan_pmax);
+      live.push_back(j);
+    }
+    int iter = 0;
+    const auto finish = [&](int j) {
+      if (sys[j].log) { sys[j].log->iterations = iter; sys[j].log->residual = std::fabs(sys[j].resid); }
+    };
+    std::vector<MatvecJob> jobs;
+    std::vector<const double*> zs;
+    while (!live.empty()) {                    // outer (restart) loop, :166 -- the systems still running restart together
+      jobs.clear();
+      for (int j : live) jobs.push_back({sys[j].cur_p, sys[j].x, wv(j)});      // w = A x at each system's current order
+      KRY_TRY(batch_matvecs(plan, n, jobs, s));
+      std::vector<int> act;
+      for (int j : live) {
+        BatchSystem& S = sys[j];
+        double beta = 0;
+        KRY_TRY(norm(j, wv(j), -1.0, S.b, &beta));                             // w -= b; beta = |w|
+        if (beta == 0.0) { S.resid = 0.0; finish(j); continue; }               // x solves the system exactly
+        hipLaunchKernelGGL(scale_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, wv(j), -1.0 / beta, (const double*)nullptr, Vc(0, j));
+        S.ar.sv[0] = beta;
+        S.resid = S.ar.sv[0] / S.normb;
+        act.push_back(j);
+      }
+      if (act.empty()) break;
+      int i = -1;
+      for (;;) {                               // inner loop, :186 -- one column of every system of act
+        ++i;
+        ++iter;
+        for (int j : act) sys[j].cur_p = order_for(so, sys[j].resid, plan_pmax);
+        KRY_TRY(apply_pc(act, i, so.flexible != 0, &zs));
+        jobs.clear();
+        for (size_t a = 0; a < act.size(); ++a) jobs.push_back({sys[act[a]].cur_p, zs[a], wv(act[a])});
+        KRY_TRY(batch_matvecs(plan, n, jobs, s));
+        mgs_columns(act, i + 1);
+        KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2) * act.size(), hipMemcpyDeviceToHost, s));
+        KRY_HIP(hipStreamSynchronize(s));
+        std::vector<int> stay;
+        for (size_t a = 0; a < act.size(); ++a) {
+          const int j = act[a];
+          BatchSystem& S = sys[j];
+          S.ar.column(i, ws->h_pin + a * (size_t)(i + 2));
+          S.resid = S.ar.sv[i + 1] / S.normb;
+          if (S.log && S.log->p && S.log->resid && iter <= S.log->capacity) { S.log->p[iter - 1] = S.cur_p; S.log->resid[iter - 1] = std::fabs(S.resid); }
+          if (std::fabs(S.resid) > so.residual) { stay.push_back(j); continue; }
+          KRY_TRY(update(j, i));               // converged (or not a number): this system's solve ends here, as its own loops would
+          finish(j);
+        }
+        act.swap(stay);
+        if (act.empty() || !(i + 1 < R && i + 1 <= so.max_iters)) break;
+      }
+      for (int j : act) KRY_TRY(update(j, i));
+      if (iter < so.max_iters) { live.swap(act); continue; }
+      for (int j : act) finish(j);
+      break;
+    }
+    KRY_HIP(hipStreamSynchronize(s));
+    return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres_batch: a launch failed");
+  }
+};
+
+int solve_batch(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
+                const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth) {
+  int device = 0, plan_pmax = 0;
+  int64_t n = 0;
+  SolverWs** slot = nullptr;
+  KRY_TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
+  // the inner loop runs while i + 1 < R and i + 1 <= max_iters (GMRES.hpp:221): at most min(R, max_iters + 1) columns
+  const int most = (int)std::min<int64_t>(so.restart, (int64_t)so.max_iters + 1);
+  fmmbem::BatchWs* ws = nullptr;
+  KRY_TRY(ensure_batch(slot, device, n, k, most + 1, so.flexible ? most : 0, &ws));
+  BatchSolver B{plan, so, M, s, depth, M ? M->kind : FMMBEM_PC_IDENTITY, plan_pmax, n, ws->ld, ws, {}};
+  B.sys.reserve((size_t)k);
+  for (int j = 0; j < k; ++j) B.sys.emplace_back(xs[j], bs[j], logs ? logs[j] : nullptr, so.restart);
+  return B.run();
 }
 
 }  // namespace
@@ -534,5 +970,75 @@ extern "C" int fmmbem_gmres(fmmbem_plan* plan, const fmmbem_solver_options* opts
   if (rc != FMMBEM_OK) return rc;
   KRY_HIP(hipMemcpy(x, d_x, bytes, hipMemcpyDeviceToHost));
   if (log) log->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return FMMBEM_OK;
+}
+
+namespace {
+int batch_entry_args(const fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, const void* x, const void* b, const char* who) {
+  if (!plan || !opts || !x || !b) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": null argument");
+  if (k < 1) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": k < 1 systems");
+  return FMMBEM_OK;
+}
+}  // namespace
+
+extern "C" int fmmbem_gmres_batch_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* d_x, size_t ldx,
+                                         const double* d_b, size_t ldb, const fmmbem_preconditioner* M, fmmbem_solver_log* logs, void* stream) {
+  KRY_TRY(batch_entry_args(plan, opts, k, d_x, d_b, "fmmbem_gmres_batch_device"));
+  if (ldx < fmmbem::plan_unknowns(plan) || ldb < fmmbem::plan_unknowns(plan))
+    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres_batch_device: leading dimension shorter than a vector");
+  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
+  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
+  DevGuard guard(device);
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<double*> xs((size_t)k);
+  std::vector<const double*> bs((size_t)k);
+  std::vector<fmmbem_solver_log*> lg((size_t)k, nullptr);
+  for (int j = 0; j < k; ++j) { xs[j] = d_x + (size_t)j * ldx; bs[j] = d_b + (size_t)j * ldb; if (logs) lg[j] = logs + j; }
+  const int rc = solve_batch(plan, *opts, k, xs.data(), bs.data(), M, lg.data(), static_cast<hipStream_t>(stream), 0);
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;               // the wall time of the call, for every system
+  return rc;
+}
+
+extern "C" int fmmbem_gmres_batch(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* x, size_t ldx,
+                                  const double* b, size_t ldb, const fmmbem_preconditioner* M, fmmbem_solver_log* logs) {
+  KRY_TRY(batch_entry_args(plan, opts, k, x, b, "fmmbem_gmres_batch"));
+  if (ldx < fmmbem::plan_unknowns(plan) || ldb < fmmbem::plan_unknowns(plan))
+    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres_batch: leading dimension shorter than a vector");
+  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
+  KRY_TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
+  DevGuard guard(device);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
+  fmmbem::BatchWs* ws = &(*slot)->batch;
+  const int64_t ld = (n + 1) & ~int64_t(1);
+  const size_t bytes = sizeof(double) * (size_t)n;
+  if (ws->xb_doubles < (size_t)2 * k * ld) {  // all x, then all b: staged once per solve
+    ws->xb_doubles = 0;
+    KRY_TRY(grow(&ws->d_xb, (size_t)2 * k * ld));
+    ws->xb_doubles = (size_t)2 * k * ld;
+  }
+  double* d_x = ws->d_xb;
+  double* d_b = ws->d_xb + (size_t)k * ld;
+  fmmbem_preconditioner Md;
+  const fmmbem_preconditioner* Mp = M;
+  if (M && M->kind == FMMBEM_PC_DIAGONAL) {
+    KRY_TRY(grow(&ws->d_recip, (size_t)n));
+    KRY_HIP(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
+    Md = *M;
+    Md.reciprocals = ws->d_recip;
+    Mp = &Md;
+  }
+  KRY_HIP(hipMemcpy2D(d_x, sizeof(double) * (size_t)ld, x, sizeof(double) * ldx, bytes, (size_t)k, hipMemcpyHostToDevice));
+  KRY_HIP(hipMemcpy2D(d_b, sizeof(double) * (size_t)ld, b, sizeof(double) * ldb, bytes, (size_t)k, hipMemcpyHostToDevice));
+  std::vector<double*> xs((size_t)k);
+  std::vector<const double*> bs((size_t)k);
+  std::vector<fmmbem_solver_log*> lg((size_t)k, nullptr);
+  for (int j = 0; j < k; ++j) { xs[j] = d_x + (size_t)j * ld; bs[j] = d_b + (size_t)j * ld; if (logs) lg[j] = logs + j; }
+  const int rc = solve_batch(plan, *opts, k, xs.data(), bs.data(), Mp, lg.data(), nullptr, 0);
+  if (rc != FMMBEM_OK) return rc;
+  KRY_HIP(hipMemcpy2D(x, sizeof(double) * ldx, d_x, sizeof(double) * (size_t)ld, bytes, (size_t)k, hipMemcpyDeviceToHost));
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;
   return FMMBEM_OK;
 }

@@ -42,6 +42,7 @@ int fail(int code, const std::string& msg) {          // also used by mesh_io.cp
 struct SolverWs;                                      // krylov.hip
 void solver_ws_destroy(SolverWs* ws);
 int plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, int* p_max, SolverWs*** slot);
+size_t plan_unknowns(const fmmbem_plan* plan);
 }  // namespace fmmbem
 
 namespace {
@@ -2741,3 +2742,8 @@ int fmmbem::plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, 
   return FMMBEM_OK;
 }
 
+// doubles of one x vector of the plan: what the batched solver checks its leading dimensions against before anything else
+size_t fmmbem::plan_unknowns(const fmmbem_plan* plan) {
+  if (plan->targets) return (size_t)plan->hp.n_src;
+  return (size_t)plan->hp.n * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);
+}

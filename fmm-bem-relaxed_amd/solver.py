@@ -238,6 +238,21 @@ def _c_options(opts, stokes, flexible, initial_p):
     return o
 
 
+def _c_preconditioner(M, who):
+    from . import _capi
+    if M is None:
+        return None
+    pc = _capi.Preconditioner()
+    if isinstance(M, Diagonal):
+        pc.kind, pc.reciprocals = _capi.PC_DIAGONAL, M.recip.data_ptr()
+    elif isinstance(M, _InnerSolver):
+        pc.kind, pc.inner_plan = _capi.PC_INNER_PLAN, M.plan._h
+        pc.inner = _c_options(M.options, False, False, M.options.max_p)
+    else:
+        raise TypeError("%s: M must be None, Diagonal, LocalInnerSolver or BlockDiagonal" % who)
+    return pc
+
+
 def gmres_capi(MV, x, b, opts, M=None, log=None, stokes=False, flexible=False):
     """The same solve through the C ABI's device-resident solver (include/fmmbem.h fmmbem_gmres_device; csrc/krylov.hip):
     what a C or C++ caller of the library gets.  MV: an FMM_plan; x, b: float64 CUDA tensors (x updated in place);
@@ -245,16 +260,7 @@ def gmres_capi(MV, x, b, opts, M=None, log=None, stokes=False, flexible=False):
     import ctypes as C
     from . import _capi
     o = _c_options(opts, stokes, flexible, MV.kernel().P)
-    pc = None
-    if M is not None:
-        pc = _capi.Preconditioner()
-        if isinstance(M, Diagonal):
-            pc.kind, pc.reciprocals = _capi.PC_DIAGONAL, M.recip.data_ptr()
-        elif isinstance(M, _InnerSolver):
-            pc.kind, pc.inner_plan = _capi.PC_INNER_PLAN, M.plan._h
-            pc.inner = _c_options(M.options, False, False, M.options.max_p)
-        else:
-            raise TypeError("gmres_capi: M must be None, Diagonal, LocalInnerSolver or BlockDiagonal")
+    pc = _c_preconditioner(M, "gmres_capi")
     cap = max(1, opts.max_iters + opts.restart + 2)
     ps, rs = (C.c_int32 * cap)(), (C.c_double * cap)()
     lg = _capi.SolverLog()
@@ -264,6 +270,43 @@ def gmres_capi(MV, x, b, opts, M=None, log=None, stokes=False, flexible=False):
     if log is not None:
         log.extend((k + 1, int(ps[k]), float(rs[k])) for k in range(min(lg.iterations, cap)))
     return x, lg.iterations, lg.residual, lg.seconds
+
+
+def gmres_capi_batch(MV, X, B, opts, M=None, logs=None, stokes=False, flexible=False):
+    """k right-hand sides on one plan through fmmbem_gmres_batch_device: k independent solves in lockstep, each bit for bit its
+    gmres_capi solve, their matvecs batched by order and their Arnoldi columns one launch chain (include/fmmbem.h).
+    X, B: float64 CUDA tensors (k, n) -- (k, n, 3) for Stokes -- on the plan's device, rows contiguous (the row stride is the
+    leading dimension); X holds the initial guesses and is updated in place.  logs: optional list of k lists, each receiving
+    (iteration, p, |residual|) per inner iteration of its system.  Runs on torch's current stream.
+    Returns (X, [iterations], [|residual|], seconds)."""
+    import ctypes as C
+    from . import _capi
+    if X.shape != B.shape or X.dim() != (3 if stokes else 2) or X.shape[0] < 1:
+        raise ValueError("gmres_capi_batch: X and B must both be (k, n%s) with k >= 1" % (", 3" if stokes else ""))
+    k, n = X.shape[0], MV.n * MV.dof
+    for t in (X, B):
+        if t.dtype != torch.float64 or not t.is_cuda or t[0].numel() != n or not t[0].is_contiguous() or (k > 1 and t.stride(0) < n):
+            raise ValueError("gmres_capi_batch: float64 CUDA tensors of k contiguous rows of %d values required" % n)
+    if logs is not None and len(logs) != k:
+        raise ValueError("gmres_capi_batch: logs must hold one list per system")
+    o = _c_options(opts, stokes, flexible, MV.kernel().P)
+    pc = _c_preconditioner(M, "gmres_capi_batch")
+    cap = max(1, opts.max_iters + opts.restart + 2)
+    ps, rs = [(C.c_int32 * cap)() for _ in range(k)], [(C.c_double * cap)() for _ in range(k)]
+    lg = (_capi.SolverLog * k)()
+    for j in range(k):
+        lg[j].capacity = cap
+        lg[j].p = C.cast(ps[j], C.POINTER(C.c_int32))
+        lg[j].resid = C.cast(rs[j], C.POINTER(C.c_double))
+    ldx = X.stride(0) if k > 1 else n
+    ldb = B.stride(0) if k > 1 else n
+    _capi.check(_capi.lib().fmmbem_gmres_batch_device(MV._h, C.byref(o), k, X.data_ptr(), ldx, B.data_ptr(), ldb,
+                                                      C.byref(pc) if pc is not None else None, lg,
+                                                      torch.cuda.current_stream(X.device).cuda_stream))
+    if logs is not None:
+        for j in range(k):
+            logs[j].extend((i + 1, int(ps[j][i]), float(rs[j][i])) for i in range(min(lg[j].iterations, cap)))
+    return X, [lg[j].iterations for j in range(k)], [lg[j].residual for j in range(k)], lg[0].seconds
 
 
 class Diagonal:

@@ -395,6 +395,28 @@ int fmmbem_gmres_device(fmmbem_plan *plan, const fmmbem_solver_options *opts, do
 int fmmbem_gmres(fmmbem_plan *plan, const fmmbem_solver_options *opts, double *x, const double *b,
                  const fmmbem_preconditioner *M, fmmbem_solver_log *log);
 
+/* Several right-hand sides on one plan: k INDEPENDENT solves of the loop above, advanced in lockstep -- not a block Krylov
+ * method: every system keeps its own Krylov space, Hessenberg matrix, rotations, residual estimate and relaxed order.  For
+ * every system j the solution, iterations, residual and the p[] / resid[] histories are bit for bit what
+ * fmmbem_gmres_device(plan, opts, x_j, b_j, M, &logs[j]) gives for it alone.  What the k systems share is the work per
+ * iteration: the matvecs of the systems that ask for the same order go through one fmmbem_plan_execute_batch_device (one pass
+ * over the near-field matrix where fmmbem_plan_batch_width > 1), the Arnoldi columns of all of them are one chain of i + 3
+ * launches (per 64 systems) and reach the host in one copy behind one synchronisation.  Restart length and max_iters are
+ * common; a system that converges leaves, the others restart together.
+ * System j is x + j*ldx (initial guess in, solution out) and b + j*ldb, n_panels * dof doubles each, ORIGINAL panel order; the
+ * doubles between vectors are neither read nor written.  logs: NULL or k logs, each used as fmmbem_gmres uses its one (seconds:
+ * the wall time of the whole call).  One set of options and one preconditioner serve all systems; an INNER_PLAN
+ * preconditioner's inner solves are themselves one batched solve on the inner plan.
+ * k < 1, a null pointer, ldx or ldb shorter than a vector: FMMBEM_ERR_INVALID, checked first; everything else is refused as
+ * fmmbem_gmres(_device) refuses it.  The workspace (k times the single solver's) is allocated on the first batched solve and
+ * kept with the plan; if that fails the call returns FMMBEM_ERR_ALLOC and single solves still work. */
+int fmmbem_gmres_batch_device(fmmbem_plan *plan, const fmmbem_solver_options *opts, int k,
+                              double *d_x, size_t ldx, const double *d_b, size_t ldb,
+                              const fmmbem_preconditioner *M, fmmbem_solver_log *logs, void *stream);
+int fmmbem_gmres_batch(fmmbem_plan *plan, const fmmbem_solver_options *opts, int k,
+                       double *x, size_t ldx, const double *b, size_t ldb,
+                       const fmmbem_preconditioner *M, fmmbem_solver_log *logs);
+
 /* ---- split execute of a plan created with shard_upward = 1 and shard_world > 1 (no reference counterpart:
  * the reference is single-node) ----------------------------------------------------------
  *   upward:   x -> P2M and M2M of the boxes this shard owns -> d_send (exchange_doubles(p) doubles)

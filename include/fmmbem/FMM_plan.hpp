@@ -811,6 +811,41 @@ SolveReport solve(PlanAdapter<Kernel>& MV, std::vector<typename Kernel::charge_t
   }
   return rep;
 }
+
+// k right-hand sides on one plan (fmmbem_gmres_batch): every system bit for bit its own solve() above
+template <class Kernel, class Options>
+std::vector<SolveReport> solve_batch(PlanAdapter<Kernel>& MV, std::vector<std::vector<typename Kernel::charge_type>>& xs,
+                                     const std::vector<std::vector<typename Kernel::result_type>>& bs, const Options& opts,
+                                     const fmmbem_preconditioner* pc, bool flexible) {
+  if (xs.empty() || xs.size() != bs.size()) throw Error(FMMBEM_ERR_INVALID, "GMRES_batch: X and B must hold the same number (>= 1) of vectors");
+  const size_t k = xs.size(), n = xs[0].size();
+  for (size_t j = 0; j < k; ++j)
+    if (xs[j].size() != n || bs[j].size() != n) throw Error(FMMBEM_ERR_INVALID, "GMRES_batch: every x and b must have the plan's length");
+  constexpr size_t dof = sizeof(typename Kernel::charge_type) / sizeof(double);
+  const size_t ld = n * dof;
+  MV.reserve_order((int)opts.max_p);
+  fmmbem_solver_options c = c_solver_options<Kernel>(opts, flexible, MV.kernel().p());
+  std::vector<SolveReport> rep(k);
+  std::vector<fmmbem_solver_log> logs(k);
+  const int cap = opts.max_iters + opts.restart + 2;
+  std::vector<double> x(k * ld), b(k * ld);
+  for (size_t j = 0; j < k; ++j) {
+    rep[j].p.assign((size_t)cap, 0);
+    rep[j].resid.assign((size_t)cap, 0.0);
+    logs[j].capacity = cap; logs[j].p = rep[j].p.data(); logs[j].resid = rep[j].resid.data();
+    std::memcpy(x.data() + j * ld, KernelBinding<Kernel>::in(xs[j]), ld * sizeof(double));
+    std::memcpy(b.data() + j * ld, KernelBinding<Kernel>::in(bs[j]), ld * sizeof(double));
+  }
+  check(fmmbem_gmres_batch(MV.handle(), &c, (int)k, x.data(), ld, b.data(), ld, pc, logs.data()));
+  for (size_t j = 0; j < k; ++j) {
+    std::memcpy(KernelBinding<Kernel>::out(xs[j]), x.data() + j * ld, ld * sizeof(double));
+    rep[j].iterations = logs[j].iterations; rep[j].residual = logs[j].residual; rep[j].seconds = logs[j].seconds;
+    rep[j].p.resize((size_t)std::min(logs[j].iterations, cap));
+    rep[j].resid.resize(rep[j].p.size());
+    if (solver_output()) std::printf("system %d: final residual: %.4e, after %d iterations\n", (int)j, rep[j].residual, rep[j].iterations);
+  }
+  return rep;
+}
 }  // namespace detail
 
 // In a nested namespace reached through a using-directive: `fmmbem::GMRES(...)` finds the functions, argument-dependent
@@ -842,6 +877,37 @@ SolveReport FGMRES(PlanAdapter<Kernel>& MV, std::vector<typename Kernel::charge_
   std::vector<double> recip;
   detail::describe<Kernel>(M, x.size(), pc, recip);
   return detail::solve(MV, x, b, opts, &pc, true);
+}
+// Several right-hand sides on one plan, solved in lockstep (fmmbem_gmres_batch, include/fmmbem.h): xs[j] holds the initial guess of
+// system j and receives its solution, bit for bit what GMRES(MV, xs[j], bs[j], opts[, M]) gives; one report per system.  Not in
+// the reference.  The kernel object's order is left as it was (the systems end at different orders).
+template <class Kernel, class Options>
+std::vector<SolveReport> GMRES_batch(PlanAdapter<Kernel>& MV, std::vector<std::vector<typename Kernel::charge_type>>& xs,
+                                     const std::vector<std::vector<typename Kernel::result_type>>& bs, const Options& opts) {
+  return detail::solve_batch(MV, xs, bs, opts, nullptr, false);
+}
+template <class Kernel, class Options, class PC>
+std::vector<SolveReport> GMRES_batch(PlanAdapter<Kernel>& MV, std::vector<std::vector<typename Kernel::charge_type>>& xs,
+                                     const std::vector<std::vector<typename Kernel::result_type>>& bs, const Options& opts, PC&& M) {
+  if (xs.empty()) throw Error(FMMBEM_ERR_INVALID, "GMRES_batch: no systems");
+  fmmbem_preconditioner pc = {};
+  std::vector<double> recip;
+  detail::describe<Kernel>(M, xs[0].size(), pc, recip);
+  return detail::solve_batch(MV, xs, bs, opts, &pc, false);
+}
+template <class Kernel, class Options>
+std::vector<SolveReport> FGMRES_batch(PlanAdapter<Kernel>& MV, std::vector<std::vector<typename Kernel::charge_type>>& xs,
+                                      const std::vector<std::vector<typename Kernel::result_type>>& bs, const Options& opts) {
+  return detail::solve_batch(MV, xs, bs, opts, nullptr, true);
+}
+template <class Kernel, class Options, class PC>
+std::vector<SolveReport> FGMRES_batch(PlanAdapter<Kernel>& MV, std::vector<std::vector<typename Kernel::charge_type>>& xs,
+                                      const std::vector<std::vector<typename Kernel::result_type>>& bs, const Options& opts, PC&& M) {
+  if (xs.empty()) throw Error(FMMBEM_ERR_INVALID, "FGMRES_batch: no systems");
+  fmmbem_preconditioner pc = {};
+  std::vector<double> recip;
+  detail::describe<Kernel>(M, xs[0].size(), pc, recip);
+  return detail::solve_batch(MV, xs, bs, opts, &pc, true);
 }
 }  // namespace device_solvers
 using namespace device_solvers;
