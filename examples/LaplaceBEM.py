@@ -10,6 +10,8 @@ same report lines (timing, potential at the exterior point (3,3,3) :346-369, rel
 -field N (not a flag of the reference): after the solve, the same representation formula on N points of the sphere of radius 3
 through a plan over those target points (FMM_plan(K, panels, targets=...), the reference's FMM_plan(K, sources, targets, opts)),
 one more report line with its largest error against the exact exterior solution 1/|x|.
+-near_f32 P (not a flag of the reference): the operator's matvecs at orders p <= P stream the float copy of the near matrix
+(fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
 """
 import math
 import os
@@ -100,7 +102,7 @@ def main(argv):
     if len(argv) == 1:
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
-    second_kind, mesh, field = False, None, 0
+    second_kind, mesh, field, near_f32 = False, None, 0, 0
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -143,6 +145,8 @@ def main(argv):
             i += 1; mesh = argv[i]
         elif a == "-field":
             i += 1; field = int(argv[i])
+        elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
+            i += 1; near_f32 = int(argv[i])
         else:
             print('[W]: Unknown command line arg: "%s"' % a)
             print_help_and_exit()
@@ -162,7 +166,9 @@ def main(argv):
     opts.set_max_per_box(ncrit)
     bc = np.full(n, 1 if second_kind else 0, dtype=np.uint8)           # panels switch_BC() for the second kind (:190-191)
     K = fb.LaplaceSphericalBEM(p, k)
-    plan = fb.FMM_plan(K, v, opts, bc=bc, p_max=p)
+    plan = fb.FMM_plan(K, v, opts, bc=bc, p_max=p, near_f32_max_p=near_f32)    # the operator of the solve; the right-hand side stays FP64
+    if near_f32:
+        print("float near field: matvecs at p <= %d stream %.3f GB of float entries" % (near_f32, plan.stats()["near_f32_bytes"] / 1e9))
     dev = torch.device("cuda", 0)
     charges = torch.ones(n, dtype=torch.float64, device=dev)
 

@@ -8,6 +8,9 @@ kind stokeslet system solved by the relaxed GMRES of GMRES_Stokes.hpp (:307-330)
 against 6 pi mu, area and pointwise traction errors (:337-372).  All matvecs run in libfmmbem_hip.so.
 
     python examples/StokesBEM.py -recursions 4 -p 10
+
+-near_f32 P (not a flag of the reference): the operator's matvecs at orders p <= P stream the float copy of the near matrix
+(fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
 """
 import math
 import os
@@ -51,7 +54,7 @@ def main(argv):
     recursions, p, k, kfine, cells, mu, p_min = 4, 8, 4, 19, 1, 1e-3, 5
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
-    rbc = False
+    rbc, near_f32 = False, 0
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -97,6 +100,8 @@ def main(argv):
             i += 1; ncrit = int(argv[i])
         elif a == "-eval":
             i += 1
+        elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
+            i += 1; near_f32 = int(argv[i])
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
@@ -141,7 +146,9 @@ def main(argv):
     print("done")
     setup_time = time.time() - tic
 
-    plan = fb.FMM_plan(kernel(), v, opts, p_max=p)
+    plan = fb.FMM_plan(kernel(), v, opts, p_max=p, near_f32_max_p=near_f32)
+    if near_f32:
+        print("float near field: matvecs at p <= %d stream %.3f GB of float entries" % (near_f32, plan.stats()["near_f32_bytes"] / 1e9))
     # x(panels.size(), charge_type(1.)): Vec<3,double> with ONE argument is the zero vector
     x = torch.zeros(3 * n, dtype=torch.float64, device=dev)
     log = _Logged()

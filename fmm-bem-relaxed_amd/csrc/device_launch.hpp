@@ -11,6 +11,11 @@ namespace fmmbem {
 hipError_t launch_near_assemble(const DevicePlan& d, hipStream_t s);
 hipError_t launch_gather_x(const DevicePlan& d, const double* x, hipStream_t s);
 hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s);
+// float near field (fmmbem_options.near_f32_max_p): which plans the float kernels serve; the copy of the stored values into
+// DevicePlan::near_f32 (after the assembly); the pass that streams it instead of launch_near_spmv
+bool near_f32_ok(int dof, int max_runs, bool stokes_sym);
+hipError_t launch_near_to_f32(const DevicePlan& d, hipStream_t s);
+hipError_t launch_near_spmv_f32(const DevicePlan& d, hipStream_t s);
 struct HybridStreams { hipStream_t recompute = nullptr; hipEvent_t fork = nullptr, join_recompute = nullptr; };
 hipError_t launch_near_hybrid(const DevicePlan& d, hipStream_t s, const HybridStreams& hs);   // near_stream_fraction < 1
 hipError_t launch_kernel_entries(const DevicePlan& d, int m, double* out, hipStream_t s);   // panels [0,m) targets, [m,2m) sources

@@ -110,6 +110,15 @@ struct DevicePlan {
   const uint8_t* near_rec = nullptr;
   const RcItem* rc_items = nullptr;  int rc_nitems = 0;
   int near_nitems_stream = 0;                        // Laplace hybrid plans: the streamed items are near_recs[0 .. near_nitems_stream)
+  // Float near field (fmmbem_options.near_f32_max_p > 0 on a plan where it applies; null otherwise): a copy of the stored values
+  // rounded to float, streamed by near_spmv_pipe_f32 / near_spmv_sym3_f32 at the low orders.  near_val / near_sym stay as they are.
+  //   Laplace: per leaf a row-major block nrows x stride32, stride32 = ncols rounded up to a multiple of 4 (rows 16-B aligned,
+  //            padding columns zero); near_recs_f32 = near_recs with val_off / stride of THIS layout.
+  //   Stokes:  per panel row three planes of ncp2 = (ncp + 1) / 2 float4: plane k holds the k-th 16-byte pair of near_sym for the
+  //            source panels 2j and 2j + 1 (an odd ncp padded with zeros): 24 bytes per panel pair.
+  float* near_f32 = nullptr;
+  const int64_t* near_f32_off = nullptr;             // [nl] offset of a leaf's block in near_f32 (floats)
+  const NearItem* near_recs_f32 = nullptr;
   // boxes / expansions
   const double* box_center;
   double2 *M, *L, *Mh;

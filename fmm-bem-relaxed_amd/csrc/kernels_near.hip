@@ -1555,6 +1555,280 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
 }
 
 // ---------------------------------------------------------------------------------------------
+// Float near field (fmmbem_options.near_f32_max_p; DESIGN.md section 8 "Float near field").  An execute at a low order streams a
+// copy of the stored values rounded to float (DevicePlan::near_f32: 4 bytes per Laplace entry, 24 per Stokes panel pair) instead
+// of near_val / near_sym; x in LDS, the accumulators and y stay doubles, so the result differs from the FP64 kernel's by the
+// rounding of the entries alone: |dy_i| <= 2^-24 (|A| |x|)_i.
+//   near_to_f32 / near_sym_to_f32     once per plan, after the assembly: the copy, round to nearest even
+//   near_spmv_pipe_f32                spmv_pipe_run on the float rows: a lane's nontemporal 16-byte load is FOUR columns
+//   near_spmv_sym3_f32                near_spmv_sym3 on the float planes: a lane's three 16-byte loads are TWO source panels
+// Row sums in a fixed order (lanes over the 16-byte vectors in increasing column, wave_sum, the colsplit parts in wavefront
+// order, later chunks added into y): the same bits every run; not the FP64 kernels' order (four columns per lane step, not two).
+// ---------------------------------------------------------------------------------------------
+typedef float fvec4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(kSpmvWaves * kWave) void near_to_f32_kernel(DevicePlan d) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  for (int t = d.leaf_begin + blockIdx.x; t < d.leaf_end; t += gridDim.x) {
+    const int nrows = d.leaf_nrows[t], ncols = d.near_ncols[t], stride = d.near_stride[t];
+    const int s32 = (ncols + 3) & ~3;
+    const double* src = d.near_val + d.near_off[t];
+    float* dst = d.near_f32 + d.near_f32_off[t];
+    for (int r = wave; r < nrows; r += kSpmvWaves)
+      for (int c = lane; c < s32; c += kWave) dst[(int64_t)r * s32 + c] = c < ncols ? (float)src[(int64_t)r * stride + c] : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kSpmvWaves * kWave) void near_sym_to_f32_kernel(DevicePlan d) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  for (int t = d.leaf_begin + blockIdx.x; t < d.leaf_end; t += gridDim.x) {
+    const int nrows = d.leaf_nrows[t], ncp = d.near_ncols[t], ncp2 = (ncp + 1) >> 1;
+    const dvec2* src = reinterpret_cast<const dvec2*>(d.near_sym + d.near_sym_off[t]);
+    fvec4* dst = reinterpret_cast<fvec4*>(d.near_f32 + d.near_f32_off[t]);
+    for (int rk = wave; rk < 3 * nrows; rk += kSpmvWaves)          // (panel row, plane)
+      for (int j = lane; j < ncp2; j += kWave) {
+        const dvec2 a = src[(int64_t)rk * ncp + 2 * j];
+        const dvec2 b = 2 * j + 1 < ncp ? src[(int64_t)rk * ncp + 2 * j + 1] : dvec2{0, 0};
+        dst[(int64_t)rk * ncp2 + j] = fvec4{(float)a.x, (float)a.y, (float)b.x, (float)b.y};
+      }
+  }
+}
+
+// x chunk in LDS for the float rows: the four columns of 16-byte vector j live as two 16-byte pairs, columns 4j, 4j+1 at pair j of
+// the first half and 4j+2, 4j+3 at pair j of the second, so that the lanes of a wavefront read consecutive 16-byte slots
+// (columns in their natural order put the lanes 32 bytes apart: a 2-way bank conflict on every read)
+__device__ __forceinline__ int f32_xpos(int c) { return ((c >> 1) & 1) * (kSpmvPipeChunk / 2) + ((c >> 2) << 1) + (c & 1); }
+
+// LDS as spmv_pipe_run: xs_all [2][kSpmvPipeChunk] doubles, runbuf [2][2][max_runs] ints, part [kSpmvWaves][kColRows]
+template <int kRows, int kVecs, int kOcc>
+__global__ __launch_bounds__(kSpmvWaves * kWave, kOcc) void near_spmv_pipe_f32_kernel(DevicePlan d) {
+  extern __shared__ double xs_all[];
+  __shared__ double part[kSpmvWaves][kColRows];
+  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * kSpmvPipeChunk);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int mr = d.max_runs, nitems = d.near_nitems, tid = threadIdx.x, step = gridDim.x;
+  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(d.near_recs_f32));
+
+  int item = blockIdx.x;
+  if (item >= nitems) return;
+  NearItem it = load_item(recs + item);
+  NearItem nx = load_item(recs + (item + step < nitems ? item + step : nitems - 1));
+  for (int i = tid; i < it.nruns; i += blockDim.x) { runbuf[i] = d.near_run_row0[it.run_begin + i]; runbuf[mr + i] = d.near_run_off[it.run_begin + i]; }
+  for (int i = tid; i < nx.nruns; i += blockDim.x) { runbuf[2 * mr + i] = d.near_run_row0[nx.run_begin + i]; runbuf[3 * mr + i] = d.near_run_off[nx.run_begin + i]; }
+  __syncthreads();
+  {
+    const Runs runs{runbuf, runbuf + mr, it.nruns};
+    const int cw = it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk;
+    for (int c = tid; c < cw; c += blockDim.x) xs_all[f32_xpos(c)] = c < it.ncols ? d.xt[column_to_row(runs, c)] : 0.0;
+  }
+  __syncthreads();
+  int xb = 0, rb = 0;
+  for (;; item += step) {
+    const bool more = item + step < nitems;
+    const int i2 = item + 2 * step;
+    const NearItem nn = load_item(recs + (i2 < nitems ? i2 : nitems - 1));
+    // ---- set-up of the following items, in flight while this item's rows stream ----
+    double px[kSpmvPre];
+    int pr0 = 0, pr1 = 0;
+    const bool prun = i2 < nitems && tid < nn.nruns;     // max_runs <= blockDim.x is checked by the launcher
+    if (more) {
+      const Runs nruns{runbuf + (rb ^ 1) * 2 * mr, runbuf + (rb ^ 1) * 2 * mr + mr, nx.nruns};
+      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
+#pragma unroll
+      for (int u = 0; u < kSpmvPre; ++u) {
+        const int c = tid + u * (kSpmvWaves * kWave);
+        px[u] = (c < ncw && c < nx.ncols) ? d.xt[column_to_row(nruns, c)] : 0.0;
+      }
+      if (prun) { pr0 = d.near_run_row0[nn.run_begin + tid]; pr1 = d.near_run_off[nn.run_begin + tid]; }
+    }
+    // ---- this item ----
+    const int nrows = it.nrows, ncols = it.ncols, stride = it.stride;   // stride: floats, a multiple of 4
+    const bool colsplit = it.colsplit != 0;
+    const float* blk = d.near_f32 + it.val_off;
+    double* yt = d.yt + it.yrow;
+    double* xs = xs_all + xb * kSpmvPipeChunk;
+    const dvec2* xv = reinterpret_cast<const dvec2*>(xs);
+    const Runs runs{runbuf + rb * 2 * mr, runbuf + rb * 2 * mr + mr, it.nruns};
+    for (int c0 = 0; c0 < stride; c0 += kSpmvPipeChunk) {
+      const int cw = stride - c0 < kSpmvPipeChunk ? stride - c0 : kSpmvPipeChunk;
+      if (c0) {                                       // further chunks of a wide leaf: staged in place
+        __syncthreads();
+        for (int c = tid; c < cw; c += blockDim.x) xs[f32_xpos(c)] = c0 + c < ncols ? d.xt[column_to_row(runs, c0 + c)] : 0.0;
+        __syncthreads();
+      }
+      const int nvec = cw >> 2;                       // 16-B vectors (four columns) of this chunk per row
+      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
+      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
+      const int rstep = colsplit ? 1 : kSpmvWaves;
+      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
+        const fvec4* row[kRows];
+        double acc[kRows];
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int ri = r + i * rstep;
+          row[i] = reinterpret_cast<const fvec4*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
+          acc[i] = 0;
+        }
+        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
+          fvec4 v[kRows][kVecs];
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            const bool ok = cc < v1;
+#pragma unroll
+            for (int i = 0; i < kRows; ++i) v[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : fvec4{0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            if (cc < v1) {
+              const dvec2 xa = xv[cc], xc = xv[kSpmvPipeChunk / 4 + cc];
+#pragma unroll
+              for (int i = 0; i < kRows; ++i)
+                acc[i] = fma((double)v[i][u].x, xa.x, fma((double)v[i][u].y, xa.y, fma((double)v[i][u].z, xc.x, fma((double)v[i][u].w, xc.y, acc[i]))));
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) acc[i] = wave_sum(acc[i]);
+        if (lane == 0) {
+#pragma unroll
+          for (int i = 0; i < kRows; ++i) {
+            const int ri = r + i * rstep;
+            if (ri < nrows) {
+              if (colsplit) part[wave][ri] = acc[i];
+              else yt[ri] = c0 ? yt[ri] + acc[i] : acc[i];
+            }
+          }
+        }
+      }
+      if (colsplit) {
+        __syncthreads();
+        if (tid < nrows) {
+          const double sum = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+          yt[tid] = c0 ? yt[tid] + sum : sum;
+        }
+      }
+    }
+    if (!more) break;
+    // ---- hand over: next item's x and the item after's runs into the halves nobody reads now ----
+    {
+      double* xn = xs_all + (xb ^ 1) * kSpmvPipeChunk;
+      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
+#pragma unroll
+      for (int u = 0; u < kSpmvPre; ++u) {
+        const int c = tid + u * (kSpmvWaves * kWave);
+        if (c < ncw) xn[f32_xpos(c)] = px[u];
+      }
+    }
+    if (prun) { runbuf[rb * 2 * mr + tid] = pr0; runbuf[rb * 2 * mr + mr + tid] = pr1; }
+    __syncthreads();
+    it = nx; nx = nn; xb ^= 1; rb ^= 1;
+  }
+}
+
+// per PAIR of source panels three 16-byte vectors and the pairs' x components (16-byte LDS reads) feed eighteen FMAs
+template <int kRows, int kVecs, int kOcc>
+__global__ __launch_bounds__(kSpmvWaves * kWave, kOcc) void near_spmv_sym3_f32_kernel(DevicePlan d) {
+  extern __shared__ double xs[];                      // [3][kSymChunk] doubles, then the run descriptors
+  __shared__ double part[kSpmvWaves][kColRows][3];
+  int* run_row0 = reinterpret_cast<int*>(xs + 3 * kSymChunk);
+  int* run_off = run_row0 + d.max_runs;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const dvec2* xv0 = reinterpret_cast<const dvec2*>(xs);
+  const dvec2* xv1 = reinterpret_cast<const dvec2*>(xs + kSymChunk);
+  const dvec2* xv2 = reinterpret_cast<const dvec2*>(xs + 2 * kSymChunk);
+  for (int item = blockIdx.x; item < d.sym_nitems; item += gridDim.x) {
+    const int4 it = d.sym_items[item];
+    const int t = it.x, r0 = it.y, nrows = it.z;       // panel rows
+    const bool colsplit = it.w != 0;
+    const int ncp = d.near_ncols[t], ncp2 = (ncp + 1) >> 1;
+    const Runs runs = load_runs(d, t, run_row0, run_off);
+    const fvec4* blk = reinterpret_cast<const fvec4*>(d.near_f32 + d.near_f32_off[t]) + (int64_t)r0 * 3 * ncp2;
+    double* yt = d.yt + 3 * (int64_t)(d.leaf_row0[t] + r0);
+    for (int c0 = 0; c0 < ncp; c0 += kSymChunk) {
+      const int cw = ncp - c0 < kSymChunk ? ncp - c0 : kSymChunk;
+      const int cw2 = (cw + 1) >> 1;                   // pairs of this chunk; the padding panel of an odd ncp reads x = 0
+      if (c0) __syncthreads();
+      for (int c = threadIdx.x; c < 2 * cw2; c += blockDim.x) {
+        double a = 0, b = 0, e = 0;
+        if (c < cw) {
+          const double* xp = d.xt + 3 * (int64_t)column_to_row(runs, c0 + c);
+          a = xp[0]; b = xp[1]; e = xp[2];
+        }
+        xs[c] = a; xs[kSymChunk + c] = b; xs[2 * kSymChunk + c] = e;
+      }
+      __syncthreads();
+      const int seg = colsplit ? ((((cw2 + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : cw2;
+      const int v0 = colsplit ? wave * seg : 0, v1 = min(cw2, v0 + seg);
+      const int rstep = colsplit ? 1 : kSpmvWaves;
+      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
+        const fvec4* row[kRows];
+        double ax[kRows], ay[kRows], az[kRows];
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int ri = r + i * rstep;
+          row[i] = blk + (int64_t)(ri < nrows ? ri : r) * 3 * ncp2 + (c0 >> 1);
+          ax[i] = ay[i] = az[i] = 0;
+        }
+        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
+          fvec4 v[kRows][kVecs][3];
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            const bool ok = cc < v1;
+#pragma unroll
+            for (int i = 0; i < kRows; ++i)
+#pragma unroll
+              for (int k = 0; k < 3; ++k) v[i][u][k] = ok ? __builtin_nontemporal_load(&row[i][k * ncp2 + cc]) : fvec4{0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int u = 0; u < kVecs; ++u) {
+            const int cc = c + u * kWave;
+            if (cc < v1) {
+              const dvec2 x0 = xv0[cc], x1 = xv1[cc], x2 = xv2[cc];      // (panel 2 cc, panel 2 cc + 1) per component
+#pragma unroll
+              for (int i = 0; i < kRows; ++i) {
+                const fvec4 a = v[i][u][0], b = v[i][u][1], e = v[i][u][2];   // (xx,xy) (xz,yy) (yz,zz) of the two panels
+                const double xx0 = a.x, xy0 = a.y, xz0 = b.x, yy0 = b.y, yz0 = e.x, zz0 = e.y;
+                const double xx1 = a.z, xy1 = a.w, xz1 = b.z, yy1 = b.w, yz1 = e.z, zz1 = e.w;
+                ax[i] = fma(xx0, x0.x, fma(xy0, x1.x, fma(xz0, x2.x, fma(xx1, x0.y, fma(xy1, x1.y, fma(xz1, x2.y, ax[i]))))));
+                ay[i] = fma(xy0, x0.x, fma(yy0, x1.x, fma(yz0, x2.x, fma(xy1, x0.y, fma(yy1, x1.y, fma(yz1, x2.y, ay[i]))))));
+                az[i] = fma(xz0, x0.x, fma(yz0, x1.x, fma(zz0, x2.x, fma(xz1, x0.y, fma(yz1, x1.y, fma(zz1, x2.y, az[i]))))));
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) { ax[i] = wave_sum(ax[i]); ay[i] = wave_sum(ay[i]); az[i] = wave_sum(az[i]); }
+        if (lane == 0) {
+#pragma unroll
+          for (int i = 0; i < kRows; ++i) {
+            const int ri = r + i * rstep;
+            if (ri < nrows) {
+              if (colsplit) { part[wave][ri][0] = ax[i]; part[wave][ri][1] = ay[i]; part[wave][ri][2] = az[i]; }
+              else {
+                double* y = yt + 3 * ri;
+                y[0] = c0 ? y[0] + ax[i] : ax[i]; y[1] = c0 ? y[1] + ay[i] : ay[i]; y[2] = c0 ? y[2] + az[i] : az[i];
+              }
+            }
+          }
+        }
+      }
+      if (colsplit) {
+        __syncthreads();
+        if ((int)threadIdx.x < 3 * nrows) {
+          const int ri = threadIdx.x / 3, a = threadIdx.x % 3;
+          const double sum = ((part[0][ri][a] + part[1][ri][a]) + part[2][ri][a]) + part[3][ri][a];
+          yt[3 * ri + a] = c0 ? yt[3 * ri + a] + sum : sum;
+        }
+      }
+    }
+    __syncthreads();                                  // xs / run descriptors / part are rewritten for the next item
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Hybrid near field (fmmbem_options.near_stream_fraction < 1; round 5).  The target leaves of such a plan are of two kinds:
 //   * STREAMED leaves keep their blocks (near_sym / near_val) and are served by near_spmv_sym3 / near_spmv_pipe as before:
 //     HBM-bound, the VALU idle 95 % of the time;
@@ -2283,6 +2557,55 @@ hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s) {
   } else {
     hipLaunchKernelGGL((near_spmv_kernel<2, 4>), g, b, lds, s, d);
   }
+  return hipGetLastError();
+}
+
+// ---- float near field: the plans it serves, the copy, the pass ----
+// Laplace through the pipelined kernel (a leaf with more runs than threads, never seen, keeps the FP64 kernels), Stokes through
+// the symmetric blocks
+bool near_f32_ok(int dof, int max_runs, bool stokes_sym) { return dof == 3 ? stokes_sym : dof == 1 && max_runs <= kSpmvWaves * kWave; }
+
+hipError_t launch_near_to_f32(const DevicePlan& d, hipStream_t s) {
+  if (!d.near_f32 || !d.near_f32_off) return hipErrorInvalidValue;
+  const int nl = d.leaf_end - d.leaf_begin;
+  if (nl <= 0) return hipSuccess;
+  const dim3 g(std::min(nl, 256 * 16)), b(kSpmvWaves * kWave);
+  if (d.dof == 3) {
+    if (!d.near_sym) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(near_sym_to_f32_kernel, g, b, 0, s, d);
+  } else {
+    if (!d.near_val) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(near_to_f32_kernel, g, b, 0, s, d);
+  }
+  return hipGetLastError();
+}
+
+// Shapes (rows x 16-byte loads in flight per wavefront x workgroups per CU; FMMBEM_F32_SHAPE for sweeps), tools/near_f32_time.py,
+// near ms (profiles/r08a_near_f32_time.txt).  The FP64 kernels' own shapes at five workgroups per CU spill here (the converted
+// operands want 14 / 4 more registers), so the full shapes run at four workgroups per CU.
+//   Laplace, N = 1M (FP64 pass 0.70):     0: 2x4x4 0.505   1: 2x3x5 0.462 (default)   2: 2x2x5 0.472   3: 4x2x4 0.512
+//   Stokes, red blood cell N = 524 288 (FP64 pass 2.00):  0: 1x3x4 1.081 (default)   1: 1x2x5 1.098   2: 1x2x4 1.085   3: 1x4x4 1.078
+hipError_t launch_near_spmv_f32(const DevicePlan& d, hipStream_t s) {
+  if (d.near_rec || !d.near_f32 || !d.near_f32_off) return hipErrorInvalidValue;
+  if (d.near_nitems <= 0) return hipSuccess;
+  const dim3 b(kSpmvWaves * kWave);
+  if (d.dof == 3) {
+    if (!d.near_sym) return hipErrorInvalidValue;
+    const size_t lds3 = 3 * (size_t)kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
+    static const int shape = [] { const char* e = std::getenv("FMMBEM_F32_SHAPE"); return e ? std::atoi(e) : 0; }();
+    if (shape == 1) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 2, 5>), dim3(std::min(d.sym_nitems, 256 * 5)), b, lds3, s, d);
+    else if (shape == 2) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 2, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
+    else if (shape == 3) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 4, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
+    else hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 3, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
+    return hipGetLastError();
+  }
+  if (d.dof != 1 || !d.near_recs_f32 || d.max_runs > kSpmvWaves * kWave) return hipErrorInvalidValue;
+  const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
+  static const int shape = [] { const char* e = std::getenv("FMMBEM_F32_SHAPE"); return e ? std::atoi(e) : 1; }();
+  if (shape == 0) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 4, 4>), dim3(std::min(d.near_nitems, 256 * 4)), b, lds2, s, d);
+  else if (shape == 2) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 2, 5>), dim3(std::min(d.near_nitems, 256 * 5)), b, lds2, s, d);
+  else if (shape == 3) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<4, 2, 4>), dim3(std::min(d.near_nitems, 256 * 4)), b, lds2, s, d);
+  else hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 3, 5>), dim3(std::min(d.near_nitems, 256 * 5)), b, lds2, s, d);
   return hipGetLastError();
 }
 

@@ -227,6 +227,10 @@ struct fmmbem_plan {
   std::vector<uint8_t> near_rec_host;                          // [leaf] 1 = recomputed
   std::vector<int64_t> near_off_host, sym_off_host;            // [leaf] offsets of the stored blocks (introspection)
   int64_t near_recomputed_pairs = 0;
+  // float near field (fmmbem_options.near_f32_max_p): floats of the copy (0: not active on this plan; decided with the geometry,
+  // allocated and filled per plan in to_device_bc_begin) and what the last execute streamed
+  int64_t near_f32_floats = 0;
+  int last_near_f32 = 0;
   HybridStreams hyb;                                           // the recompute kernel and the listed entries run beside the streaming one
   int build_side_lists();
   int64_t n_classes = 0;
@@ -359,6 +363,8 @@ int fmmbem_plan::to_device(int part) {
   DEVICE_SCOPE(opts.device);
   if (part != 2) {
     on_device = true;
+    shared->on_device = true;                          // from here on a creation that fails (an allocation, say the float near
+    shared->device = opts.device;                      // field's copy) frees the geometry's uploads with the plan: nothing stays behind
     HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
     ev.assign((size_t)kRing * 2 * kStages, nullptr);
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
@@ -454,6 +460,8 @@ int fmmbem_plan::to_device(int part) {
   // recomputed pair costs the same arithmetic wherever it sits, but the source panel's 128 bytes are read once per item and
   // amortised over the item's rows -- until their pairs make up 1 - near_stream_fraction of all near pairs.
   std::vector<uint8_t> rec(nl, 0);
+  std::vector<NearItem> near_recs_host;
+  std::vector<int> near_recs_leaf;
   {
     double f = opts.near_stream_fraction;
     if (const char* e = std::getenv("FMMBEM_NEAR_STREAM_FRACTION")) f = std::atof(e);
@@ -570,6 +578,11 @@ int fmmbem_plan::to_device(int part) {
       q.pad[0] = q.pad[1] = 0;
     }
     TRY(upload(recs, &d.near_recs));
+    if (opts.near_f32_max_p > 0) {                      // the float near field lays the same items out again (below)
+      near_recs_host = recs;
+      near_recs_leaf.resize(items.size());
+      for (size_t i = 0; i < items.size(); ++i) near_recs_leaf[i] = items[i].leaf;
+    }
   }
   const bool stokes_sym = dof == 3 && opts.sparse_local && !(std::getenv("FMMBEM_STOKES_SYM") && std::atoi(std::getenv("FMMBEM_STOKES_SYM")) == 0);
   near_total_doubles = (opts.sparse_local && !stokes_sym) ? total : 0;      // allocated in to_device_bc; matrix-free mode keeps no matrix
@@ -607,6 +620,34 @@ int fmmbem_plan::to_device(int part) {
       near_bytes = sym_total * (int64_t)sizeof(double);
       sym_off_host = sym_off;
     }
+  }
+  // Float near field: the layout of the copy (device_plan.hpp near_f32) -- per leaf offsets, and for the pipelined Laplace kernel
+  // the item records again with the offsets and strides of the float rows (near_recs itself is what the FP64 kernel reads)
+  near_f32_floats = 0;
+  // The option's premise is that the rounding of the entries hides under the truncation error of the far field.  An FMM plan whose
+  // leaves are ALL near one another (every leaf pair is a P2P pair: no M2L anywhere) has no far field: its result is exact at every
+  // order, relaxation changes nothing, and there is nothing for the float error to hide under -- such a plan (a few hundred panels)
+  // takes the option as 0.  The LOCAL / BLOCK_DIAGONAL evaluators are near-field operators by definition and keep it.
+  const bool f32_premise = hp.opt.evaluator != 0 || hp.near_ptr[nl] < (int64_t)nl * nl;
+  if (opts.near_f32_max_p > 0 && opts.sparse_local && !hybrid && !targets && hp.opt.shard_world <= 1 && near_bytes > 0 &&
+      f32_premise && near_f32_ok(dof, max_runs, stokes_sym)) {
+    std::vector<int64_t> off32(nl, 0);
+    int64_t total32 = 0;
+    for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
+      off32[l] = total32;
+      total32 += dof == 3 ? (int64_t)12 * leaf_nrows[l] * ((hp.near_ncols[l] + 1) / 2) : (int64_t)leaf_nrows[l] * ((hp.near_ncols[l] + 3) & ~3);
+    }
+    TRY(upload(off32, &d.near_f32_off));
+    if (dof == 1) {
+      std::vector<NearItem> recs32(near_recs_host);
+      for (NearItem& q : recs32) {
+        const int l = near_recs_leaf[(size_t)(&q - recs32.data())], s32 = (hp.near_ncols[l] + 3) & ~3;
+        q.val_off = off32[l] + (q.val_off - near_off[l]) / near_stride[l] * s32;
+        q.stride = s32;
+      }
+      TRY(upload(recs32, &d.near_recs_f32));
+    }
+    near_f32_floats = total32;
   }
   if (hybrid) {
     // recompute items: ranges of <= 20 (Stokes: four wavefronts x five rows) or 32 (Laplace: x eight) panel rows of the recomputed
@@ -990,6 +1031,7 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
   }
   if (near_total_doubles) TRY(alloc((size_t)near_total_doubles, &d.near_val, false));
   if (sym_total_doubles) TRY(alloc((size_t)sym_total_doubles, &d.near_sym, false));
+  if (near_f32_floats) TRY(alloc((size_t)near_f32_floats, &d.near_f32, false));
   if (hybrid) {
     HIP_TRY(hipStreamCreateWithFlags(&hyb.recompute, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&hyb.fork, hipEventDisableTiming));
@@ -1003,6 +1045,7 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
   if (opts.sparse_local) {
     if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_near_assemble_stokes(d, own_stream));
     else HIP_TRY(launch_near_assemble(d, own_stream));
+    if (d.near_f32) HIP_TRY(launch_near_to_f32(d, own_stream));      // the float copy of what was just assembled
   }
   HIP_TRY(hipEventRecord(asm_ev[1], own_stream));
   return FMMBEM_OK;
@@ -1291,6 +1334,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     pending_near = false;
     return FMMBEM_OK;
   }
+  const bool near_f32 = d.near_f32 && p <= opts.near_f32_max_p;
   auto near_field = [&](hipStream_t ns) -> int {
     HIP_TRY(begin(1, ns));
     // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
@@ -1298,6 +1342,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     if (targets && zero_target_rows)
       HIP_TRY(hipMemsetAsync(d.yt + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), ns));
     if (hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
+    else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
     else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
     HIP_TRY(end(1, ns));
     return FMMBEM_OK;
@@ -1368,6 +1413,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   }));
   TRY(deliver(s));
   last_p = p;
+  last_near_f32 = near_f32 ? 1 : 0;
   if (tm) { ev_mask[ring] = mask; ++ev_count; }
   return FMMBEM_OK;
 }
@@ -1387,7 +1433,8 @@ static int batch_nv() {
 // the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch)
 int fmmbem_plan::batch_width() const {
   const bool fast = on_device && !multi && opts.kernel != FMMBEM_KERNEL_STOKES_BEM && opts.sparse_local && !hybrid &&
-                    hp.opt.shard_world <= 1 && !split_upward && !result_slices && batch_near_ok(d);
+                    hp.opt.shard_world <= 1 && !split_upward && !result_slices && batch_near_ok(d) &&
+                    !d.near_f32;                     // float near field: vector by vector, each with the bits of its single execute
   return !fast ? 1 : bat.width ? bat.width : batch_nv();
 }
 
@@ -1533,6 +1580,7 @@ void fmmbem_options_default(fmmbem_options* o) {
   o->quad_k_fine = 25;          // StokesSphericalBEM ctor default (kernel/StokesSphericalBEM.hpp:131)
   o->mu = 1e-3;
   o->near_stream_fraction = 1.0;
+  o->near_f32_max_p = 0;
 }
 
 // ---- plans that share a geometry -----------------------------------------------------------------------------
@@ -1566,7 +1614,8 @@ static bool same_geometry_options(const fmmbem_options& a, const fmmbem_options&
   return a.kernel == b.kernel && a.p_max == b.p_max && a.quad_k == b.quad_k && a.theta == b.theta && a.ncrit == b.ncrit &&
          a.sparse_local == b.sparse_local && a.host_only == b.host_only && a.device == b.device && a.shard_rank == b.shard_rank &&
          a.shard_world == b.shard_world && a.quad_k_fine == b.quad_k_fine && a.evaluator == b.evaluator && a.mu == b.mu &&
-         a.shard_upward == b.shard_upward && a.l2l_rule == b.l2l_rule && a.near_stream_fraction == b.near_stream_fraction;
+         a.shard_upward == b.shard_upward && a.l2l_rule == b.l2l_rule && a.near_stream_fraction == b.near_stream_fraction &&
+         a.near_f32_max_p == b.near_f32_max_p;
 }
 
 // live plans that hold a geometry, most recent first (a handful: operator, right-hand side, preconditioner plans).  ONE mutex: a
@@ -1613,7 +1662,7 @@ int fmmbem_plan::like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc,
   pl->near_side_entries = 0;
   pl->d.side_ptr = nullptr; pl->d.side_col = nullptr; pl->d.side_val = nullptr;
   pl->d.p2m_tab = nullptr; pl->d.p2m_tab_g = nullptr;
-  pl->d.near_val = nullptr; pl->d.near_sym = nullptr;
+  pl->d.near_val = nullptr; pl->d.near_sym = nullptr; pl->d.near_f32 = nullptr; pl->last_near_f32 = 0;
   pl->build_host_ms = 0;
   DEVICE_SCOPE(pl->opts.device);
   HIP_TRY(hipStreamCreateWithFlags(&pl->own_stream, hipStreamNonBlocking));
@@ -1891,6 +1940,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
   if (opts->l2l_rule != FMMBEM_L2L_COMPLETE && opts->l2l_rule != FMMBEM_L2L_REFERENCE) return fail(FMMBEM_ERR_INVALID, "unknown l2l_rule");
   if (opts->evaluator < FMMBEM_EVAL_FMM || opts->evaluator > FMMBEM_EVAL_BLOCK_DIAGONAL) return fail(FMMBEM_ERR_INVALID, "unknown evaluator");
+  if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
   // The geometry of a live plan, recognised: same options, same panel count, same vertex bytes (two 64-bit hashes) -- only the
   // boundary-condition flags may differ.  The new plan then shares that plan's tree, lists and tables (PlanShared) and builds
   // only what the flags decide.  This is the drivers' second plan (examples/LaplaceBEM.cpp:218-232: the same panels with the
@@ -2004,6 +2054,7 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   *out = nullptr;
   if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
   if (!target_points || n_targets == 0) return fail(FMMBEM_ERR_INVALID, "no targets");
+  if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
   if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: Laplace only (Stokes velocity at points is not implemented)");
   if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "unknown kernel id");
   if (opts->shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: shard_world > 1 is not implemented");
@@ -2017,6 +2068,7 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
   pl->opts = *opts;
   pl->opts.near_stream_fraction = 1.0;                 // the hybrid near field is taken as 1 here
+  pl->opts.near_f32_max_p = 0;                         // ... and the float near field as off
   pl->opts.shard_rank = 0; pl->opts.shard_world = 1; pl->opts.n_devices = 0;
   pl->targets = true;
   HostOptions ho;
@@ -2379,6 +2431,8 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
   o->m2l_passes = long_items ? h.rot_passes_long : h.rot_passes;
   o->near_side_entries = plan->near_side_entries;
   o->near_recomputed_pairs = plan->near_recomputed_pairs;
+  o->near_f32_bytes = plan->d.near_f32 ? plan->near_f32_floats * (int64_t)sizeof(float) : 0;
+  o->last_near_f32 = plan->last_near_f32;
   o->geometry_shared = (int32_t)plan->shared.use_count();
   o->n_devices = 1;
   o->expansion_slots = plan->on_device ? plan->d.nslots : (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 8 : 2);

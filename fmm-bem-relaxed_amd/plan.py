@@ -294,10 +294,14 @@ class FMM_plan:
     targets: the reference's FMM_plan(K, sources, targets, opts) (include/FMM_plan.hpp:45-55) -- (M, 3) points, or (M, 3, 3)
     triangles standing for their centroids; target_bc: M flags (default POTENTIAL).  execute then returns the M values
     y_i = sum_j K(t_i, s_j) x_j, the target's flag picking G or dG/dn (fmmbem_plan_create_targets; Laplace only).
+
+    near_f32_max_p: not in the reference.  0: off; 1..16: executes at an order p <= this value stream a float copy of the
+    assembled near matrix (fmmbem_options.near_f32_max_p); stats() reports near_f32_bytes (0: not active on this plan) and
+    last_near_f32.
     """
 
     def __init__(self, K, panels, opts=None, bc=None, p_max=None, device=0, shard=(0, 1), host_only=False,
-                 shard_upward=False, devices=None, replicate_upward=False, targets=None, target_bc=None):
+                 shard_upward=False, devices=None, replicate_upward=False, targets=None, target_bc=None, near_f32_max_p=0):
         opts = opts if opts is not None else FMMOptions()
         # executor/make_executor.hpp:24-60: lazy_evaluation wins, then local_evaluation, then block_diagonal; the
         # non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones
@@ -322,6 +326,7 @@ class FMM_plan:
         o.evaluator = evaluator
         o.l2l_rule = _capi.L2L_REFERENCE if getattr(opts, "reference_l2l", False) else _capi.L2L_COMPLETE
         o.near_stream_fraction = float(getattr(opts, "near_stream_fraction", 1.0))
+        o.near_f32_max_p = int(near_f32_max_p)
         o.device = int(device)
         self.device = int(device)
         if devices is not None and len(devices) > 1:

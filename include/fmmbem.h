@@ -114,6 +114,18 @@ typedef struct {
                                * 0 or 1: the single `device`.  With n_devices == 0 the environment variable FMMBEM_DEVICES=0,1,...
                                * supplies a list (for callers that cannot: the reference's unmodified drivers)                  */
   int32_t  devices[8];
+  int32_t  near_f32_max_p;    /* Float near field.  0 (default): off.  1..16: an execute at an order p <= this value streams a copy
+                               * of the assembled near matrix rounded to float (half the bytes of the pass that bounds a low-order
+                               * matvec); x, the accumulators and y stay doubles, executes above it run the FP64 kernels on the
+                               * FP64 matrix, which is always kept.  Against the FP64 pass row i of the result moves by at most
+                               * 2^-24 (|A_near| |x|)_i -- far below the truncation error of the far field at low orders
+                               * (DESIGN.md section 8 "Float near field" gives the recommended threshold); the same bits every run.
+                               * Active on assembled plans (sparse_local = 1) that are not hybrid, on one device with
+                               * shard_world = 1: fmmbem_plan_create / _create_like, every evaluator, Laplace and Stokes with the
+                               * symmetric blocks.  Accepted without effect elsewhere (target, matrix-free, hybrid, device-list,
+                               * sharded, host-only plans; FMM plans with no M2L pair at all -- every leaf near every other, a few
+                               * hundred panels: exact at every order, no truncation error for the rounding to hide under): fmmbem_stats.near_f32_bytes is then 0.  On an active plan
+                               * fmmbem_plan_batch_width is 1.  Outside 0..16: FMMBEM_ERR_INVALID.                          */
 } fmmbem_options;
 
 /* Statistics of a plan and of its last execute (times in milliseconds, device-side HIP events). */
@@ -148,6 +160,9 @@ typedef struct {
   int32_t geometry_shared;      /* plans alive that share this plan's tree, lists and tables (fmmbem_plan_create_like), itself included */
   int64_t near_recomputed_pairs;/* hybrid plans (near_stream_fraction < 1): panel pairs of this shard that are recomputed every matvec
                                  * instead of stored (near_nnz counts all of the shard's entries, near_bytes what is stored)         */
+  int64_t near_f32_bytes;       /* HBM bytes of the float copy of the near matrix (fmmbem_options.near_f32_max_p); 0: the float near
+                                 * field is not active on this plan                                                                */
+  int32_t last_near_f32;        /* 1: the last execute streamed the float copy                                                      */
 } fmmbem_stats;
 
 typedef struct fmmbem_plan fmmbem_plan;

@@ -171,6 +171,11 @@ class FMMOptions {
   // leaves with the most rows keep none and are recomputed every matvec beside the streamed rest (fmmbem.h near_stream_fraction):
   // fewer HBM bytes and a smaller footprint at the same operator, last bits differ.  Stokes plans (measured optimum 0.5-0.55).
   double near_stream_fraction = 1.0;
+  // Not in the reference: executes at an order p <= near_f32_max_p stream a float copy of the assembled near matrix, half the
+  // bytes of the pass that bounds a low-order matvec (fmmbem.h near_f32_max_p); x, the sums and y stay doubles, a result row
+  // moves by at most 2^-24 (|A_near| |x|)_i.  0 (default): off.  Plans where it does not apply take it as 0.
+  int near_f32_max_p = 0;
+  void set_near_f32_max_p(int p) { near_f32_max_p = p; }
   // Not in the reference: the devices ONE plan runs on (fmmbem.h fmmbem_options.n_devices): more than one entry shards the target
   // leaves over them inside the plan; vectors handed to the device entry points live on the first.  Empty: the constructor's
   // `device` argument (or the environment's FMMBEM_DEVICES list, which is how the reference's unmodified drivers get there).
@@ -608,6 +613,7 @@ class PlanAdapter {
     o.evaluator = opts_.c_evaluator();
     o.l2l_rule = opts_.reference_l2l ? FMMBEM_L2L_REFERENCE : FMMBEM_L2L_COMPLETE;
     o.near_stream_fraction = opts_.near_stream_fraction;
+    o.near_f32_max_p = opts_.near_f32_max_p;
     sparse_ = o.sparse_local != 0;
     fmmbem_plan* fresh = nullptr;
     if (has_targets_) {
