@@ -1018,14 +1018,132 @@ constexpr int kSpmvChunk = 2048;                     // columns of x staged in L
 constexpr int kSpmvOcc = 5;                           // wavefronts per SIMD = workgroups per CU (82 VGPRs)
 constexpr int kColRows = 8;                           // work items with fewer rows split the COLUMNS over the wavefronts
 
+typedef float fvec4 __attribute__((ext_vector_type(4)));
+
+// The x and y vectors of one pass (tree order): NV = 1 is d.xt / d.yt, the batched pass takes its BatchVecs slots
+template <int NV>
+struct NearVecs { const double* xt[NV]; double* yt[NV]; };
+
+// x chunk in LDS for the float rows: the four columns of 16-byte vector j live as two 16-byte pairs, columns 4j, 4j+1 at pair j of
+// the first half and 4j+2, 4j+3 at pair j of the second, so that the lanes of a wavefront read consecutive 16-byte slots
+// (columns in their natural order put the lanes 32 bytes apart: a 2-way bank conflict on every read)
+constexpr int kSpmvPipeChunk = 1024;                  // columns per x buffer of the pipelined form (2 x 8 KiB)
+__device__ __forceinline__ int f32_xpos(int c) { return ((c >> 1) & 1) * (kSpmvPipeChunk / 2) + ((c >> 2) << 1) + (c & 1); }
+
+// Element policies of the row loops: what a stored row is made of.  vec = a lane's nontemporal 16-byte load, 1 << kLog2Cols
+// columns; xpos = where column c of a chunk lives in the x buffer; x_at / fma_into = the x values of vector cc and the FMA chain
+// of one loaded vector into one accumulator; recs / vals = the NearItem array and the value base of the plan.
+struct NearF64 {                                      // near_val: two doubles per load, x in column order
+  typedef double elem;
+  typedef dvec2 vec;
+  typedef dvec2 xvec;
+  static constexpr int kLog2Cols = 1;
+  static __device__ __forceinline__ int xpos(int c) { return c; }
+  static __device__ __forceinline__ xvec x_at(const double* xs, int cc) { return reinterpret_cast<const dvec2*>(xs)[cc]; }
+  static __device__ __forceinline__ double fma_into(vec v, xvec x, double acc) { return fma(v.x, x.x, fma(v.y, x.y, acc)); }
+  static __device__ __forceinline__ const NearItem* recs(const DevicePlan& d) { return d.near_recs; }
+  static __device__ __forceinline__ const elem* vals(const DevicePlan& d) { return d.near_val; }
+};
+struct NearF32 {                                      // near_f32: four floats per load (stride a multiple of 4), x at f32_xpos
+  typedef float elem;
+  typedef fvec4 vec;
+  struct xvec { dvec2 a, c; };
+  static constexpr int kLog2Cols = 2;
+  static __device__ __forceinline__ int xpos(int c) { return f32_xpos(c); }
+  static __device__ __forceinline__ xvec x_at(const double* xs, int cc) {
+    const dvec2* xv = reinterpret_cast<const dvec2*>(xs);
+    return {xv[cc], xv[kSpmvPipeChunk / 4 + cc]};
+  }
+  static __device__ __forceinline__ double fma_into(vec v, xvec x, double acc) {
+    return fma((double)v.x, x.a.x, fma((double)v.y, x.a.y, fma((double)v.z, x.c.x, fma((double)v.w, x.c.y, acc))));
+  }
+  static __device__ __forceinline__ const NearItem* recs(const DevicePlan& d) { return d.near_recs_f32; }
+  static __device__ __forceinline__ const elem* vals(const DevicePlan& d) { return d.near_f32; }
+};
+
+// The rows of one work item against one staged x chunk (columns c0 .. c0 + cw of every vector at xs + v * xstride), for NV
+// vectors at once (y: the item's first row in each): every loaded matrix vector feeds the FMAs of all NV.
+// row mode: wavefront w takes rows w, w+4, ... over all columns; column mode: every wavefront takes a quarter of the columns
+// (64-B aligned) of every row and the quarters are summed in fixed order.  A chunk beyond the first is added into y.
+template <class P, int kRows, int kVecs, int NV>
+__device__ __forceinline__ void spmv_rows(const typename P::elem* blk, int stride, int c0, int cw, int nrows, bool colsplit, const double* xs,
+                                          int xstride, double (*part)[kSpmvWaves][kColRows], const NearVecs<NV>& y) {
+  typedef typename P::vec vec;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, tid = threadIdx.x;
+  const int nvec = cw >> P::kLog2Cols;                // 16-B vectors of this chunk per row
+  const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
+  const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
+  const int rstep = colsplit ? 1 : kSpmvWaves;
+  for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
+    const vec* row[kRows];
+    double acc[NV][kRows];
+#pragma unroll
+    for (int i = 0; i < kRows; ++i) {
+      const int ri = r + i * rstep;
+      row[i] = reinterpret_cast<const vec*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
+#pragma unroll
+      for (int v = 0; v < NV; ++v) acc[v][i] = 0;
+    }
+    for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
+      vec a[kRows][kVecs];
+#pragma unroll
+      for (int u = 0; u < kVecs; ++u) {
+        const int cc = c + u * kWave;
+        const bool ok = cc < v1;
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) a[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : vec{};
+      }
+#pragma unroll
+      for (int u = 0; u < kVecs; ++u) {
+        const int cc = c + u * kWave;
+        if (cc < v1) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            const typename P::xvec x = P::x_at(xs + v * xstride, cc);
+#pragma unroll
+            for (int i = 0; i < kRows; ++i) acc[v][i] = P::fma_into(a[i][u], x, acc[v][i]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int i = 0; i < kRows; ++i) acc[v][i] = wave_sum(acc[v][i]);
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < kRows; ++i) {
+        const int ri = r + i * rstep;
+        if (ri < nrows) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            double* yt = y.yt[v];
+            if (colsplit) part[v][wave][ri] = acc[v][i];
+            else yt[ri] = c0 ? yt[ri] + acc[v][i] : acc[v][i];
+          }
+        }
+      }
+    }
+  }
+  if (colsplit) {
+    __syncthreads();
+    if (tid < nrows) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        double* yt = y.yt[v];
+        const double sum = ((part[v][0][tid] + part[v][1][tid]) + part[v][2][tid]) + part[v][3][tid];
+        yt[tid] = c0 ? yt[tid] + sum : sum;
+      }
+    }
+  }
+}
+
 template <int kRows, int kVecs>
 __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_kernel(DevicePlan d) {
   extern __shared__ double xs[];                      // [kSpmvChunk] doubles, then the run descriptors
-  __shared__ double part[kSpmvWaves][kColRows];
+  __shared__ double part[1][kSpmvWaves][kColRows];
   int* run_row0 = reinterpret_cast<int*>(xs + kSpmvChunk);
   int* run_off = run_row0 + d.max_runs;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const dvec2* xv = reinterpret_cast<const dvec2*>(xs);
   const int dof = d.dof;
 
   // Persistent workgroups (a few per CU) are dealt the work items -- row ranges of one target leaf, largest
@@ -1040,7 +1158,7 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_kernel
     const int ncols = dof * d.near_ncols[t], stride = d.near_stride[t];
     const Runs runs = load_runs(d, t, run_row0, run_off);
     const double* blk = d.near_val + d.near_off[t] + (int64_t)r0 * stride;
-    double* yt = d.yt + dof * d.leaf_row0[t] + r0;
+    const NearVecs<1> y{{d.xt}, {d.yt + dof * d.leaf_row0[t] + r0}};
     // the x slice is staged kSpmvChunk columns at a time: a few coarse leaves of an adaptive tree see
     // >10^4 columns, and sizing the LDS for them would leave one workgroup per CU
     for (int c0 = 0; c0 < stride; c0 += kSpmvChunk) {
@@ -1051,68 +1169,14 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_kernel
         xs[c] = cc < ncols ? d.xt[(int64_t)dof * column_to_row(runs, pc) + (cc - pc * dof)] : 0.0;
       }
       __syncthreads();
-      const int nvec = cw >> 1;                       // 16-B vectors of this chunk per row
-      // row mode: wavefront w takes rows w, w+4, ... over all columns; column mode: every wavefront takes
-      // a quarter of the columns (64-B aligned) of every row and the quarters are summed in fixed order
-      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
-      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
-      const int rstep = colsplit ? 1 : kSpmvWaves;
-      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
-        const dvec2* row[kRows];
-        double acc[kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int ri = r + i * rstep;
-          row[i] = reinterpret_cast<const dvec2*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
-          acc[i] = 0;
-        }
-        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
-          dvec2 v[kRows][kVecs];
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            const bool ok = cc < v1;
-#pragma unroll
-            for (int i = 0; i < kRows; ++i) v[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : dvec2{0, 0};
-          }
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            if (cc < v1) {
-              const dvec2 x2 = xv[cc];
-#pragma unroll
-              for (int i = 0; i < kRows; ++i) acc[i] = fma(v[i][u].x, x2.x, fma(v[i][u].y, x2.y, acc[i]));
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) acc[i] = wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-          for (int i = 0; i < kRows; ++i) {
-            const int ri = r + i * rstep;
-            if (ri < nrows) {
-              if (colsplit) part[wave][ri] = acc[i];
-              else yt[ri] = c0 ? yt[ri] + acc[i] : acc[i];
-            }
-          }
-        }
-      }
-      if (colsplit) {
-        __syncthreads();
-        if ((int)threadIdx.x < nrows) {
-          const int ri = threadIdx.x;
-          const double sum = ((part[0][ri] + part[1][ri]) + part[2][ri]) + part[3][ri];
-          yt[ri] = c0 ? yt[ri] + sum : sum;
-        }
-      }
+      spmv_rows<NearF64, kRows, kVecs, 1>(blk, stride, c0, cw, nrows, colsplit, xs, 0, part, y);
     }
     __syncthreads();                                  // xs / run descriptors / part are rewritten for the next item
   }
 }
 
 // ---------------------------------------------------------------------------------------------
-// near_spmv, pipelined form (one unknown per panel): the same items, the same row/column-split arithmetic as
+// near_spmv, pipelined form (one unknown per panel): the same items, the same row/column-split arithmetic (spmv_rows) as
 // near_spmv_kernel above, but the set-up of item i+1 runs while item i streams.  A workgroup's time per item was
 // [x gather: one L2 round trip] [2-3 round trips of matrix rows] with two barriers, i.e. a streaming duty of ~80 %
 // (5.5 of the 7.0 TB/s a bare read of the same blocks reaches).  Here
@@ -1121,9 +1185,21 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_kernel
 //     registers BEFORE item i's rows are streamed and written to the other halves of double-buffered LDS arrays after;
 //   * one barrier per item.
 // Wider leaves stage their further chunks in place as before.
+//
+// ONE loop, spmv_pipe_run<P, kRows, kVecs, NV>, serves three kernels; they differ in the element policy P and in NV alone, so
+// the order of every sum is one text: chunks of kSpmvPipeChunk columns with a later chunk added into y; the colsplit segments
+// and the fixed sum of their parts; lane l taking the 16-byte column vectors v0 + l + 64 j in increasing j; all kRows x kVecs
+// loads issued before the first FMA; P::fma_into; wave_sum.
+//   near_spmv_pipe_kernel        NearF64, NV = 1: plain and hybrid Laplace plans (the streamed items of a hybrid plan).
+//   near_spmv_pipe_multi_kernel  NearF64, NV vectors in one pass over the matrix (fmmbem_plan_execute_batch): every nontemporal
+//                                16-byte matrix load feeds the FMAs of all NV vectors, so every result is bit for bit the single
+//                                kernel's.  16 KiB of x per vector: NV = 2, 4, 8 leave 4, 2, 1 workgroups per CU, so the loads
+//                                in flight come from kRows x kVecs per wavefront (launch_near_spmv_multi).
+//   near_spmv_pipe_f32_kernel    NearF32, NV = 1 (further down, with the float near field): a lane's load is FOUR columns.
+// LDS: xs_all [2][NV][kSpmvPipeChunk] doubles (one vector's chunk contiguous: the lanes read it as the single kernel does, free
+// of bank conflicts), then runbuf [2][2][max_runs] ints; part [NV][kSpmvWaves][kColRows].
 // ---------------------------------------------------------------------------------------------
-constexpr int kSpmvPipeChunk = 1024;                  // columns per x buffer (2 x 8 KiB)
-constexpr int kSpmvPre = kSpmvPipeChunk / (kSpmvWaves * kWave);       // x values a thread prefetches
+constexpr int kSpmvPre = kSpmvPipeChunk / (kSpmvWaves * kWave);       // x values of one vector a thread prefetches
 
 // the item records through the constant address space: scalar loads whatever else the kernel stores (6 VGPRs fewer than
 // through the generic pointer)
@@ -1135,14 +1211,25 @@ __device__ __forceinline__ NearItem load_item(const ConstNearItem* r) {
   return o;
 }
 
-// the pipelined loop over items first, first + step, ... < end of one workgroup; LDS: xs_all [2][kSpmvPipeChunk] doubles then
-// runbuf [2][2][max_runs] ints, part [kSpmvWaves][kColRows]
-template <int kRows, int kVecs>
-__device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, double* xs_all, double (*part)[kColRows], int first, int step, int end) {
-  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * kSpmvPipeChunk);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+// columns c0 .. c0 + cw of a leaf, every vector, into the x buffer xs (a whole workgroup)
+template <class P, int NV>
+__device__ __forceinline__ void spmv_stage(const NearVecs<NV>& vecs, const Runs& runs, int c0, int cw, int ncols, double* xs) {
+  for (int c = threadIdx.x; c < cw; c += blockDim.x) {
+    const bool in = c0 + c < ncols;
+    const int row = in ? column_to_row(runs, c0 + c) : 0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) xs[v * kSpmvPipeChunk + P::xpos(c)] = in ? vecs.xt[v][row] : 0.0;
+  }
+}
+
+// the pipelined loop over items first, first + step, ... < end of one workgroup
+template <class P, int kRows, int kVecs, int NV>
+__device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, const NearVecs<NV>& vecs, double* xs_all,
+                                              double (*part)[kSpmvWaves][kColRows], int first, int step, int end) {
+  constexpr int XB = NV * kSpmvPipeChunk;             // doubles of one x buffer (all vectors)
+  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * XB);
   const int mr = d.max_runs, nitems = end, tid = threadIdx.x;
-  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(d.near_recs));
+  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(P::recs(d)));
 
   int item = first;
   if (item >= nitems) return;
@@ -1152,11 +1239,7 @@ __device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, double* xs_al
   for (int i = tid; i < it.nruns; i += blockDim.x) { runbuf[i] = d.near_run_row0[it.run_begin + i]; runbuf[mr + i] = d.near_run_off[it.run_begin + i]; }
   for (int i = tid; i < nx.nruns; i += blockDim.x) { runbuf[2 * mr + i] = d.near_run_row0[nx.run_begin + i]; runbuf[3 * mr + i] = d.near_run_off[nx.run_begin + i]; }
   __syncthreads();
-  {
-    const Runs runs{runbuf, runbuf + mr, it.nruns};
-    const int cw = it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk;
-    for (int c = tid; c < cw; c += blockDim.x) xs_all[c] = c < it.ncols ? d.xt[column_to_row(runs, c)] : 0.0;
-  }
+  spmv_stage<P, NV>(vecs, Runs{runbuf, runbuf + mr, it.nruns}, 0, it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk, it.ncols, xs_all);
   __syncthreads();
   int xb = 0, rb = 0;                                 // which halves hold the current item's x chunk 0 / runs
   for (;; item += step) {
@@ -1165,7 +1248,7 @@ __device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, double* xs_al
     const NearItem nn = load_item(recs + (i2 < nitems ? i2 : nitems - 1));
     // ---- set-up of the following items, in flight while this item's rows stream ----
     // (issued behind the first matrix loads instead: the staging array lands in scratch, 0.91 ms)
-    double px[kSpmvPre];
+    double px[NV][kSpmvPre];
     int pr0 = 0, pr1 = 0;
     const bool prun = i2 < nitems && tid < nn.nruns;     // max_runs <= blockDim.x is checked by the launcher
     if (more) {
@@ -1174,87 +1257,42 @@ __device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, double* xs_al
 #pragma unroll
       for (int u = 0; u < kSpmvPre; ++u) {
         const int c = tid + u * (kSpmvWaves * kWave);
-        px[u] = (c < ncw && c < nx.ncols) ? d.xt[column_to_row(nruns, c)] : 0.0;
+        const bool in = c < ncw && c < nx.ncols;
+        const int row = in ? column_to_row(nruns, c) : 0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) px[v][u] = in ? vecs.xt[v][row] : 0.0;
       }
       if (prun) { pr0 = d.near_run_row0[nn.run_begin + tid]; pr1 = d.near_run_off[nn.run_begin + tid]; }
     }
     // ---- this item ----
-    const int nrows = it.nrows, ncols = it.ncols, stride = it.stride;
-    const bool colsplit = it.colsplit != 0;
-    const double* blk = d.near_val + it.val_off;
-    double* yt = d.yt + it.yrow;
-    double* xs = xs_all + xb * kSpmvPipeChunk;
-    const dvec2* xv = reinterpret_cast<const dvec2*>(xs);
+    const int stride = it.stride;
+    NearVecs<NV> y;                                     // this item's rows of every y
+#pragma unroll
+    for (int v = 0; v < NV; ++v) y.yt[v] = vecs.yt[v] + it.yrow;
+    const typename P::elem* blk = P::vals(d) + it.val_off;
+    double* xs = xs_all + xb * XB;
     const Runs runs{runbuf + rb * 2 * mr, runbuf + rb * 2 * mr + mr, it.nruns};
     for (int c0 = 0; c0 < stride; c0 += kSpmvPipeChunk) {
       const int cw = stride - c0 < kSpmvPipeChunk ? stride - c0 : kSpmvPipeChunk;
       if (c0) {                                       // further chunks of a wide leaf: staged in place
         __syncthreads();
-        for (int c = tid; c < cw; c += blockDim.x) xs[c] = c0 + c < ncols ? d.xt[column_to_row(runs, c0 + c)] : 0.0;
+        spmv_stage<P, NV>(vecs, runs, c0, cw, it.ncols, xs);
         __syncthreads();
       }
-      const int nvec = cw >> 1;                       // 16-B vectors of this chunk per row
-      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
-      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
-      const int rstep = colsplit ? 1 : kSpmvWaves;
-      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
-        const dvec2* row[kRows];
-        double acc[kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int ri = r + i * rstep;
-          row[i] = reinterpret_cast<const dvec2*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
-          acc[i] = 0;
-        }
-        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
-          dvec2 v[kRows][kVecs];
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            const bool ok = cc < v1;
-#pragma unroll
-            for (int i = 0; i < kRows; ++i) v[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : dvec2{0, 0};
-          }
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            if (cc < v1) {
-              const dvec2 x2 = xv[cc];
-#pragma unroll
-              for (int i = 0; i < kRows; ++i) acc[i] = fma(v[i][u].x, x2.x, fma(v[i][u].y, x2.y, acc[i]));
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) acc[i] = wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-          for (int i = 0; i < kRows; ++i) {
-            const int ri = r + i * rstep;
-            if (ri < nrows) {
-              if (colsplit) part[wave][ri] = acc[i];
-              else yt[ri] = c0 ? yt[ri] + acc[i] : acc[i];
-            }
-          }
-        }
-      }
-      if (colsplit) {
-        __syncthreads();
-        if (tid < nrows) {
-          const double sum = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-          yt[tid] = c0 ? yt[tid] + sum : sum;
-        }
-      }
+      spmv_rows<P, kRows, kVecs, NV>(blk, stride, c0, cw, it.nrows, it.colsplit != 0, xs, kSpmvPipeChunk, part, y);
     }
     if (!more) break;
     // ---- hand over: next item's x and the item after's runs into the halves nobody reads now ----
     {
-      double* xn = xs_all + (xb ^ 1) * kSpmvPipeChunk;
+      double* xn = xs_all + (xb ^ 1) * XB;
       const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
 #pragma unroll
       for (int u = 0; u < kSpmvPre; ++u) {
         const int c = tid + u * (kSpmvWaves * kWave);
-        if (c < ncw) xn[c] = px[u];
+        if (c < ncw) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v) xn[v * kSpmvPipeChunk + P::xpos(c)] = px[v][u];
+        }
       }
     }
     // runs[rb] belonged to this item; a wide leaf's later chunks were the last to read it, and every thread has passed
@@ -1275,176 +1313,21 @@ __device__ __forceinline__ void spmv_pipe_run(const DevicePlan& d, double* xs_al
 template <int kRows, int kVecs>
 __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_pipe_kernel(DevicePlan d) {
   extern __shared__ double xs_all[];
-  __shared__ double part[kSpmvWaves][kColRows];
-  spmv_pipe_run<kRows, kVecs>(d, xs_all, part, blockIdx.x, gridDim.x, d.near_rec ? d.near_nitems_stream : d.near_nitems);
+  __shared__ double part[1][kSpmvWaves][kColRows];
+  const NearVecs<1> vecs{{d.xt}, {d.yt}};
+  spmv_pipe_run<NearF64, kRows, kVecs, 1>(d, vecs, xs_all, part, blockIdx.x, gridDim.x, d.near_rec ? d.near_nitems_stream : d.near_nitems);
 }
 
-// ---------------------------------------------------------------------------------------------
-// near_spmv for NV vectors in one pass over the matrix (fmmbem_plan_execute_batch): the items, records, run descriptors and
-// pipelining of spmv_pipe_run, with every nontemporal 16-byte matrix load feeding the FMAs of all NV vectors.  Each vector's
-// row sums are formed exactly as near_spmv_pipe_kernel forms them -- chunks of kSpmvPipeChunk columns with a later chunk added
-// into y; the colsplit segments and the fixed sum of their parts; lane l taking the 16-byte column vectors v0 + l + 64 j in
-// increasing j; fma(v.x, x.x, fma(v.y, x.y, acc)); wave_sum -- so every result is bit for bit the single kernel's.
-// LDS: xs_all [2][NV][kSpmvPipeChunk] doubles (one vector's chunk contiguous: the lanes read it as the single kernel does, free
-// of bank conflicts), then runbuf [2][2][max_runs] ints; part [NV][kSpmvWaves][kColRows].  16 KiB of x per vector: NV = 2, 4, 8
-// leave 4, 2, 1 workgroups per CU, so the loads in flight come from kRows x kVecs per wavefront (launch_near_spmv_multi).
-// ---------------------------------------------------------------------------------------------
 constexpr int batch_occ(int nv) { return nv <= 2 ? 4 : nv <= 4 ? 2 : 1; }
 
 template <int kRows, int kVecs, int NV>
 __global__ __launch_bounds__(kSpmvWaves * kWave, batch_occ(NV)) void near_spmv_pipe_multi_kernel(DevicePlan d, BatchVecs bv) {
   extern __shared__ double xs_all[];
   __shared__ double part[NV][kSpmvWaves][kColRows];
-  constexpr int XB = NV * kSpmvPipeChunk;             // doubles of one x buffer (all vectors)
-  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * XB);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int mr = d.max_runs, nitems = d.near_nitems, tid = threadIdx.x;
-  const int step = gridDim.x;
-  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(d.near_recs));
-
-  int item = blockIdx.x;
-  if (item >= nitems) return;
-  NearItem it = load_item(recs + item);
-  NearItem nx = load_item(recs + (item + step < nitems ? item + step : nitems - 1));
-  for (int i = tid; i < it.nruns; i += blockDim.x) { runbuf[i] = d.near_run_row0[it.run_begin + i]; runbuf[mr + i] = d.near_run_off[it.run_begin + i]; }
-  for (int i = tid; i < nx.nruns; i += blockDim.x) { runbuf[2 * mr + i] = d.near_run_row0[nx.run_begin + i]; runbuf[3 * mr + i] = d.near_run_off[nx.run_begin + i]; }
-  __syncthreads();
-  {
-    const Runs runs{runbuf, runbuf + mr, it.nruns};
-    const int cw = it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk;
-    for (int c = tid; c < cw; c += blockDim.x) {
-      const bool in = c < it.ncols;
-      const int row = in ? column_to_row(runs, c) : 0;
+  NearVecs<NV> vecs;
 #pragma unroll
-      for (int v = 0; v < NV; ++v) xs_all[v * kSpmvPipeChunk + c] = in ? bv.xt[v][row] : 0.0;
-    }
-  }
-  __syncthreads();
-  int xb = 0, rb = 0;
-  for (;; item += step) {
-    const bool more = item + step < nitems;
-    const int i2 = item + 2 * step;
-    const NearItem nn = load_item(recs + (i2 < nitems ? i2 : nitems - 1));
-    // ---- set-up of the following items, in flight while this item's rows stream ----
-    double px[NV][kSpmvPre];
-    int pr0 = 0, pr1 = 0;
-    const bool prun = i2 < nitems && tid < nn.nruns;
-    if (more) {
-      const Runs nruns{runbuf + (rb ^ 1) * 2 * mr, runbuf + (rb ^ 1) * 2 * mr + mr, nx.nruns};
-      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
-#pragma unroll
-      for (int u = 0; u < kSpmvPre; ++u) {
-        const int c = tid + u * (kSpmvWaves * kWave);
-        const bool in = c < ncw && c < nx.ncols;
-        const int row = in ? column_to_row(nruns, c) : 0;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) px[v][u] = in ? bv.xt[v][row] : 0.0;
-      }
-      if (prun) { pr0 = d.near_run_row0[nn.run_begin + tid]; pr1 = d.near_run_off[nn.run_begin + tid]; }
-    }
-    // ---- this item ----
-    const int nrows = it.nrows, ncols = it.ncols, stride = it.stride;
-    const bool colsplit = it.colsplit != 0;
-    const double* blk = d.near_val + it.val_off;
-    double* xs = xs_all + xb * XB;
-    const Runs runs{runbuf + rb * 2 * mr, runbuf + rb * 2 * mr + mr, it.nruns};
-    for (int c0 = 0; c0 < stride; c0 += kSpmvPipeChunk) {
-      const int cw = stride - c0 < kSpmvPipeChunk ? stride - c0 : kSpmvPipeChunk;
-      if (c0) {                                       // further chunks of a wide leaf: staged in place
-        __syncthreads();
-        for (int c = tid; c < cw; c += blockDim.x) {
-          const bool in = c0 + c < ncols;
-          const int row = in ? column_to_row(runs, c0 + c) : 0;
-#pragma unroll
-          for (int v = 0; v < NV; ++v) xs[v * kSpmvPipeChunk + c] = in ? bv.xt[v][row] : 0.0;
-        }
-        __syncthreads();
-      }
-      const int nvec = cw >> 1;
-      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
-      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
-      const int rstep = colsplit ? 1 : kSpmvWaves;
-      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
-        const dvec2* row[kRows];
-        double acc[NV][kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int ri = r + i * rstep;
-          row[i] = reinterpret_cast<const dvec2*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
-#pragma unroll
-          for (int v = 0; v < NV; ++v) acc[v][i] = 0;
-        }
-        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
-          dvec2 a[kRows][kVecs];
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            const bool ok = cc < v1;
-#pragma unroll
-            for (int i = 0; i < kRows; ++i) a[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : dvec2{0, 0};
-          }
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            if (cc < v1) {
-#pragma unroll
-              for (int v = 0; v < NV; ++v) {
-                const dvec2 x2 = reinterpret_cast<const dvec2*>(xs + v * kSpmvPipeChunk)[cc];
-#pragma unroll
-                for (int i = 0; i < kRows; ++i) acc[v][i] = fma(a[i][u].x, x2.x, fma(a[i][u].y, x2.y, acc[v][i]));
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-          for (int i = 0; i < kRows; ++i) acc[v][i] = wave_sum(acc[v][i]);
-        if (lane == 0) {
-#pragma unroll
-          for (int i = 0; i < kRows; ++i) {
-            const int ri = r + i * rstep;
-            if (ri < nrows) {
-#pragma unroll
-              for (int v = 0; v < NV; ++v) {
-                double* yt = bv.yt[v] + it.yrow;
-                if (colsplit) part[v][wave][ri] = acc[v][i];
-                else yt[ri] = c0 ? yt[ri] + acc[v][i] : acc[v][i];
-              }
-            }
-          }
-        }
-      }
-      if (colsplit) {
-        __syncthreads();
-        if (tid < nrows) {
-#pragma unroll
-          for (int v = 0; v < NV; ++v) {
-            double* yt = bv.yt[v] + it.yrow;
-            const double sum = ((part[v][0][tid] + part[v][1][tid]) + part[v][2][tid]) + part[v][3][tid];
-            yt[tid] = c0 ? yt[tid] + sum : sum;
-          }
-        }
-      }
-    }
-    if (!more) break;
-    // ---- hand over: next item's x and the item after's runs into the halves nobody reads now ----
-    {
-      double* xn = xs_all + (xb ^ 1) * XB;
-      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
-#pragma unroll
-      for (int u = 0; u < kSpmvPre; ++u) {
-        const int c = tid + u * (kSpmvWaves * kWave);
-        if (c < ncw) {
-#pragma unroll
-          for (int v = 0; v < NV; ++v) xn[v * kSpmvPipeChunk + c] = px[v][u];
-        }
-      }
-    }
-    if (prun) { runbuf[rb * 2 * mr + tid] = pr0; runbuf[rb * 2 * mr + mr + tid] = pr1; }
-    __syncthreads();
-    it = nx; nx = nn; xb ^= 1; rb ^= 1;
-  }
+  for (int v = 0; v < NV; ++v) { vecs.xt[v] = bv.xt[v]; vecs.yt[v] = bv.yt[v]; }
+  spmv_pipe_run<NearF64, kRows, kVecs, NV>(d, vecs, xs_all, part, blockIdx.x, gridDim.x, d.near_nitems);
 }
 
 }  // namespace
@@ -1560,12 +1443,11 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
 // of near_val / near_sym; x in LDS, the accumulators and y stay doubles, so the result differs from the FP64 kernel's by the
 // rounding of the entries alone: |dy_i| <= 2^-24 (|A| |x|)_i.
 //   near_to_f32 / near_sym_to_f32     once per plan, after the assembly: the copy, round to nearest even
-//   near_spmv_pipe_f32                spmv_pipe_run on the float rows: a lane's nontemporal 16-byte load is FOUR columns
+//   near_spmv_pipe_f32                spmv_pipe_run with the NearF32 policy: a lane's nontemporal 16-byte load is FOUR columns
 //   near_spmv_sym3_f32                near_spmv_sym3 on the float planes: a lane's three 16-byte loads are TWO source panels
 // Row sums in a fixed order (lanes over the 16-byte vectors in increasing column, wave_sum, the colsplit parts in wavefront
 // order, later chunks added into y): the same bits every run; not the FP64 kernels' order (four columns per lane step, not two).
 // ---------------------------------------------------------------------------------------------
-typedef float fvec4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(kSpmvWaves * kWave) void near_to_f32_kernel(DevicePlan d) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -1593,138 +1475,12 @@ __global__ __launch_bounds__(kSpmvWaves * kWave) void near_sym_to_f32_kernel(Dev
       }
   }
 }
-
-// x chunk in LDS for the float rows: the four columns of 16-byte vector j live as two 16-byte pairs, columns 4j, 4j+1 at pair j of
-// the first half and 4j+2, 4j+3 at pair j of the second, so that the lanes of a wavefront read consecutive 16-byte slots
-// (columns in their natural order put the lanes 32 bytes apart: a 2-way bank conflict on every read)
-__device__ __forceinline__ int f32_xpos(int c) { return ((c >> 1) & 1) * (kSpmvPipeChunk / 2) + ((c >> 2) << 1) + (c & 1); }
-
-// LDS as spmv_pipe_run: xs_all [2][kSpmvPipeChunk] doubles, runbuf [2][2][max_runs] ints, part [kSpmvWaves][kColRows]
 template <int kRows, int kVecs, int kOcc>
 __global__ __launch_bounds__(kSpmvWaves * kWave, kOcc) void near_spmv_pipe_f32_kernel(DevicePlan d) {
   extern __shared__ double xs_all[];
-  __shared__ double part[kSpmvWaves][kColRows];
-  int* const runbuf = reinterpret_cast<int*>(xs_all + 2 * kSpmvPipeChunk);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int mr = d.max_runs, nitems = d.near_nitems, tid = threadIdx.x, step = gridDim.x;
-  const ConstNearItem* recs = reinterpret_cast<const ConstNearItem*>(reinterpret_cast<uintptr_t>(d.near_recs_f32));
-
-  int item = blockIdx.x;
-  if (item >= nitems) return;
-  NearItem it = load_item(recs + item);
-  NearItem nx = load_item(recs + (item + step < nitems ? item + step : nitems - 1));
-  for (int i = tid; i < it.nruns; i += blockDim.x) { runbuf[i] = d.near_run_row0[it.run_begin + i]; runbuf[mr + i] = d.near_run_off[it.run_begin + i]; }
-  for (int i = tid; i < nx.nruns; i += blockDim.x) { runbuf[2 * mr + i] = d.near_run_row0[nx.run_begin + i]; runbuf[3 * mr + i] = d.near_run_off[nx.run_begin + i]; }
-  __syncthreads();
-  {
-    const Runs runs{runbuf, runbuf + mr, it.nruns};
-    const int cw = it.stride < kSpmvPipeChunk ? it.stride : kSpmvPipeChunk;
-    for (int c = tid; c < cw; c += blockDim.x) xs_all[f32_xpos(c)] = c < it.ncols ? d.xt[column_to_row(runs, c)] : 0.0;
-  }
-  __syncthreads();
-  int xb = 0, rb = 0;
-  for (;; item += step) {
-    const bool more = item + step < nitems;
-    const int i2 = item + 2 * step;
-    const NearItem nn = load_item(recs + (i2 < nitems ? i2 : nitems - 1));
-    // ---- set-up of the following items, in flight while this item's rows stream ----
-    double px[kSpmvPre];
-    int pr0 = 0, pr1 = 0;
-    const bool prun = i2 < nitems && tid < nn.nruns;     // max_runs <= blockDim.x is checked by the launcher
-    if (more) {
-      const Runs nruns{runbuf + (rb ^ 1) * 2 * mr, runbuf + (rb ^ 1) * 2 * mr + mr, nx.nruns};
-      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
-#pragma unroll
-      for (int u = 0; u < kSpmvPre; ++u) {
-        const int c = tid + u * (kSpmvWaves * kWave);
-        px[u] = (c < ncw && c < nx.ncols) ? d.xt[column_to_row(nruns, c)] : 0.0;
-      }
-      if (prun) { pr0 = d.near_run_row0[nn.run_begin + tid]; pr1 = d.near_run_off[nn.run_begin + tid]; }
-    }
-    // ---- this item ----
-    const int nrows = it.nrows, ncols = it.ncols, stride = it.stride;   // stride: floats, a multiple of 4
-    const bool colsplit = it.colsplit != 0;
-    const float* blk = d.near_f32 + it.val_off;
-    double* yt = d.yt + it.yrow;
-    double* xs = xs_all + xb * kSpmvPipeChunk;
-    const dvec2* xv = reinterpret_cast<const dvec2*>(xs);
-    const Runs runs{runbuf + rb * 2 * mr, runbuf + rb * 2 * mr + mr, it.nruns};
-    for (int c0 = 0; c0 < stride; c0 += kSpmvPipeChunk) {
-      const int cw = stride - c0 < kSpmvPipeChunk ? stride - c0 : kSpmvPipeChunk;
-      if (c0) {                                       // further chunks of a wide leaf: staged in place
-        __syncthreads();
-        for (int c = tid; c < cw; c += blockDim.x) xs[f32_xpos(c)] = c0 + c < ncols ? d.xt[column_to_row(runs, c0 + c)] : 0.0;
-        __syncthreads();
-      }
-      const int nvec = cw >> 2;                       // 16-B vectors (four columns) of this chunk per row
-      const int seg = colsplit ? ((((nvec + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : nvec;
-      const int v0 = colsplit ? wave * seg : 0, v1 = min(nvec, v0 + seg);
-      const int rstep = colsplit ? 1 : kSpmvWaves;
-      for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
-        const fvec4* row[kRows];
-        double acc[kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int ri = r + i * rstep;
-          row[i] = reinterpret_cast<const fvec4*>(blk + (int64_t)(ri < nrows ? ri : r) * stride + c0);
-          acc[i] = 0;
-        }
-        for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
-          fvec4 v[kRows][kVecs];
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            const bool ok = cc < v1;
-#pragma unroll
-            for (int i = 0; i < kRows; ++i) v[i][u] = ok ? __builtin_nontemporal_load(&row[i][cc]) : fvec4{0, 0, 0, 0};
-          }
-#pragma unroll
-          for (int u = 0; u < kVecs; ++u) {
-            const int cc = c + u * kWave;
-            if (cc < v1) {
-              const dvec2 xa = xv[cc], xc = xv[kSpmvPipeChunk / 4 + cc];
-#pragma unroll
-              for (int i = 0; i < kRows; ++i)
-                acc[i] = fma((double)v[i][u].x, xa.x, fma((double)v[i][u].y, xa.y, fma((double)v[i][u].z, xc.x, fma((double)v[i][u].w, xc.y, acc[i]))));
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) acc[i] = wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-          for (int i = 0; i < kRows; ++i) {
-            const int ri = r + i * rstep;
-            if (ri < nrows) {
-              if (colsplit) part[wave][ri] = acc[i];
-              else yt[ri] = c0 ? yt[ri] + acc[i] : acc[i];
-            }
-          }
-        }
-      }
-      if (colsplit) {
-        __syncthreads();
-        if (tid < nrows) {
-          const double sum = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-          yt[tid] = c0 ? yt[tid] + sum : sum;
-        }
-      }
-    }
-    if (!more) break;
-    // ---- hand over: next item's x and the item after's runs into the halves nobody reads now ----
-    {
-      double* xn = xs_all + (xb ^ 1) * kSpmvPipeChunk;
-      const int ncw = nx.stride < kSpmvPipeChunk ? nx.stride : kSpmvPipeChunk;
-#pragma unroll
-      for (int u = 0; u < kSpmvPre; ++u) {
-        const int c = tid + u * (kSpmvWaves * kWave);
-        if (c < ncw) xn[f32_xpos(c)] = px[u];
-      }
-    }
-    if (prun) { runbuf[rb * 2 * mr + tid] = pr0; runbuf[rb * 2 * mr + mr + tid] = pr1; }
-    __syncthreads();
-    it = nx; nx = nn; xb ^= 1; rb ^= 1;
-  }
+  __shared__ double part[1][kSpmvWaves][kColRows];
+  const NearVecs<1> vecs{{d.xt}, {d.yt}};
+  spmv_pipe_run<NearF32, kRows, kVecs, 1>(d, vecs, xs_all, part, blockIdx.x, gridDim.x, d.near_nitems);
 }
 
 // per PAIR of source panels three 16-byte vectors and the pairs' x components (16-byte LDS reads) feed eighteen FMAs
