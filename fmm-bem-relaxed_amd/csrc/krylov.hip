@@ -105,10 +105,10 @@ __global__ __launch_bounds__(kThreads) void mgs_step_kernel(int64_t n, double* _
   }
 }
 
-// The sweep of mgs_step_kernel on its vector path, statement for statement, as a function: the multi-system kernel below runs
-// it once per system (whose vectors always start on 16-byte boundaries).  mgs_step_kernel itself stays as it is -- wrapping it
-// round this function moves its instructions -- so the two must be kept in step; tests/test_gpu_gmres_batch.py holds them to
-// the same bits.
+// The sweep of mgs_step_kernel on its vector path, statement for statement, as a function: the multi-system kernel below, the
+// solver's, runs it once per system (whose vectors always start on 16-byte boundaries).  mgs_step_kernel itself, the kernel of
+// fmmbem_mgs_column_device, stays as it is -- wrapping it round this function moves its instructions -- so the two must be
+// kept in step ("Multi-right-hand-side GMRES").
 __device__ __forceinline__ void mgs_step_body(int64_t n, double* __restrict__ w, const double* __restrict__ v_prev,
                                               const double* __restrict__ part_prev, const double* __restrict__ v_dot,
                                               double* __restrict__ part_out) {
@@ -154,7 +154,7 @@ __device__ __forceinline__ void mgs_step_body(int64_t n, double* __restrict__ w,
   }
 }
 
-// The systems of one multi-system launch (fmmbem_gmres_batch): blockIdx.y picks a workspace slot from a table passed by value
+// The systems of one launch of the solver below: blockIdx.y picks a workspace slot from a table passed by value
 constexpr int kSysPerLaunch = 64;
 struct SysTable {
   int count;
@@ -255,8 +255,9 @@ extern "C" int fmmbem_mgs_scratch_doubles(int max_cols) { return (max_cols + 1) 
 
 // ================================================================================================================
 // Relaxed GMRES / FGMRES resident on the device (include/fmmbem.h; examples/BEM/GMRES.hpp:143-252, :276-380,
-// GMRES_Stokes.hpp:173-320, SolverOptions.hpp:25-38).  Host side: the (R+1) x R Hessenberg matrix, the Givens rotations, the
-// residual estimate, predict_p, restart, back substitution.  Device side: everything of length n.
+// GMRES_Stokes.hpp:173-320, SolverOptions.hpp:25-38) for k >= 1 right-hand sides on one plan: k independent solves advanced
+// in lockstep.  Host side, per system: the (R+1) x R Hessenberg matrix, the Givens rotations, the residual estimate,
+// predict_p, back substitution.  Device side: everything of length n.  fmmbem_gmres(_device) is k = 1.
 // ================================================================================================================
 namespace {
 
@@ -283,15 +284,12 @@ __global__ __launch_bounds__(kThreads) void axpy_norm_kernel(int64_t n, double* 
   }
 }
 
-// out = a * in  (V_0 = -w / beta), or out = r .* in (the diagonal preconditioner) when r
-__global__ __launch_bounds__(kThreads) void scale_kernel(int64_t n, const double* __restrict__ in, double a, const double* __restrict__ r,
-                                                          double* __restrict__ out) {
-  for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
-    out[i] = r ? r[i] * in[i] : a * in[i];
+// out = a * in  (V_0 = -w / beta)
+__global__ __launch_bounds__(kThreads) void scale_kernel(int64_t n, const double* __restrict__ in, double a, double* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) out[i] = a * in[i];
 }
 
-// out = r .* in for every system of the table, `slot` strides of ld from the bases: the diagonal preconditioner of
-// fmmbem_gmres_batch in one launch
+// out = r .* in for every system of the table, `slot` strides of ld from the bases: the diagonal preconditioner in one launch
 __global__ __launch_bounds__(kThreads) void scale_multi_kernel(int64_t n, const double* __restrict__ in, const double* __restrict__ r,
                                                                 double* __restrict__ out, int64_t ld, SysTable t) {
   const int64_t off = t.slot[blockIdx.y] * ld;
@@ -318,27 +316,18 @@ __global__ __launch_bounds__(kThreads) void update_x_kernel(int64_t n, double* _
 
 namespace fmmbem {
 
-// Workspace of fmmbem_gmres_batch: `cap` systems side by side.  Column c of system j is at ((c * cap) + j) * ld of V (and Z), w
-// and z of system j at j * ld: column c of all systems is equally spaced, so one batched execute takes it as it lies.
-// Separate from the single solver's buffers: neither solver frees or resizes what the other one holds.
-struct BatchWs {
+// Workspace of the solver, kept with the plan between solves: `cap` systems side by side.  Column c of system j is at
+// ((c * cap) + j) * ld of V (and Z), w and z of system j at j * ld: column c of all systems is equally spaced, so one batched
+// execute takes it as it lies.  A solve of fewer systems than cap runs in the first slots of the wider workspace.
+struct SolverWs {
+  int device = 0;
   int cap = 0;
   int64_t n = 0, ld = 0;
   int vcols = 0, zcols = 0, hcap = 0;
   double *V = nullptr, *Z = nullptr, *w = nullptr, *z = nullptr, *d_h = nullptr, *d_scratch = nullptr, *d_y = nullptr;
-  double *d_xb = nullptr, *d_recip = nullptr;       // staging of the host-pointer entry point
+  double *d_xb = nullptr, *d_recip = nullptr;       // staging of the host-pointer entry points
   size_t xb_doubles = 0;
   double* h_pin = nullptr;                          // pinned, 2 * cap * hcap: the Hessenberg columns, then the y coefficients
-};
-
-struct SolverWs {
-  BatchWs batch;
-  int device = 0;
-  int64_t n = 0, ld = 0;
-  int vcols = 0, zcols = 0, hcap = 0;
-  double *V = nullptr, *Z = nullptr, *w = nullptr, *z = nullptr, *d_h = nullptr, *d_scratch = nullptr, *d_y = nullptr;
-  double *d_xb = nullptr, *d_recip = nullptr;       // staging of the host-pointer entry point
-  double* h_pin = nullptr;                          // pinned: the Hessenberg column / the y coefficients cross here
 };
 
 void solver_ws_destroy(SolverWs* ws) {
@@ -349,10 +338,6 @@ void solver_ws_destroy(SolverWs* ws) {
   for (double* p : {ws->V, ws->Z, ws->w, ws->z, ws->d_h, ws->d_scratch, ws->d_y, ws->d_xb, ws->d_recip})
     if (p) (void)hipFree(p);
   if (ws->h_pin) (void)hipHostFree(ws->h_pin);
-  const BatchWs& b = ws->batch;
-  for (double* p : {b.V, b.Z, b.w, b.z, b.d_h, b.d_scratch, b.d_y, b.d_xb, b.d_recip})
-    if (p) (void)hipFree(p);
-  if (b.h_pin) (void)hipHostFree(b.h_pin);
   (void)hipSetDevice(prev);
   delete ws;
 }
@@ -401,38 +386,44 @@ void reset_ws(SolverWs* ws) {
   if (ws->h_pin) (void)hipHostFree(ws->h_pin);
   ws->h_pin = nullptr;
   ws->n = ws->ld = 0;
-  ws->vcols = ws->zcols = ws->hcap = 0;
+  ws->cap = ws->vcols = ws->zcols = ws->hcap = 0;
 }
 
-int grow_ws(SolverWs* ws, int64_t n, int vcols, int zcols) {
-  const int64_t ld = (n + 1) & ~int64_t(1);                      // even stride: every basis vector on a 16-byte boundary
-  if (ws->n != n) {
+int grow_ws(SolverWs* ws, int64_t n, int k, int vcols, int zcols) {
+  const int64_t ld = (n + 1) & ~int64_t(1);                      // even stride: every vector of every system on a 16-byte boundary
+  if (ws->n != n || ws->cap < k) {
     reset_ws(ws);
-    KRY_TRY(grow(&ws->w, (size_t)ld));
-    KRY_TRY(grow(&ws->z, (size_t)ld));
-    ws->n = n; ws->ld = ld;
+    KRY_TRY(grow(&ws->w, (size_t)ld * k));
+    KRY_TRY(grow(&ws->z, (size_t)ld * k));
+    ws->n = n; ws->ld = ld; ws->cap = k;
   }
-  if (ws->vcols < vcols) { ws->vcols = 0; KRY_TRY(grow(&ws->V, (size_t)ld * vcols)); ws->vcols = vcols; }
-  if (ws->zcols < zcols) { ws->zcols = 0; KRY_TRY(grow(&ws->Z, (size_t)ld * zcols)); ws->zcols = zcols; }
+  const size_t col = (size_t)ld * ws->cap;
+  if (ws->vcols < vcols) { ws->vcols = 0; KRY_TRY(grow(&ws->V, col * vcols)); ws->vcols = vcols; }
+  if (ws->zcols < zcols) { ws->zcols = 0; KRY_TRY(grow(&ws->Z, col * zcols)); ws->zcols = zcols; }
   if (ws->hcap < vcols + 1) {
     const int hcap = vcols + 1;
     ws->hcap = 0;
-    KRY_TRY(grow(&ws->d_h, (size_t)hcap));
-    KRY_TRY(grow(&ws->d_y, (size_t)hcap));
-    KRY_TRY(grow(&ws->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap)));
+    KRY_TRY(grow(&ws->d_h, (size_t)hcap * ws->cap));
+    KRY_TRY(grow(&ws->d_y, (size_t)hcap * ws->cap));
+    KRY_TRY(grow(&ws->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap) * ws->cap));
     if (ws->h_pin) (void)hipHostFree(ws->h_pin);
     ws->h_pin = nullptr;
-    KRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_pin), sizeof(double) * (size_t)hcap, hipHostMallocDefault));
+    KRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_pin), sizeof(double) * 2 * (size_t)hcap * ws->cap, hipHostMallocDefault));
     ws->hcap = hcap;                                             // sizes are committed only once every buffer of the group exists
   }
   return FMMBEM_OK;
 }
 
-// the workspace a plan keeps between solves (an inner-plan preconditioner solves once per outer iteration: no allocation there)
-int ensure_ws(SolverWs** slot, int device, int64_t n, int vcols, int zcols, SolverWs** out) {
+SolverWs* plan_ws(SolverWs** slot, int device) {
   if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
-  SolverWs* ws = *slot;
-  const int rc = grow_ws(ws, n, vcols, zcols);
+  return *slot;
+}
+
+// the workspace a plan keeps between solves (an inner-plan preconditioner solves once per outer iteration: no allocation
+// there), wide enough for k systems; a failed allocation leaves it empty
+int ensure_ws(SolverWs** slot, int device, int64_t n, int k, int vcols, int zcols, SolverWs** out) {
+  SolverWs* ws = plan_ws(slot, device);
+  const int rc = grow_ws(ws, n, k, vcols, zcols);
   if (rc != FMMBEM_OK) { reset_ws(ws); return rc; }
   *out = ws;
   return FMMBEM_OK;
@@ -441,20 +432,6 @@ int ensure_ws(SolverWs** slot, int device, int64_t n, int vcols, int zcols, Solv
 int sweep_grid(int64_t n) {
   const int64_t want = (n + kThreads - 1) / kThreads;
   return (int)std::max<int64_t>(1, std::min<int64_t>(want, kBlocks));
-}
-
-// |w| (after w += a v when v) -> host; one synchronisation
-int axpy_norm(int64_t n, double* w, double a, const double* v, double* d_scratch, double* d_h, double* h_pin, hipStream_t s, double* out) {
-  hipLaunchKernelGGL(axpy_norm_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, w, a, v, d_scratch);
-  hipLaunchKernelGGL(mgs_finish_kernel, dim3(1), dim3(kThreads), 0, s, d_scratch, 0, d_h);      // ncols = 0: row 0 is a norm
-  KRY_HIP(hipMemcpyAsync(h_pin, d_h, sizeof(double), hipMemcpyDeviceToHost, s));
-  KRY_HIP(hipStreamSynchronize(s));
-  *out = h_pin[0];
-  return FMMBEM_OK;
-}
-
-int axpy_norm(SolverWs* ws, double* w, double a, const double* v, hipStream_t s, double* out) {
-  return axpy_norm(ws->n, w, a, v, ws->d_scratch, ws->d_h, ws->h_pin, s, out);
 }
 
 // SolverOptions::predict_p (SolverOptions.hpp:25-38), the (unsigned) cast of the reference kept as far as it matters: a
@@ -491,10 +468,7 @@ void plane_rotation(double dx, double dy, double* cs, double* sn) {             
   else { const double t = dy / dx; *cs = 1.0 / std::sqrt(1.0 + t * t); *sn = t * *cs; }
 }
 
-int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const double* d_b, const fmmbem_preconditioner* M,
-          fmmbem_solver_log* log, hipStream_t s, int depth);
-
-// what a solve refuses before it touches anything, the single solver and the batched one alike
+// what a solve refuses before it touches anything
 int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem_preconditioner* M, int depth, int* device, int64_t* n,
                 int* plan_pmax, SolverWs*** slot) {
   KRY_TRY(fmmbem::plan_solver_info(plan, device, n, plan_pmax, slot));
@@ -545,165 +519,33 @@ struct Arnoldi {
   }
 };
 
-// z = M(v): returns in *z either v itself (identity) or ws->z / the given buffer
-int apply_pc(SolverWs* ws, const fmmbem_preconditioner* M, const double* v, double* zbuf, const double** z, hipStream_t s, int depth) {
-  const int kind = M ? M->kind : FMMBEM_PC_IDENTITY;
-  if (kind == FMMBEM_PC_IDENTITY) { *z = v; return FMMBEM_OK; }
-  if (kind == FMMBEM_PC_DIAGONAL) {
-    hipLaunchKernelGGL(scale_kernel, dim3(sweep_grid(ws->n)), dim3(kThreads), 0, s, ws->n, v, 0.0, M->reciprocals, zbuf);
-    *z = zbuf;
-    return FMMBEM_OK;
-  }
-  // LocalPC.hpp:35-41: fill(y, 0); GMRES(plan, y, x, options)
-  KRY_HIP(hipMemsetAsync(zbuf, 0, sizeof(double) * (size_t)ws->n, s));
-  KRY_TRY(solve(M->inner_plan, M->inner, zbuf, v, nullptr, nullptr, s, depth + 1));
-  *z = zbuf;
-  return FMMBEM_OK;
-}
-
-int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, double* d_x, const double* d_b, const fmmbem_preconditioner* M,
-          fmmbem_solver_log* log, hipStream_t s, int depth) {
-  int device = 0, plan_pmax = 0;
-  int64_t n = 0;
-  SolverWs** slot = nullptr;
-  KRY_TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
-  const int kind = M ? M->kind : FMMBEM_PC_IDENTITY;
-  const int R = so.restart;
-  // the inner loop runs while i + 1 < R and i + 1 <= max_iters (GMRES.hpp:221): at most min(R, max_iters + 1) columns
-  const int most = (int)std::min<int64_t>(R, (int64_t)so.max_iters + 1);
-  SolverWs* ws = nullptr;
-  KRY_TRY(ensure_ws(slot, device, n, most + 1, so.flexible ? most : 0, &ws));
-  const int64_t ld = ws->ld;
-  const int grid = sweep_grid(n);
-  Arnoldi ar(R);
-  std::vector<double>& sv = ar.sv;
-  if (log) { log->iterations = 0; log->residual = 0.0; }
-
-  // scale residual by |b| (GMRES.hpp:162)
-  double normb = 0;
-  KRY_TRY(axpy_norm(ws, const_cast<double*>(d_b), 0.0, nullptr, s, &normb));
-  if (normb == 0.0) return FMMBEM_OK;        // b = 0: the reference divides by zero and stops on NaN; x = x0 is returned
-  int cur_p = std::min(so.initial_p > 0 ? so.initial_p : so.max_p, plan_pmax);
-  int iter = 0, i = 0;
-  double resid = 0;
-  do {                                       // outer (restart) loop, :166
-    KRY_TRY(fmmbem_plan_execute_device(plan, cur_p, d_x, ws->w, s));           // w = A x at the kernel's current order
-    double beta = 0;
-    KRY_TRY(axpy_norm(ws, ws->w, -1.0, d_b, s, &beta));                        // w -= b; beta = |w|
-    if (beta == 0.0) { resid = 0.0; break; }                                   // x solves the system exactly
-    hipLaunchKernelGGL(scale_kernel, dim3(grid), dim3(kThreads), 0, s, n, ws->w, -1.0 / beta, (const double*)nullptr, ws->V);   // V_0 = -w / beta
-    sv[0] = beta;
-    i = -1;
-    resid = sv[0] / normb;
-    do {                                     // inner loop, :186
-      ++i;
-      ++iter;
-      cur_p = order_for(so, resid, plan_pmax);
-      const double* z = nullptr;
-      KRY_TRY(apply_pc(ws, M, ws->V + (int64_t)i * ld, so.flexible ? ws->Z + (int64_t)i * ld : ws->z, &z, s, depth));
-      KRY_TRY(fmmbem_plan_execute_device(plan, cur_p, z, ws->w, s));
-      // modified Gram-Schmidt against V_0..V_i, |w|, V_{i+1} = w / |w| (:203-212): one library call, then the column to the host
-      KRY_TRY(fmmbem_mgs_column_device(n, ws->w, ws->V, ld, i + 1, ws->d_h, ws->V + (int64_t)(i + 1) * ld, ws->d_scratch, s));
-      KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, s));
-      KRY_HIP(hipStreamSynchronize(s));
-      ar.column(i, ws->h_pin);
-      resid = sv[i + 1] / normb;
-      if (log && log->p && log->resid && iter <= log->capacity) { log->p[iter - 1] = cur_p; log->resid[iter - 1] = std::fabs(resid); }
-      if (std::fabs(resid) < so.residual) break;
-    } while (i + 1 < R && i + 1 <= so.max_iters && std::fabs(resid) > so.residual);
-    ar.back_substitute(i);
-    // update the solution (:237-241; FGMRES :368-371)
-    if (kind == FMMBEM_PC_INNER_PLAN && !so.flexible) {
-      for (int j = 0; j <= i; ++j) {         // x += y_j M(V_j): the inner solve again, column by column, as the reference
-        const double* z = nullptr;
-        KRY_TRY(apply_pc(ws, M, ws->V + (int64_t)j * ld, ws->z, &z, s, depth));
-        hipLaunchKernelGGL(mgs_axpy_kernel, dim3(grid), dim3(kThreads), 0, s, n, d_x, sv[j], z);
-      }
-    } else {
-      for (int j = 0; j <= i; ++j) ws->h_pin[j] = sv[j];
-      KRY_HIP(hipMemcpyAsync(ws->d_y, ws->h_pin, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
-      // FGMRES with the identity: Z_j = V_j was never copied (apply_pc hands V_j back), the update reads V
-      hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, d_x, (so.flexible && kind != FMMBEM_PC_IDENTITY) ? ws->Z : ws->V, ld, i + 1, ws->d_y,
-                         (!so.flexible && kind == FMMBEM_PC_DIAGONAL) ? M->reciprocals : (const double*)nullptr);
-      KRY_HIP(hipStreamSynchronize(s));      // h_pin is reused by the next cycle
-    }
-  } while (std::fabs(resid) > so.residual && iter < so.max_iters);
-  KRY_HIP(hipStreamSynchronize(s));
-  if (log) { log->iterations = iter; log->residual = std::fabs(resid); }
-  return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres: a launch failed");
-}
-
-
 // ================================================================================================================
-// fmmbem_gmres_batch: k independent solves of the loop above on one plan, advanced in lockstep.  Every system keeps its own
+// The solver: k independent solves of the reference's loop on one plan, advanced in lockstep.  Every system keeps its own
 // Krylov space, Hessenberg matrix, rotations, residual estimate and order; restart length and max_iters are common, so the
 // systems still running share the column index i and the iteration count.  Per iteration: the matvecs of the systems that ask
-// for the same order are one fmmbem_plan_execute_batch_device, the Arnoldi columns of all of them one chain of i + 3 launches
-// with the system as the grid's second dimension, and their Hessenberg columns cross to the host in one copy behind one
-// synchronisation.  Each system runs the operations of solve() on its own data in solve()'s order: same bits.
+// for the same order are one fmmbem_plan_execute_batch_device (the matvec of a one-system solve is fmmbem_plan_execute_device),
+// the Arnoldi columns of all of them one chain of i + 3 launches with the system as the grid's second dimension, and their
+// Hessenberg columns cross to the host in one copy behind one synchronisation.  No operation on a system's data depends on k or
+// on the other systems: a system of a k-system solve gets the bits of its own one-system solve.
 // ================================================================================================================
-void reset_batch(fmmbem::BatchWs* b) {
-  for (double** p : {&b->w, &b->z, &b->V, &b->Z, &b->d_h, &b->d_y, &b->d_scratch}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (b->h_pin) (void)hipHostFree(b->h_pin);
-  b->h_pin = nullptr;
-  b->n = b->ld = 0;
-  b->cap = b->vcols = b->zcols = b->hcap = 0;
-}
-
-int grow_batch(fmmbem::BatchWs* b, int64_t n, int k, int vcols, int zcols) {
-  const int64_t ld = (n + 1) & ~int64_t(1);                      // even stride: every vector of every system on a 16-byte boundary
-  if (b->n != n || b->cap < k) {
-    reset_batch(b);
-    KRY_TRY(grow(&b->w, (size_t)ld * k));
-    KRY_TRY(grow(&b->z, (size_t)ld * k));
-    b->n = n; b->ld = ld; b->cap = k;
-  }
-  const size_t col = (size_t)ld * b->cap;
-  if (b->vcols < vcols) { b->vcols = 0; KRY_TRY(grow(&b->V, col * vcols)); b->vcols = vcols; }
-  if (b->zcols < zcols) { b->zcols = 0; KRY_TRY(grow(&b->Z, col * zcols)); b->zcols = zcols; }
-  if (b->hcap < vcols + 1) {
-    const int hcap = vcols + 1;
-    b->hcap = 0;
-    KRY_TRY(grow(&b->d_h, (size_t)hcap * b->cap));
-    KRY_TRY(grow(&b->d_y, (size_t)hcap * b->cap));
-    KRY_TRY(grow(&b->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap) * b->cap));
-    if (b->h_pin) (void)hipHostFree(b->h_pin);
-    b->h_pin = nullptr;
-    KRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_pin), sizeof(double) * 2 * (size_t)hcap * b->cap, hipHostMallocDefault));
-    b->hcap = hcap;
-  }
-  return FMMBEM_OK;
-}
-
-// as ensure_ws: a failed allocation leaves the batched workspace empty (the next batched solve allocates from scratch) and does
-// not touch the single solver's
-int ensure_batch(SolverWs** slot, int device, int64_t n, int k, int vcols, int zcols, fmmbem::BatchWs** out) {
-  if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
-  fmmbem::BatchWs* b = &(*slot)->batch;
-  const int rc = grow_batch(b, n, k, vcols, zcols);
-  if (rc != FMMBEM_OK) { reset_batch(b); return rc; }
-  *out = b;
-  return FMMBEM_OK;
-}
-
-struct BatchSystem {
+struct System {
   double* x;
   const double* b;
   fmmbem_solver_log* log;
   Arnoldi ar;
   double normb = 0, resid = 0;
   int cur_p = 0;
-  BatchSystem(double* x_, const double* b_, fmmbem_solver_log* log_, int R) : x(x_), b(b_), log(log_), ar(R) {}
+  System(double* x_, const double* b_, fmmbem_solver_log* log_, int R) : x(x_), b(b_), log(log_), ar(R) {}
 };
 
 struct MatvecJob { int p; const double* x; double* y; };
 
-// y = A x for every job, the jobs of one order through fmmbem_plan_execute_batch_device: as many vectors per call as lie
-// equally spaced in x and in y (all of a group when it is one column of the workspace and no system between them has left)
-int batch_matvecs(fmmbem_plan* plan, int64_t n, const std::vector<MatvecJob>& jobs, hipStream_t s) {
+// y = A x for every job of a k-system solve.  k = 1: the single entry point, which replays the plan's graphs when they are on
+// (fmmbem_plan_set_graphs); the batch entry point never does.  Otherwise the jobs of one order go through
+// fmmbem_plan_execute_batch_device, a lone one included: as many vectors per call as lie equally spaced in x and in y (all of
+// a group when it is one column of the workspace and no system between them has left)
+int batch_matvecs(fmmbem_plan* plan, int64_t n, int k, const std::vector<MatvecJob>& jobs, hipStream_t s) {
+  if (k == 1) return fmmbem_plan_execute_device(plan, jobs[0].p, jobs[0].x, jobs[0].y, s);
   std::vector<char> done(jobs.size(), 0);
   for (size_t a = 0; a < jobs.size(); ++a) {
     if (done[a]) continue;
@@ -730,21 +572,20 @@ int batch_matvecs(fmmbem_plan* plan, int64_t n, const std::vector<MatvecJob>& jo
   return FMMBEM_OK;
 }
 
-int solve_batch(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
-                const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth);
+int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
+          const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth);
 
-struct BatchSolver {
+struct Solver {
   fmmbem_plan* plan;
   const fmmbem_solver_options& so;
   const fmmbem_preconditioner* M;
   hipStream_t s;
   int depth, kind, plan_pmax;
   int64_t n, ld;
-  fmmbem::BatchWs* ws;
-  std::vector<BatchSystem> sys;
+  SolverWs* ws;
+  std::vector<System> sys;
 
   double* wv(int j) const { return ws->w + (int64_t)j * ld; }
-  double* zv(int j) const { return ws->z + (int64_t)j * ld; }
   double* Vc(int c, int j) const { return ws->V + ((int64_t)c * ws->cap + j) * ld; }
   double* Zc(int c, int j) const { return ws->Z + ((int64_t)c * ws->cap + j) * ld; }
   double* scratch(int j) const { return ws->d_scratch + (size_t)j * fmmbem_mgs_scratch_doubles(ws->hcap); }
@@ -759,11 +600,17 @@ struct BatchSolver {
     }
   }
 
+  // |w| (after w += a v when v) of system j -> host; one synchronisation
   int norm(int j, double* w, double a, const double* v, double* out) const {
-    return axpy_norm(n, w, a, v, scratch(j), ws->d_h, ws->h_pin, s, out);
+    hipLaunchKernelGGL(axpy_norm_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, w, a, v, scratch(j));
+    hipLaunchKernelGGL(mgs_finish_kernel, dim3(1), dim3(kThreads), 0, s, scratch(j), 0, ws->d_h);      // ncols = 0: row 0 is a norm
+    KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double), hipMemcpyDeviceToHost, s));
+    KRY_HIP(hipStreamSynchronize(s));
+    *out = ws->h_pin[0];
+    return FMMBEM_OK;
   }
 
-  // z_j = M(column c of system j) for the systems of act -> zs; one launch (diagonal) or one batched inner solve
+  // z_j = M(column c of system j) for the systems of act -> zs; one launch (diagonal) or one inner solve of all of them
   int apply_pc(const std::vector<int>& act, int c, bool keep, std::vector<const double*>* zs) const {
     zs->clear();
     if (kind == FMMBEM_PC_IDENTITY) {
@@ -778,7 +625,7 @@ struct BatchSolver {
       });
       return FMMBEM_OK;
     }
-    // LocalPC.hpp:35-41: fill(y, 0); GMRES(plan, y, x, options) -- for all systems of act in one batched solve on the inner plan
+    // LocalPC.hpp:35-41: fill(y, 0); GMRES(plan, y, x, options) -- for all systems of act in one solve on the inner plan
     std::vector<double*> y;
     std::vector<const double*> v;
     for (int j : act) {
@@ -787,7 +634,7 @@ struct BatchSolver {
     }
     // one memset from the first to the last system of act: a system in between that has left has finished with its z
     KRY_HIP(hipMemsetAsync(y.front(), 0, sizeof(double) * (size_t)((int64_t)(act.back() - act.front()) * ld + n), s));
-    return solve_batch(M->inner_plan, M->inner, (int)act.size(), y.data(), v.data(), nullptr, nullptr, s, depth + 1);
+    return solve(M->inner_plan, M->inner, (int)act.size(), y.data(), v.data(), nullptr, nullptr, s, depth + 1);
   }
 
   // the Arnoldi column of every system of act: fmmbem_mgs_column_device with the system as the grid's second dimension; the
@@ -809,7 +656,7 @@ struct BatchSolver {
 
   // back substitution and x += ... of system j after column i (GMRES.hpp:228-241; FGMRES :368-371)
   int update(int j, int i) {
-    BatchSystem& S = sys[j];
+    System& S = sys[j];
     S.ar.back_substitute(i);
     const int grid = sweep_grid(n);
     if (kind == FMMBEM_PC_INNER_PLAN && !so.flexible) {
@@ -826,6 +673,7 @@ struct BatchSolver {
     double* dy = ws->d_y + (size_t)ws->hcap * j;
     for (int c = 0; c <= i; ++c) hy[c] = S.ar.sv[c];
     KRY_HIP(hipMemcpyAsync(dy, hy, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
+    // FGMRES with the identity: Z_c = V_c was never copied (apply_pc hands V_c back), the update reads V
     hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, (so.flexible && kind != FMMBEM_PC_IDENTITY) ? Zc(0, j) : Vc(0, j), ld * ws->cap, i + 1, dy,
                        (!so.flexible && kind == FMMBEM_PC_DIAGONAL) ? M->reciprocals : (const double*)nullptr);
     return FMMBEM_OK;
@@ -836,10 +684,10 @@ struct BatchSolver {
     const int k = (int)sys.size();
     std::vector<int> live;
     for (int j = 0; j < k; ++j) {
-      BatchSystem& S = sys[j];
+      System& S = sys[j];
       if (S.log) { S.log->iterations = 0; S.log->residual = 0.0; }
       KRY_TRY(norm(j, const_cast<double*>(S.b), 0.0, nullptr, &S.normb));      // scale residual by |b| (GMRES.hpp:162)
-      if (S.normb == 0.0) continue;            // b = 0: x = x0 is returned, as the single solver
+      if (S.normb == 0.0) continue;            // b = 0: the reference divides by zero and stops on NaN; x = x0 is returned
       S.cur_p = std::min(so.initial_p > 0 ? so.initial_p : so.max_p, plan_pmax);
       live.push_back(j);
     }
@@ -852,14 +700,14 @@ struct BatchSolver {
     while (!live.empty()) {                    // outer (restart) loop, :166 -- the systems still running restart together
       jobs.clear();
       for (int j : live) jobs.push_back({sys[j].cur_p, sys[j].x, wv(j)});      // w = A x at each system's current order
-      KRY_TRY(batch_matvecs(plan, n, jobs, s));
+      KRY_TRY(batch_matvecs(plan, n, k, jobs, s));
       std::vector<int> act;
       for (int j : live) {
-        BatchSystem& S = sys[j];
+        System& S = sys[j];
         double beta = 0;
         KRY_TRY(norm(j, wv(j), -1.0, S.b, &beta));                             // w -= b; beta = |w|
         if (beta == 0.0) { S.resid = 0.0; finish(j); continue; }               // x solves the system exactly
-        hipLaunchKernelGGL(scale_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, wv(j), -1.0 / beta, (const double*)nullptr, Vc(0, j));
+        hipLaunchKernelGGL(scale_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, wv(j), -1.0 / beta, Vc(0, j));   // V_0 = -w / beta
         S.ar.sv[0] = beta;
         S.resid = S.ar.sv[0] / S.normb;
         act.push_back(j);
@@ -873,23 +721,24 @@ struct BatchSolver {
         KRY_TRY(apply_pc(act, i, so.flexible != 0, &zs));
         jobs.clear();
         for (size_t a = 0; a < act.size(); ++a) jobs.push_back({sys[act[a]].cur_p, zs[a], wv(act[a])});
-        KRY_TRY(batch_matvecs(plan, n, jobs, s));
+        KRY_TRY(batch_matvecs(plan, n, k, jobs, s));
+        // modified Gram-Schmidt against V_0..V_i, |w|, V_{i+1} = w / |w| (:203-212), then the columns to the host
         mgs_columns(act, i + 1);
         KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2) * act.size(), hipMemcpyDeviceToHost, s));
         KRY_HIP(hipStreamSynchronize(s));
         std::vector<int> stay;
         for (size_t a = 0; a < act.size(); ++a) {
           const int j = act[a];
-          BatchSystem& S = sys[j];
+          System& S = sys[j];
           S.ar.column(i, ws->h_pin + a * (size_t)(i + 2));
           S.resid = S.ar.sv[i + 1] / S.normb;
           if (S.log && S.log->p && S.log->resid && iter <= S.log->capacity) { S.log->p[iter - 1] = S.cur_p; S.log->resid[iter - 1] = std::fabs(S.resid); }
           if (std::fabs(S.resid) > so.residual) { stay.push_back(j); continue; }
-          KRY_TRY(update(j, i));               // converged (or not a number): this system's solve ends here, as its own loops would
+          KRY_TRY(update(j, i));               // converged (or not a number): this system's solve ends here
           finish(j);
         }
         act.swap(stay);
-        if (act.empty() || !(i + 1 < R && i + 1 <= so.max_iters)) break;
+        if (act.empty() || !(i + 1 < R && i + 1 <= so.max_iters)) break;      // :221
       }
       for (int j : act) KRY_TRY(update(j, i));
       if (iter < so.max_iters) { live.swap(act); continue; }
@@ -897,24 +746,94 @@ struct BatchSolver {
       break;
     }
     KRY_HIP(hipStreamSynchronize(s));
-    return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres_batch: a launch failed");
+    return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres: a launch failed");
   }
 };
 
-int solve_batch(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
-                const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth) {
+int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* const* xs, const double* const* bs,
+          const fmmbem_preconditioner* M, fmmbem_solver_log* const* logs, hipStream_t s, int depth) {
   int device = 0, plan_pmax = 0;
   int64_t n = 0;
   SolverWs** slot = nullptr;
   KRY_TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
   // the inner loop runs while i + 1 < R and i + 1 <= max_iters (GMRES.hpp:221): at most min(R, max_iters + 1) columns
   const int most = (int)std::min<int64_t>(so.restart, (int64_t)so.max_iters + 1);
-  fmmbem::BatchWs* ws = nullptr;
-  KRY_TRY(ensure_batch(slot, device, n, k, most + 1, so.flexible ? most : 0, &ws));
-  BatchSolver B{plan, so, M, s, depth, M ? M->kind : FMMBEM_PC_IDENTITY, plan_pmax, n, ws->ld, ws, {}};
-  B.sys.reserve((size_t)k);
-  for (int j = 0; j < k; ++j) B.sys.emplace_back(xs[j], bs[j], logs ? logs[j] : nullptr, so.restart);
-  return B.run();
+  SolverWs* ws = nullptr;
+  KRY_TRY(ensure_ws(slot, device, n, k, most + 1, so.flexible ? most : 0, &ws));
+  Solver S{plan, so, M, s, depth, M ? M->kind : FMMBEM_PC_IDENTITY, plan_pmax, n, ws->ld, ws, {}};
+  S.sys.reserve((size_t)k);
+  for (int j = 0; j < k; ++j) S.sys.emplace_back(xs[j], bs[j], logs ? logs[j] : nullptr, so.restart);
+  return S.run();
+}
+
+// the k systems of an entry point: vectors ldx / ldb apart on the device, logs one after the other
+int solve_strided(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* d_x, size_t ldx, const double* d_b, size_t ldb,
+                  const fmmbem_preconditioner* M, fmmbem_solver_log* logs, hipStream_t s) {
+  std::vector<double*> xs((size_t)k);
+  std::vector<const double*> bs((size_t)k);
+  std::vector<fmmbem_solver_log*> lg((size_t)k, nullptr);
+  for (int j = 0; j < k; ++j) { xs[j] = d_x + (size_t)j * ldx; bs[j] = d_b + (size_t)j * ldb; if (logs) lg[j] = logs + j; }
+  return solve(plan, so, k, xs.data(), bs.data(), M, lg.data(), s, 0);
+}
+
+int entry_args(const fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, const void* x, size_t ldx, const void* b, size_t ldb,
+               const char* who) {
+  if (!plan || !opts || !x || !b) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": null argument");
+  if (k < 1) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": k < 1 systems");
+  if (ldx < fmmbem::plan_unknowns(plan) || ldb < fmmbem::plan_unknowns(plan))
+    return fail(FMMBEM_ERR_INVALID, std::string(who) + ": leading dimension shorter than a vector");
+  return FMMBEM_OK;
+}
+
+// the device-pointer entry points; log->seconds is the wall time of the call, set even when the solve fails
+int gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* d_x, size_t ldx, const double* d_b, size_t ldb,
+                 const fmmbem_preconditioner* M, fmmbem_solver_log* logs, void* stream, const char* who) {
+  KRY_TRY(entry_args(plan, opts, k, d_x, ldx, d_b, ldb, who));
+  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
+  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
+  DevGuard guard(device);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = solve_strided(plan, *opts, k, d_x, ldx, d_b, ldb, M, logs, static_cast<hipStream_t>(stream));
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;               // the wall time of the call, for every system
+  return rc;
+}
+
+// the host-pointer entry points: all x, then all b (and the reciprocals of a diagonal preconditioner) staged on the device once
+// per solve -- the only PCIe traffic of length n -- in buffers the workspace's reset / grow never touch
+int gmres_host(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* x, size_t ldx, const double* b, size_t ldb,
+               const fmmbem_preconditioner* M, fmmbem_solver_log* logs, const char* who) {
+  KRY_TRY(entry_args(plan, opts, k, x, ldx, b, ldb, who));
+  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
+  KRY_TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
+  DevGuard guard(device);
+  const auto t0 = std::chrono::steady_clock::now();
+  SolverWs* ws = plan_ws(slot, device);
+  const int64_t ld = (n + 1) & ~int64_t(1);
+  const size_t bytes = sizeof(double) * (size_t)n;
+  if (ws->xb_doubles < (size_t)2 * k * ld) {
+    ws->xb_doubles = 0;
+    KRY_TRY(grow(&ws->d_xb, (size_t)2 * k * ld));
+    ws->xb_doubles = (size_t)2 * k * ld;
+  }
+  double* d_x = ws->d_xb;
+  double* d_b = ws->d_xb + (size_t)k * ld;
+  fmmbem_preconditioner Md;
+  const fmmbem_preconditioner* Mp = M;
+  if (M && M->kind == FMMBEM_PC_DIAGONAL) {
+    if (!ws->d_recip) KRY_TRY(grow(&ws->d_recip, (size_t)n));                // n is the plan's: allocated once
+    KRY_HIP(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
+    Md = *M;
+    Md.reciprocals = ws->d_recip;
+    Mp = &Md;
+  }
+  KRY_HIP(hipMemcpy2D(d_x, sizeof(double) * (size_t)ld, x, sizeof(double) * ldx, bytes, (size_t)k, hipMemcpyHostToDevice));
+  KRY_HIP(hipMemcpy2D(d_b, sizeof(double) * (size_t)ld, b, sizeof(double) * ldb, bytes, (size_t)k, hipMemcpyHostToDevice));
+  KRY_TRY(solve_strided(plan, *opts, k, d_x, (size_t)ld, d_b, (size_t)ld, Mp, logs, nullptr));
+  KRY_HIP(hipMemcpy2D(x, sizeof(double) * ldx, d_x, sizeof(double) * (size_t)ld, bytes, (size_t)k, hipMemcpyDeviceToHost));
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;
+  return FMMBEM_OK;
 }
 
 }  // namespace
@@ -925,120 +844,25 @@ extern "C" void fmmbem_solver_options_default(fmmbem_solver_options* o) {     //
   o->relax_type = FMMBEM_RELAX_BOURAS; o->order_rule = FMMBEM_ORDER_GMRES; o->flexible = 0; o->initial_p = 0;
 }
 
+// one system: k = 1, the vector's own length as both leading dimensions
 extern "C" int fmmbem_gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, double* d_x, const double* d_b,
                                    const fmmbem_preconditioner* M, fmmbem_solver_log* log, void* stream) {
-  if (!plan || !opts || !d_x || !d_b) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres_device: null argument");
-  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
-  DevGuard guard(device);
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = solve(plan, *opts, d_x, d_b, M, log, static_cast<hipStream_t>(stream), 0);
-  if (log) log->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  const size_t n = plan ? fmmbem::plan_unknowns(plan) : 0;
+  return gmres_device(plan, opts, 1, d_x, n, d_b, n, M, log, stream, "fmmbem_gmres_device");
 }
 
 extern "C" int fmmbem_gmres(fmmbem_plan* plan, const fmmbem_solver_options* opts, double* x, const double* b,
                             const fmmbem_preconditioner* M, fmmbem_solver_log* log) {
-  if (!plan || !opts || !x || !b) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: null argument");
-  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
-  DevGuard guard(device);
-  const auto t0 = std::chrono::steady_clock::now();
-  if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
-  SolverWs* ws = *slot;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  if (!ws->d_xb || ws->n != n) {             // x and b staged once per solve: the only PCIe traffic of length n
-    KRY_TRY(grow(&ws->d_xb, (size_t)2 * ((n + 1) & ~int64_t(1))));
-    if (ws->d_recip) { (void)hipFree(ws->d_recip); ws->d_recip = nullptr; }
-  }
-  double* d_x = ws->d_xb;
-  double* d_b = ws->d_xb + ((n + 1) & ~int64_t(1));
-  fmmbem_preconditioner Md;
-  const fmmbem_preconditioner* Mp = M;
-  if (M && M->kind == FMMBEM_PC_DIAGONAL) {
-    if (!M->reciprocals) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: diagonal preconditioner without reciprocals");
-    if (!ws->d_recip) KRY_TRY(grow(&ws->d_recip, (size_t)n));
-    KRY_HIP(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
-    Md = *M;
-    Md.reciprocals = ws->d_recip;
-    Mp = &Md;
-  }
-  KRY_HIP(hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice));
-  KRY_HIP(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice));
-  // ensure_ws below may see n change and must not free what was just staged: d_xb / d_recip are not touched by it
-  const int rc = solve(plan, *opts, d_x, d_b, Mp, log, nullptr, 0);
-  if (rc != FMMBEM_OK) return rc;
-  KRY_HIP(hipMemcpy(x, d_x, bytes, hipMemcpyDeviceToHost));
-  if (log) log->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return FMMBEM_OK;
+  const size_t n = plan ? fmmbem::plan_unknowns(plan) : 0;
+  return gmres_host(plan, opts, 1, x, n, b, n, M, log, "fmmbem_gmres");
 }
-
-namespace {
-int batch_entry_args(const fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, const void* x, const void* b, const char* who) {
-  if (!plan || !opts || !x || !b) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": null argument");
-  if (k < 1) return fail(FMMBEM_ERR_INVALID, std::string(who) + ": k < 1 systems");
-  return FMMBEM_OK;
-}
-}  // namespace
 
 extern "C" int fmmbem_gmres_batch_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* d_x, size_t ldx,
                                          const double* d_b, size_t ldb, const fmmbem_preconditioner* M, fmmbem_solver_log* logs, void* stream) {
-  KRY_TRY(batch_entry_args(plan, opts, k, d_x, d_b, "fmmbem_gmres_batch_device"));
-  if (ldx < fmmbem::plan_unknowns(plan) || ldb < fmmbem::plan_unknowns(plan))
-    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres_batch_device: leading dimension shorter than a vector");
-  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
-  DevGuard guard(device);
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<double*> xs((size_t)k);
-  std::vector<const double*> bs((size_t)k);
-  std::vector<fmmbem_solver_log*> lg((size_t)k, nullptr);
-  for (int j = 0; j < k; ++j) { xs[j] = d_x + (size_t)j * ldx; bs[j] = d_b + (size_t)j * ldb; if (logs) lg[j] = logs + j; }
-  const int rc = solve_batch(plan, *opts, k, xs.data(), bs.data(), M, lg.data(), static_cast<hipStream_t>(stream), 0);
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;               // the wall time of the call, for every system
-  return rc;
+  return gmres_device(plan, opts, k, d_x, ldx, d_b, ldb, M, logs, stream, "fmmbem_gmres_batch_device");
 }
 
 extern "C" int fmmbem_gmres_batch(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* x, size_t ldx,
                                   const double* b, size_t ldb, const fmmbem_preconditioner* M, fmmbem_solver_log* logs) {
-  KRY_TRY(batch_entry_args(plan, opts, k, x, b, "fmmbem_gmres_batch"));
-  if (ldx < fmmbem::plan_unknowns(plan) || ldb < fmmbem::plan_unknowns(plan))
-    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres_batch: leading dimension shorter than a vector");
-  int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
-  DevGuard guard(device);
-  const auto t0 = std::chrono::steady_clock::now();
-  if (!*slot) { *slot = new SolverWs; (*slot)->device = device; }
-  fmmbem::BatchWs* ws = &(*slot)->batch;
-  const int64_t ld = (n + 1) & ~int64_t(1);
-  const size_t bytes = sizeof(double) * (size_t)n;
-  if (ws->xb_doubles < (size_t)2 * k * ld) {  // all x, then all b: staged once per solve
-    ws->xb_doubles = 0;
-    KRY_TRY(grow(&ws->d_xb, (size_t)2 * k * ld));
-    ws->xb_doubles = (size_t)2 * k * ld;
-  }
-  double* d_x = ws->d_xb;
-  double* d_b = ws->d_xb + (size_t)k * ld;
-  fmmbem_preconditioner Md;
-  const fmmbem_preconditioner* Mp = M;
-  if (M && M->kind == FMMBEM_PC_DIAGONAL) {
-    KRY_TRY(grow(&ws->d_recip, (size_t)n));
-    KRY_HIP(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
-    Md = *M;
-    Md.reciprocals = ws->d_recip;
-    Mp = &Md;
-  }
-  KRY_HIP(hipMemcpy2D(d_x, sizeof(double) * (size_t)ld, x, sizeof(double) * ldx, bytes, (size_t)k, hipMemcpyHostToDevice));
-  KRY_HIP(hipMemcpy2D(d_b, sizeof(double) * (size_t)ld, b, sizeof(double) * ldb, bytes, (size_t)k, hipMemcpyHostToDevice));
-  std::vector<double*> xs((size_t)k);
-  std::vector<const double*> bs((size_t)k);
-  std::vector<fmmbem_solver_log*> lg((size_t)k, nullptr);
-  for (int j = 0; j < k; ++j) { xs[j] = d_x + (size_t)j * ld; bs[j] = d_b + (size_t)j * ld; if (logs) lg[j] = logs + j; }
-  const int rc = solve_batch(plan, *opts, k, xs.data(), bs.data(), Mp, lg.data(), nullptr, 0);
-  if (rc != FMMBEM_OK) return rc;
-  KRY_HIP(hipMemcpy2D(x, sizeof(double) * ldx, d_x, sizeof(double) * (size_t)ld, bytes, (size_t)k, hipMemcpyDeviceToHost));
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;
-  return FMMBEM_OK;
+  return gmres_host(plan, opts, k, x, ldx, b, ldb, M, logs, "fmmbem_gmres_batch");
 }

@@ -423,8 +423,9 @@ int fmmbem_gmres(fmmbem_plan *plan, const fmmbem_solver_options *opts, double *x
  * the wall time of the whole call).  One set of options and one preconditioner serve all systems; an INNER_PLAN
  * preconditioner's inner solves are themselves one batched solve on the inner plan.
  * k < 1, a null pointer, ldx or ldb shorter than a vector: FMMBEM_ERR_INVALID, checked first; everything else is refused as
- * fmmbem_gmres(_device) refuses it.  The workspace (k times the single solver's) is allocated on the first batched solve and
- * kept with the plan; if that fails the call returns FMMBEM_ERR_ALLOC and single solves still work. */
+ * fmmbem_gmres(_device) refuses it.  fmmbem_gmres(_device) is this solver with k = 1.  The plan keeps one workspace for all
+ * its solves, as wide as the widest so far (k times that of one system); if growing it fails the call returns
+ * FMMBEM_ERR_ALLOC, the workspace is left empty and the next solve, of any k, allocates again. */
 int fmmbem_gmres_batch_device(fmmbem_plan *plan, const fmmbem_solver_options *opts, int k,
                               double *d_x, size_t ldx, const double *d_b, size_t ldb,
                               const fmmbem_preconditioner *M, fmmbem_solver_log *logs, void *stream);

@@ -64,6 +64,31 @@ def test_invalid_arguments_then_gmres_refusals(fb, which):
     assert L.fmmbem_gmres(pl._h, C.byref(o), xp, bp, None, None) == single
 
 
+def test_single_entry_refusals_on_a_host_only_plan(fb):
+    """fmmbem_gmres on a host-only plan: null arguments are INVALID; after them the plan's own refusal comes before the checks
+    of the options (restart = 0) and of the preconditioner (DIAGONAL without reciprocals), and nothing is written"""
+    from fmm_bem_relaxed_amd import _capi
+    pl = _plans(fb)["laplace"]
+    L = fb.lib()
+    x, b = np.full(pl.n, 2.0), np.ones(pl.n)
+    xp, bp = x.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)
+    o = _options()
+    assert L.fmmbem_gmres(None, C.byref(o), xp, bp, None, None) == INVALID
+    assert L.fmmbem_gmres(pl._h, None, xp, bp, None, None) == INVALID
+    assert L.fmmbem_gmres(pl._h, C.byref(o), None, bp, None, None) == INVALID
+    assert L.fmmbem_gmres(pl._h, C.byref(o), xp, None, None, None) == INVALID
+    assert b"fmmbem_gmres: null argument" in L.fmmbem_last_error()
+    o.restart = 0
+    assert L.fmmbem_gmres(pl._h, C.byref(o), xp, bp, None, None) == NO_DEVICE
+    o = _options()
+    pc = _capi.Preconditioner()
+    pc.kind, pc.reciprocals = _capi.PC_DIAGONAL, None
+    log = _capi.SolverLog()
+    assert L.fmmbem_gmres(pl._h, C.byref(o), xp, bp, C.byref(pc), C.byref(log)) == NO_DEVICE
+    assert (x == 2.0).all() and (b == 1.0).all() and log.iterations == 0
+    assert pl.stats()["n_panels"] == pl.n
+
+
 def test_python_wrapper_is_exported_and_checks_shapes(fb):
     import torch
     assert fb.gmres_capi_batch is not None

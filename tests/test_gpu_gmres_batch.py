@@ -332,6 +332,47 @@ def test_single_solves_around_a_batched_solve(fb):
     assert_same(again, got, 2, what="second batch")
 
 
+def test_single_solve_on_a_plan_with_graphs_on(fb):
+    """fmmbem_plan_set_graphs(plan, 1): a single fmmbem_gmres_device runs its matvecs through fmmbem_plan_execute_device, which
+    captures and replays the plan's graphs (the batched execute never does), and gives the bits of the same solve on a
+    graphs-off plan.  fmmbem_plan_stats reports nothing about graphs, so the replay is observed as a repeat of the solve -- every
+    order it asks for captured by now -- returning the same bits.  A k = 3 solve on that plan afterwards equals its singles."""
+    v = fb.unit_sphere(4)
+    B = rhs(v, 3)
+    so = options(fb, max_p=8)
+    X0 = np.zeros_like(B)
+    off = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, p_max=8)
+    want = singles(fb, off, X0, B, so)
+    off.close()
+    assert all(r < so.residual for r in want[2]) and len(set(want[1])) > 1
+    plan = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, p_max=8)
+    plan.set_graphs(True)
+    one = tuple([part[1]] for part in want)
+    assert_same(singles(fb, plan, X0[1:2], B[1:2], so), one, what="graphs on")
+    assert_same(singles(fb, plan, X0[1:2], B[1:2], so), one, what="graphs on, repeat")
+    assert_same(batch(fb, plan, X0, B, so), want, what="k = 3 after the graphed single solves")
+    assert_same(singles(fb, plan, X0[1:2], B[1:2], so), one, what="graphs on, after the batched solve")
+    plan.close()
+
+
+def test_host_entry_refuses_bad_options_before_staging(fb):
+    """fmmbem_gmres with restart = 0, and with a DIAGONAL preconditioner without reciprocals: FMMBEM_ERR_INVALID, x untouched"""
+    from fmm_bem_relaxed_amd import _capi
+    from fmm_bem_relaxed_amd.solver import _c_options
+    v, plan, B = mesh_plan(fb, "sphere5")
+    x, b = np.full(B.shape[1], 2.0), B[1].copy()
+    L = _capi.lib()
+    o = _c_options(options(fb, restart=0), False, False, plan.kernel().P)
+    assert L.fmmbem_gmres(plan._h, C.byref(o), x.ctypes.data, b.ctypes.data, None, None) == 1
+    assert b"restart >= 1" in L.fmmbem_last_error()
+    o = _c_options(options(fb), False, False, plan.kernel().P)
+    pc = _capi.Preconditioner()
+    pc.kind, pc.reciprocals = _capi.PC_DIAGONAL, None
+    assert L.fmmbem_gmres(plan._h, C.byref(o), x.ctypes.data, b.ctypes.data, C.byref(pc), None) == 1
+    assert b"without reciprocals" in L.fmmbem_last_error()
+    assert (x == 2.0).all()
+
+
 def test_fgmres_without_a_preconditioner_is_gmres(fb):
     """FGMRES with the identity keeps Z_j = V_j: the same operations as GMRES, so fmmbem_gmres_device with flexible = 1 and
     M = NULL gives the bits of flexible = 0 and M = NULL (the Laplace order rules coincide: max(1, predict_p)) -- on a plan whose
