@@ -11,6 +11,9 @@ against 6 pi mu, area and pointwise traction errors (:337-372).  All matvecs run
 
 -near_f32 P (not a flag of the reference): the operator's matvecs at orders p <= P stream the float copy of the near matrix
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
+
+-field N (not a flag of the reference): after the solve, the velocity of the single layer with the solved density on N points of the
+sphere of radius 3, summed on the device by fb.Direct (Stokes has no target plan); prints the largest and the mean magnitude.
 """
 import math
 import os
@@ -48,13 +51,22 @@ class _Logged(list):
         print("it: %03d, res: %.3e, fmm_req_p: %01d" % (row[0], row[2], row[1]))
 
 
+def sphere_points(m, radius):
+    """m points spread over a sphere (golden-angle spiral), as LaplaceBEM.py -field places them"""
+    i = np.arange(m) + 0.5
+    z = 1 - 2 * i / m
+    r = np.sqrt(1 - z * z)
+    phi = math.pi * (3 - math.sqrt(5)) * i
+    return radius * np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+
+
 def main(argv):
     if len(argv) == 1:
         print_help_and_exit()
     recursions, p, k, kfine, cells, mu, p_min = 4, 8, 4, 19, 1, 1e-3, 5
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
-    rbc, near_f32 = False, 0
+    rbc, near_f32, field = False, 0, 0
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -102,6 +114,8 @@ def main(argv):
             i += 1
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
             i += 1; near_f32 = int(argv[i])
+        elif a == "-field":                                # not in the reference: the solved layer's velocity off the surface
+            i += 1; field = int(argv[i])
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
@@ -185,6 +199,12 @@ def main(argv):
     print("\n\n\n\tdrag error per panel : %.5e, average panel area: %.5e" % (drag_error / n, area.sum() / n))
     print("\tArea error : %.5e" % (abs(area.sum() - analytical_area) / analytical_area))
     print("\n\nPOINTWISE ERRORS\n\terror: %.3e" % math.sqrt(e / e2))
+    if field > 0:
+        direct = fb.Direct(kernel(), v)
+        u = direct.matvec_torch(x, torch.from_numpy(sphere_points(field, 3.0)).to(dev)).cpu().numpy()
+        direct.close()
+        mag = np.linalg.norm(u, axis=1)
+        print("field: %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field, float(mag.max()), float(mag.mean())))
     return it, res, drag_error, [row[1] for row in log]
 
 

@@ -103,6 +103,7 @@ SYMBOLS = (
     "fmmbem_plan_create_targets", "fmmbem_plan_target_info", "fmmbem_plan_get_target_boxes", "fmmbem_plan_get_target_perm",
     "fmmbem_plan_execute_batch", "fmmbem_plan_execute_batch_device", "fmmbem_plan_batch_width",
     "fmmbem_gmres_batch_device", "fmmbem_gmres_batch",
+    "fmmbem_direct_create", "fmmbem_direct_apply", "fmmbem_direct_apply_device", "fmmbem_direct_chunk", "fmmbem_direct_destroy",
 )
 
 
@@ -188,6 +189,12 @@ def lib():
     for fn in (L.fmmbem_ops_m2m, L.fmmbem_ops_m2l, L.fmmbem_ops_l2l):
         fn.argtypes = [vp, i32, i32, vp, vp, vp]
     L.fmmbem_ops_l2p.argtypes = [vp, i32, vp, vp, C.c_size_t, vp, vp, vp]
+    L.fmmbem_direct_create.argtypes = [C.POINTER(Options), C.c_size_t, vp, C.POINTER(vp)]
+    L.fmmbem_direct_apply.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    L.fmmbem_direct_apply_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.fmmbem_direct_chunk.argtypes = []
+    L.fmmbem_direct_destroy.argtypes = [vp]
+    L.fmmbem_direct_destroy.restype = None
     _lib = L
     return L
 

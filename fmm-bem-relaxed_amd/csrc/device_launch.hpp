@@ -80,5 +80,12 @@ hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipSt
 // P2M for nv vectors: the streaming kernel once where launch_p2m streams (one live slot, p >= 8), else launch_p2m per vector
 hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s);
 
+// ---- Direct sum (kernels_direct.hip): y_i = sum_j K(t_i, panel j) x_j over ALL of d's panels, m targets ----
+int direct_chunk();                                    // FMMBEM_DIRECT_CHUNK: sources per partial sum
+int64_t direct_chunks(int64_t n_sources);              // partial sums per target
+// point i = (tx, ty, tz)[i * tstride]; tbc null: flags 0; part: direct_chunks(d.n) * m * d.dof doubles of scratch; y: m * d.dof
+hipError_t launch_direct(const DevicePlan& d, int64_t m, const double* tx, const double* ty, const double* tz, int tstride,
+                         const uint8_t* tbc, const double* x, double* part, double* y, hipStream_t s);
+
 
 }  // namespace fmmbem

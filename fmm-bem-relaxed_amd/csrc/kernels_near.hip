@@ -6,6 +6,7 @@
 //   near_spmv       y_tree = A_near * x_tree      (Matvec<>, include/Matvec.hpp:14-33) -- HBM-bound hot kernel
 //   scatter_y       y[perm[i]] = y_tree[i]        (EvalInteractionLazySparse.hpp:146-148)
 #include "device_launch.hpp"
+#include "near_entry.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -27,151 +28,6 @@ __device__ inline void wave_lds_fence() {             // LDS writes of this wave
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct V3 { double x, y, z; };
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline V3 cross(V3 u, V3 v) { return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
-__device__ inline double norm(V3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
-__device__ inline V3 mul3(const double* M, V3 v) {       // row-major 3x3 times vector (include/Mat3.hpp:76-82)
-  return {M[0] * v.x + M[1] * v.y + M[2] * v.z, M[3] * v.x + M[4] * v.y + M[5] * v.z, M[6] * v.x + M[7] * v.y + M[8] * v.z};
-}
-
-// 5-point Gauss-Legendre in the polar angle along one triangle edge
-// (examples/BEM/SemiAnalytical.hpp:13-71, LAPLACE branch; only G is needed by the Laplace near field)
-__device__ inline double edge_angle_integral(double z, double x, double v1, double v2) {
-  const double t1 = atan2(v1, x), t2 = atan2(v2, x);
-  const double dt = t2 - t1, tm = (t2 + t1) / 2;
-  const double az = fabs(z);
-  const double xk[5] = {-9.06179846e-01, -5.38469310e-01, 1.78162900e-17, 9.06179846e-01, 5.38469310e-01};
-  const double wk[5] = {0.23692689, 0.47862867, 0.56888889, 0.23692689, 0.47862867};
-  double G = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const double tk = dt / 2 * xk[i] + tm;
-    const double Rt = x / cos(tk);
-    const double R = sqrt(Rt * Rt + z * z);
-    G += wk[i] * (R - az) * dt / 2;
-  }
-  return G;
-}
-
-// contribution of one edge v1->v2, in the panel plane with the collocation point at the origin and
-// height p above the plane (examples/BEM/SemiAnalytical.hpp:81-145)
-__device__ inline double edge_term(V3 v1, V3 v2, double p) {
-  const V3 e = sub(v2, v1);
-  const double len = norm(e);
-  const V3 u = {e.x / len, e.y / len, e.z / len};
-  const V3 o = cross(V3{0, 0, 1}, u);
-  double R[9] = {o.x, u.x, 0, o.y, u.y, 0, o.z, u.z, 1};
-  V3 a = mul3(R, v1);
-  if (a.x < 0) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = -R[i];
-    R[8] = 1.;
-    a = mul3(R, v1);
-  }
-  const V3 b = mul3(R, v2);
-  if ((a.y > 0 && b.y < 0) || (a.y < 0 && b.y > 0))
-    return edge_angle_integral(p, a.x, 0, a.y) + edge_angle_integral(p, a.x, b.y, 0);
-  return -edge_angle_integral(p, a.x, a.y, b.y);
-}
-
-// int_panel 1/|x - y| dS(y), semi-analytically (examples/BEM/SemiAnalytical.hpp:148-203)
-__device__ inline double semi_analytic_G(V3 y0, V3 y1, V3 y2, V3 x) {
-  const V3 xp = sub(x, y0), e1 = sub(y1, y0), e2 = sub(y2, y0);
-  V3 X = e1, Z = cross(e1, e2);
-  const double xn = norm(X), zn = norm(Z);
-  X = {X.x / xn, X.y / xn, X.z / xn};
-  Z = {Z.x / zn, Z.y / zn, Z.z / zn};
-  const V3 Y = cross(Z, X);
-  const double rot[9] = {X.x, X.y, X.z, Y.x, Y.y, Y.z, Z.x, Z.y, Z.z};
-  const V3 q0 = mul3(rot, V3{0, 0, 0}), q1 = mul3(rot, e1), q2 = mul3(rot, e2), xq = mul3(rot, xp);
-  const V3 f0 = {q0.x - xq.x, q0.y - xq.y, q0.z}, f1 = {q1.x - xq.x, q1.y - xq.y, q1.z}, f2 = {q2.x - xq.x, q2.y - xq.y, q2.z};
-  return edge_term(f0, f1, xq.z) + edge_term(f1, f2, xq.z) + edge_term(f2, f0, xq.z);
-}
-
-// the 16-point "K_fine" rule keyed 17 (examples/BEM/GaussQuadrature.hpp:86-116), barycentric
-__constant__ double kFine[16][4] = {
-    {1. / 3, 1. / 3, 1. / 3, 0.144315607677787},
-    {0.081414823414554, 0.459292588292723, 0.459292588292723, 0.095091634267285},
-    {0.459292588292723, 0.081414823414554, 0.459292588292723, 0.095091634267285},
-    {0.459292588292723, 0.459292588292723, 0.081414823414554, 0.095091634267285},
-    {0.658861384496480, 0.170569307751760, 0.170569307751760, 0.103217370534718},
-    {0.170569307751760, 0.658861384496480, 0.170569307751760, 0.103217370534718},
-    {0.170569307751760, 0.170569307751760, 0.658861384496480, 0.103217370534718},
-    {0.898905543365938, 0.050547228317031, 0.050547228317031, 0.032458497623198},
-    {0.050547228317031, 0.898905543365938, 0.050547228317031, 0.032458497623198},
-    {0.050547228317031, 0.050547228317031, 0.898905543365938, 0.032458497623198},
-    {0.008394777409958, 0.263112829634638, 0.728492392955404, 0.027230314174435},
-    {0.008394777409958, 0.728492392955404, 0.263112829634638, 0.027230314174435},
-    {0.263112829634638, 0.008394777409958, 0.728492392955404, 0.027230314174435},
-    {0.263112829634638, 0.728492392955404, 0.008394777409958, 0.027230314174435},
-    {0.728492392955404, 0.008394777409958, 0.263112829634638, 0.027230314174435},
-    {0.728492392955404, 0.263112829634638, 0.008394777409958, 0.027230314174435}};
-
-// One near-matrix entry: target centroid t with BC flag, source panel j (tree index).
-// kernel/LaplaceSphericalBEM.hpp:273-297 -> eval_G (:159-205) / eval_dGdn (:208-264)
-// In two parts, so that the assembly can run the expensive regime with full wavefronts: laplace_entry_far gives the entry of a
-// pair in the far regime (the K stored Gauss points; also the 2 pi of a NORMAL_DERIV self pair) or says `deferred`;
-// laplace_entry_near gives the near regime (semi-analytic G, :166-178; the 16-point rule for dG/dn, :222-243).
-// the far regime's arithmetic on a source panel held in registers (one text for both callers: the bits must not depend on who asks)
-template <class Quad>
-__device__ __forceinline__ double laplace_far_from(V3 t, int tbc, V3 c, double A, V3 nrm, int nq, const double* qw, Quad&& quad, bool& deferred) {
-  const double dist = norm(sub(t, c));
-  const bool nearby = sqrt(2 * A) / dist >= 0.5;
-  deferred = false;
-  if (tbc == 0) {                                   // POTENTIAL target: int G
-    if (nearby) { deferred = true; return 0; }
-    double r = 0;
-    for (int q = 0; q < nq; ++q) {
-      const V3 qp = quad(q);
-      r += qw[q] * A / norm(sub(t, qp));
-    }
-    return r;
-  }
-  // NORMAL_DERIV target: int dG/dn
-  if (dist < 1e-8) return 2 * M_PI;
-  if (nearby) { deferred = true; return 0; }
-  double r = 0;
-  for (int q = 0; q < nq; ++q) {
-    const V3 qp = quad(q);
-    const V3 dx = sub(qp, t);
-    const double r2 = dx.x * dx.x + dx.y * dx.y + dx.z * dx.z;
-    r += qw[q] * A * (dx.x * nrm.x + dx.y * nrm.y + dx.z * nrm.z) / (r2 * sqrt(r2));
-  }
-  return r;
-}
-__device__ inline double laplace_entry_far(const DevicePlan& d, V3 t, int tbc, int64_t j, bool& deferred) {
-  const int64_t N = d.n;
-  const V3 c = {d.cx[j], d.cy[j], d.cz[j]};
-  const V3 nrm = tbc ? V3{d.nx[j], d.ny[j], d.nz[j]} : V3{0, 0, 0};
-  return laplace_far_from(t, tbc, c, d.area[j], nrm, d.nq, d.qw,
-                          [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; }, deferred);
-}
-__device__ inline double laplace_entry_near(const DevicePlan& d, V3 t, int tbc, int64_t j) {
-  const int64_t N = d.n;
-  const V3 v0 = {d.vert[0 * N + j], d.vert[1 * N + j], d.vert[2 * N + j]};
-  const V3 v1 = {d.vert[3 * N + j], d.vert[4 * N + j], d.vert[5 * N + j]};
-  const V3 v2 = {d.vert[6 * N + j], d.vert[7 * N + j], d.vert[8 * N + j]};
-  if (tbc == 0) return semi_analytic_G(v0, v1, v2, t);
-  const double A = d.area[j];
-  const V3 nrm = {d.nx[j], d.ny[j], d.nz[j]};
-  double r = 0;
-  for (int q = 0; q < 16; ++q) {
-    const V3 pt = {v0.x * kFine[q][0] + v1.x * kFine[q][1] + v2.x * kFine[q][2],
-                   v0.y * kFine[q][0] + v1.y * kFine[q][1] + v2.y * kFine[q][2],
-                   v0.z * kFine[q][0] + v1.z * kFine[q][1] + v2.z * kFine[q][2]};
-    const V3 dx = sub(pt, t);
-    const double r2 = dx.x * dx.x + dx.y * dx.y + dx.z * dx.z;
-    r += kFine[q][3] * A * (dx.x * nrm.x + dx.y * nrm.y + dx.z * nrm.z) / (r2 * sqrt(r2));
-  }
-  return r;
-}
-__device__ inline double laplace_entry(const DevicePlan& d, V3 t, int tbc, int64_t j) {
-  bool deferred;
-  const double v = laplace_entry_far(d, t, tbc, j, deferred);
-  return deferred ? laplace_entry_near(d, t, tbc, j) : v;
 }
 
 // Column staging shared by near_assemble and near_spmv.  The columns of a target leaf's row block are
@@ -340,170 +196,6 @@ __global__ __launch_bounds__(256) void near_assemble_cols_kernel(DevicePlan d) {
     }
     __syncthreads();
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Stokes (velocity boundary condition): one near-matrix entry is the 3x3 block
-//   (1/2mu) int_source ( I/r + d d^T / r^3 ) dS,  d = target centroid - y
-// (kernel/StokesSphericalBEM.hpp:260-375).  Regimes: far -> the K stored Gauss points (:352-369);
-// near (sqrt(2A)/dist >= 0.5) -> the K_fine rule on the vertices (:302-321); self -> Fata's closed form.
-// ---------------------------------------------------------------------------------------------
-__device__ inline void stokeslet_point(double* res, double wA, V3 t, V3 pnt) {
-  const V3 dd = sub(t, pnt);
-  const double r2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-  double invR2 = 1. / r2;
-  if (r2 < 1e-8) invR2 = 0;
-  const double f = wA * invR2 * sqrt(invR2);
-  const double dv[3] = {dd.x, dd.y, dd.z};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) res[3 * i + j] += f * ((i == j ? r2 : 0.0) + dv[i] * dv[j]);
-}
-
-// Self term: AnalyticalIntegral::FataAnalytical<STOKES>(y1,y2,y3,.,x = centroid, self = true, G)
-// (examples/BEM/FataAnalytical.hpp:414-690, self branch :535-539) + Integration<STOKES>::integrate (:273-341).
-// With the collocation point in the panel plane (et = 0) and chi left at {0,0,0} in the self branch, only
-// omega (three logarithms) and the rho-difference terms survive.
-__device__ inline void stokes_self(V3 y1, V3 y2, V3 y3, V3 x, double* IU) {
-  const double pi = M_PI;
-  const V3 v1 = sub(y2, y1), v3 = sub(y3, y1);
-  const double snrm = v1.x * v1.x + v1.y * v1.y + v1.z * v1.z, nrm = sqrt(snrm);
-  const double al = (v1.x * v3.x + v1.y * v3.y + v1.z * v3.z) / snrm;
-  V3 e2 = {v3.x - al * v1.x, v3.y - al * v1.y, v3.z - al * v1.z};
-  const double nrx = norm(e2);
-  const V3 e1 = {v1.x / nrm, v1.y / nrm, v1.z / nrm};
-  e2 = {e2.x / nrx, e2.y / nrx, e2.z / nrx};
-  const V3 e3 = {e1.y * e2.z - e2.y * e1.z, e1.z * e2.x - e2.z * e1.x, e1.x * e2.y - e2.x * e1.y};
-  const double bQ = v1.x * e1.x + v1.y * e1.y + v1.z * e1.z;
-  const double aQ = v3.x * e2.x + v3.y * e2.y + v3.z * e2.z;
-  const double cQ = v3.x * e1.x + v3.y * e1.y + v3.z * e1.z;
-  const double bmc = bQ - cQ, aQs = aQ * aQ;
-  const double th0 = acos(cQ / sqrt(cQ * cQ + aQs)), th1 = acos(bmc / sqrt(bmc * bmc + aQs));
-  const double alpha2 = pi - th1, alpha3 = pi + th0;
-  const double cs2 = cos(alpha2), sn2 = sin(alpha2), cs3 = cos(alpha3), sn3 = sin(alpha3);
-  const V3 r1 = sub(x, y1);
-  const double xi = r1.x * e1.x + r1.y * e1.y + r1.z * e1.z;
-  const double zt = r1.x * e2.x + r1.y * e2.y + r1.z * e2.z;
-  double q[3];
-  const double p11 = -xi, p12 = bQ - xi;
-  q[0] = -zt;
-  const double x3 = cQ + p11, z3 = aQ + q[0];
-  const double p22 = p12 * cs2 + q[0] * sn2, p23 = x3 * cs2 + z3 * sn2;
-  q[1] = q[0] * cs2 - p12 * sn2;
-  const double p31 = p11 * cs3 + q[0] * sn3, p33 = x3 * cs3 + z3 * sn3;
-  q[2] = q[0] * cs3 - p11 * sn3;
-  const double rho[3] = {sqrt(p11 * p11 + q[0] * q[0]), sqrt(p12 * p12 + q[0] * q[0]), sqrt(p33 * p33 + q[2] * q[2])};
-  const double omega = q[0] * log((p11 + rho[0]) / (p12 + rho[1])) + q[1] * log((p22 + rho[1]) / (p23 + rho[2])) +
-                       q[2] * log((p33 + rho[2]) / (p31 + rho[0]));
-  const double alpha[3] = {0., alpha2, alpha3};
-  const double rb[3] = {rho[0] - rho[1], rho[1] - rho[2], rho[2] - rho[0]};
-  double Ixx = 0, Izz = 0, Izx = 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Ixx += (rb[i] * sin(alpha[i])) * cos(alpha[i]);
-    Izz += (-rb[i] * cos(alpha[i])) * sin(alpha[i]);
-    Izx += (rb[i] * sin(alpha[i])) * sin(alpha[i]);
-  }
-  const double E[3][3] = {{e1.x, e1.y, e1.z}, {e2.x, e2.y, e2.z}, {e3.x, e3.y, e3.z}};
-  const double coef[3][3] = {{omega + Ixx, Izx, 0.0}, {Izx, omega + Izz, 0.0}, {0.0, 0.0, omega}};
-#pragma unroll
-  for (int i = 0; i < 9; ++i) IU[i] = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) IU[3 * i + j] += coef[a][b] * E[a][i] * E[b][j];
-}
-
-// one Gauss point of the traction (double-layer) integrand: res += w A (d . n) d d^T / r^5, d = target - point
-// (kernel/StokesSphericalBEM.hpp:205-225, 236-252)
-__device__ inline void stresslet_point(double* res, double wA, V3 t, V3 pnt, V3 nrm) {
-  const V3 dd = sub(t, pnt);
-  const double r2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
-  double invR2 = 1. / r2;
-  if (r2 < 1e-8) invR2 = 0;
-  const double invR5 = invR2 * invR2 * sqrt(invR2);
-  const double dn = dd.x * nrm.x + dd.y * nrm.y + dd.z * nrm.z;
-  const double f = wA * dn * invR5;
-  const double dv[3] = {dd.x, dd.y, dd.z};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) res[3 * i + j] += f * dv[i] * dv[j];
-}
-
-// tbc = the TARGET's flag (kernel/StokesSphericalBEM.hpp:377-389): 0 VELOCITY -> eval_velocity_integral (:260-375),
-// 1 TRACTION -> eval_traction_integral (:160-258): self 2 pi I, near K_fine, far K points, times -3, no 1/(2 mu)
-// In two parts like laplace_entry: stokes_far_from gives the block of a pair in the far regime (the K stored Gauss points; the
-// 2 pi I of a TRACTION self pair) from a source panel held in registers, or says `deferred`; stokes_entry_near the near regime
-// (the K_fine rule on the vertices, the closed form of the self pair).  One text for the arithmetic, whoever asks.
-template <class Quad>
-__device__ __forceinline__ bool stokes_far_from(const DevicePlan& d, V3 t, int tbc, V3 c, double A, V3 nrm, Quad&& quad, double* out) {
-  const double dist = norm(sub(t, c));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[i] = 0;
-  if (tbc) {
-    if (fabs(dist) < 1e-8) { out[0] = out[4] = out[8] = 2 * M_PI; return false; }
-    if (sqrt(2 * A) / dist >= 0.5) return true;
-    for (int q = 0; q < d.nq; ++q) stresslet_point(out, d.qw[q] * A, t, quad(q), nrm);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out[i] *= -3.;
-    return false;
-  }
-  if (sqrt(2 * A) / dist >= 0.5) return true;
-  for (int q = 0; q < d.nq; ++q) stokeslet_point(out, d.qw[q] * A, t, quad(q));
-  const double sc = 1. / 2 / d.mu;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[i] *= sc;
-  return false;
-}
-__device__ inline void stokes_entry_near(const DevicePlan& d, V3 t, int tbc, int64_t j, double* out) {
-  const int64_t N = d.n;
-  const V3 c = {d.cx[j], d.cy[j], d.cz[j]};
-  const double A = d.area[j];
-  const double dist = norm(sub(t, c));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[i] = 0;
-  const V3 v0 = {d.vert[0 * N + j], d.vert[1 * N + j], d.vert[2 * N + j]};
-  const V3 v1 = {d.vert[3 * N + j], d.vert[4 * N + j], d.vert[5 * N + j]};
-  const V3 v2 = {d.vert[6 * N + j], d.vert[7 * N + j], d.vert[8 * N + j]};
-  if (tbc) {
-    const V3 nrm = {d.nx[j], d.ny[j], d.nz[j]};
-    for (int q = 0; q < d.nqf; ++q) {
-      const V3 pt = {v0.x * d.qf[4 * q + 0] + v1.x * d.qf[4 * q + 1] + v2.x * d.qf[4 * q + 2],
-                     v0.y * d.qf[4 * q + 0] + v1.y * d.qf[4 * q + 1] + v2.y * d.qf[4 * q + 2],
-                     v0.z * d.qf[4 * q + 0] + v1.z * d.qf[4 * q + 1] + v2.z * d.qf[4 * q + 2]};
-      stresslet_point(out, d.qf[4 * q + 3] * A, t, pt, nrm);
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out[i] *= -3.;
-    return;
-  }
-  if (dist < 1e-8) {
-    stokes_self(v0, v1, v2, t, out);
-  } else {
-    for (int q = 0; q < d.nqf; ++q) {
-      const V3 pt = {v0.x * d.qf[4 * q + 0] + v1.x * d.qf[4 * q + 1] + v2.x * d.qf[4 * q + 2],
-                     v0.y * d.qf[4 * q + 0] + v1.y * d.qf[4 * q + 1] + v2.y * d.qf[4 * q + 2],
-                     v0.z * d.qf[4 * q + 0] + v1.z * d.qf[4 * q + 1] + v2.z * d.qf[4 * q + 2]};
-      stokeslet_point(out, d.qf[4 * q + 3] * A, t, pt);
-    }
-  }
-  const double sc = 1. / 2 / d.mu;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[i] *= sc;
-}
-__device__ inline void stokes_entry(const DevicePlan& d, V3 t, int tbc, int64_t j, double* out) {
-  const int64_t N = d.n;
-  const V3 c = {d.cx[j], d.cy[j], d.cz[j]};
-  const V3 nrm = tbc ? V3{d.nx[j], d.ny[j], d.nz[j]} : V3{0, 0, 0};
-  if (stokes_far_from(d, t, tbc, c, d.area[j], nrm,
-                      [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; }, out))
-    stokes_entry_near(d, t, tbc, j, out);
 }
 
 // one thread per (target panel, source panel) pair of the leaf block; writes its 3x3 block into the

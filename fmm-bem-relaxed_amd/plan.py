@@ -258,6 +258,110 @@ def kernel_entries(K, targets, sources, target_bc=None, device=0):
     return out
 
 
+class Direct:
+    """Direct::matvec (include/Direct.hpp:232-302) on the device: y_i = sum_j K(t_i, s_j) x_j over ALL the panels, every entry the
+    one kernel_entries gives for that pair (fmmbem_direct_*, csrc/kernels_direct.hip).  Laplace and Stokes; no tree, no matrix.
+
+    panels: (N, 3, 3) source triangles; they carry no flags -- the TARGET's flag picks the operator (Laplace G / dG/dn; Stokes
+    velocity / the double layer with the source's normal).  The order of addition is fixed (chunks of .chunk sources, ascending),
+    so a result's bits do not depend on how many targets a call holds.
+    """
+
+    def __init__(self, K, panels, device=0):
+        v = np.ascontiguousarray(panels, dtype=np.float64).reshape(-1, 9)
+        self._K = K
+        self.n = v.shape[0]
+        self.device = int(device)
+        self.dof = 3 if isinstance(K, StokesSphericalBEM) else 1
+        o = _capi.Options()
+        _capi.lib().fmmbem_options_default(C.byref(o))
+        o.quad_k, o.device = K.K, self.device
+        if self.dof == 3:
+            o.kernel, o.mu, o.quad_k_fine = _capi.KERNEL_STOKES_BEM, K.Mu, K.K_fine
+        h = C.c_void_p()
+        self._h = None
+        _capi.check(_capi.lib().fmmbem_direct_create(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self._h = h
+
+    @property
+    def chunk(self):
+        """sources per partial sum (fmmbem_direct_chunk)"""
+        return _capi.lib().fmmbem_direct_chunk()
+
+    def kernel(self):
+        return self._K
+
+    def _targets(self, targets, target_bc):
+        if targets is None:
+            t, m = None, self.n
+        else:
+            t = np.asarray(targets, dtype=np.float64)
+            if t.ndim == 3 and t.shape[1:] == (3, 3):
+                t = (t[:, 0] + t[:, 1] + t[:, 2]) / 3          # a Panel target: its centre, as FMM_plan(targets=...) takes it
+            if t.ndim != 2 or t.shape[1] != 3:
+                raise ValueError("targets must be (M, 3) points or (M, 3, 3) triangles")
+            t, m = np.ascontiguousarray(t), t.shape[0]
+        if target_bc is not None:
+            target_bc = np.ascontiguousarray(target_bc, dtype=np.uint8)
+            if target_bc.shape != (m,):
+                raise ValueError("target_bc must have one flag per target")
+        return t, target_bc, m
+
+    def matvec(self, x, targets=None, target_bc=None):
+        """x: (N,) -- (N, 3) for Stokes.  targets: (M, 3) points or (M, 3, 3) triangles standing for their centroids; None: the
+        symmetric form, the targets are the panels' own centroids and target_bc their flags.  Returns (M,) or (M, 3).  numpy in,
+        numpy out (host)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        want = (self.n,) if self.dof == 1 else (self.n, 3)
+        if x.shape != want:
+            raise ValueError("x must have shape %r" % (want,))
+        t, bc, m = self._targets(targets, target_bc)
+        y = np.empty((m,) if self.dof == 1 else (m, 3))
+        vp = C.c_void_p
+        _capi.check(_capi.lib().fmmbem_direct_apply(self._h, m, None if t is None else t.ctypes.data_as(vp),
+                                                    None if bc is None else bc.ctypes.data_as(vp), x.ctypes.data_as(vp), y.ctypes.data_as(vp)))
+        return y
+
+    def matvec_torch(self, x, targets=None, target_bc=None, out=None):
+        """The same sum on device tensors, asynchronous on torch's current stream.  x: contiguous float64 CUDA tensor of N * dof
+        values; targets: contiguous float64 CUDA tensor (M, 3) or None; target_bc: uint8 CUDA tensor (M,) or None."""
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
+            raise ValueError("x must be a contiguous float64 CUDA tensor with dof values per panel")
+        if x.device.index != self.device:
+            raise ValueError("x lives on cuda:%s but the Direct sum was built on device %d" % (x.device.index, self.device))
+        m = self.n
+        if targets is not None:
+            if (targets.dtype != torch.float64 or targets.device != x.device or not targets.is_contiguous() or targets.dim() != 2
+                    or targets.shape[1] != 3):
+                raise ValueError("targets must be a contiguous float64 tensor (M, 3) on x's device")
+            m = targets.shape[0]
+        if target_bc is not None and (target_bc.dtype != torch.uint8 or target_bc.device != x.device or not target_bc.is_contiguous()
+                                      or tuple(target_bc.shape) != (m,)):
+            raise ValueError("target_bc must be a contiguous uint8 tensor (M,) on x's device")
+        shape = (m,) if self.dof == 1 else (m, 3)
+        if out is None:
+            out = x.new_empty(shape)
+        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
+        vp = C.c_void_p
+        _capi.check(_capi.lib().fmmbem_direct_apply_device(
+            self._h, m, None if targets is None else vp(targets.data_ptr()), None if target_bc is None else vp(target_bc.data_ptr()),
+            vp(x.data_ptr()), vp(out.data_ptr()), vp(torch.cuda.current_stream(x.device).cuda_stream)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _capi.lib().fmmbem_direct_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _read(fn, *paths):
     n = C.c_size_t(0)
     args = [os.fsencode(p) for p in paths]

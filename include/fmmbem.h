@@ -337,6 +337,34 @@ int fmmbem_ops_l2l(fmmbem_ops *ops, int p, int n_slots, const double *L_source, 
 int fmmbem_ops_l2p(fmmbem_ops *ops, int p, const double *L, const double center[3], size_t n, const double *vertices,
                    const uint8_t *bc, double *result);
 
+/* ---- Direct sum: y_i = sum_j K(t_i, s_j) x_j over ALL sources, on the device (Direct::matvec, include/Direct.hpp:232-302) ----
+ * The O(N M) sum the reference checks its FMM and its exterior field against, with every entry the one fmmbem_kernel_entries gives
+ * for that pair, summed where it is made (csrc/kernels_direct.hip).  No tree, no matrix: the handle holds the source panels in the
+ * caller's order.  Laplace and Stokes; for Stokes this is the route to velocity / double-layer values at points off the surface.
+ *   fmmbem_direct_create reads opts->kernel, quad_k, quad_k_fine, mu, device.  source_vertices: n_sources x 9.
+ *   target_points: n_targets x 3, or NULL for the symmetric form (Direct.hpp:291-302): the targets are the sources' own centroids as
+ *     the device computed them, n_targets must equal n_sources and target_bc holds the panels' flags.
+ *   target_bc: n_targets flags or NULL (all 0).  The TARGET's flag picks the operator -- Laplace G or dG/dn; Stokes velocity, or the
+ *     double layer with the SOURCE's normal -- the sources carry no flags.
+ *   x: n_sources x dof, y: n_targets x dof (dof = 3 for Stokes), y is OVERWRITTEN.
+ * Order of addition, fixed: the sources are cut into chunks of fmmbem_direct_chunk() consecutive panels; a target's partial sum over
+ * a chunk is acc = fma(K_ij, x_j, acc) in ascending j from 0 (Stokes: per component, the block's columns 0, 1, 2 of source j in
+ * turn); y_i is the partial sums added in ascending chunk order.  A result's bits therefore depend on the inputs only -- not on
+ * n_targets, on how a set of targets is split over calls, or on the run.
+ * Errors: null arguments, n == 0, a bad quadrature key, mu <= 0 (Stokes), a vertex or target point that is not finite, n_targets !=
+ * n_sources in the symmetric form: FMMBEM_ERR_INVALID from one host pass before any device is touched (the _device form cannot read
+ * its points and checks the rest); no device: FMMBEM_ERR_NO_DEVICE.  The partial sums live in a buffer the handle owns and grows on
+ * demand (at most 256 MB: more targets are served in slabs); if growing fails the call returns FMMBEM_ERR_ALLOC, the buffer is
+ * left empty and the handle stays usable.  fmmbem_direct_apply_device is asynchronous on `stream`; a handle is not thread-safe. */
+typedef struct fmmbem_direct fmmbem_direct;
+int fmmbem_direct_create(const fmmbem_options *opts, size_t n_sources, const double *source_vertices, fmmbem_direct **out);
+int fmmbem_direct_apply(fmmbem_direct *direct, size_t n_targets, const double *target_points, const uint8_t *target_bc,
+                        const double *x, double *y);
+int fmmbem_direct_apply_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const uint8_t *d_target_bc,
+                               const double *d_x, double *d_y, void *stream);
+int fmmbem_direct_chunk(void);
+void fmmbem_direct_destroy(fmmbem_direct *direct);
+
 /* ---- the orthogonalisation step of the callers above the matvec (examples/BEM/GMRES.hpp:203-212: modified Gram-Schmidt of
  * w against V_0 .. V_{ncols-1}, then the normalised next basis vector), device vectors, ONE call per Arnoldi column:
  *   for k < ncols:  h[k] = <w, V_k>;  w -= h[k] V_k;      h[ncols] = |w|;   vnext = w / h[ncols]
