@@ -12,6 +12,9 @@ through a plan over those target points (FMM_plan(K, panels, targets=...), the r
 one more report line with its largest error against the exact exterior solution 1/|x|.
 -near_f32 P (not a flag of the reference): the operator's matvecs at orders p <= P stream the float copy of the near matrix
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
+-block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
+block-diagonal operator inverted once on the device (solver.BlockInverse) where -fgmres -diagonal iterates on them; the same
+report lines as the other modes.
 """
 import math
 import os
@@ -36,7 +39,9 @@ def print_help_and_exit():
           "-second_kind : enable 'second-kind' option to solve second-kind integral equations\n"
           "-fixed_p : enable 'non-relaxed' option\n"
           "-solver_tol <double> : Set the solver tolerance, default = 1e-5\n"
-          "-max_iters <int>, -gmres, -fgmres, -local, -diagonal, -mesh <file.msh>\n-help : print this message")
+          "-max_iters <int>, -gmres, -fgmres, -local, -diagonal, -mesh <file.msh>\n"
+          "-block_inverse : (not a flag of the reference) GMRES preconditioned by the exact inverse of the leaf-diagonal blocks\n"
+          "-help : print this message")
     sys.exit(0)
 
 
@@ -145,6 +150,8 @@ def main(argv):
             i += 1; mesh = argv[i]
         elif a == "-field":
             i += 1; field = int(argv[i])
+        elif a == "-block_inverse":                        # not in the reference: solver.BlockInverse
+            solver, pc = "gmres", "block_inverse"
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
             i += 1; near_f32 = int(argv[i])
         else:
@@ -195,6 +202,9 @@ def main(argv):
     elif solver == "gmres" and pc == "diagonal":
         print("Solver: GMRES\nPreconditioner: Diagonal")
         x, it, res = fb.gmres(plan, x, b, so, M=fb.Diagonal(plan, dev), log=log)
+    elif pc == "block_inverse":
+        print("Solver: GMRES\nPreconditioner: Block inverse")
+        x, it, res = fb.gmres(plan, x, b, so, M=fb.BlockInverse(fb, fb.LaplaceSphericalBEM(p, k), v, bc=bc, ncrit=ncrit), log=log)
     elif solver == "fgmres" and pc == "identity":
         print("Solver: FMRES\nPreconditioner: Identity")
         x, it, res = fb.fgmres(plan, x, b, so, lambda z: z, log=log)

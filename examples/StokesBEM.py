@@ -14,6 +14,9 @@ against 6 pi mu, area and pointwise traction errors (:337-372).  All matvecs run
 
 -field N (not a flag of the reference): after the solve, the velocity of the single layer with the solved density on N points of the
 sphere of radius 3, summed on the device by fb.Direct (Stokes has no target plan); prints the largest and the mean magnitude.
+
+-block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
+block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
 """
 import math
 import os
@@ -39,7 +42,9 @@ def print_help_and_exit():
           "-cells <int> : number of red blood cells to generate\n"
           "-fixed_p : Disable relaxation\n"
           "-pmin <int>, -mu <double>, -kfine <int>, -solver_tol <double>, -mesh <file.msh>, -vert <f> -face <f>,\n"
-          "-fgmres, -diagonal, -local\n-help : print this message")
+          "-fgmres, -diagonal, -local\n"
+          "-block_inverse : (not a flag of the reference) GMRES preconditioned by the exact inverse of the leaf-diagonal blocks\n"
+          "-help : print this message")
     sys.exit(0)
 
 
@@ -112,6 +117,8 @@ def main(argv):
             i += 1; ncrit = int(argv[i])
         elif a == "-eval":
             i += 1
+        elif a == "-block_inverse":                        # not in the reference: solver.BlockInverse
+            solver, pc = "gmres", "block_inverse"
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
             i += 1; near_f32 = int(argv[i])
         elif a == "-field":                                # not in the reference: the solved layer's velocity off the surface
@@ -167,7 +174,10 @@ def main(argv):
     x = torch.zeros(3 * n, dtype=torch.float64, device=dev)
     log = _Logged()
     tic = time.time()
-    if solver == "gmres":
+    if pc == "block_inverse":
+        print("Solver: GMRES, Preconditioner: Block inverse")
+        x, it, res = fb.gmres(plan, x, b.reshape(-1), so, M=fb.BlockInverse(fb, kernel(), v, ncrit=ncrit), log=log, stokes=True)
+    elif solver == "gmres":
         print("Solver: GMRES, Preconditioner: Identity")
         x, it, res = fb.gmres(plan, x, b.reshape(-1), so, log=log, stokes=True)
     elif pc == "identity":

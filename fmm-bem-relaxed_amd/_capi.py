@@ -77,7 +77,7 @@ class SolverLog(C.Structure):
                 ("p", C.POINTER(C.c_int32)), ("resid", C.POINTER(C.c_double))]
 
 
-PC_IDENTITY, PC_DIAGONAL, PC_INNER_PLAN = 0, 1, 2
+PC_IDENTITY, PC_DIAGONAL, PC_INNER_PLAN, PC_BLOCK_INVERSE = 0, 1, 2, 3
 ORDER_GMRES, ORDER_GMRES_STOKES, ORDER_FGMRES, ORDER_FGMRES_STOKES = 0, 1, 2, 3
 
 
@@ -104,6 +104,8 @@ SYMBOLS = (
     "fmmbem_plan_execute_batch", "fmmbem_plan_execute_batch_device", "fmmbem_plan_batch_width",
     "fmmbem_gmres_batch_device", "fmmbem_gmres_batch",
     "fmmbem_direct_create", "fmmbem_direct_apply", "fmmbem_direct_apply_device", "fmmbem_direct_chunk", "fmmbem_direct_destroy",
+    "fmmbem_plan_block_inverse_build", "fmmbem_plan_block_inverse_apply_device", "fmmbem_plan_block_inverse_apply",
+    "fmmbem_plan_block_inverse_bytes",
 )
 
 
@@ -195,6 +197,10 @@ def lib():
     L.fmmbem_direct_chunk.argtypes = []
     L.fmmbem_direct_destroy.argtypes = [vp]
     L.fmmbem_direct_destroy.restype = None
+    L.fmmbem_plan_block_inverse_build.argtypes = [vp]
+    L.fmmbem_plan_block_inverse_apply_device.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.fmmbem_plan_block_inverse_apply.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
+    L.fmmbem_plan_block_inverse_bytes.argtypes = [vp, i64p]
     _lib = L
     return L
 

@@ -25,6 +25,7 @@ struct SolverWs;
 int plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, int* p_max, SolverWs*** slot);
 void solver_ws_destroy(SolverWs* ws);
 size_t plan_unknowns(const fmmbem_plan* plan);      // plan.hip: doubles of one x vector (any plan, host-only ones included)
+bool plan_block_inverse_built(const fmmbem_plan* plan);   // plan.hip: fmmbem_plan_block_inverse_build has succeeded on it
 }
 
 namespace {
@@ -468,6 +469,14 @@ void plane_rotation(double dx, double dy, double* cs, double* sn) {             
   else { const double t = dy / dx; *cs = 1.0 / std::sqrt(1.0 + t * t); *sn = t * *cs; }
 }
 
+// a block-inverse preconditioner (kind 3) without a plan of its own: refused with the null arguments, before the operator
+// plan's own refusals (kinds 0-2 keep their order: the plan first)
+int check_block_inverse_args(const fmmbem_plan* plan, const fmmbem_preconditioner* M) {
+  if (M && M->kind == FMMBEM_PC_BLOCK_INVERSE && (!M->inner_plan || M->inner_plan == plan))
+    return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner needs a plan of its own");
+  return FMMBEM_OK;
+}
+
 // what a solve refuses before it touches anything
 int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem_preconditioner* M, int depth, int* device, int64_t* n,
                 int* plan_pmax, SolverWs*** slot) {
@@ -483,7 +492,15 @@ int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem
     KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
     if (dv != *device || nn != *n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
   }
-  if (kind < 0 || kind > FMMBEM_PC_INNER_PLAN) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: unknown preconditioner kind");
+  if (kind == FMMBEM_PC_BLOCK_INVERSE) {
+    KRY_TRY(check_block_inverse_args(plan, M));
+    int dv = 0, pm = 0; int64_t nn = 0; SolverWs** sl = nullptr;
+    KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
+    if (dv != *device || nn != *n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
+    if (!fmmbem::plan_block_inverse_built(M->inner_plan))
+      return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the block-inverse preconditioner's plan has no inverse built (fmmbem_plan_block_inverse_build)");
+  }
+  if (kind < 0 || kind > FMMBEM_PC_BLOCK_INVERSE) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: unknown preconditioner kind");
   return FMMBEM_OK;
 }
 
@@ -625,6 +642,16 @@ struct Solver {
       });
       return FMMBEM_OK;
     }
+    if (kind == FMMBEM_PC_BLOCK_INVERSE) {
+      // one pass over the inverses per run of neighbouring systems (all of act until one of them has left)
+      for (size_t a = 0; a < act.size();) {
+        size_t cnt = 1;
+        while (a + cnt < act.size() && act[a + cnt] == act[a] + (int)cnt) ++cnt;
+        KRY_TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, (int)cnt, Vc(c, act[a]), (size_t)ld, out + (int64_t)act[a] * ld, (size_t)ld, s));
+        a += cnt;
+      }
+      return FMMBEM_OK;
+    }
     // LocalPC.hpp:35-41: fill(y, 0); GMRES(plan, y, x, options) -- for all systems of act in one solve on the inner plan
     std::vector<double*> y;
     std::vector<const double*> v;
@@ -673,6 +700,16 @@ struct Solver {
     double* dy = ws->d_y + (size_t)ws->hcap * j;
     for (int c = 0; c <= i; ++c) hy[c] = S.ar.sv[c];
     KRY_HIP(hipMemcpyAsync(dy, hy, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
+    if (kind == FMMBEM_PC_BLOCK_INVERSE && !so.flexible) {
+      // M is linear and constant: x += M (sum_c y_c V_c), one pass over the inverses instead of one per column.  The sum is
+      // formed in this system's w, which the Arnoldi column has finished with
+      KRY_HIP(hipMemsetAsync(wv(j), 0, sizeof(double) * (size_t)n, s));
+      hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, wv(j), Vc(0, j), ld * ws->cap, i + 1, dy, (const double*)nullptr);
+      double* zj = ws->z + (int64_t)j * ld;
+      KRY_TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, 1, wv(j), (size_t)ld, zj, (size_t)ld, s));
+      hipLaunchKernelGGL(mgs_axpy_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, 1.0, zj);
+      return FMMBEM_OK;
+    }
     // FGMRES with the identity: Z_c = V_c was never copied (apply_pc hands V_c back), the update reads V
     hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, (so.flexible && kind != FMMBEM_PC_IDENTITY) ? Zc(0, j) : Vc(0, j), ld * ws->cap, i + 1, dy,
                        (!so.flexible && kind == FMMBEM_PC_DIAGONAL) ? M->reciprocals : (const double*)nullptr);
@@ -789,6 +826,7 @@ int entry_args(const fmmbem_plan* plan, const fmmbem_solver_options* opts, int k
 int gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* d_x, size_t ldx, const double* d_b, size_t ldb,
                  const fmmbem_preconditioner* M, fmmbem_solver_log* logs, void* stream, const char* who) {
   KRY_TRY(entry_args(plan, opts, k, d_x, ldx, d_b, ldb, who));
+  KRY_TRY(check_block_inverse_args(plan, M));
   int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
   KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
   DevGuard guard(device);
@@ -804,6 +842,7 @@ int gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, do
 int gmres_host(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* x, size_t ldx, const double* b, size_t ldb,
                const fmmbem_preconditioner* M, fmmbem_solver_log* logs, const char* who) {
   KRY_TRY(entry_args(plan, opts, k, x, ldx, b, ldb, who));
+  KRY_TRY(check_block_inverse_args(plan, M));
   int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
   KRY_TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
   DevGuard guard(device);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "../../include/fmmbem.h"
+#include "blockinv.hpp"
 #include "device_launch.hpp"
 #include "host_plan.hpp"
 #include "host_tables.hpp"
@@ -43,6 +45,7 @@ struct SolverWs;                                      // krylov.hip
 void solver_ws_destroy(SolverWs* ws);
 int plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, int* p_max, SolverWs*** slot);
 size_t plan_unknowns(const fmmbem_plan* plan);
+bool plan_block_inverse_built(const fmmbem_plan* plan);
 }  // namespace fmmbem
 
 namespace {
@@ -245,6 +248,21 @@ struct fmmbem_plan {
   double *stage_x = nullptr, *stage_y = nullptr;               // device staging for host-pointer execute
   fmmbem::SolverWs* solver_ws = nullptr;                       // workspace of fmmbem_gmres* on this plan (krylov.hip), kept between solves
   hipStream_t own_stream = nullptr;
+  // Exact block-Jacobi preconditioner of a BLOCK_DIAGONAL plan (fmmbem_plan_block_inverse_build; kernels_blockinv.hip): the
+  // inverses of the leaves' self blocks in storage of their own -- near_val / near_sym stay what execute applies
+  struct BlockInverse {
+    bool built = false;
+    BlockInvDev dev;
+    int max_m = 0;                                             // unknowns of the largest leaf
+    int64_t doubles = 0;                                       // of all inverses together
+    double* stage = nullptr;                                   // device staging of the host-pointer apply: v, then z
+    size_t stage_doubles = 0;
+  };
+  BlockInverse binv;
+  void block_inverse_free() {
+    for (void* p : {(void*)binv.dev.val, (void*)binv.dev.off, (void*)binv.dev.bad, (void*)binv.stage}) if (p) (void)hipFree(p);
+    binv = BlockInverse{};
+  }
   // Dual plans (fmmbem_plan_create_targets): hp holds the source tree and the target tree as one plan (HostPlan::build_targets);
   // x has hp.n_src entries, y hp.n_targets.  Every source feeds both expansions (the TARGET's flag picks the kernel): P2M runs once
   // per live slot with the flags of all sources set to that slot's (bc_all[slot]) and that slot's moment table.
@@ -312,6 +330,7 @@ struct fmmbem_plan {
     if (solver_ws) fmmbem::solver_ws_destroy(solver_ws);
     if (on_device) {
       DeviceGuard guard(opts.device);
+      block_inverse_free();
       for (void* p : allocs) (void)hipFree(p);
       for (auto& e : ev) (void)hipEventDestroy(e);
       for (auto& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -1655,6 +1674,7 @@ int fmmbem_plan::like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc,
   pl->asm_ev[0] = pl->asm_ev[1] = nullptr;
   pl->d_dev = nullptr; pl->stage_x = pl->stage_y = nullptr; pl->solver_ws = nullptr; pl->d_cut = nullptr;
   pl->bat = BatchBufs{};
+  pl->binv = BlockInverse{};
   pl->multi.reset();
   pl->result_slices = false; pl->pending_mask = 0; pl->pending_near = false;
   pl->timing = 0; pl->last_p = 0; pl->ev_count = 0;
@@ -2363,6 +2383,106 @@ int fmmbem_plan_batch_width(const fmmbem_plan* plan, int* width) {
   return FMMBEM_OK;
 }
 
+// ---- exact block-Jacobi preconditioner: the leaf blocks of a BLOCK_DIAGONAL plan inverted on the device (include/fmmbem.h) ----
+static_assert(kBlockInvMax == FMMBEM_BLOCK_INVERSE_MAX, "the header states the largest leaf the kernels serve");
+int fmmbem_plan_block_inverse_build(fmmbem_plan* plan) {
+  const char* who = "fmmbem_plan_block_inverse_build: ";
+  if (!plan) return fail(FMMBEM_ERR_INVALID, std::string(who) + "null plan");
+  if (plan->targets || plan->opts.evaluator != FMMBEM_EVAL_BLOCK_DIAGONAL)
+    return fail(FMMBEM_ERR_INVALID, std::string(who) + "needs a plan created with evaluator BLOCK_DIAGONAL");
+  if (!plan->opts.sparse_local) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "a matrix-free plan holds no blocks to invert");
+  if (plan->multi || plan->opts.n_devices > 1) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "not on a plan over a device list");
+  if (plan->hp.opt.shard_world > 1 || plan->opts.shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "not on a shard of an operator");
+  if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, std::string(who) + "plan was built host-only; the blocks live on the device");
+  if (plan->binv.built) return FMMBEM_OK;
+  if (plan->hybrid || (!plan->d.near_val && !plan->d.near_sym)) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "the plan stores no leaf blocks");
+  const HostPlan& h = plan->hp;
+  const int dof = plan->d.dof;
+  // every leaf of a BLOCK_DIAGONAL plan is its own and only source (EvalDiagonalSparse.hpp:33-49)
+  std::vector<int> selfcol((size_t)h.nleaves(), 0);
+  std::vector<int64_t> off((size_t)(h.leaf_end - h.leaf_begin) + 1, 0);
+  int max_m = 0;
+  for (int l = h.leaf_begin; l < h.leaf_end; ++l) {
+    if (h.near_ptr[l + 1] - h.near_ptr[l] != 1 || h.near_src[h.near_ptr[l]] != l)
+      return fail(FMMBEM_ERR_INVALID, std::string(who) + "internal: a leaf whose row block is not its self block");
+    const int tb = h.leaf_box[l];
+    const int m = dof * (h.box_body_end[tb] - h.box_body_begin[tb]);
+    max_m = std::max(max_m, m);
+    off[(size_t)(l - h.leaf_begin) + 1] = off[(size_t)(l - h.leaf_begin)] + (int64_t)m * m;
+  }
+  if (max_m > kBlockInvMax)
+    return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "a leaf holds " + std::to_string(max_m) + " unknowns; the kernels serve at most " +
+                                            std::to_string(kBlockInvMax) + " (ncrit * dof)");
+  DEVICE_SCOPE(plan->opts.device);
+  fmmbem_plan::BlockInverse& bi = plan->binv;
+  int* d_selfcol = nullptr;
+  const int none = INT_MAX;
+  int bad = none;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&bi.dev.val), sizeof(double) * (size_t)std::max<int64_t>(off.back(), 1));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(const_cast<int64_t**>(&bi.dev.off)), sizeof(int64_t) * off.size());
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&bi.dev.bad), sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_selfcol), sizeof(int) * std::max<size_t>(selfcol.size(), 1));
+  if (e != hipSuccess) {
+    if (d_selfcol) (void)hipFree(d_selfcol);
+    plan->block_inverse_free();
+    return fail(e == hipErrorOutOfMemory ? FMMBEM_ERR_ALLOC : FMMBEM_ERR_HIP, std::string(who) + hipGetErrorString(e));
+  }
+  hipStream_t s = plan->own_stream;
+  e = hipMemcpy(const_cast<int64_t*>(bi.dev.off), off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(bi.dev.bad, &none, sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_selfcol, selfcol.data(), sizeof(int) * selfcol.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_blockinv_build(plan->d, bi.dev, d_selfcol, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipMemcpy(&bad, bi.dev.bad, sizeof(int), hipMemcpyDeviceToHost);
+  (void)hipFree(d_selfcol);
+  if (e != hipSuccess) { plan->block_inverse_free(); return fail(FMMBEM_ERR_HIP, std::string(who) + hipGetErrorString(e)); }
+  if (bad != none) {                                   // the plan stays as it was: no inverse attached
+    plan->block_inverse_free();
+    const int tb = h.leaf_box[bad];
+    return fail(FMMBEM_ERR_INVALID, std::string(who) + "leaf " + std::to_string(bad) + " (tree panels " + std::to_string(h.box_body_begin[tb]) + ".." +
+                                        std::to_string(h.box_body_end[tb] - 1) + "): zero or non-finite pivot, its block is singular");
+  }
+  bi.max_m = max_m;
+  bi.doubles = off.back();
+  bi.built = true;
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_block_inverse_apply_device(fmmbem_plan* plan, int k, const double* d_v, size_t ldv, double* d_z, size_t ldz, void* stream) {
+  TRY(batch_args(plan, k, d_v, ldv, d_z, ldz));
+  if (!plan->binv.built) return fail(FMMBEM_ERR_INVALID, "fmmbem_plan_block_inverse_apply: no inverse built on this plan (fmmbem_plan_block_inverse_build)");
+  DEVICE_SCOPE(plan->opts.device);
+  HIP_TRY(launch_blockinv_apply(plan->d, plan->binv.dev, plan->binv.max_m, k, d_v, ldv, d_z, ldz, static_cast<hipStream_t>(stream)));
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_block_inverse_apply(fmmbem_plan* plan, int k, const double* v, size_t ldv, double* z, size_t ldz) {
+  TRY(batch_args(plan, k, v, ldv, z, ldz));
+  if (!plan->binv.built) return fail(FMMBEM_ERR_INVALID, "fmmbem_plan_block_inverse_apply: no inverse built on this plan (fmmbem_plan_block_inverse_build)");
+  DEVICE_SCOPE(plan->opts.device);
+  fmmbem_plan::BlockInverse& bi = plan->binv;
+  const size_t n = (size_t)plan->hp.n * plan->d.dof;
+  if (bi.stage_doubles < 2 * n * (size_t)k) {
+    if (bi.stage) (void)hipFree(bi.stage);
+    bi.stage = nullptr; bi.stage_doubles = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&bi.stage), sizeof(double) * 2 * n * (size_t)k));
+    bi.stage_doubles = 2 * n * (size_t)k;
+  }
+  double *sv = bi.stage, *sz = bi.stage + n * (size_t)k;
+  hipStream_t s = plan->own_stream;
+  HIP_TRY(hipMemcpy2DAsync(sv, sizeof(double) * n, v, sizeof(double) * ldv, sizeof(double) * n, (size_t)k, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_blockinv_apply(plan->d, bi.dev, bi.max_m, k, sv, n, sz, n, s));
+  HIP_TRY(hipMemcpy2DAsync(z, sizeof(double) * ldz, sz, sizeof(double) * n, sizeof(double) * n, (size_t)k, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan_block_inverse_bytes(const fmmbem_plan* plan, int64_t* bytes) {
+  if (!plan || !bytes) return fail(FMMBEM_ERR_INVALID, "null argument");
+  *bytes = plan->binv.built ? plan->binv.doubles * (int64_t)sizeof(double) : 0;
+  return FMMBEM_OK;
+}
+
 int fmmbem_host_register(void* ptr, size_t bytes) {
   if (!ptr || !bytes) return fail(FMMBEM_ERR_INVALID, "null buffer");
   HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
@@ -2797,6 +2917,9 @@ int fmmbem::plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, 
 }
 
 // doubles of one x vector of the plan: what the batched solver checks its leading dimensions against before anything else
+// kind 3 of fmmbem_preconditioner: has fmmbem_plan_block_inverse_build succeeded on this plan?
+bool fmmbem::plan_block_inverse_built(const fmmbem_plan* plan) { return plan && plan->binv.built; }
+
 size_t fmmbem::plan_unknowns(const fmmbem_plan* plan) {
   if (plan->targets) return (size_t)plan->hp.n_src;
   return (size_t)plan->hp.n * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);

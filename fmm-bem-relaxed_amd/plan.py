@@ -632,6 +632,50 @@ class FMM_plan:
         _capi.check(_capi.lib().fmmbem_plan_batch_width(self._h, C.byref(w)))
         return w.value
 
+    # ---- exact block-Jacobi preconditioner of a BLOCK_DIAGONAL plan (fmmbem_plan_block_inverse_*; not in the reference) ----
+    def block_inverse_build(self):
+        """Invert every leaf's self block on the device, once; execute keeps applying the blocks themselves.  A second call is
+        a no-op.  Raises FmmBemError (status 1, the message names the leaf) when a block is singular."""
+        _capi.check(_capi.lib().fmmbem_plan_block_inverse_build(self._h))
+
+    def block_inverse_bytes(self):
+        """HBM bytes of the inverses: what one apply streams (0 before block_inverse_build)."""
+        b = C.c_int64(0)
+        _capi.check(_capi.lib().fmmbem_plan_block_inverse_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def block_inverse_apply(self, v):
+        """z = M v, M the inverse of the block-diagonal operator.  v: (n,) -- (n, 3) for Stokes -- or k such vectors stacked in
+        front; the same shape comes back.  numpy in, numpy out (host)."""
+        x = np.ascontiguousarray(v, dtype=np.float64)
+        want = (self.n,) if self.dof == 1 else (self.n, self.dof)
+        if x.shape != want and (x.ndim != 1 + len(want) or x.shape[1:] != want or x.shape[0] < 1):
+            raise ValueError("v must have shape %r, or (k,) + that with k >= 1" % (want,))
+        k = 1 if x.shape == want else x.shape[0]
+        z = np.empty_like(x)
+        ld = self.n * self.dof
+        _capi.check(_capi.lib().fmmbem_plan_block_inverse_apply(self._h, k, x.ctypes.data_as(C.c_void_p), ld,
+                                                                z.ctypes.data_as(C.c_void_p), ld))
+        return z
+
+    def block_inverse_apply_torch(self, v, out=None):
+        """The same on device tensors, asynchronous on torch's current stream.  v: contiguous float64 CUDA tensor of n * dof
+        values, or (k, n * dof); out: a tensor of v's shape that does not overlap it."""
+        import torch
+        nd = self.n * self.dof
+        if v.dtype != torch.float64 or not v.is_cuda or not v.is_contiguous() or v.numel() < nd or (v.numel() != nd and (v.dim() != 2 or v.shape[1] != nd)):
+            raise ValueError("v must be a contiguous float64 CUDA tensor of n * dof values, or of shape (k, n * dof)")
+        if v.device.index != self.device:
+            raise ValueError("v lives on cuda:%s but the plan was built on device %d" % (v.device.index, self.device))
+        if out is None:
+            out = torch.empty_like(v)
+        elif out.dtype != torch.float64 or out.device != v.device or not out.is_contiguous() or out.shape != v.shape or out.data_ptr() == v.data_ptr():
+            raise ValueError("out must be a contiguous float64 tensor of v's shape on v's device, and not v itself")
+        _capi.check(_capi.lib().fmmbem_plan_block_inverse_apply_device(
+            self._h, v.numel() // nd, C.c_void_p(v.data_ptr()), nd, C.c_void_p(out.data_ptr()), nd,
+            C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)))
+        return out
+
     # ---- introspection ----
     def set_timing(self, on=True):
         """True / 1: HIP events around every stage; 2: around the near-field kernel only (an event record costs ~5 us of

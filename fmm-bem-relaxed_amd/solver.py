@@ -248,15 +248,17 @@ def _c_preconditioner(M, who):
     elif isinstance(M, _InnerSolver):
         pc.kind, pc.inner_plan = _capi.PC_INNER_PLAN, M.plan._h
         pc.inner = _c_options(M.options, False, False, M.options.max_p)
+    elif isinstance(M, BlockInverse):
+        pc.kind, pc.inner_plan = _capi.PC_BLOCK_INVERSE, M.plan._h
     else:
-        raise TypeError("%s: M must be None, Diagonal, LocalInnerSolver or BlockDiagonal" % who)
+        raise TypeError("%s: M must be None, Diagonal, LocalInnerSolver, BlockDiagonal or BlockInverse" % who)
     return pc
 
 
 def gmres_capi(MV, x, b, opts, M=None, log=None, stokes=False, flexible=False):
     """The same solve through the C ABI's device-resident solver (include/fmmbem.h fmmbem_gmres_device; csrc/krylov.hip):
     what a C or C++ caller of the library gets.  MV: an FMM_plan; x, b: float64 CUDA tensors (x updated in place);
-    M: None, a Diagonal, or a LocalInnerSolver / BlockDiagonal.  Returns (x, iterations, |residual|, seconds)."""
+    M: None, a Diagonal, a LocalInnerSolver / BlockDiagonal, or a BlockInverse.  Returns (x, iterations, |residual|, seconds)."""
     import ctypes as C
     from . import _capi
     o = _c_options(opts, stokes, flexible, MV.kernel().P)
@@ -352,6 +354,26 @@ class BlockDiagonal(_InnerSolver):
         o.local_evaluation, o.lazy_evaluation, o.sparse_local, o.block_diagonal = False, False, True, True
         o.set_mac_theta(0.5)
         super().__init__(fb, K, panels, o, bc, device)
+
+
+class BlockInverse:
+    """The exact block-Jacobi preconditioner (not in the reference): z = M v with M the inverse of the block-diagonal operator
+    that Preconditioners::BlockDiagonal only iterates on.  Owns a BLOCK_DIAGONAL plan of the operator's panels
+    (BlockDiagonal::local_options(), BlockDiagonalPC.hpp:53-63, with the operator's leaf size) whose leaf blocks are inverted
+    once on the device (FMM_plan.block_inverse_build); an application is one streaming pass (FMM_plan.block_inverse_apply_torch).
+    M is constant and linear, so plain gmres may be used where the inner-solver forms need fgmres."""
+
+    def __init__(self, fb, K, panels, bc=None, device=0, ncrit=None):
+        o = fb.FMMOptions()
+        o.local_evaluation, o.lazy_evaluation, o.sparse_local, o.block_diagonal = False, False, True, True
+        o.set_mac_theta(0.5)
+        if ncrit is not None:
+            o.set_max_per_box(ncrit)
+        self.plan = fb.FMM_plan(K, panels, o, bc=bc, device=device)
+        self.plan.block_inverse_build()
+
+    def __call__(self, v):
+        return self.plan.block_inverse_apply_torch(v.contiguous())
 
 
 def laplace_bem_first_kind(fb, panels, p=12, k=3, tol=1e-5, theta=0.5, ncrit=64, max_iters=500, device=0, log=None):

@@ -262,6 +262,30 @@ int fmmbem_plan_execute_batch_device(fmmbem_plan *plan, int p, int k, const doub
  * (also on a host-only plan). */
 int fmmbem_plan_batch_width(const fmmbem_plan *plan, int *width);
 
+/* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
+ * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES
+ * iteration on that operator instead).  A BLOCK_DIAGONAL plan holds every leaf's self block assembled in HBM; build inverts
+ * each of them once on the device -- Gauss-Jordan with partial pivoting, the pivot the largest magnitude of its column, the
+ * lowest row among equals -- into storage of its own; apply is then one streaming pass over the inverses (8 bytes per entry of
+ * the blocks) for up to 4 vectors at a time.  fmmbem_plan_execute on the plan is unchanged: it applies the blocks.
+ *   build: the plan must have been created with evaluator FMMBEM_EVAL_BLOCK_DIAGONAL and sparse_local = 1 on one device with
+ *     shard_world = 1.  Checked in this order: null -> FMMBEM_ERR_INVALID; another evaluator or a target plan -> _INVALID;
+ *     matrix-free, a device list or a shard -> _UNSUPPORTED; host-only -> _NO_DEVICE; a leaf of more than
+ *     FMMBEM_BLOCK_INVERSE_MAX unknowns (ncrit * dof) -> _UNSUPPORTED.  A zero or non-finite pivot -> _INVALID, the message names
+ *     the leaf, and the plan stays usable with no inverse attached.  A second build on a plan that has its inverse returns OK.
+ *   apply: vector j is v + j*ldv, result j is z + j*ldz, n_panels x dof doubles each in the caller's panel order; v and z must
+ *     not overlap; every entry of z is written.  Row r of a leaf's result is acc = fma(M(r, c), v_c, acc) over the leaf's
+ *     columns c in ascending order from acc = 0: the bits depend on the inputs only, not on k or on the run.  k < 1, a null
+ *     pointer, a leading dimension shorter than a vector, or a plan without an inverse: FMMBEM_ERR_INVALID.  The device form is
+ *     asynchronous on `stream`; the host form returns when z is written.
+ *   bytes: HBM bytes of the inverses (0 before build); fmmbem_stats reports none of them. */
+#define FMMBEM_BLOCK_INVERSE_MAX 768
+int fmmbem_plan_block_inverse_build(fmmbem_plan *block_diagonal_plan);
+int fmmbem_plan_block_inverse_apply_device(fmmbem_plan *plan, int k, const double *d_v, size_t ldv,
+                                           double *d_z, size_t ldz, void *stream);
+int fmmbem_plan_block_inverse_apply(fmmbem_plan *plan, int k, const double *v, size_t ldv, double *z, size_t ldz);
+int fmmbem_plan_block_inverse_bytes(const fmmbem_plan *plan, int64_t *bytes);
+
 /* Toggle per-stage HIP-event timing.  While enabled every execute records HIP events around each
  * kernel on the stream it runs on (no synchronisation is added); fmmbem_plan_stats() waits for the
  * recorded events and reports the mean stage times of up to the last 64 executes.  Enabling resets
@@ -410,14 +434,18 @@ void fmmbem_solver_options_default(fmmbem_solver_options *opts);   /* SolverOpti
 typedef enum {
   FMMBEM_PC_IDENTITY = 0,    /* Preconditioners::Identity (Preconditioner.hpp:8-17)                                       */
   FMMBEM_PC_DIAGONAL = 1,    /* Preconditioners::Diagonal (:19-42): z = reciprocals .* v, in whatever order the caller built them */
-  FMMBEM_PC_INNER_PLAN = 2   /* Preconditioners::LocalInnerSolver / BlockDiagonal (LocalPC.hpp:26-59, BlockDiagonalPC.hpp:16-60):
+  FMMBEM_PC_INNER_PLAN = 2,  /* Preconditioners::LocalInnerSolver / BlockDiagonal (LocalPC.hpp:26-59, BlockDiagonalPC.hpp:16-60):
                               * z = GMRES(inner_plan, 0, v, inner) on a plan created with evaluator LOCAL or BLOCK_DIAGONAL */
+  FMMBEM_PC_BLOCK_INVERSE = 3 /* z = fmmbem_plan_block_inverse_apply_device(inner_plan, v): inner_plan = a BLOCK_DIAGONAL plan of the
+                              * same panels on the same device with its inverse built; .inner is ignored.  M is exact, constant and
+                              * linear: plain GMRES applies it once per column and ONCE to the combination sum_c y_c V_c in the
+                              * solution update */
 } fmmbem_preconditioner_kind;
 typedef struct {
   int32_t kind;                      /* fmmbem_preconditioner_kind                                                     */
   const double *reciprocals;         /* DIAGONAL: n_panels * dof values; a DEVICE pointer for fmmbem_gmres_device, a host
                                       * pointer for fmmbem_gmres                                                       */
-  fmmbem_plan *inner_plan;           /* INNER_PLAN: same panels, same device                                           */
+  fmmbem_plan *inner_plan;           /* INNER_PLAN, BLOCK_INVERSE: same panels, same device                            */
   fmmbem_solver_options inner;       /* INNER_PLAN: LocalPC.hpp:52-54 uses residual 1e-1, variable_p 0, max_iters 1     */
 } fmmbem_preconditioner;
 

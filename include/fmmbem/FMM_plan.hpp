@@ -676,7 +676,7 @@ class FMM_plan<StokesSphericalBEM> : public fmmbem::PlanAdapter<StokesSphericalB
 // The relaxed solvers with the reference's argument lists, resident on the device (fmmbem_gmres, include/fmmbem.h):
 //
 //     fmmbem::GMRES(plan, x, b, solver_options);          // examples/BEM/GMRES.hpp:119-128;  GMRES_Stokes.hpp the same on Vec<3,double>
-//     fmmbem::GMRES(plan, x, b, solver_options, M);       // :131-141, M = Preconditioners::Identity / Diagonal<T>, fmmbem::InnerSolverPC
+//     fmmbem::GMRES(plan, x, b, solver_options, M);       // :131-141, M = Preconditioners::Identity / Diagonal<T>, fmmbem::InnerSolverPC, fmmbem::BlockInversePC
 //     fmmbem::FGMRES(plan, x, b, solver_options[, M]);    // :254-274
 //
 // The reference's own GMRES.hpp keeps working against this header (every matvec then moves x and y across PCIe and the
@@ -760,6 +760,46 @@ class InnerSolverPC {
   fmmbem_solver_options inner_;
 };
 
+// The exact block-Jacobi preconditioner (not in the reference): y = M x with M the INVERSE of the leaf-diagonal operator that
+// Preconditioners::BlockDiagonal only iterates on.  Owns a BLOCK_DIAGONAL plan of the operator's panels and options
+// (BlockDiagonalPC.hpp:53-63 with the operator's leaf size), whose leaf blocks are inverted once on the device
+// (fmmbem_plan_block_inverse_build; throws Error when a block is singular); an application is one streaming pass.  As a functor
+// (x, y) it works with any solver; fmmbem::GMRES / FGMRES(_batch) recognise it and apply it on the device
+// (FMMBEM_PC_BLOCK_INVERSE).  M is constant and linear: plain GMRES may be used where the inner-solver forms need FGMRES.
+template <class Kernel>
+class BlockInversePC {
+ public:
+  typedef typename Kernel::charge_type value_type;
+  BlockInversePC(const Kernel& k, const std::vector<typename Kernel::source_type>& sources, const FMMOptions& operator_options = FMMOptions(),
+                 int device = 0)
+      : opts_(make_options(operator_options)), plan_(k, sources, opts_, 0, device) {
+    check(fmmbem_plan_block_inverse_build(plan_.handle()));
+  }
+  void operator()(const std::vector<value_type>& x, std::vector<value_type>& y) {
+    y.resize(x.size());
+    const size_t n = x.size() * (sizeof(value_type) / sizeof(double));
+    check(fmmbem_plan_block_inverse_apply(plan_.handle(), 1, KernelBinding<Kernel>::in(x), n, KernelBinding<Kernel>::out(y), n));
+  }
+  fmmbem_plan* handle() { return plan_.handle(); }
+  int64_t bytes() {                               // HBM bytes of the inverses: what one application streams
+    int64_t b = 0;
+    check(fmmbem_plan_block_inverse_bytes(plan_.handle(), &b));
+    return b;
+  }
+
+ private:
+  static FMMOptions make_options(FMMOptions o) {
+    o.lazy_evaluation = false;
+    o.local_evaluation = false;
+    o.block_diagonal = true;
+    o.sparse_local = true;
+    o.devices.clear();                            // the inverse lives on one device
+    return o;
+  }
+  FMMOptions opts_;
+  PlanAdapter<Kernel> plan_;
+};
+
 namespace detail {
 
 // A preconditioner functor of the reference's shape, M(x, y), reduced to what the device solver takes.  Identity and
@@ -791,6 +831,12 @@ void describe(InnerSolverPC<Kernel>& M, size_t, fmmbem_preconditioner& pc, std::
   pc.kind = FMMBEM_PC_INNER_PLAN;
   pc.inner_plan = M.handle();
   pc.inner = M.inner_options();
+}
+
+template <class Kernel>
+void describe(BlockInversePC<Kernel>& M, size_t, fmmbem_preconditioner& pc, std::vector<double>&) {
+  pc.kind = FMMBEM_PC_BLOCK_INVERSE;
+  pc.inner_plan = M.handle();
 }
 
 template <class Kernel, class Options>
