@@ -17,6 +17,14 @@ sphere of radius 3, summed on the device by fb.Direct (Stokes has no target plan
 
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
+
+-stokes_batch K (not a flag of the reference): the operator plan is created with fmmbem_options.stokes_batch_width = K (2, 3, 4): one
+pass over the near matrix serves K vectors of a batch; the report lines are the same, plus one line that states the width.
+
+-resistance (not a flag of the reference): after the report, the translational resistance matrix of the body -- the unit translations
+e_x, e_y, e_z solved as ONE lockstep batch (gmres_capi_batch) on the operator plan, column j the force of translation e_j -- and its
+largest deviation from 6 pi mu I, exact for the unit sphere, relative to 6 pi mu.  With -stokes_batch 3 the three matvecs of an
+iteration share one near-field pass.
 """
 import math
 import os
@@ -44,6 +52,8 @@ def print_help_and_exit():
           "-pmin <int>, -mu <double>, -kfine <int>, -solver_tol <double>, -mesh <file.msh>, -vert <f> -face <f>,\n"
           "-fgmres, -diagonal, -local\n"
           "-block_inverse : (not a flag of the reference) GMRES preconditioned by the exact inverse of the leaf-diagonal blocks\n"
+          "-stokes_batch <int> : (not a flag of the reference) vectors one near-field pass of a batch serves: 2, 3 or 4\n"
+          "-resistance : (not a flag of the reference) the 3 x 3 translational resistance matrix, three solves in one batch\n"
           "-help : print this message")
     sys.exit(0)
 
@@ -72,6 +82,7 @@ def main(argv):
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
     rbc, near_f32, field = False, 0, 0
+    stokes_batch, resistance = 0, False
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -121,6 +132,10 @@ def main(argv):
             solver, pc = "gmres", "block_inverse"
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
             i += 1; near_f32 = int(argv[i])
+        elif a == "-stokes_batch":                         # not in the reference: fmmbem_options.stokes_batch_width
+            i += 1; stokes_batch = int(argv[i])
+        elif a == "-resistance":                           # not in the reference: three unit translations as one batch solve
+            resistance = True
         elif a == "-field":                                # not in the reference: the solved layer's velocity off the surface
             i += 1; field = int(argv[i])
         elif a == "-disable_sparse":
@@ -167,7 +182,9 @@ def main(argv):
     print("done")
     setup_time = time.time() - tic
 
-    plan = fb.FMM_plan(kernel(), v, opts, p_max=p, near_f32_max_p=near_f32)
+    plan = fb.FMM_plan(kernel(), v, opts, p_max=p, near_f32_max_p=near_f32, stokes_batch_width=stokes_batch)
+    if stokes_batch:
+        print("batched near field: one pass serves %d vectors" % plan.batch_width())
     if near_f32:
         print("float near field: matvecs at p <= %d stream %.3f GB of float entries" % (near_f32, plan.stats()["near_f32_bytes"] / 1e9))
     # x(panels.size(), charge_type(1.)): Vec<3,double> with ONE argument is the zero vector
@@ -215,6 +232,20 @@ def main(argv):
         direct.close()
         mag = np.linalg.norm(u, axis=1)
         print("field: %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field, float(mag.max()), float(mag.mean())))
+    if resistance:
+        # unit translation e_j on every panel: the right-hand side 4 pi e_j (as b above), the force of the solved traction
+        B = torch.zeros((3, n, 3), dtype=torch.float64, device=dev)
+        for j in range(3):
+            B[j, :, j] = 4 * math.pi
+        X = torch.zeros_like(B)
+        plan.kernel().set_p(p)
+        X, its, _, seconds = fb.gmres_capi_batch(plan, X, B, so, stokes=True)
+        torch.cuda.synchronize()
+        R = (X.cpu().numpy() * area[None, :, None]).sum(axis=1).T          # R[i][j]: force component i of translation e_j
+        print("\nresistance matrix (3 translations in one batch of width %d, %s iterations, %.4es):" % (plan.batch_width(), its, seconds))
+        for row in R:
+            print("\t% .6e % .6e % .6e" % tuple(row))
+        print("resistance deviation from 6 pi mu I: %.5e" % (float(np.abs(R - analytical * np.eye(3)).max()) / analytical))
     return it, res, drag_error, [row[1] for row in log]
 
 

@@ -27,7 +27,7 @@ class Options(C.Structure):
                 ("device", C.c_int32), ("shard_rank", C.c_int32), ("shard_world", C.c_int32),
                 ("quad_k_fine", C.c_int32), ("evaluator", C.c_int32), ("mu", C.c_double),
                 ("shard_upward", C.c_int32), ("l2l_rule", C.c_int32), ("near_stream_fraction", C.c_double), ("n_devices", C.c_int32), ("devices", C.c_int32 * 8),
-                ("near_f32_max_p", C.c_int32)]
+                ("near_f32_max_p", C.c_int32), ("stokes_batch_width", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -109,6 +109,11 @@ SYMBOLS = (
 )
 
 
+# the functions that take fmmbem_options: bound to their _r2 symbols by lib()
+OPTIONS_R2 = ("fmmbem_options_default", "fmmbem_plan_create", "fmmbem_plan_create_targets", "fmmbem_kernel_entries",
+              "fmmbem_ops_create", "fmmbem_direct_create")
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -125,6 +130,10 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
+    # Options above is the second layout of fmmbem_options (128 bytes): the six functions that take it are the _r2 entry points, as
+    # the macros of include/fmmbem.h bind them for C callers; the plain names stay exported for programs built with the first layout
+    for name in OPTIONS_R2:
+        setattr(L, name, getattr(L, name + "_r2"))
     vp, i32, i64p = C.c_void_p, C.c_int, C.POINTER(C.c_int64)
     L.fmmbem_options_default.argtypes = [C.POINTER(Options)]
     L.fmmbem_options_default.restype = None

@@ -71,12 +71,16 @@ struct BatchVecs {                                     // per vector of the pass
   double* yt[kBatchMax];
   double2* M[kBatchMax];
   int nv;                                              // vectors of this pass; the kernels may also run slots nv .. width-1 (scratch)
-  int width;                                           // slots allocated: 2, 4 or 8
+  int width;                                           // slots allocated: 2, 4 or 8 (Stokes: 2, 3 or 4)
 };
 // the pipelined one-unknown SpMV (near_spmv_pipe_kernel) for nv vectors: bit for bit nv calls of launch_near_spmv; plans where
 // launch_near_spmv takes that kernel only (batch_near_ok)
 bool batch_near_ok(const DevicePlan& d);
 hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s);
+// near_spmv_sym3 (Stokes, symmetric blocks) for nv = 2 .. 4 vectors: bit for bit nv calls of launch_near_spmv; the plans it serves
+// at a pass of `width` vectors (fmmbem_options.stokes_batch_width)
+bool batch_near_sym3_ok(const DevicePlan& d, int width);
+hipError_t launch_near_sym3_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s);
 // P2M for nv vectors: the streaming kernel once where launch_p2m streams (one live slot, p >= 8), else launch_p2m per vector
 hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s);
 

@@ -1039,11 +1039,23 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, batch_occ(NV)) void near_spmv_p
 #endif
 constexpr int kSymOcc = FMMBEM_SYM_OCC;               // workgroups per CU
 constexpr int kSymChunk = FMMBEM_SYM_CHUNK;           // source panels of x staged at a time (3 x 8 KiB)
-template <int kRows, int kVecs>
-__global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_kernel(DevicePlan d) {
-  extern __shared__ double xs[];                      // [3][kSymChunk] doubles, then the run descriptors
-  __shared__ double part[kSpmvWaves][kColRows][3];
-  int* run_row0 = reinterpret_cast<int*>(xs + 3 * kSymChunk);
+//
+// ONE loop, sym3_run<kRows, kVecs, NV>, serves two kernels that differ in NV alone, so the order of every sum is one text: chunks
+// of kSymChunk source panels with a later chunk added into y; the colsplit segments and the fixed sum ((p0 + p1) + p2) + p3 of
+// their parts; lane l taking the columns v0 + l, stepping by kVecs * 64; all kRows x kVecs x 3 loads issued before the first FMA;
+// the three nested FMAs per component; wave_sum.
+//   near_spmv_sym3_kernel        NV = 1: d.xt -> d.yt.
+//   near_spmv_sym3_multi_kernel  NV = 2, 3, 4 vectors in one pass over the matrix (fmmbem_options.stokes_batch_width): every
+//                                nontemporal 16-byte load feeds the FMAs of all NV vectors, so every result is bit for bit the single
+//                                kernel's.  24 KiB of x per vector leave 3, 2, 1 workgroups per CU: the loads in flight come from
+//                                kRows x kVecs per wavefront (launch_near_sym3_multi).
+// LDS: xs [NV][3][kSymChunk] doubles (one vector's image is the single kernel's: the lanes read it free of bank conflicts), then
+// the run descriptors; part [NV][kSpmvWaves][kColRows][3].
+template <int kRows, int kVecs, int NV>
+__device__ __forceinline__ void sym3_run(const DevicePlan& d, const NearVecs<NV>& vecs, double* xs,
+                                         double (*part)[kSpmvWaves][kColRows][3]) {
+  constexpr int XV = 3 * kSymChunk;                   // doubles of one vector's x image
+  int* run_row0 = reinterpret_cast<int*>(xs + NV * XV);
   int* run_off = run_row0 + d.max_runs;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   for (int item = blockIdx.x; item < d.sym_nitems; item += gridDim.x) {
@@ -1053,13 +1065,19 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
     const int ncp = d.near_ncols[t];
     const Runs runs = load_runs(d, t, run_row0, run_off);
     const dvec2* blk = reinterpret_cast<const dvec2*>(d.near_sym + d.near_sym_off[t]) + (int64_t)r0 * 3 * ncp;
-    double* yt = d.yt + 3 * (int64_t)(d.leaf_row0[t] + r0);
+    double* yt[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) yt[n] = vecs.yt[n] + 3 * (int64_t)(d.leaf_row0[t] + r0);
     for (int c0 = 0; c0 < ncp; c0 += kSymChunk) {
       const int cw = ncp - c0 < kSymChunk ? ncp - c0 : kSymChunk;
       if (c0) __syncthreads();
       for (int c = threadIdx.x; c < cw; c += blockDim.x) {
-        const double* xp = d.xt + 3 * (int64_t)column_to_row(runs, c0 + c);
-        xs[c] = xp[0]; xs[kSymChunk + c] = xp[1]; xs[2 * kSymChunk + c] = xp[2];
+        const int64_t j = 3 * (int64_t)column_to_row(runs, c0 + c);
+#pragma unroll
+        for (int n = 0; n < NV; ++n) {
+          const double* xp = vecs.xt[n] + j;
+          xs[n * XV + c] = xp[0]; xs[n * XV + kSymChunk + c] = xp[1]; xs[n * XV + 2 * kSymChunk + c] = xp[2];
+        }
       }
       __syncthreads();
       const int seg = colsplit ? ((((cw + kSpmvWaves - 1) / kSpmvWaves) + 3) & ~3) : cw;
@@ -1067,12 +1085,13 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
       const int rstep = colsplit ? 1 : kSpmvWaves;
       for (int r = colsplit ? 0 : wave; r < nrows; r += colsplit ? kRows : kRows * kSpmvWaves) {
         const dvec2* row[kRows];
-        double ax[kRows], ay[kRows], az[kRows];
+        double ax[NV][kRows], ay[NV][kRows], az[NV][kRows];
 #pragma unroll
         for (int i = 0; i < kRows; ++i) {
           const int ri = r + i * rstep;
           row[i] = blk + (int64_t)(ri < nrows ? ri : r) * 3 * ncp + c0;
-          ax[i] = ay[i] = az[i] = 0;
+#pragma unroll
+          for (int n = 0; n < NV; ++n) ax[n][i] = ay[n][i] = az[n][i] = 0;
         }
         for (int c = v0 + lane; c < v1; c += kVecs * kWave) {
           dvec2 v[kRows][kVecs][3];
@@ -1089,28 +1108,36 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
           for (int u = 0; u < kVecs; ++u) {
             const int cc = c + u * kWave;
             if (cc < v1) {
-              const double x0 = xs[cc], x1 = xs[kSymChunk + cc], x2 = xs[2 * kSymChunk + cc];
 #pragma unroll
-              for (int i = 0; i < kRows; ++i) {
-                const dvec2 a = v[i][u][0], b = v[i][u][1], e = v[i][u][2];   // (xx,xy) (xz,yy) (yz,zz)
-                ax[i] = fma(a.x, x0, fma(a.y, x1, fma(b.x, x2, ax[i])));
-                ay[i] = fma(a.y, x0, fma(b.y, x1, fma(e.x, x2, ay[i])));
-                az[i] = fma(b.x, x0, fma(e.x, x1, fma(e.y, x2, az[i])));
+              for (int n = 0; n < NV; ++n) {
+                const double x0 = xs[n * XV + cc], x1 = xs[n * XV + kSymChunk + cc], x2 = xs[n * XV + 2 * kSymChunk + cc];
+#pragma unroll
+                for (int i = 0; i < kRows; ++i) {
+                  const dvec2 a = v[i][u][0], b = v[i][u][1], e = v[i][u][2];   // (xx,xy) (xz,yy) (yz,zz)
+                  ax[n][i] = fma(a.x, x0, fma(a.y, x1, fma(b.x, x2, ax[n][i])));
+                  ay[n][i] = fma(a.y, x0, fma(b.y, x1, fma(e.x, x2, ay[n][i])));
+                  az[n][i] = fma(b.x, x0, fma(e.x, x1, fma(e.y, x2, az[n][i])));
+                }
               }
             }
           }
         }
 #pragma unroll
-        for (int i = 0; i < kRows; ++i) { ax[i] = wave_sum(ax[i]); ay[i] = wave_sum(ay[i]); az[i] = wave_sum(az[i]); }
+        for (int n = 0; n < NV; ++n)
+#pragma unroll
+          for (int i = 0; i < kRows; ++i) { ax[n][i] = wave_sum(ax[n][i]); ay[n][i] = wave_sum(ay[n][i]); az[n][i] = wave_sum(az[n][i]); }
         if (lane == 0) {
 #pragma unroll
           for (int i = 0; i < kRows; ++i) {
             const int ri = r + i * rstep;
             if (ri < nrows) {
-              if (colsplit) { part[wave][ri][0] = ax[i]; part[wave][ri][1] = ay[i]; part[wave][ri][2] = az[i]; }
-              else {
-                double* y = yt + 3 * ri;
-                y[0] = c0 ? y[0] + ax[i] : ax[i]; y[1] = c0 ? y[1] + ay[i] : ay[i]; y[2] = c0 ? y[2] + az[i] : az[i];
+#pragma unroll
+              for (int n = 0; n < NV; ++n) {
+                if (colsplit) { part[n][wave][ri][0] = ax[n][i]; part[n][wave][ri][1] = ay[n][i]; part[n][wave][ri][2] = az[n][i]; }
+                else {
+                  double* y = yt[n] + 3 * ri;
+                  y[0] = c0 ? y[0] + ax[n][i] : ax[n][i]; y[1] = c0 ? y[1] + ay[n][i] : ay[n][i]; y[2] = c0 ? y[2] + az[n][i] : az[n][i];
+                }
               }
             }
           }
@@ -1120,13 +1147,36 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
         __syncthreads();
         if ((int)threadIdx.x < 3 * nrows) {
           const int ri = threadIdx.x / 3, a = threadIdx.x % 3;
-          const double sum = ((part[0][ri][a] + part[1][ri][a]) + part[2][ri][a]) + part[3][ri][a];
-          yt[3 * ri + a] = c0 ? yt[3 * ri + a] + sum : sum;
+#pragma unroll
+          for (int n = 0; n < NV; ++n) {
+            const double sum = ((part[n][0][ri][a] + part[n][1][ri][a]) + part[n][2][ri][a]) + part[n][3][ri][a];
+            yt[n][3 * ri + a] = c0 ? yt[n][3 * ri + a] + sum : sum;
+          }
         }
       }
     }
     __syncthreads();                                  // xs / run descriptors / part are rewritten for the next item
   }
+}
+
+template <int kRows, int kVecs>
+__global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_kernel(DevicePlan d) {
+  extern __shared__ double xs[];                      // [3][kSymChunk] doubles, then the run descriptors
+  __shared__ double part[1][kSpmvWaves][kColRows][3];
+  const NearVecs<1> vecs{{d.xt}, {d.yt}};
+  sym3_run<kRows, kVecs, 1>(d, vecs, xs, part);
+}
+
+constexpr int sym3_multi_occ(int nv) { return nv <= 2 ? 3 : nv == 3 ? 2 : 1; }   // workgroups per CU that 24 KiB of x per vector leave
+
+template <int kRows, int kVecs, int NV>
+__global__ __launch_bounds__(kSpmvWaves * kWave, sym3_multi_occ(NV)) void near_spmv_sym3_multi_kernel(DevicePlan d, BatchVecs bv) {
+  extern __shared__ double xs[];                      // [NV][3][kSymChunk] doubles, then the run descriptors
+  __shared__ double part[NV][kSpmvWaves][kColRows][3];
+  NearVecs<NV> vecs;
+#pragma unroll
+  for (int n = 0; n < NV; ++n) { vecs.xt[n] = bv.xt[n]; vecs.yt[n] = bv.yt[n]; }
+  sym3_run<kRows, kVecs, NV>(d, vecs, xs, part);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2090,6 +2140,44 @@ hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipSt
   else if (nv == 4) BATCH_SHAPES(4) else BATCH_SHAPES(8)
 #undef BATCH_SHAPES
 #undef BATCH_NEAR
+  return hipGetLastError();
+}
+
+// ---- Stokes plans with the symmetric blocks (fmmbem_options.stokes_batch_width): near_spmv_sym3 for 2, 3 or 4 vectors ----
+// dynamic LDS of a pass of `width` vectors: the x images and the run descriptors (the column-split parts, 768 bytes per vector, are
+// static), within the 160 KiB of a CU
+constexpr size_t kSym3MultiLds = 156 * 1024;
+bool batch_near_sym3_ok(const DevicePlan& d, int width) {
+  return !d.near_rec && d.dof == 3 && d.near_sym && d.sym_items && width >= 2 && width <= 4 &&
+         (size_t)width * 3 * kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int) <= kSym3MultiLds;
+}
+
+// One pass over near_sym for b.nv vectors, each y bit for bit launch_near_spmv's; a pass of one vector is launch_near_spmv itself.
+// The kernel is instantiated for every count 2, 3, 4, so a short pass runs the instantiation of its own size and no slot is spare.
+// Shape per NV (panel rows x source-panel vectors in flight per wavefront): 1x4, 1x4, 2x4.  The x images leave 3, 2, 1 workgroups
+// per CU; the alternatives that were measured (1x3, 2x2; 1x6, 2x3; 1x6, 2x6) are in profiles/r13a_stokes_batch_time.txt and
+// DESIGN.md section 8 "Stokes batched near field".
+hipError_t launch_near_sym3_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s) {
+  if (b.nv < 1 || b.nv > b.width || !batch_near_sym3_ok(d, b.width)) return hipErrorInvalidValue;
+  if (b.nv == 1) {
+    DevicePlan d1 = d;
+    d1.xt = b.xt[0]; d1.yt = b.yt[0];
+    return launch_near_spmv(d1, s);
+  }
+  if (d.near_nitems <= 0 || d.sym_nitems <= 0) return hipSuccess;
+  const size_t lds = (size_t)b.nv * 3 * kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
+  const dim3 g(std::min(d.sym_nitems, 256 * sym3_multi_occ(b.nv))), t(kSpmvWaves * kWave);
+#define SYM3_MULTI(R, V, NV)                                                                                                         \
+  {                                                                                                                                  \
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(near_spmv_sym3_multi_kernel<R, V, NV>),        \
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSym3MultiLds);                    \
+    if (attr != hipSuccess) return attr;                                                                                             \
+    hipLaunchKernelGGL((near_spmv_sym3_multi_kernel<R, V, NV>), g, t, lds, s, d, b);                                                 \
+  }
+  if (b.nv == 2) SYM3_MULTI(1, 4, 2)
+  else if (b.nv == 3) SYM3_MULTI(1, 4, 3)
+  else SYM3_MULTI(2, 4, 4)
+#undef SYM3_MULTI
   return hipGetLastError();
 }
 

@@ -1449,18 +1449,21 @@ static int batch_nv() {
   return nv;
 }
 
-// the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch)
+// the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch), and
+// the Stokes plans with the symmetric blocks that ask for it (fmmbem_options.stokes_batch_width)
 int fmmbem_plan::batch_width() const {
-  const bool fast = on_device && !multi && opts.kernel != FMMBEM_KERNEL_STOKES_BEM && opts.sparse_local && !hybrid &&
-                    hp.opt.shard_world <= 1 && !split_upward && !result_slices && batch_near_ok(d) &&
-                    !d.near_f32;                     // float near field: vector by vector, each with the bits of its single execute
-  return !fast ? 1 : bat.width ? bat.width : batch_nv();
+  const bool one = on_device && !multi && opts.sparse_local && !hybrid && hp.opt.shard_world <= 1 && !split_upward && !result_slices &&
+                   !d.near_f32;                      // float near field: vector by vector, each with the bits of its single execute
+  if (!one) return 1;
+  if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM)
+    return !targets && opts.stokes_batch_width >= 2 && batch_near_sym3_ok(d, opts.stokes_batch_width) ? opts.stokes_batch_width : 1;
+  return !batch_near_ok(d) ? 1 : bat.width ? bat.width : batch_nv();
 }
 
 // all or nothing: a failed allocation leaves the plan as it was (FMMBEM_ERR_ALLOC; single executes are unaffected)
 int fmmbem_plan::batch_alloc(hipStream_t s) {
   if (bat.width) return FMMBEM_OK;
-  const int w = batch_nv();
+  const int w = opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? opts.stokes_batch_width : batch_nv();
   const size_t nt = (size_t)hp.n * d.dof, nm = (size_t)hp.nboxes * d.nslots * d.s_max;
   BatchBufs b;
   std::vector<void*> got;
@@ -1496,7 +1499,8 @@ int fmmbem_plan::batch_alloc(hipStream_t s) {
 }
 
 // The fast path: per pass of up to bat.width vectors the gathers, ONE near-field pass and one P2M pass (launch_near_spmv_multi,
-// launch_p2m_multi), then M2M .. L2P and the delivery once per vector, with the launchers of run() on d pointing at that
+// launch_p2m_multi; a Stokes plan: launch_near_sym3_multi, and P2M with the single launcher per vector: there is no batched far
+// field), then M2M .. L2P and the delivery once per vector, with the launchers of run() on d pointing at that
 // vector's buffers.  The same kernels in the same order per vector as run(): the same bits.  host: x and y are host pointers,
 // staged through stage_x / stage_y(_targets) one vector at a time, in stream order.  With stage timing on, each pass records
 // its near-field and P2M passes (fmmbem_plan_stats ms_near, ms_p2m: means per pass).
@@ -1505,8 +1509,9 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
   DEVICE_SCOPE(opts.device);
   TRY(batch_alloc(s));
   const int w = bat.width;
-  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n);
-  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n);
+  const bool stokes = d.dof == 3;                      // never a target plan (batch_width)
+  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n * d.dof);
+  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n * d.dof);
   double* sy = targets ? stage_y_targets : stage_y;
   BatchVecs bv{};
   bv.width = w;
@@ -1535,37 +1540,42 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
       if (targets && zero_target_rows)
         HIP_TRY(hipMemsetAsync(bat.yt[j] + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), s));
     }
-    // stage timing on: a pass is one record of the ring with two stages, its near-field pass (1) and its P2M (3)
+    // stage timing on: a pass is one record of the ring with two stages, its near-field pass (1) and its P2M (3); a Stokes pass
+    // records its near-field pass alone (P2M runs per vector, below)
     hipEvent_t* set = timing ? &ev[(size_t)(ev_count % kRing) * 2 * kStages] : nullptr;
     if (set) HIP_TRY(hipEventRecord(set[2 * 1], s));
-    HIP_TRY(launch_near_spmv_multi(d, bv, s));
-    if (set) { HIP_TRY(hipEventRecord(set[2 * 1 + 1], s)); HIP_TRY(hipEventRecord(set[2 * 3], s)); }
-    if (targets) {                                     // as p2m_targets: once per live slot
-      for (int f = 0; f < 2; ++f) {
-        if (!has_bc[f]) continue;
-        DevicePlan dp = d;
-        dp.bc = bc_all[f];
-        dp.n_act = 1; dp.act[0] = f;
-        if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
-        HIP_TRY(launch_p2m_multi(dp, bv, p, s));
-      }
-    } else HIP_TRY(launch_p2m_multi(d, bv, p, s));
+    if (stokes) HIP_TRY(launch_near_sym3_multi(d, bv, s)); else HIP_TRY(launch_near_spmv_multi(d, bv, s));
+    if (set) HIP_TRY(hipEventRecord(set[2 * 1 + 1], s));
+    if (!stokes) {
+      if (set) HIP_TRY(hipEventRecord(set[2 * 3], s));
+      if (targets) {                                   // as p2m_targets: once per live slot
+        for (int f = 0; f < 2; ++f) {
+          if (!has_bc[f]) continue;
+          DevicePlan dp = d;
+          dp.bc = bc_all[f];
+          dp.n_act = 1; dp.act[0] = f;
+          if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
+          HIP_TRY(launch_p2m_multi(dp, bv, p, s));
+        }
+      } else HIP_TRY(launch_p2m_multi(d, bv, p, s));
+      if (set) HIP_TRY(hipEventRecord(set[2 * 3 + 1], s));
+    }
     if (set) {
-      HIP_TRY(hipEventRecord(set[2 * 3 + 1], s));
-      ev_mask[ev_count % kRing] = (1u << 1) | (1u << 3);
+      ev_mask[ev_count % kRing] = stokes ? (1u << 1) : (1u << 1) | (1u << 3);
       ++ev_count;
     }
     for (int j = 0; j < nv; ++j) {
       double* yj = host ? sy : y + (size_t)(j0 + j) * ldy;
       {
         View view(*this, j);
+        if (stokes) HIP_TRY(launch_p2m_stokes(d, p, s));
         TRY(m2m_pass(p, false, s));
         const bool rot = use_rot(p);
         if (!rot) HIP_TRY(launch_mh_prep(d, p, s));
         if (rot) HIP_TRY(launch_m2l_rot(d, d_dev, p, s));
         else HIP_TRY(launch_m2l(d, d_dev, p, s));
         TRY(l2l_pass(p, s));
-        HIP_TRY(launch_l2p(d, p, d.yt, s));
+        if (stokes) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s)); else HIP_TRY(launch_l2p(d, p, d.yt, s));
         if (targets) {
           HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : yj, s));
           if (d_target_point) {
@@ -1600,6 +1610,7 @@ void fmmbem_options_default(fmmbem_options* o) {
   o->mu = 1e-3;
   o->near_stream_fraction = 1.0;
   o->near_f32_max_p = 0;
+  o->stokes_batch_width = 0;
 }
 
 // ---- plans that share a geometry -----------------------------------------------------------------------------
@@ -1961,6 +1972,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   if (opts->l2l_rule != FMMBEM_L2L_COMPLETE && opts->l2l_rule != FMMBEM_L2L_REFERENCE) return fail(FMMBEM_ERR_INVALID, "unknown l2l_rule");
   if (opts->evaluator < FMMBEM_EVAL_FMM || opts->evaluator > FMMBEM_EVAL_BLOCK_DIAGONAL) return fail(FMMBEM_ERR_INVALID, "unknown evaluator");
   if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
+  if (opts->stokes_batch_width < 0 || opts->stokes_batch_width > 4) return fail(FMMBEM_ERR_INVALID, "stokes_batch_width outside 0..4");
   // The geometry of a live plan, recognised: same options, same panel count, same vertex bytes (two 64-bit hashes) -- only the
   // boundary-condition flags may differ.  The new plan then shares that plan's tree, lists and tables (PlanShared) and builds
   // only what the flags decide.  This is the drivers' second plan (examples/LaplaceBEM.cpp:218-232: the same panels with the
@@ -1994,7 +2006,10 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
           break;
         }
     }
-    if (copy) return fmmbem_plan::like_finish(std::move(copy), bc, out);
+    if (copy) {
+      copy->opts.stokes_batch_width = opts->stokes_batch_width;     // no part of the geometry: the new plan's own
+      return fmmbem_plan::like_finish(std::move(copy), bc, out);
+    }
   }
   std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan);
   if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
@@ -2075,6 +2090,7 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
   if (!target_points || n_targets == 0) return fail(FMMBEM_ERR_INVALID, "no targets");
   if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
+  if (opts->stokes_batch_width < 0 || opts->stokes_batch_width > 4) return fail(FMMBEM_ERR_INVALID, "stokes_batch_width outside 0..4");
   if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: Laplace only (Stokes velocity at points is not implemented)");
   if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "unknown kernel id");
   if (opts->shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: shard_world > 1 is not implemented");
@@ -2900,6 +2916,49 @@ const char* fmmbem_status_string(int status) {
 const char* fmmbem_last_error(void) { return g_last_error.c_str(); }
 int fmmbem_version(void) { return FMMBEM_VERSION; }
 
+}  // extern "C"
+
+// ---- the first layout of fmmbem_options (include/fmmbem.h: 120 bytes, no stokes_batch_width) under the plain names ----
+// Programs compiled against the earlier header call these: the struct they hold ends where stokes_batch_width begins, so nothing
+// here reads or writes past it; the field is taken as 0.
+#undef fmmbem_options_default
+#undef fmmbem_plan_create
+#undef fmmbem_plan_create_targets
+#undef fmmbem_kernel_entries
+#undef fmmbem_ops_create
+#undef fmmbem_direct_create
+static constexpr size_t kOptionsR1 = offsetof(fmmbem_options, stokes_batch_width);
+static_assert(kOptionsR1 == 120 && sizeof(fmmbem_options) == 128, "layouts of fmmbem_options (include/fmmbem.h)");
+struct OptionsR1 {                                     // the caller's 120 bytes widened to today's struct
+  fmmbem_options o;
+  const fmmbem_options* p;
+  explicit OptionsR1(const fmmbem_options* r1) : p(r1 ? &o : nullptr) {
+    std::memset(&o, 0, sizeof(o));
+    if (r1) std::memcpy(&o, r1, kOptionsR1);
+  }
+};
+extern "C" {
+void fmmbem_options_default(fmmbem_options* o) {
+  if (!o) return;
+  fmmbem_options full;
+  fmmbem_options_default_r2(&full);
+  std::memcpy(o, &full, kOptionsR1);
+}
+int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double* vertices, const uint8_t* bc, fmmbem_plan** out) {
+  return fmmbem_plan_create_r2(OptionsR1(opts).p, n_panels, vertices, bc, out);
+}
+int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, const double* vertices, const uint8_t* bc,
+                               size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
+  return fmmbem_plan_create_targets_r2(OptionsR1(opts).p, n_panels, vertices, bc, n_targets, target_points, target_bc, out);
+}
+int fmmbem_kernel_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
+                          const double* source_vertices, double* out) {
+  return fmmbem_kernel_entries_r2(OptionsR1(opts).p, n, target_vertices, target_bc, source_vertices, out);
+}
+int fmmbem_ops_create(const fmmbem_options* opts, fmmbem_ops** out) { return fmmbem_ops_create_r2(OptionsR1(opts).p, out); }
+int fmmbem_direct_create(const fmmbem_options* opts, size_t n_sources, const double* source_vertices, fmmbem_direct** out) {
+  return fmmbem_direct_create_r2(OptionsR1(opts).p, n_sources, source_vertices, out);
+}
 }  // extern "C"
 
 // what the solver of krylov.hip needs to know about a plan; it reaches the matvec through the public entry point

@@ -33,6 +33,9 @@ class FMMOptions:
         # not in the reference: share of the near-field pairs kept as a matrix; < 1: the rest is recomputed every matvec by the
         # same kernel between its streamed items (include/fmmbem.h, fmmbem_options.near_stream_fraction)
         self.near_stream_fraction = 1.0
+        # not in the reference: vectors one near-field pass of a Stokes plan serves in a batch (0, 1: off; 2, 3, 4;
+        # include/fmmbem.h, fmmbem_options.stokes_batch_width)
+        self.stokes_batch_width = 0
 
     def set_mac_theta(self, theta):     # FMMOptions.hpp:50-52
         self.theta = float(theta)
@@ -402,10 +405,15 @@ class FMM_plan:
     near_f32_max_p: not in the reference.  0: off; 1..16: executes at an order p <= this value stream a float copy of the
     assembled near matrix (fmmbem_options.near_f32_max_p); stats() reports near_f32_bytes (0: not active on this plan) and
     last_near_f32.
+
+    stokes_batch_width: not in the reference.  0 or 1: off; 2, 3, 4: on a Stokes plan one pass over the near matrix serves that
+    many vectors of execute_batch / gmres_capi_batch (fmmbem_options.stokes_batch_width), every result the bits of its single
+    execute; batch_width() reports it where it is active.  None (default): opts.stokes_batch_width.
     """
 
     def __init__(self, K, panels, opts=None, bc=None, p_max=None, device=0, shard=(0, 1), host_only=False,
-                 shard_upward=False, devices=None, replicate_upward=False, targets=None, target_bc=None, near_f32_max_p=0):
+                 shard_upward=False, devices=None, replicate_upward=False, targets=None, target_bc=None, near_f32_max_p=0,
+                 stokes_batch_width=None):
         opts = opts if opts is not None else FMMOptions()
         # executor/make_executor.hpp:24-60: lazy_evaluation wins, then local_evaluation, then block_diagonal; the
         # non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones
@@ -431,6 +439,7 @@ class FMM_plan:
         o.l2l_rule = _capi.L2L_REFERENCE if getattr(opts, "reference_l2l", False) else _capi.L2L_COMPLETE
         o.near_stream_fraction = float(getattr(opts, "near_stream_fraction", 1.0))
         o.near_f32_max_p = int(near_f32_max_p)
+        o.stokes_batch_width = int(getattr(opts, "stokes_batch_width", 0) if stokes_batch_width is None else stokes_batch_width)
         o.device = int(device)
         self.device = int(device)
         if devices is not None and len(devices) > 1:

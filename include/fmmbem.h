@@ -22,6 +22,18 @@ extern "C" {
 #endif
 
 #define FMMBEM_VERSION 1
+
+/* fmmbem_options is in its second layout: stokes_batch_width was appended and sizeof grew from 120 to 128 bytes.  The six
+ * functions that take the struct are therefore bound, through the names below, to entry points that know the 128-byte layout;
+ * the library keeps exporting the plain names with the 120-byte layout (the new field taken as 0), so a program compiled against
+ * the earlier header runs on this library unchanged -- fmmbem_options_default never writes past the struct its caller holds.
+ * Callers that look symbols up by name (dlsym, ctypes) and hold the struct below ask for the _r2 names. */
+#define fmmbem_options_default     fmmbem_options_default_r2
+#define fmmbem_plan_create         fmmbem_plan_create_r2
+#define fmmbem_plan_create_targets fmmbem_plan_create_targets_r2
+#define fmmbem_kernel_entries      fmmbem_kernel_entries_r2
+#define fmmbem_ops_create          fmmbem_ops_create_r2
+#define fmmbem_direct_create       fmmbem_direct_create_r2
 #define FMMBEM_PMAX 16          /* expansion orders 1..16 are pre-compiled */
 
 typedef enum {
@@ -126,6 +138,19 @@ typedef struct {
                                * sharded, host-only plans; FMM plans with no M2L pair at all -- every leaf near every other, a few
                                * hundred panels: exact at every order, no truncation error for the rounding to hide under): fmmbem_stats.near_f32_bytes is then 0.  On an active plan
                                * fmmbem_plan_batch_width is 1.  Outside 0..16: FMMBEM_ERR_INVALID.                          */
+  int32_t  stokes_batch_width;/* Multi-vector near field of a Stokes plan.  0 or 1 (default 0): off, a batch runs its vectors one after
+                               * another.  2, 3, 4: one pass over the near matrix serves that many vectors of
+                               * fmmbem_plan_execute_batch(_device) and of the lockstep fmmbem_gmres_batch(_device) -- the matrix is
+                               * two thirds of a Stokes matvec and does not depend on the vector; fmmbem_plan_batch_width returns the
+                               * value.  Every result stays bit for bit that vector's single execute; the far field runs per vector.
+                               * Per slot the plan then keeps x and y in tree order and one multipole set, allocated at the first
+                               * batch call.  Active on Stokes plans (VELOCITY, TRACTION or mixed targets; the FMM, LOCAL and
+                               * BLOCK_DIAGONAL evaluators) with the assembled near field in symmetric blocks, not hybrid, the float
+                               * near field not active, on one device with shard_world = 1; fmmbem_plan_create_like inherits it from
+                               * its base.  Accepted without effect elsewhere (Laplace, hybrid, matrix-free, device-list, sharded,
+                               * host-only plans, plans with the float copy): the width stays what it was.  The field is appended:
+                               * sizeof(fmmbem_options) grows by 8 (the _r2 names above).  Outside 0..4: FMMBEM_ERR_INVALID.
+                               * DESIGN.md section 8 "Stokes batched near field" has the measured times per width.               */
 } fmmbem_options;
 
 /* Statistics of a plan and of its last execute (times in milliseconds, device-side HIP events). */
@@ -142,6 +167,8 @@ typedef struct {
   double  build_host_ms, build_assemble_ms;
   /* per-stage device times: MEAN over the executes recorded since timing was (re)enabled */
   double  ms_total, ms_gather, ms_near, ms_scatter, ms_p2m, ms_m2m, ms_mh, ms_m2l, ms_l2l, ms_l2p;
+  /* (a fast-path pass of fmmbem_plan_execute_batch records ms_near and ms_p2m only -- on a Stokes plan with stokes_batch_width
+   * ms_near only: its P2M runs per vector, unrecorded) */
   int64_t timed_executes;       /* how many executes the means cover                                 */
   int64_t l2l_reference_omitted;/* L2L edges FMMBEM_L2L_REFERENCE leaves out of this tree (0: the rules coincide) */
   int64_t m2l_items, m2l_passes;/* rotation M2L: work items (one wavefront each) and 64-pair passes over them; pairs / (64 passes)
@@ -247,12 +274,15 @@ int fmmbem_plan_near_device(fmmbem_plan *plan, const double *d_x, double *d_y, v
  * streamed matrix counts as not hybrid), one device, shard_world = 1, no result slices; single, create_like and target plans;
  * the FMM, LOCAL and BLOCK_DIAGONAL evaluators: one pass over the near-field matrix serves every vector of the pass (and one
  * pass over the P2M tables, where a single execute streams them: one live slot, p >= 8); M2M, M2L, L2L, L2P, the gather and
- * the delivery run once per vector.  Every other plan (Stokes, hybrid, matrix-free, device lists, shard_world > 1, result
+ * the delivery run once per vector.  Stokes plans created with fmmbem_options.stokes_batch_width = 2, 3 or 4 (see there for the
+ * plans it is active on) take the same path with near_spmv_sym3 for that many vectors; P2M, like the rest of the far field, runs
+ * per vector.  Every other plan (Stokes without that option, hybrid, matrix-free, device lists, shard_world > 1, result
  * slices) runs the k vectors one after another inside the call.
  * Batch buffers (per vector of a pass: x and y in tree order, one multipole set) are allocated on the plan's device at the
  * first batch call and kept until destroy; if that fails the call returns FMMBEM_ERR_ALLOC and single executes still work.
  * Batches never capture or replay graphs, whatever fmmbem_plan_set_graphs says.  With stage timing on, a fast-path pass records
- * its near-field and P2M passes only (fmmbem_plan_stats: ms_near, ms_p2m per pass); a batch run vector by vector records as
+ * its near-field and P2M passes only (fmmbem_plan_stats: ms_near, ms_p2m per pass; a Stokes pass its near-field pass alone:
+ * its P2M runs per vector and is not recorded, ms_p2m then covers no batch work); a batch run vector by vector records as
  * its single executes do.
  * The host form takes HOST pointers and returns when y is written; the device form is asynchronous on `stream`. */
 int fmmbem_plan_execute_batch(fmmbem_plan *plan, int p, int k, const double *x, size_t ldx, double *y, size_t ldy);

@@ -176,6 +176,11 @@ class FMMOptions {
   // moves by at most 2^-24 (|A_near| |x|)_i.  0 (default): off.  Plans where it does not apply take it as 0.
   int near_f32_max_p = 0;
   void set_near_f32_max_p(int p) { near_f32_max_p = p; }
+  // Not in the reference: vectors ONE near-field pass of a Stokes plan serves in a batched execute or a lockstep batch solve
+  // (fmmbem.h stokes_batch_width): 2, 3 or 4; every result the bits of its single execute.  0 (default) or 1: off.  Plans where it
+  // does not apply (Laplace, hybrid, matrix-free, device lists, the float near field) keep their width.
+  int stokes_batch_width = 0;
+  void set_stokes_batch_width(int k) { stokes_batch_width = k; }
   // Not in the reference: the devices ONE plan runs on (fmmbem.h fmmbem_options.n_devices): more than one entry shards the target
   // leaves over them inside the plan; vectors handed to the device entry points live on the first.  Empty: the constructor's
   // `device` argument (or the environment's FMMBEM_DEVICES list, which is how the reference's unmodified drivers get there).
@@ -614,6 +619,7 @@ class PlanAdapter {
     o.l2l_rule = opts_.reference_l2l ? FMMBEM_L2L_REFERENCE : FMMBEM_L2L_COMPLETE;
     o.near_stream_fraction = opts_.near_stream_fraction;
     o.near_f32_max_p = opts_.near_f32_max_p;
+    o.stokes_batch_width = opts_.stokes_batch_width;
     sparse_ = o.sparse_local != 0;
     fmmbem_plan* fresh = nullptr;
     if (has_targets_) {
