@@ -128,3 +128,24 @@ def test_python_surface(fb):
     with pytest.raises(fb.FmmBemError) as e:
         bd.block_inverse_apply(np.zeros(bd.n))
     assert e.value.status == INVALID
+
+
+# ---- the pivoting inputs of tests/test_gpu_block_inverse_pivot.py: their property holds on the oracle's blocks -------------
+
+def test_pivoting_inputs_exchange_rows_on_the_oracles_blocks(oracle_mod):
+    """The GPU tests count exchanges on the blocks they read back from the plan; here the same count on the CPU oracle's
+    entries, so that the inputs are known to pivot wherever the suite runs."""
+    import block_inverse_cases as bic
+    for name, beyond in (("laplace-257-f1", 256), ("stokes-86-vel", 256)):
+        (A,) = bic.oracle_blocks(oracle_mod, name)
+        assert A.shape[0] == (257 if name.startswith("laplace") else 258)
+        inv, piv, bad = bic.gauss_jordan(A)
+        assert bad is None
+        print("%s: %d exchanges, %d with a pivot row >= %d" % (name, bic.exchanges(piv), bic.exchanges(piv, beyond), beyond))
+        assert bic.exchanges(piv) > 0 and bic.exchanges(piv, beyond) > 0
+        assert np.abs(inv @ A - np.eye(len(A))).max() <= 1e-8            # the restatement inverts
+    blocks = bic.oracle_blocks(oracle_mod, "multi-mixed")
+    assert sorted(len(A) for A in blocks) == [1, 1, 31, 270, 297]
+    counts = {len(A): bic.exchanges(bic.gauss_jordan(A)[1]) for A in blocks}
+    print("multi-mixed: exchanges by leaf size", counts)
+    assert counts[297] > 0 and counts[270] > 0                           # both leaves of more than 256 rows
