@@ -59,7 +59,9 @@ unsigned rot_nop_orders_l2l();
 int l2p_group_leaves(int kernel);                      // most leaves an L2P work group may hold (the kernels' LDS slice per wavefront)
 hipError_t launch_m2l_rot_zero(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2l_level(const DevicePlan& d, const ShiftOpDev& op, int p, int first, int count, hipStream_t s);
-hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s);
+// y[i] += the far field of row i (tree order).  With perm: y_out[perm[i]] = y[i] + the far field instead, y left as it is --
+// the result scatter folded into L2P's store (Laplace only; the caller makes sure the L2P groups cover every row)
+hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s, const uint32_t* perm = nullptr, double* y_out = nullptr);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

@@ -923,15 +923,19 @@ __global__ __launch_bounds__(kL2LWaves * kWave) void l2l_kernel(DevicePlan d, Sh
 // every load of a batch in flight before the first LDS write.  (Leaf by leaf in a loop it was three dependent round trips per
 // leaf, 24 per group, most of the kernel's time: 91 -> see DESIGN.md section 4.)  Returns through the references this lane's leaf
 // within the group, that leaf's first lane, the rows of the group; my_* = what lane k found for leaf k.
+// scale: nullptr, or S doubles in LDS, one per stored coefficient index -- every slot of every leaf is staged times scale[i] (the Laplace
+// L2P folds the harmonic's prefactor into the coefficient here, once per leaf and not once per panel; read beside the loads)
 template <class SlotOf>
 __device__ __forceinline__ void l2p_stage_group(const DevicePlan& d, int l0, int nl, int slots, int S, int lane, double2* Lw, SlotOf slot_of,
-                                                int& my_leaf, int& my_box, int& my_nr, int& g, int& first, int& total) {
+                                                int& my_leaf, int& my_box, int& my_nr, int& g, int& first, int& total,
+                                                const double* scale = nullptr) {
   my_leaf = 0; my_box = 0; my_nr = 0;
   if (lane < nl) { my_leaf = d.l2p_leaf[l0 + lane]; my_box = d.leaf_box[my_leaf]; my_nr = d.leaf_nrows[my_leaf]; }
   const int per = slots * S, T = nl * per;
   constexpr int U = 8;
   for (int e0 = 0; e0 < T; e0 += U * kWave) {
     double2 v[U];
+    double sc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int e = e0 + u * kWave + lane;
@@ -939,10 +943,12 @@ __device__ __forceinline__ void l2p_stage_group(const DevicePlan& d, int l0, int
       const int k = ee / per, rem = ee - k * per, a = rem / S, i = rem - a * S;
       const int box = __shfl(my_box, k, kWave);
       v[u] = d.L[((size_t)box * d.nslots + slot_of(a)) * d.s_max + i];
+      sc[u] = scale ? scale[i] : 1.0;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int e = e0 + u * kWave + lane;
+      if (scale) { v[u].x *= sc[u]; v[u].y *= sc[u]; }
       if (e < T) Lw[e] = v[u];
     }
   }
@@ -960,29 +966,53 @@ constexpr int kL2PLeaves = 8, kL2PWaves = 4;
 constexpr int kL2PLeavesStokes = 4;
 constexpr int kL2PUnrollMax = 12;                     // orders with an L2P kernel of their own (the orders of the rotation kernels)
 static bool l2p_generic() { const char* e = std::getenv("FMMBEM_L2P_GENERIC"); return e && std::atoi(e) != 0; }   // A/B runs
+// The Legendre step of the Laplace L2P, carried on q_n = rho^n P_n^m:  q_{n+1} = c1 (rho cos a) q_n - c2 rho^2 q_{n-1},
+// c1 = (2n+1)/(n-m+1), c2 = (n+m)/(n-m+1) (c1 = 2m+1, c2 = 0 on the diagonal n = m): the doubles fill_step_tables forms, and
+// kRecip[k] is the host's 1.0 / k.  With n and m known at compile time they fold to literals; the run-time kernel reads the
+// same doubles from its LDS tables, so the two kernels agree bit for bit.
+__host__ __device__ constexpr double l2p_c1(int n, int m) { return n == m ? (double)(2 * m + 1) : (double)(2 * n + 1) * (1.0 / (double)(n - m + 1)); }
+__host__ __device__ constexpr double l2p_c2(int n, int m) { return n == m ? 0.0 : (double)(n + m) * (1.0 / (double)(n - m + 1)); }
+// L2P's LDS tables.  sG[i], i = n (n + 1) / 2 + m the stored coefficient index: w_m sqrt((n-m)!/(n+m)!), w_0 = 1, w_m = 2 -- what a
+// staged coefficient is multiplied by.  sC1 / sC2 in step order (m-major as fill_step_tables), filled for the run-time order only.
+__device__ inline void fill_l2p_tables(const DevicePlan& d, int P, int S, int lane, bool steps, double* sG, double* sC1, double* sC2) {
+  for (int i = lane; i < S; i += kWave) {
+    const int n = kJK.j[i], m = kJK.k[i];
+    sG[i] = (m == 0 ? 1.0 : 2.0) * d.tabPref[n * n + n + m];
+    if (steps) {
+      const int t = m * P - m * (m - 1) / 2 + (n - m);
+      sC1[t] = n == m ? (double)(2 * m + 1) : (double)(2 * n + 1) * kRecip[n - m + 1];
+      sC2[t] = n == m ? 0.0 : (double)(n + m) * kRecip[n - m + 1];
+    }
+  }
+}
 // store: y[i] = the far field (the near field runs beside this on another stream and the two meet in the delivery kernel)
 // instead of y[i] += (the near field is already there).
-// PT > 0: the order at compile time -- both loops unrolled, every table entry and every coefficient at a constant LDS offset,
-// no loop counters or index arithmetic left (the runtime-order loop spends more instructions on those than on the recurrences:
-// L2P at N = 1M, p = 10: 0.089 ms generic, see DESIGN.md section 4 for the unrolled figure).  PT = 0: any order (p > kL2PUnrollMax).
+// perm: nullptr, or the result leaves here -- yout[perm[i]] = y[i] + far field, y itself untouched: the scatter to the caller's
+// panel order folded into the last store (the plans whose L2P groups cover every row, plan.hip).
+// PT > 0: the order at compile time -- both loops unrolled, the step constants literals and every coefficient at a constant LDS
+// offset, no loop counters or index arithmetic left (the runtime-order loop spends more instructions on those than on the
+// recurrences: see DESIGN.md section 4).  PT = 0: any order (p > kL2PUnrollMax), step constants from LDS.
+// Per (n, m) term seven FP64 operations: the prefactor and the weight of the harmonic are in the staged coefficient (sG), and the
+// recurrence runs on q = rho^n P_n^m.
 template <int PT>
-__global__ __launch_bounds__(kL2PWaves * kWave) __attribute__((amdgpu_waves_per_eu(4))) void l2p_kernel(DevicePlan d, const int Prt, double* __restrict__ y, const int store) {
-  extern __shared__ double2 l2p_lds[];                  // step tables (3 S doubles), then [wave][leaf][active slot][S]
+__global__ __launch_bounds__(kL2PWaves * kWave) __attribute__((amdgpu_waves_per_eu(4))) void l2p_kernel(DevicePlan d, const int Prt, double* __restrict__ y, const int store,
+                                                                                                     const uint32_t* __restrict__ perm, double* __restrict__ yout) {
+  extern __shared__ double2 l2p_lds[];                  // tables (3 S doubles), then [wave][leaf][active slot][S]
   const int P = PT > 0 ? PT : Prt;
   const int S = P * (P + 1) / 2, na = d.n_act;
-  double* sPref = reinterpret_cast<double*>(l2p_lds);
-  double* sC1 = sPref + S;
+  double* sG = reinterpret_cast<double*>(l2p_lds);
+  double* sC1 = sG + S;
   double* sC2 = sC1 + S;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
   double2* Lw = l2p_lds + (3 * S + 1) / 2 + (size_t)wave * kL2PLeaves * na * S;
-  if (wave == 0) fill_step_tables(d, P, lane, sPref, sC1, sC2);
+  if (wave == 0) fill_l2p_tables(d, P, S, lane, PT == 0, sG, sC1, sC2);
   __syncthreads();
   for (int gi = blockIdx.x * nwaves + wave; gi < d.n_l2p_grp; gi += gridDim.x * nwaves) {
     const int l0 = d.l2p_grp[gi], nl = d.l2p_grp[gi + 1] - l0;
     wave_lds_sync();                                    // the previous group's reads are done
     int g, first, total, my_leaf, my_box, my_nr;        // this lane's leaf within the group, its first lane, rows of the group
     const int act0 = d.act[0], act1 = d.act[1];
-    l2p_stage_group(d, l0, nl, na, S, lane, Lw, [&](int a) { return a == 0 ? act0 : act1; }, my_leaf, my_box, my_nr, g, first, total);
+    l2p_stage_group(d, l0, nl, na, S, lane, Lw, [&](int a) { return a == 0 ? act0 : act1; }, my_leaf, my_box, my_nr, g, first, total, sG);
     wave_lds_sync();
     if (nl == 1) { g = 0; first = 0; }                  // single leaf: every lane, chunk by chunk
     const int leaf = __shfl(my_leaf, g < 0 ? 0 : g, kWave), box = __shfl(my_box, g < 0 ? 0 : g, kWave);
@@ -993,27 +1023,30 @@ __global__ __launch_bounds__(kL2PWaves * kWave) __attribute__((amdgpu_waves_per_
       if (g < 0 || r_in_leaf >= nrows) continue;
       const int64_t i = row0 + r_in_leaf;
       const int tb = d.bc[i] ? 1 : 0;
+      const int64_t dst = perm ? (int64_t)perm[i] : i;  // issued here, with the centroid: nothing waits for it but the store
       const double2* Lt = Lw + (size_t)(g * na + (na == 2 ? tb : 0)) * S;
       const Sph s = cart2sph(d.cx[i] - c0, d.cy[i] - c1, d.cz[i] - c2);
+      const double z = s.rho * s.ca, rho2 = s.rho * s.rho;
       double r = 0;
       double pn = 1, rhom = 1, er = 1, ei = 0, fact = 1;
       auto order = [&](int m, int& step, auto unrolled) FMMBEM_INLINE {
-        // unrolled: an offset the compiler cannot see through, tied to the sum so far -- at constant addresses all 4 S LDS reads of
+        // unrolled: an offset the compiler cannot see through, tied to the sum so far -- at constant addresses all LDS reads of
         // a row are otherwise issued at its head (or lifted out of the chunk loop): 512 VGPRs and scratch at p = 10
         int tz = 0;
         if constexpr (decltype(unrolled)::value) asm volatile("" : "+v"(tz), "+v"(r));
-        const double *tPref = sPref + tz, *tC1 = sC1 + tz, *tC2 = sC2 + tz;
         const double2* Lm = Lt + tz;
-        double p = pn, p1 = p, rhon = rhom;
-        const double w = m == 0 ? 1.0 : 2.0;
+        double q = pn * rhom, q1 = q;                       // rho^n P_n^m and its predecessor
         auto degree = [&](int n) FMMBEM_INLINE {
-          const double mag = rhon * p * tPref[step];
-          const double2 Lc = Lm[n * (n + 1) / 2 + m];
-          r += w * (Lc.x * (mag * er) - Lc.y * (mag * ei));        // Re(L * Ynm), Ynm = mag e^{+i m beta}
-          const double pcur = p;
-          p = tC1[step] * s.ca * pcur - tC2[step] * p1;
-          p1 = pcur;
-          rhon *= s.rho;
+          const double2 Lc = Lm[n * (n + 1) / 2 + m];      // the coefficient times w_m pref(n, m)
+          const double u = fma(Lc.x, er, -(Lc.y * ei));    // Re(L' e^{+i m beta})
+          r = fma(u, q, r);
+          double k1, k2;
+          if constexpr (decltype(unrolled)::value) { k1 = l2p_c1(n, m); k2 = l2p_c2(n, m); }
+          else { k1 = sC1[step]; k2 = sC2[step]; }
+          const double zq = z * q;
+          const double qn = n == m ? k1 * zq : fma(k1, zq, -(k2 * (rho2 * q1)));   // the diagonal: k2 = 0
+          q1 = q;
+          q = qn;
           ++step;
         };
         if constexpr (decltype(unrolled)::value) {
@@ -1037,7 +1070,8 @@ __global__ __launch_bounds__(kL2PWaves * kWave) __attribute__((amdgpu_waves_per_
 #pragma nounroll
         for (int m = 0; m < P; ++m) order(m, step, std::false_type{});
       }
-      y[i] = (store ? 0.0 : y[i]) + (tb ? -r : r);
+      const double v = (store ? 0.0 : y[i]) + (tb ? -r : r);
+      if (perm) yout[dst] = v; else y[i] = v;
     }
   }
 }
@@ -1371,11 +1405,11 @@ hipError_t launch_l2l_level(const DevicePlan& d, const ShiftOpDev& op, int p, in
 
 int l2p_group_leaves(int kernel) { return kernel == 1 ? kL2PLeavesStokes : kL2PLeaves; }   // 1 = FMMBEM_KERNEL_STOKES_BEM
 
-hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s) {
+hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s, const uint32_t* perm, double* y_out) {
   constexpr bool store = false;                         // the kernels can also overwrite y (a far field on its own); no caller does
   if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
   if (d.n_l2p <= 0) return hipSuccess;
-  if (p < 1 || p > kPmaxDev) return hipErrorInvalidValue;
+  if (p < 1 || p > kPmaxDev || (perm && !y_out)) return hipErrorInvalidValue;
   const int S = p * (p + 1) / 2;
   const size_t per_wave = sizeof(double2) * (size_t)kL2PLeaves * d.n_act * S;          // 7 KB at p = 10, 35 KB at p = 16 with both slots
   int nw = (int)((48 * 1024) / per_wave);
@@ -1383,11 +1417,11 @@ hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s) {
   const int nblk = (d.n_l2p_grp + nw - 1) / nw;
   const size_t lds = sizeof(double2) * (size_t)((3 * S + 1) / 2) + nw * per_wave;
   const dim3 grid(nblk < 256 * 8 ? nblk : 256 * 8), block(nw * kWave);
-#define L2P_CASE(PP) case PP: hipLaunchKernelGGL(l2p_kernel<PP>, grid, block, lds, s, d, p, y, store ? 1 : 0); break;
+#define L2P_CASE(PP) case PP: hipLaunchKernelGGL(l2p_kernel<PP>, grid, block, lds, s, d, p, y, store ? 1 : 0, perm, y_out); break;
   switch (p <= kL2PUnrollMax && !l2p_generic() ? p : 0) {
     L2P_CASE(1) L2P_CASE(2) L2P_CASE(3) L2P_CASE(4) L2P_CASE(5) L2P_CASE(6) L2P_CASE(7) L2P_CASE(8)
     L2P_CASE(9) L2P_CASE(10) L2P_CASE(11) L2P_CASE(12)
-    default: hipLaunchKernelGGL(l2p_kernel<0>, grid, block, lds, s, d, p, y, store ? 1 : 0);
+    default: hipLaunchKernelGGL(l2p_kernel<0>, grid, block, lds, s, d, p, y, store ? 1 : 0, perm, y_out);
   }
 #undef L2P_CASE
   return hipGetLastError();

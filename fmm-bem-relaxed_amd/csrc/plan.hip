@@ -221,6 +221,15 @@ struct fmmbem_plan {
   unsigned pending_mask = 0;                                   // stages recorded by the upward half of a split execute
   bool pending_near = false;                                   // split execute: the near field already ran (fmmbem_plan_near_split_device)
   bool result_slices = false;                                  // execute delivers the owned rows in tree order (fmmbem_plan_set_result_slices)
+  // L2P's last store delivers the result, y[perm[i]] = y_tree[i] + far field, and no scatter kernel runs: a Laplace plan on its own
+  // panels, one shard, whose L2P groups cover every row (decided once, to_device).  FMMBEM_L2P_SCATTER=0 keeps the separate kernel
+  // (read per execute, for A/B runs).  The same single rounded add either way: the same bits.
+  bool l2p_scatter = false;
+  bool l2p_delivers(bool near_only, int phase) const {
+    if (!l2p_scatter || result_slices || near_only || phase != 0) return false;
+    const char* e = std::getenv("FMMBEM_L2P_SCATTER");
+    return !(e && std::atoi(e) == 0);
+  }
   int64_t* d_cut = nullptr;                                    // tree-order row cuts of all shards, on the device
   std::vector<ShiftOpDev> up_ops, down_ops;                    // M2M / L2L operators, index p - 1
   int64_t near_bytes = 0;
@@ -759,6 +768,9 @@ int fmmbem_plan::to_device(int part) {
     grp.push_back((int)l2p_leaf.size());
     d.n_l2p_grp = l2p_leaf.empty() ? 0 : (int)grp.size() - 1;
     TRY(upload(grp, &d.l2p_grp));
+    int64_t covered = 0;                               // the L2P leaves are distinct leaves: all rows are theirs when the counts agree
+    for (int lf : l2p_leaf) covered += hp.box_body_end[hp.leaf_box[lf]] - hp.box_body_begin[hp.leaf_box[lf]];
+    l2p_scatter = d.kernel == FMMBEM_KERNEL_LAPLACE_BEM && !targets && hp.opt.shard_world <= 1 && d.n_l2p > 0 && covered == (int64_t)hp.n;
   }
   TRY(upload(hp.m2m_parents, &d.m2m_parent)); TRY(upload(hp.l2l_children, &d.l2l_child));
   TRY(upload(hp.box_child_begin, &d.box_child_begin)); TRY(upload(hp.box_child_end, &d.box_child_end));
@@ -1369,9 +1381,11 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   // the result leaves the plan once, at the very end: the owned rows of y_tree (near + far field) scattered to the caller's
   // panel order (zeros elsewhere when the plan is a shard), or -- result_slices -- copied as they are, tree order, to the
   // head of d_y, for the caller's all-gather (fmmbem_plan_assemble_slices_device puts the gathered slices in panel order)
+  const bool fold = l2p_delivers(near_only, phase);  // L2P stores into d_y: the scatter stage then brackets nothing
   auto deliver = [&](hipStream_t ns) -> int {
     HIP_TRY(begin(2, ns));
-    if (result_slices) {
+    if (fold) {                                        // L2P has stored the result at y[perm[i]]
+    } else if (result_slices) {
       HIP_TRY(hipMemcpyAsync(d_y, d.yt + d.row_begin * d.dof, sizeof(double) * (size_t)(d.row_end - d.row_begin) * d.dof,
                              hipMemcpyDeviceToDevice, ns));
     } else if (targets) {                              // the target rows -> distinct points -> the targets as given
@@ -1396,7 +1410,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   }
   const bool near_here = !(phase == 2 && pending_near);
   pending_near = false;
-  TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0), xbuf, [&](hipStream_t s) -> int {
+  TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0) + (fold ? 16 : 0), xbuf, [&](hipStream_t s) -> int {
   if (near_here) TRY(near_field(s));
   if (!near_only) {
     if (phase == 0) {
@@ -1425,11 +1439,13 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     HIP_TRY(end(7, s));
     HIP_TRY(begin(8, s));
     if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s));
-    else HIP_TRY(launch_l2p(d, p, d.yt, s));
+    else if (!fold) HIP_TRY(launch_l2p(d, p, d.yt, s));
+    else if (!graph_ok) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, d_y));
     HIP_TRY(end(8, s));
   }
   return FMMBEM_OK;
   }));
+  if (fold && graph_ok) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, d_y));   // takes the caller's pointer: after the graph, as the scatter
   TRY(deliver(s));
   last_p = p;
   last_near_f32 = near_f32 ? 1 : 0;
@@ -1575,8 +1591,12 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
         if (rot) HIP_TRY(launch_m2l_rot(d, d_dev, p, s));
         else HIP_TRY(launch_m2l(d, d_dev, p, s));
         TRY(l2l_pass(p, s));
-        if (stokes) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s)); else HIP_TRY(launch_l2p(d, p, d.yt, s));
-        if (targets) {
+        const bool fold = l2p_delivers(false, 0);
+        if (stokes) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s));
+        else if (fold) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, yj));
+        else HIP_TRY(launch_l2p(d, p, d.yt, s));
+        if (fold) {                                    // delivered by L2P
+        } else if (targets) {
           HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : yj, s));
           if (d_target_point) {
             const int64_t nt = hp.n_targets;

@@ -168,7 +168,8 @@ typedef struct {
   /* per-stage device times: MEAN over the executes recorded since timing was (re)enabled */
   double  ms_total, ms_gather, ms_near, ms_scatter, ms_p2m, ms_m2m, ms_mh, ms_m2l, ms_l2l, ms_l2p;
   /* (a fast-path pass of fmmbem_plan_execute_batch records ms_near and ms_p2m only -- on a Stokes plan with stokes_batch_width
-   * ms_near only: its P2M runs per vector, unrecorded) */
+   * ms_near only: its P2M runs per vector, unrecorded; where L2P's last store delivers the result -- a Laplace plan on its own
+   * panels, one shard, every row under an L2P leaf -- ms_scatter brackets no kernel and ms_l2p includes the delivery) */
   int64_t timed_executes;       /* how many executes the means cover                                 */
   int64_t l2l_reference_omitted;/* L2L edges FMMBEM_L2L_REFERENCE leaves out of this tree (0: the rules coincide) */
   int64_t m2l_items, m2l_passes;/* rotation M2L: work items (one wavefront each) and 64-pair passes over them; pairs / (64 passes)
