@@ -145,45 +145,17 @@ static std::shared_future<std::shared_ptr<const OrderTables>> order_tables() {
   return fut;
 }
 
-// What a plan holds that depends on the GEOMETRY and the options only -- the octree, the permutation, every pair list, the work
-// items and run descriptors, the panels' points, the operator tables -- on the host and in HBM.  Plans of the same panels that
-// differ in the boundary-condition flags alone (the drivers' right-hand-side plan beside the operator, examples/LaplaceBEM.cpp:
-// 209-232, StokesBEM.cpp:266-270) share ONE of these through a reference count (fmmbem_plan_create_like, and fmmbem_plan_create
-// itself when it recognises the geometry of a live plan); freed with the last plan that points to it.
-struct PlanShared {
-  HostPlan hp;
-  std::vector<void*> allocs;
-  int device = 0;
-  bool on_device = false;
-  uint64_t fingerprint[2] = {0, 0};                            // of the vertex bytes (original order), 0 0: not taken
-  ~PlanShared() {
-    if (!on_device) return;
-    DeviceGuard guard(device);
-    for (void* p : allocs) (void)hipFree(p);
-  }
-};
+// (first, items, pairs) of one level launch of the rotation kernels (kernels_m2l_rot.hip with FMMBEM_ROT_OP = 1, 2)
+struct ShiftRot { int item_first = 0, n_items = 0, pairs = 0, level_boxes = 0, pair_first = 0, unit_first = 0, n_units = 0; };   // level_boxes: boxes of the child level in the WHOLE tree; units: parents (M2M) / pairs (L2L) of the one-pair-per-wavefront kernel
 
-struct fmmbem_plan {
-  fmmbem_options opts;
-  std::shared_ptr<PlanShared> shared;
-  HostPlan& hp;                                                // = shared->hp
-  DevicePlan d;
-  bool on_device = false;
-  bool has_bc[2] = {false, false};                             // boundary-condition flags present among THIS plan's panels
-  std::vector<void*> allocs;                                   // what this plan alone owns: everything that depends on the flags
-  std::vector<void*>* alloc_list = nullptr;                    // where upload() / alloc() record: shared->allocs or allocs
-  int64_t near_total_doubles = 0, sym_total_doubles = 0;       // sizes of the stored near blocks (allocated per plan)
-  fmmbem_plan() : shared(std::make_shared<PlanShared>()), hp(shared->hp) { alloc_list = &shared->allocs; }
-  explicit fmmbem_plan(std::shared_ptr<PlanShared> sh) : shared(std::move(sh)), hp(shared->hp) { alloc_list = &allocs; }   // the handle of a multi-device plan
-  // A plan over SEVERAL devices of one process (fmmbem_options.n_devices > 1): this handle then owns one shard plan per device and
-  // does the copies between them itself (MultiDevice, further down); everything else in this struct belongs to single-device plans
-  std::shared_ptr<struct MultiDevice> multi;
-  fmmbem_plan(const fmmbem_plan&) = default;                   // used by like(): shares `shared`; like() then replaces what must not be shared
+// The device side of what depends on the GEOMETRY and the options only: written once by geometry creation (to_device_near,
+// to_device_far, and the options in fmmbem_plan_create*), never changed afterwards.  A plan reads it through a const reference.
+struct PlanGeometry {
+  fmmbem_options opts{};                                       // as given to the creation: what same_geometry_options compares
+  DevicePlan gd;                                               // the geometry's fields of a plan's DevicePlan (gd.n: the panel count)
   std::vector<std::pair<int, int>> m2m_launch, l2l_launch;     // (first, count) per level
   std::vector<std::pair<int, int>> m2m_shared_launch;          // sharded upward pass: parents spanning shards
-  // the same launches for the rotation kernels (kernels_m2l_rot.hip with FMMBEM_ROT_OP = 1, 2): (first item, items, pairs)
-  struct ShiftRot { int item_first = 0, n_items = 0, pairs = 0, level_boxes = 0, pair_first = 0, unit_first = 0, n_units = 0; };   // level_boxes: boxes of the child level in the WHOLE tree; units: parents (M2M) / pairs (L2L) of the one-pair-per-wavefront kernel
-  std::vector<ShiftRot> m2m_rot, m2m_shared_rot, l2l_rot;
+  std::vector<ShiftRot> m2m_rot, m2m_shared_rot, l2l_rot;      // the same launches for the rotation kernels
   const int *up_rsrc = nullptr, *up_rcls = nullptr, *up_rtgt = nullptr, *up_ritem = nullptr;
   const int *dn_rsrc = nullptr, *dn_rcls = nullptr, *dn_rtgt = nullptr, *dn_ritem = nullptr;
   // one pair per WAVEFRONT (kernels_shift.hip, shift_lanes.hpp): the same bits as the one-pair-per-lane kernels, ~5 us for a
@@ -206,6 +178,88 @@ struct fmmbem_plan {
   int shift_stream_off[12] = {};
   int shift_rot_min = 2048;                                    // boxes on a tree level from which the rotation kernels take it
   bool shift_rot = true;
+  bool split_upward = false;                                   // P2M/M2M sharded by owner, multipoles all-gathered by the caller
+  // L2P's last store delivers the result, y[perm[i]] = y_tree[i] + far field, and no scatter kernel runs: a Laplace plan on its own
+  // panels, one shard, whose L2P groups cover every row (decided once, to_device_far).  FMMBEM_L2P_SCATTER=0 keeps the separate
+  // kernel (read per execute, for A/B runs).  The same single rounded add either way: the same bits.
+  bool l2p_scatter = false;
+  std::vector<ShiftOpDev> up_ops, down_ops;                    // M2M / L2L operators, index p - 1
+  // sizes of the stored near blocks (allocated per plan, to_device_bc_begin)
+  int64_t near_total_doubles = 0, sym_total_doubles = 0;
+  int64_t near_bytes = 0;
+  // hybrid near field (fmmbem_options.near_stream_fraction < 1): which leaves keep no matrix; host copies of the block offsets
+  bool hybrid = false;
+  std::vector<uint8_t> near_rec_host;                          // [leaf] 1 = recomputed
+  std::vector<int64_t> near_off_host, sym_off_host;            // [leaf] offsets of the stored blocks (introspection)
+  int64_t near_recomputed_pairs = 0;
+  // float near field (fmmbem_options.near_f32_max_p): floats of the copy (0: not active on this geometry; the copy itself is
+  // allocated and filled per plan in to_device_bc_begin)
+  int64_t near_f32_floats = 0;
+  int64_t n_classes = 0;
+  // which M2L an execute at order p takes: the rotation kernel for the orders it is instantiated for (p <= 12), the double-sum
+  // kernels above; FMMBEM_M2L_ROT=0: the double sum at every order (A/B runs, tools/m2l_ab.py)
+  int rot_max = kRotPmax;
+  bool use_rot(int p) const { return p <= rot_max && m2l_rot_supported(p); }
+};
+
+// What a plan holds that depends on the GEOMETRY and the options only -- the octree, the permutation, every pair list, the work
+// items and run descriptors, the panels' points, the operator tables, the launch lists -- on the host and in HBM.  Plans of the
+// same panels that differ in the boundary-condition flags alone (the drivers' right-hand-side plan beside the operator,
+// examples/LaplaceBEM.cpp:209-232, StokesBEM.cpp:266-270) share ONE of these through a reference count (fmmbem_plan_create_like,
+// and fmmbem_plan_create itself when it recognises a geometry that is still alive); freed with the last plan that points to it.
+struct PlanShared {
+  HostPlan hp;
+  PlanGeometry geo;
+  std::vector<void*> allocs;
+  int device = 0;
+  bool on_device = false;
+  uint64_t fingerprint[2] = {0, 0};                            // of the vertex bytes (original order), 0 0: not taken
+  ~PlanShared() {
+    if (!on_device) return;
+    DeviceGuard guard(device);
+    for (void* p : allocs) (void)hipFree(p);
+  }
+};
+
+// The flag side of a plan's DevicePlan: what to_device_bc_begin / to_device_bc_end / build_side_lists decide and allocate, with
+// the types of the DevicePlan fields of the same names.  compose_d() is the only place a plan's d is put together.
+struct FlagFields {
+  const uint8_t* bc = nullptr;
+  int n_act = 0, nslots = 2;
+  int act[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int stokes_velocity_targets = 1, stokes_traction_targets = 0;
+  double *near_val = nullptr, *near_sym = nullptr;
+  float* near_f32 = nullptr;
+  double *ys = nullptr, *xt4 = nullptr;
+  double2 *M = nullptr, *L = nullptr, *Mh = nullptr;
+  double *xt = nullptr, *yt = nullptr;
+  const double2 *p2m_tab = nullptr, *p2m_tab_g = nullptr;
+  int64_t p2m_tab_row0 = 0;
+  const int64_t* side_ptr = nullptr;
+  const int* side_col = nullptr;
+  const double* side_val = nullptr;
+  const int4* side_items = nullptr;  int side_nitems = 0;
+};
+
+struct fmmbem_plan {
+  fmmbem_options opts{};
+  const std::shared_ptr<PlanShared> shared;
+  HostPlan& hp;                                                // = shared->hp
+  const PlanGeometry& g;                                       // = shared->geo
+  FlagFields fd;
+  DevicePlan d;                                                // = g.gd + fd (compose_d)
+  const DevicePlan* d_dev = nullptr;                           // copy of d in device memory
+  bool on_device = false;
+  bool has_bc[2] = {false, false};                             // boundary-condition flags present among THIS plan's panels
+  std::vector<void*> allocs;                                   // what this plan alone owns: everything that depends on the flags
+  std::vector<void*>* alloc_list = &allocs;                    // where upload() / alloc() record: shared->allocs (geometry creation) or allocs
+  // every plan is built on a shared block: a new one (fmmbem_plan_create*), a live one (like()), a shard's (the handle of a
+  // multi-device plan).  Never copied: what a plan owns has one owner.
+  explicit fmmbem_plan(std::shared_ptr<PlanShared> sh) : shared(std::move(sh)), hp(shared->hp), g(shared->geo) {}
+  fmmbem_plan(const fmmbem_plan&) = delete;
+  // A plan over SEVERAL devices of one process (fmmbem_options.n_devices > 1): this handle then owns one shard plan per device and
+  // does the copies between them itself (MultiDevice, further down); everything else in this struct belongs to single-device plans
+  std::shared_ptr<struct MultiDevice> multi;
   // hipGraphs of the launch chain between the gather and the delivery of a matvec (those two take the caller's pointers),
   // one per (region of the execute, order p, exchange buffer): captured on own_stream the SECOND time a region runs at an
   // order (the first run goes out launch by launch, so that every one-time initialisation inside the launchers has happened),
@@ -214,38 +268,24 @@ struct fmmbem_plan {
   struct GraphEntry { int region, p; const void* buf; int runs; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;
   bool use_graphs = false;
-  int m2m_pass(int p, bool shared, hipStream_t s);
-  int l2l_pass(int p, hipStream_t s);
-  const DevicePlan* d_dev = nullptr;                            // copy of d in device memory
-  bool split_upward = false;                                   // P2M/M2M sharded by owner, multipoles all-gathered by the caller
+  // the launchers of one stage on the DevicePlan given (the plan's d; a batch: vector j's view of it)
+  int m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const;
+  int l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const;
+  template <class Launch> int p2m_targets(const DevicePlan& dv, Launch&& launch) const;
+  int deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream_t s) const;
   unsigned pending_mask = 0;                                   // stages recorded by the upward half of a split execute
   bool pending_near = false;                                   // split execute: the near field already ran (fmmbem_plan_near_split_device)
   bool result_slices = false;                                  // execute delivers the owned rows in tree order (fmmbem_plan_set_result_slices)
-  // L2P's last store delivers the result, y[perm[i]] = y_tree[i] + far field, and no scatter kernel runs: a Laplace plan on its own
-  // panels, one shard, whose L2P groups cover every row (decided once, to_device).  FMMBEM_L2P_SCATTER=0 keeps the separate kernel
-  // (read per execute, for A/B runs).  The same single rounded add either way: the same bits.
-  bool l2p_scatter = false;
-  bool l2p_delivers(bool near_only, int phase) const {
-    if (!l2p_scatter || result_slices || near_only || phase != 0) return false;
+  bool l2p_delivers(bool near_only, int phase) const {         // (PlanGeometry::l2p_scatter)
+    if (!g.l2p_scatter || result_slices || near_only || phase != 0) return false;
     const char* e = std::getenv("FMMBEM_L2P_SCATTER");
     return !(e && std::atoi(e) == 0);
   }
   int64_t* d_cut = nullptr;                                    // tree-order row cuts of all shards, on the device
-  std::vector<ShiftOpDev> up_ops, down_ops;                    // M2M / L2L operators, index p - 1
-  int64_t near_bytes = 0;
   int64_t near_side_entries = 0;                               // matrix-free plans: listed near-regime pairs (12 bytes each)
-  // hybrid near field (fmmbem_options.near_stream_fraction < 1): which leaves keep no matrix; host copies of the block offsets
-  bool hybrid = false;
-  std::vector<uint8_t> near_rec_host;                          // [leaf] 1 = recomputed
-  std::vector<int64_t> near_off_host, sym_off_host;            // [leaf] offsets of the stored blocks (introspection)
-  int64_t near_recomputed_pairs = 0;
-  // float near field (fmmbem_options.near_f32_max_p): floats of the copy (0: not active on this plan; decided with the geometry,
-  // allocated and filled per plan in to_device_bc_begin) and what the last execute streamed
-  int64_t near_f32_floats = 0;
-  int last_near_f32 = 0;
+  int last_near_f32 = 0;                                       // float near field: what the last execute streamed
   HybridStreams hyb;                                           // the recompute kernel and the listed entries run beside the streaming one
   int build_side_lists();
-  int64_t n_classes = 0;
   double build_host_ms = 0, build_assemble_ms = 0;
   // execute state
   int timing = 0;                                              // 0 off, 1 events around every stage, 2 around the near-field kernel only
@@ -282,7 +322,6 @@ struct fmmbem_plan {
   const uint32_t* d_target_point = nullptr;                    // given target -> distinct point (only when some coincide)
   double* y_points = nullptr;                                  // the result per distinct point (only when some coincide)
   double* stage_y_targets = nullptr;                           // device staging of y for host-pointer execute
-  int p2m_targets(int p, hipStream_t s);
 
   template <class T, class A>
   int upload(const std::vector<T, A>& v, const T** out) {
@@ -305,20 +344,20 @@ struct fmmbem_plan {
     *out = static_cast<T*>(p);
     return FMMBEM_OK;
   }
-  // which M2L an execute at order p takes: the rotation kernel for the orders it is instantiated for (p <= 12), the double-sum
-  // kernels above; FMMBEM_M2L_ROT=0: the double sum at every order (A/B runs, tools/m2l_ab.py)
-  int rot_max = kRotPmax;
-  bool use_rot(int p) const { return p <= rot_max && m2l_rot_supported(p); }
-  const double* create_vertices = nullptr;                   // fmmbem_plan_create: the caller's vertices while to_device runs (panel set-up on the device)
-  // part 0: everything.  part 1: the near field's share -- panels, leaves, near lists, the assembly LAUNCHED -- as soon as the
-  // host plan holds them (HostOptions::after_near_lists); part 2: the rest, when the host plan is complete
-  int to_device(int part = 0);                               // the geometry's share (-> shared), then to_device_bc
+  const double* create_vertices = nullptr;                   // fmmbem_plan_create: the caller's vertices while to_device_near runs (panel set-up on the device)
+  // Geometry creation, the only writers of a PlanGeometry (-> shared).  to_device_near: the near field's share -- panels, leaves,
+  // near lists, and the flag side's assembly LAUNCHED (to_device_bc_begin) -- as soon as the host plan holds them
+  // (HostOptions::after_near_lists); to_device_far: the rest, when the host plan is complete, then to_device_bc_end
+  int to_device_near(PlanGeometry& g);
+  int to_device_far(PlanGeometry& g);
+  int open_device();                                         // this plan's stream and event ring
+  // what depends on the boundary-condition flags (-> this plan)
+  void compose_d();
   int to_device_bc(const uint8_t* bc_tree);
   int to_device_bc_begin(const uint8_t* bc_tree);
   int to_device_bc_end();
-  hipEvent_t asm_ev[2] = {nullptr, nullptr};     // what depends on the boundary-condition flags (-> this plan)
-  static int like(const fmmbem_plan& base, const uint8_t* bc, fmmbem_plan** out);
-  static int like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc, fmmbem_plan** out);
+  hipEvent_t asm_ev[2] = {nullptr, nullptr};                 // around the assembly, between to_device_bc_begin and _end
+  static int like(std::shared_ptr<PlanShared> sh, const fmmbem_options& o, const uint8_t* bc, fmmbem_plan** out);
   // phase 0: whole matvec; 1: upward half (gather, P2M, M2M of owned boxes, pack -> xbuf); 2: the rest (xbuf = gathered)
   int run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, int phase = 0, double* xbuf = nullptr);
   // Batched execute (fmmbem_plan_execute_batch).  Per vector of a pass: tree-order x and y, one multipole set, and a copy of d
@@ -332,6 +371,7 @@ struct fmmbem_plan {
     DevicePlan* dev[kBatchMax] = {};
   };
   BatchBufs bat;
+  DevicePlan batch_view(const BatchBufs& b, int j) const { DevicePlan dj = d; dj.xt = b.xt[j]; dj.yt = b.yt[j]; dj.M = b.M[j]; return dj; }   // d on vector j's buffers
   int batch_width() const;                                     // > 1: the fast path (one near-field pass for several vectors)
   int batch_alloc(hipStream_t s);
   int run_batch(int p, int k, const double* x, size_t ldx, double* y, size_t ldy, hipStream_t s, bool host);
@@ -341,8 +381,9 @@ struct fmmbem_plan {
       DeviceGuard guard(opts.device);
       block_inverse_free();
       for (void* p : allocs) (void)hipFree(p);
-      for (auto& e : ev) (void)hipEventDestroy(e);
-      for (auto& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+      for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+      for (hipEvent_t e : asm_ev) if (e) (void)hipEventDestroy(e);      // a creation that failed between to_device_bc_begin and _end
+      for (auto& ge : graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
       if (own_stream) (void)hipStreamDestroy(own_stream);
       if (hyb.recompute) (void)hipStreamDestroy(hyb.recompute);
       for (hipEvent_t e : {hyb.fork, hyb.join_recompute}) if (e) (void)hipEventDestroy(e);
@@ -383,33 +424,43 @@ __global__ void expand_targets_kernel(const uint32_t* __restrict__ point, const 
   if (k < n) y[k] = yp[point[k]];
 }
 
-int fmmbem_plan::to_device(int part) {
+// phase times of a plan build on stderr (FMMBEM_BUILD_TRACE: tuning aid)
+struct BuildTrace {
+  const bool on = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
+  double t_last = now_ms();
+  void operator()(const char* what) {
+    if (!on) return;
+    (void)hipDeviceSynchronize();
+    const double now = now_ms();
+    std::fprintf(stderr, "to_device %-28s %8.2f ms\n", what, now - t_last);
+    t_last = now;
+  }
+};
+
+int fmmbem_plan::open_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
   if (opts.device < 0 || opts.device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
   DEVICE_SCOPE(opts.device);
-  if (part != 2) {
-    on_device = true;
-    shared->on_device = true;                          // from here on a creation that fails (an allocation, say the float near
-    shared->device = opts.device;                      // field's copy) frees the geometry's uploads with the plan: nothing stays behind
-    HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
-    ev.assign((size_t)kRing * 2 * kStages, nullptr);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-  }
+  on_device = true;
+  HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+  ev.assign((size_t)kRing * 2 * kStages, nullptr);
+  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  if (const char* ge = getenv("FMMBEM_GRAPH")) use_graphs = atoi(ge) != 0;
+  return FMMBEM_OK;
+}
 
-  const bool trace = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;     // phase times on stderr (tuning aid)
-  double t_last = now_ms();
-  auto mark = [&](const char* what) {
-    if (!trace) return;
-    (void)hipDeviceSynchronize();
-    const double now = now_ms();
-    std::fprintf(stderr, "to_device %-28s %8.2f ms\n", what, now - t_last);
-    t_last = now;
-  };
+int fmmbem_plan::to_device_near(PlanGeometry& g) {
+  TRY(open_device());
+  DEVICE_SCOPE(opts.device);
+  shared->on_device = true;                            // from here on a creation that fails (an allocation, say the float near
+  shared->device = opts.device;                        // field's copy) frees the geometry's uploads with the plan: nothing stays behind
+  alloc_list = &shared->allocs;
+  BuildTrace mark;
   const HarmonicTables T;
   const int nl = hp.nleaves(), nb = hp.nboxes, pm = hp.opt.p_max;
-  if (part != 2) {                                     // ======== the near field's share ========
+  DevicePlan& d = g.gd;                                // the geometry's fields of the plan's d; compose_d adds the flag side
   mark("streams, events, tables");
   d = DevicePlan{};
   d.n = hp.n; d.nq = hp.rule.n; d.nboxes = nb; d.nleaves = nl;
@@ -509,8 +560,8 @@ int fmmbem_plan::to_device(int part) {
     });
     for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) max_runs_owned = std::max(max_runs_owned, nruns_of[l]);
     for (int l = 0; l < nl; ++l) run_ptr[l + 1] = run_ptr[l] + nruns_of[l];
-    hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && rule_ok && (dof == 3 ? stokes_sym_on : max_runs_owned <= 256);
-    if (hybrid) {
+    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && rule_ok && (dof == 3 ? stokes_sym_on : max_runs_owned <= 256);
+    if (g.hybrid) {
       if (!(f >= 0.0)) f = 0.0;
       std::vector<int> order(nl);
       for (int l = 0; l < nl; ++l) order[l] = l;
@@ -525,8 +576,8 @@ int fmmbem_plan::to_device(int part) {
         rec[l] = 1;
         acc += (double)leaf_nrows[l] * hp.near_ncols[l];
       }
-      near_recomputed_pairs = 0;
-      for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) if (rec[l]) near_recomputed_pairs += (int64_t)leaf_nrows[l] * hp.near_ncols[l];
+      g.near_recomputed_pairs = 0;
+      for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) if (rec[l]) g.near_recomputed_pairs += (int64_t)leaf_nrows[l] * hp.near_ncols[l];
     }
   }
   run_row0.resize((size_t)run_ptr[nl]); run_off.resize((size_t)run_ptr[nl]);
@@ -556,10 +607,9 @@ int fmmbem_plan::to_device(int part) {
     max_runs = std::max(max_runs, (int)(run_ptr[l + 1] - run_ptr[l]));
   }
   d.max_runs = max_runs;
-  if (const char* e = getenv("FMMBEM_M2L_ROT")) { if (atoi(e) == 0) rot_max = 0; }
-  if (const char* ge = getenv("FMMBEM_GRAPH")) use_graphs = atoi(ge) != 0;
+  if (const char* e = getenv("FMMBEM_M2L_ROT")) { if (atoi(e) == 0) g.rot_max = 0; }
   d.max_ncols = max_cols;
-  near_bytes = total * (int64_t)sizeof(double);
+  g.near_bytes = total * (int64_t)sizeof(double);
   TRY(upload(leaf_row0, &d.leaf_row0)); TRY(upload(leaf_nrows, &d.leaf_nrows)); TRY(upload(hp.leaf_box, &d.leaf_box));
   TRY(upload(run_ptr, &d.near_ptr)); TRY(upload(run_row0, &d.near_run_row0)); TRY(upload(run_off, &d.near_run_off));
   TRY(upload(hp.near_ncols, &d.near_ncols)); TRY(upload(near_stride, &d.near_stride)); TRY(upload(near_off, &d.near_off));
@@ -578,7 +628,7 @@ int fmmbem_plan::to_device(int part) {
       const int nr = idof * leaf_nrows[l];
       const int64_t row_bytes = opts.sparse_local ? (int64_t)near_stride[l] * 8 : (int64_t)hp.near_ncols[l] * 8;
       if (nr == 0 || row_bytes == 0) continue;
-      if (hybrid && (dof == 3 || rec[l])) continue;     // hybrid plans: Stokes builds its stream items below; a recomputed leaf has none
+      if (g.hybrid && (dof == 3 || rec[l])) continue;     // hybrid plans: Stokes builds its stream items below; a recomputed leaf has none
       int per = (int)std::max<int64_t>(1, kItemBytes / row_bytes);
       if (per >= 8) per &= ~7; else per = std::min(4, nr);
       const int cnt = (nr + per - 1) / per;
@@ -613,9 +663,8 @@ int fmmbem_plan::to_device(int part) {
     }
   }
   const bool stokes_sym = dof == 3 && opts.sparse_local && !(std::getenv("FMMBEM_STOKES_SYM") && std::atoi(std::getenv("FMMBEM_STOKES_SYM")) == 0);
-  near_total_doubles = (opts.sparse_local && !stokes_sym) ? total : 0;      // allocated in to_device_bc; matrix-free mode keeps no matrix
-  if (!near_total_doubles) near_bytes = 0;
-  d.near_val = nullptr;
+  g.near_total_doubles = (opts.sparse_local && !stokes_sym) ? total : 0;      // allocated in to_device_bc; matrix-free mode keeps no matrix
+  if (!g.near_total_doubles) g.near_bytes = 0;
   {
     // Stokes: the near blocks in their symmetric 6-value form, the only copy (FMMBEM_STOKES_SYM=0: the 9-value rows instead)
     if (stokes_sym) {
@@ -644,20 +693,20 @@ int fmmbem_plan::to_device(int part) {
       d.sym_nitems = (int)packed.size();
       TRY(upload(packed, &d.sym_items));
       TRY(upload(sym_off, &d.near_sym_off));
-      sym_total_doubles = std::max<int64_t>(sym_total, 1);          // allocated in to_device_bc
-      near_bytes = sym_total * (int64_t)sizeof(double);
-      sym_off_host = sym_off;
+      g.sym_total_doubles = std::max<int64_t>(sym_total, 1);          // allocated in to_device_bc
+      g.near_bytes = sym_total * (int64_t)sizeof(double);
+      g.sym_off_host = sym_off;
     }
   }
   // Float near field: the layout of the copy (device_plan.hpp near_f32) -- per leaf offsets, and for the pipelined Laplace kernel
   // the item records again with the offsets and strides of the float rows (near_recs itself is what the FP64 kernel reads)
-  near_f32_floats = 0;
+  g.near_f32_floats = 0;
   // The option's premise is that the rounding of the entries hides under the truncation error of the far field.  An FMM plan whose
   // leaves are ALL near one another (every leaf pair is a P2P pair: no M2L anywhere) has no far field: its result is exact at every
   // order, relaxation changes nothing, and there is nothing for the float error to hide under -- such a plan (a few hundred panels)
   // takes the option as 0.  The LOCAL / BLOCK_DIAGONAL evaluators are near-field operators by definition and keep it.
   const bool f32_premise = hp.opt.evaluator != 0 || hp.near_ptr[nl] < (int64_t)nl * nl;
-  if (opts.near_f32_max_p > 0 && opts.sparse_local && !hybrid && !targets && hp.opt.shard_world <= 1 && near_bytes > 0 &&
+  if (opts.near_f32_max_p > 0 && opts.sparse_local && !g.hybrid && !targets && hp.opt.shard_world <= 1 && g.near_bytes > 0 &&
       f32_premise && near_f32_ok(dof, max_runs, stokes_sym)) {
     std::vector<int64_t> off32(nl, 0);
     int64_t total32 = 0;
@@ -675,9 +724,9 @@ int fmmbem_plan::to_device(int part) {
       }
       TRY(upload(recs32, &d.near_recs_f32));
     }
-    near_f32_floats = total32;
+    g.near_f32_floats = total32;
   }
-  if (hybrid) {
+  if (g.hybrid) {
     // recompute items: ranges of <= 20 (Stokes: four wavefronts x five rows) or 32 (Laplace: x eight) panel rows of the recomputed
     // leaves (kernels_near.hip near_recompute3 / near_recompute1)
     struct RItem { int leaf, r0, nr; int64_t pairs; };
@@ -718,8 +767,8 @@ int fmmbem_plan::to_device(int part) {
       d.rc_src = rs; d.rc_nrm = rn;
     }
   }
-  near_rec_host = rec;
-  near_off_host = near_off;
+  g.near_rec_host = rec;
+  g.near_off_host = near_off;
 
   mark("near lists + items");
   // boxes, expansions, tables
@@ -743,10 +792,16 @@ int fmmbem_plan::to_device(int part) {
   }
 
   mark("boxes + harmonic tables");
-  TRY(to_device_bc_begin(hp.panels.bc.data()));        // the near-matrix assembly runs on the GPU from here, under the host work below
-  }                                                    // ======== the rest ========
-  if (part == 1) return FMMBEM_OK;
+  return to_device_bc_begin(hp.panels.bc.data());    // the near-matrix assembly runs on the GPU from here, under the host work that follows
+}
+
+int fmmbem_plan::to_device_far(PlanGeometry& g) {
+  DEVICE_SCOPE(opts.device);
   alloc_list = &shared->allocs;
+  BuildTrace mark;
+  const HarmonicTables T;
+  const int nb = hp.nboxes, pm = hp.opt.p_max;
+  DevicePlan& d = g.gd;
   // far-field lists
   std::vector<int> p2m_leaf, l2p_leaf;
   for (int b : hp.p2m_leaves) p2m_leaf.push_back(hp.box_leaf_index[b]);
@@ -770,31 +825,31 @@ int fmmbem_plan::to_device(int part) {
     TRY(upload(grp, &d.l2p_grp));
     int64_t covered = 0;                               // the L2P leaves are distinct leaves: all rows are theirs when the counts agree
     for (int lf : l2p_leaf) covered += hp.box_body_end[hp.leaf_box[lf]] - hp.box_body_begin[hp.leaf_box[lf]];
-    l2p_scatter = d.kernel == FMMBEM_KERNEL_LAPLACE_BEM && !targets && hp.opt.shard_world <= 1 && d.n_l2p > 0 && covered == (int64_t)hp.n;
+    g.l2p_scatter = d.kernel == FMMBEM_KERNEL_LAPLACE_BEM && !targets && hp.opt.shard_world <= 1 && d.n_l2p > 0 && covered == (int64_t)hp.n;
   }
   TRY(upload(hp.m2m_parents, &d.m2m_parent)); TRY(upload(hp.l2l_children, &d.l2l_child));
   TRY(upload(hp.box_child_begin, &d.box_child_begin)); TRY(upload(hp.box_child_end, &d.box_child_end));
   TRY(upload(hp.box_parent, &d.box_parent));
   for (size_t l = 0; l + 1 < hp.m2m_level_ptr.size(); ++l)
     if (hp.m2m_level_ptr[l + 1] > hp.m2m_level_ptr[l])
-      m2m_launch.emplace_back(hp.m2m_level_ptr[l], hp.m2m_level_ptr[l + 1] - hp.m2m_level_ptr[l]);
+      g.m2m_launch.emplace_back(hp.m2m_level_ptr[l], hp.m2m_level_ptr[l + 1] - hp.m2m_level_ptr[l]);
   for (size_t l = 0; l + 1 < hp.l2l_level_ptr.size(); ++l)
     if (hp.l2l_level_ptr[l + 1] > hp.l2l_level_ptr[l])
-      l2l_launch.emplace_back(hp.l2l_level_ptr[l], hp.l2l_level_ptr[l + 1] - hp.l2l_level_ptr[l]);
+      g.l2l_launch.emplace_back(hp.l2l_level_ptr[l], hp.l2l_level_ptr[l + 1] - hp.l2l_level_ptr[l]);
   for (size_t l = 0; l + 1 < hp.m2m_shared_ptr.size(); ++l)
     if (hp.m2m_shared_ptr[l + 1] > hp.m2m_shared_ptr[l])
-      m2m_shared_launch.emplace_back(hp.m2m_shared_ptr[l], hp.m2m_shared_ptr[l + 1] - hp.m2m_shared_ptr[l]);
+      g.m2m_shared_launch.emplace_back(hp.m2m_shared_ptr[l], hp.m2m_shared_ptr[l + 1] - hp.m2m_shared_ptr[l]);
   // sharded upward pass: who sends which multipoles
-  split_upward = hp.opt.shard_upward && hp.opt.shard_world > 1;
-  d.xch_rank = hp.opt.shard_rank; d.xch_world = split_upward ? hp.opt.shard_world : 0; d.xch_max = 0;
+  g.split_upward = hp.opt.shard_upward && hp.opt.shard_world > 1;
+  d.xch_rank = hp.opt.shard_rank; d.xch_world = g.split_upward ? hp.opt.shard_world : 0; d.xch_max = 0;
   for (int r = 0; r < 9; ++r) d.xch_ptr[r] = 0;
-  if (split_upward) {
+  if (g.split_upward) {
     if (hp.opt.shard_world > 8) return fail(FMMBEM_ERR_UNSUPPORTED, "sharded upward pass: at most 8 shards");
     for (int r = 0; r <= hp.opt.shard_world; ++r) d.xch_ptr[r] = hp.xch_ptr[r];
     for (int r = 0; r < hp.opt.shard_world; ++r) d.xch_max = std::max(d.xch_max, hp.xch_ptr[r + 1] - hp.xch_ptr[r]);
   }
   TRY(upload(hp.xch_box, &d.xch_box));
-  if (split_upward && hp.opt.shard_upward == 2) {      // selective exchange: only what the receiver reads
+  if (g.split_upward && hp.opt.shard_upward == 2) {      // selective exchange: only what the receiver reads
     TRY(upload(hp.xsel_send_box, &d.xsel_send_box)); TRY(upload(hp.xsel_recv_box, &d.xsel_recv_box));
     d.xsel_send_n = (int)hp.xsel_send_box.size(); d.xsel_recv_n = (int)hp.xsel_recv_box.size();
   }
@@ -839,7 +894,7 @@ int fmmbem_plan::to_device(int part) {
     TRY(upload(up_cls, &d.up_cls)); TRY(upload(down_cls, &d.down_cls));
     // ---- M2M / L2L by rotation: pair lists per level launch, items, records, constant streams ----
     {
-      TRY(upload(up_rec_h, &up_rec)); TRY(upload(dn_rec_h, &dn_rec));
+      TRY(upload(up_rec_h, &g.up_rec)); TRY(upload(dn_rec_h, &g.dn_rec));
       std::vector<int> rs, rc, rt, ri, len, uptr;
       auto level_boxes = [&](int l) { return l >= 0 && l < hp.nlevels ? hp.level_off[l + 1] - hp.level_off[l] : 0; };
       // items of the shifts: whole targets, ONE pass (at most 64 pairs) -- the shift kernels carry nothing between passes
@@ -875,12 +930,12 @@ int fmmbem_plan::to_device(int part) {
           out.push_back(sr);
         }
       };
-      add_m2m(m2m_launch, m2m_rot);
-      add_m2m(m2m_shared_launch, m2m_shared_rot);
-      TRY(upload(rs, &up_rsrc)); TRY(upload(rc, &up_rcls)); TRY(upload(rt, &up_rtgt)); TRY(upload(ri, &up_ritem));
-      TRY(upload(uptr, &up_unit_ptr));
+      add_m2m(g.m2m_launch, g.m2m_rot);
+      add_m2m(g.m2m_shared_launch, g.m2m_shared_rot);
+      TRY(upload(rs, &g.up_rsrc)); TRY(upload(rc, &g.up_rcls)); TRY(upload(rt, &g.up_rtgt)); TRY(upload(ri, &g.up_ritem));
+      TRY(upload(uptr, &g.up_unit_ptr));
       rs.clear(); rc.clear(); rt.clear(); ri.clear();
-      for (auto [first, count] : l2l_launch) {
+      for (auto [first, count] : g.l2l_launch) {
         ShiftRot sr;
         sr.item_first = (int)ri.size();
         const int base = (int)rs.size();
@@ -895,13 +950,13 @@ int fmmbem_plan::to_device(int part) {
         sr.n_items = (int)ri.size() - sr.item_first - 1;
         sr.pairs = count;
         sr.level_boxes = count > 0 ? level_boxes(hp.box_level[hp.l2l_children[first]]) : 0;
-        l2l_rot.push_back(sr);
+        g.l2l_rot.push_back(sr);
       }
-      TRY(upload(rs, &dn_rsrc)); TRY(upload(rc, &dn_rcls)); TRY(upload(rt, &dn_rtgt)); TRY(upload(ri, &dn_ritem));
+      TRY(upload(rs, &g.dn_rsrc)); TRY(upload(rc, &g.dn_rcls)); TRY(upload(rt, &g.dn_rtgt)); TRY(upload(ri, &g.dn_ritem));
       const std::shared_ptr<const OrderTables> otp = order_tables().get();      // (built on a thread of their own since plan_create began)
       const OrderTables& ot = *otp;
-      for (int q = 1; q <= kRotPmax; ++q) shift_stream_off[q - 1] = ot.shift_off[q - 1];
-      TRY(upload(ot.ups, &up_stream)); TRY(upload(ot.dns, &dn_stream));
+      for (int q = 1; q <= kRotPmax; ++q) g.shift_stream_off[q - 1] = ot.shift_off[q - 1];
+      TRY(upload(ot.ups, &g.up_stream)); TRY(upload(ot.dns, &g.dn_stream));
       {                                                // one pair per wavefront: class tables and the lanes' tables per order
         const int nclass = (int)up_rec_h.size() / 8, cs = sl_class_doubles(pm);
         std::vector<double> cu((size_t)nclass * cs), cd((size_t)nclass * cs);
@@ -909,15 +964,15 @@ int fmmbem_plan::to_device(int part) {
           sl_class_table(up_rec_h.data() + (size_t)c * 8, pm, kRotM2M, cu.data() + (size_t)c * cs);
           sl_class_table(dn_rec_h.data() + (size_t)c * 8, pm, kRotL2L, cd.data() + (size_t)c * cs);
         }
-        TRY(upload(cu, &sl_up_class)); TRY(upload(cd, &sl_dn_class));
-        for (int q = 1; q <= kShiftLanesPmax; ++q) { sl_rot_off[q] = ot.sl_rot_off[q]; sl_ax_off[q] = ot.sl_ax_off[q]; }
-        TRY(upload(ot.urc, &sl_up_rc)); TRY(upload(ot.urs, &sl_up_rs)); TRY(upload(ot.uxc, &sl_up_xc)); TRY(upload(ot.uxs, &sl_up_xs));
-        TRY(upload(ot.drc, &sl_dn_rc)); TRY(upload(ot.drs, &sl_dn_rs)); TRY(upload(ot.dxc, &sl_dn_xc)); TRY(upload(ot.dxs, &sl_dn_xs));
-        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES")) shift_lanes = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES_MAX")) shift_lanes_max = std::atoi(e);
+        TRY(upload(cu, &g.sl_up_class)); TRY(upload(cd, &g.sl_dn_class));
+        for (int q = 1; q <= kShiftLanesPmax; ++q) { g.sl_rot_off[q] = ot.sl_rot_off[q]; g.sl_ax_off[q] = ot.sl_ax_off[q]; }
+        TRY(upload(ot.urc, &g.sl_up_rc)); TRY(upload(ot.urs, &g.sl_up_rs)); TRY(upload(ot.uxc, &g.sl_up_xc)); TRY(upload(ot.uxs, &g.sl_up_xs));
+        TRY(upload(ot.drc, &g.sl_dn_rc)); TRY(upload(ot.drs, &g.sl_dn_rs)); TRY(upload(ot.dxc, &g.sl_dn_xc)); TRY(upload(ot.dxs, &g.sl_dn_xs));
+        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES")) g.shift_lanes = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES_MAX")) g.shift_lanes_max = std::atoi(e);
       }
-      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT")) shift_rot = std::atoi(e) != 0;
-      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT_MIN")) shift_rot_min = std::atoi(e);
+      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT")) g.shift_rot = std::atoi(e) != 0;
+      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT_MIN")) g.shift_rot_min = std::atoi(e);
     }
     const cplx *pu = nullptr, *pd = nullptr;
     TRY(upload(up_tab, &pu)); TRY(upload(down_tab, &pd));
@@ -930,8 +985,8 @@ int fmmbem_plan::to_device(int part) {
       o.T = v.T; o.V = v.V; o.maxp = v.maxp;
       return FMMBEM_OK;
     };
-    up_ops.resize(pm); down_ops.resize(pm);
-    for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], up_ops[p - 1])); TRY(up_op(ops.down_v[p - 1], down_ops[p - 1])); }
+    g.up_ops.resize(pm); g.down_ops.resize(pm);
+    for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], g.up_ops[p - 1])); TRY(up_op(ops.down_v[p - 1], g.down_ops[p - 1])); }
   }
 
   mark("shift classes + operators");
@@ -947,12 +1002,12 @@ int fmmbem_plan::to_device(int part) {
     TRY(upload(tgt, &d.m2l_tgt)); TRY(upload(mh, &d.mh_box));
     TRY(upload(hp.m2l_ptr, &d.m2l_ptr)); TRY(upload(hp.m2l_src, &d.m2l_src)); TRY(upload(hp.m2l_cls, &d.m2l_cls));
     mark("m2l lists upload");
-    n_classes = (int64_t)hp.m2l_class_rep.size() / 2;
+    g.n_classes = (int64_t)hp.m2l_class_rep.size() / 2;
     const int R = 2 * pm;
     d.g_max = m2l_entries(pm);
-    std::vector<double> gtab((size_t)n_classes * d.g_max);
-    std::vector<cplx> ztab((size_t)n_classes * pm);
-    parallel_rows(n_classes, 64, [&](int64_t c_begin, int64_t c_end) {
+    std::vector<double> gtab((size_t)g.n_classes * d.g_max);
+    std::vector<cplx> ztab((size_t)g.n_classes * pm);
+    parallel_rows(g.n_classes, 64, [&](int64_t c_begin, int64_t c_end) {
     std::vector<cplx> h;
     for (int64_t c = c_begin; c < c_end; ++c) {
       // translation = c_target - c_source (executor/M2L.hpp:40), rebuilt from the exact integer class
@@ -1001,8 +1056,8 @@ int fmmbem_plan::to_device(int part) {
     TRY(upload(hp.rot_item_ptr, &d.rot_item_ptr)); TRY(upload(hp.rot_empty, &d.rot_empty));
     d.n_rot_items_long = (int)hp.rot_item_ptr_long.size() - 1;
     TRY(upload(hp.rot_item_ptr_long, &d.rot_item_ptr_long));
-    std::vector<double> rec((size_t)n_classes * 8, 0.0);
-    for (int64_t c = 0; c < n_classes; ++c) {
+    std::vector<double> rec((size_t)g.n_classes * 8, 0.0);
+    for (int64_t c = 0; c < g.n_classes; ++c) {
       double tr[3];
       for (int k = 0; k < 3; ++k) tr[k] = 0.5 * hp.cell[k] * double(hp.m2l_class_vec[3 * c + k]);
       rot_record(tr, rec.data() + (size_t)c * 8);
@@ -1014,8 +1069,6 @@ int fmmbem_plan::to_device(int part) {
   }
 
   mark("rotation lists");
-  shared->on_device = true;
-  shared->device = opts.device;
   return to_device_bc_end();
 }
 
@@ -1027,32 +1080,46 @@ int fmmbem_plan::to_device_bc(const uint8_t* bc_tree) {
   return to_device_bc_end();
 }
 
-// First half: the flags, the near-matrix storage, and the assembly LAUNCHED (own_stream, asynchronous) -- to_device calls this as
+// The one place a plan's d is made, fresh plan or derived: the geometry's fields as they stand, then every field of the flag side
+// (a field that is not listed here is null in every plan)
+void fmmbem_plan::compose_d() {
+  d = g.gd;
+  d.bc = fd.bc; d.n_act = fd.n_act; d.nslots = fd.nslots;
+  for (int i = 0; i < 12; ++i) d.act[i] = fd.act[i];
+  d.stokes_velocity_targets = fd.stokes_velocity_targets; d.stokes_traction_targets = fd.stokes_traction_targets;
+  d.near_val = fd.near_val; d.near_sym = fd.near_sym; d.near_f32 = fd.near_f32;
+  d.ys = fd.ys; d.xt4 = fd.xt4;
+  d.M = fd.M; d.L = fd.L; d.Mh = fd.Mh; d.xt = fd.xt; d.yt = fd.yt;
+  d.p2m_tab = fd.p2m_tab; d.p2m_tab_g = fd.p2m_tab_g; d.p2m_tab_row0 = fd.p2m_tab_row0;
+  d.side_ptr = fd.side_ptr; d.side_col = fd.side_col; d.side_val = fd.side_val; d.side_items = fd.side_items; d.side_nitems = fd.side_nitems;
+}
+
+// First half: the flags, the near-matrix storage, and the assembly LAUNCHED (own_stream, asynchronous) -- to_device_near calls this as
 // soon as the panels and the near lists are in HBM, so that the 20-50 ms of panel integrals run on the GPU while the host goes on
 // tabulating and uploading the far-field operators.
 int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
   DEVICE_SCOPE(opts.device);
   alloc_list = &allocs;
-  d.n_act = 0;
+  fd.n_act = 0;
   if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) {
     // StokesSphericalBEM: M[2][4] per box (kernel/StokesSphericalBEM.hpp:143-153).  The TARGET's flag picks the operator
     // (:377-389): velocity targets read the four potentials of the single layer (slots 0..3), TRACTION targets the seven of
     // the double layer (slots 4..10, kernels_far.hip p2m_apply_kernel<3>); every source feeds the groups that have readers
-    d.stokes_velocity_targets = has_bc[0] ? 1 : 0;
-    d.stokes_traction_targets = (has_bc[1] && hp.opt.evaluator == 0) ? 1 : 0;
-    if (!d.stokes_velocity_targets && !d.stokes_traction_targets) d.stokes_velocity_targets = 1;
-    d.nslots = d.stokes_traction_targets ? 11 : 8;
-    if (d.stokes_velocity_targets) for (int s = 0; s < 4; ++s) d.act[d.n_act++] = s;
-    if (d.stokes_traction_targets) for (int s = 4; s < 11; ++s) d.act[d.n_act++] = s;
+    fd.stokes_velocity_targets = has_bc[0] ? 1 : 0;
+    fd.stokes_traction_targets = (has_bc[1] && hp.opt.evaluator == 0) ? 1 : 0;
+    if (!fd.stokes_velocity_targets && !fd.stokes_traction_targets) fd.stokes_velocity_targets = 1;
+    fd.nslots = fd.stokes_traction_targets ? 11 : 8;
+    if (fd.stokes_velocity_targets) for (int s = 0; s < 4; ++s) fd.act[fd.n_act++] = s;
+    if (fd.stokes_traction_targets) for (int s = 4; s < 11; ++s) fd.act[fd.n_act++] = s;
   } else {
-    d.nslots = 2;
-    for (int s = 0; s < 2; ++s) if (has_bc[s]) d.act[d.n_act++] = s;
+    fd.nslots = 2;
+    for (int s = 0; s < 2; ++s) if (has_bc[s]) fd.act[fd.n_act++] = s;
   }
   {
     uint8_t* dbc = nullptr;
     TRY(alloc((size_t)hp.n, &dbc, false));
     HIP_TRY(hipMemcpy(dbc, bc_tree, (size_t)hp.n, hipMemcpyHostToDevice));
-    d.bc = dbc;
+    fd.bc = dbc;
   }
   for (int f = 0; targets && f < 2; ++f) {
     uint8_t* all = nullptr;
@@ -1060,23 +1127,24 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
     HIP_TRY(hipMemset(all, f, (size_t)hp.n));
     bc_all[f] = all;
   }
-  if (near_total_doubles) TRY(alloc((size_t)near_total_doubles, &d.near_val, false));
-  if (sym_total_doubles) TRY(alloc((size_t)sym_total_doubles, &d.near_sym, false));
-  if (near_f32_floats) TRY(alloc((size_t)near_f32_floats, &d.near_f32, false));
-  if (hybrid) {
+  if (g.near_total_doubles) TRY(alloc((size_t)g.near_total_doubles, &fd.near_val, false));
+  if (g.sym_total_doubles) TRY(alloc((size_t)g.sym_total_doubles, &fd.near_sym, false));
+  if (g.near_f32_floats) TRY(alloc((size_t)g.near_f32_floats, &fd.near_f32, false));
+  if (g.hybrid) {
     HIP_TRY(hipStreamCreateWithFlags(&hyb.recompute, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&hyb.fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&hyb.join_recompute, hipEventDisableTiming));
-    TRY(alloc((size_t)hp.n * d.dof, &d.ys, true));
-    if (d.rc_src) TRY(alloc((size_t)hp.n * 4, &d.xt4, true));
+    TRY(alloc((size_t)hp.n * g.gd.dof, &fd.ys, true));
+    if (g.gd.rc_src) TRY(alloc((size_t)hp.n * 4, &fd.xt4, true));
   }
+  compose_d();
   // near-field assembly on the device, in flight from here on (everything it reads is uploaded; to_device_bc_end waits for it)
   HIP_TRY(hipEventCreate(&asm_ev[0])); HIP_TRY(hipEventCreate(&asm_ev[1]));
   HIP_TRY(hipEventRecord(asm_ev[0], own_stream));
   if (opts.sparse_local) {
     if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_near_assemble_stokes(d, own_stream));
     else HIP_TRY(launch_near_assemble(d, own_stream));
-    if (d.near_f32) HIP_TRY(launch_near_to_f32(d, own_stream));      // the float copy of what was just assembled
+    if (fd.near_f32) HIP_TRY(launch_near_to_f32(d, own_stream));      // the float copy of what was just assembled
   }
   HIP_TRY(hipEventRecord(asm_ev[1], own_stream));
   return FMMBEM_OK;
@@ -1085,21 +1153,13 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
 int fmmbem_plan::to_device_bc_end() {
   DEVICE_SCOPE(opts.device);
   alloc_list = &allocs;
-  const bool trace = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
-  double t_last = now_ms();
-  auto mark = [&](const char* what) {
-    if (!trace) return;
-    (void)hipDeviceSynchronize();
-    const double now = now_ms();
-    std::fprintf(stderr, "to_device %-28s %8.2f ms\n", what, now - t_last);
-    t_last = now;
-  };
-  const int dof = d.dof, nb = hp.nboxes;
-  TRY(alloc((size_t)nb * d.nslots * d.s_max, &d.M, true));
-  TRY(alloc((size_t)nb * d.nslots * d.s_max, &d.L, true));
-  TRY(alloc((size_t)nb * d.nslots * d.s_max, &d.Mh, true));
-  TRY(alloc((size_t)hp.n * dof, &d.xt, true));
-  TRY(alloc((size_t)hp.n * dof, &d.yt, true));
+  BuildTrace mark;
+  const int dof = g.gd.dof, nb = hp.nboxes;
+  TRY(alloc((size_t)nb * fd.nslots * g.gd.s_max, &fd.M, true));
+  TRY(alloc((size_t)nb * fd.nslots * g.gd.s_max, &fd.L, true));
+  TRY(alloc((size_t)nb * fd.nslots * g.gd.s_max, &fd.Mh, true));
+  TRY(alloc((size_t)hp.n * dof, &fd.xt, true));
+  TRY(alloc((size_t)hp.n * dof, &fd.yt, true));
   TRY(alloc((size_t)hp.n * dof, &stage_x, true));
   TRY(alloc((size_t)hp.n * dof, &stage_y, true));
 
@@ -1119,20 +1179,21 @@ int fmmbem_plan::to_device_bc_end() {
     int64_t r0 = hp.n, r1 = 0;
     for (int b : hp.p2m_leaves) { r0 = std::min<int64_t>(r0, hp.box_body_begin[b]); r1 = std::max<int64_t>(r1, hp.box_body_end[b]); }
     if (r1 < r0) r0 = r1 = 0;
-    d.p2m_tab_row0 = r0;
+    fd.p2m_tab_row0 = r0;
+    compose_d();                                       // the geometry is complete by now: the tables are built from the whole of d
     const size_t count = (size_t)(r1 - r0) * ntab * d.p2m_stride;
     const bool stokes = opts.kernel == FMMBEM_KERNEL_STOKES_BEM;
     const size_t count_g = (size_t)(r1 - r0) * 3 * d.p2m_stride;
-    if (stokes && d.stokes_traction_targets && d.n_p2m > 0 && !(e && std::atoi(e) == 0) && count_g * sizeof(double2) <= ((size_t)16 << 30)) {
+    if (stokes && fd.stokes_traction_targets && d.n_p2m > 0 && !(e && std::atoi(e) == 0) && count_g * sizeof(double2) <= ((size_t)16 << 30)) {
       // the double layer's gradient records; without them (switch, or more than 16 GB) its P2M runs the recurrences per matvec
       double2* tab = nullptr;
       TRY(alloc(count_g, &tab, true));
       HIP_TRY(hipDeviceSynchronize());
       HIP_TRY(launch_p2m_table_grad(d, tab, own_stream));
       HIP_TRY(hipStreamSynchronize(own_stream));
-      d.p2m_tab_g = tab;
+      fd.p2m_tab_g = tab;
     }
-    const bool want = !stokes || d.stokes_velocity_targets;
+    const bool want = !stokes || fd.stokes_velocity_targets;
     if (want && !(e && std::atoi(e) == 0) && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
       for (int f = 0; f < 2; ++f) {                    // (a dual plan: the table of every live slot, all sources; else one table)
         if (targets && !has_bc[f]) continue;
@@ -1146,9 +1207,10 @@ int fmmbem_plan::to_device_bc_end() {
         p2m_tab_slot[f] = tab;
         if (!targets) break;
       }
-      d.p2m_tab = p2m_tab_slot[0] ? p2m_tab_slot[0] : p2m_tab_slot[1];
+      fd.p2m_tab = p2m_tab_slot[0] ? p2m_tab_slot[0] : p2m_tab_slot[1];
     }
   }
+  compose_d();
   mark("p2m table");
   // the near-field assembly launched by to_device_bc_begin: its device time
   HIP_TRY(hipStreamSynchronize(own_stream));
@@ -1160,9 +1222,10 @@ int fmmbem_plan::to_device_bc_end() {
     asm_ev[0] = asm_ev[1] = nullptr;
   }
   const double t0 = now_ms();
-  if ((!opts.sparse_local || hybrid) && hp.row_end > hp.row_begin) TRY(build_side_lists());
+  if ((!opts.sparse_local || g.hybrid) && hp.row_end > hp.row_begin) TRY(build_side_lists());
   build_assemble_ms += now_ms() - t0;
   mark("near assembly (waited for)");
+  compose_d();
   {                                                    // the plan itself, readable from the device
     void* pd = nullptr;
     HIP_TRY(hipMalloc(&pd, sizeof(DevicePlan)));
@@ -1195,14 +1258,14 @@ int fmmbem_plan::build_side_lists() {
     const int* d_row = nullptr;
     int* d_col = nullptr;
     double* d_val = nullptr;
-    TRY(upload(ptr, &d.side_ptr)); TRY(upload(row, &d_row));
+    TRY(upload(ptr, &fd.side_ptr)); TRY(upload(row, &d_row));
     TRY(alloc((size_t)nside, &d_col, false)); TRY(alloc((size_t)nside * (dof == 3 ? 9 : 1), &d_val, false));
-    HIP_TRY(launch_mf_side(d, 1, nullptr, d.side_ptr, d_col, nullptr, nullptr, nside, own_stream));
+    HIP_TRY(launch_mf_side(d, 1, nullptr, fd.side_ptr, d_col, nullptr, nullptr, nside, own_stream));
     HIP_TRY(launch_mf_side(d, 2, nullptr, nullptr, d_col, d_row, d_val, nside, own_stream));
     HIP_TRY(hipStreamSynchronize(own_stream));
-    d.side_col = d_col; d.side_val = d_val;
+    fd.side_col = d_col; fd.side_val = d_val;
     near_side_entries = nside;
-    if (hybrid) {
+    if (g.hybrid) {
       // work items of near_side_items (kernels_near.hip): runs of consecutive rows that hold <= 256 listed entries together (a workgroup takes the
       // entries one per thread, then a thread per row adds the row's products in entry order); a row of more than 256 is an item
       // of its own, taken 256 at a time
@@ -1215,8 +1278,8 @@ int fmmbem_plan::build_side_lists() {
         sitems.push_back(make_int4((int)ptr[(size_t)i], (int)ptr[(size_t)j], (int)i, (int)j));
         i = j;
       }
-      d.side_nitems = (int)sitems.size();
-      TRY(upload(sitems, &d.side_items));
+      fd.side_nitems = (int)sitems.size();
+      TRY(upload(sitems, &fd.side_items));
     }
     for (void* tmp : {(void*)d_cnt, (void*)const_cast<int*>(d_row)}) {        // creation-time scratch
       (void)hipFree(tmp);
@@ -1230,59 +1293,83 @@ int fmmbem_plan::build_side_lists() {
 // shift_lanes_max pairs of this plan, the one-pair-per-LANE rotation kernel (kernels_m2l_rot.hip, ~20 us a pass whatever it holds)
 // above -- the two give the same bits, so every plan and every shard chooses by its own share.  p > 12 (and FMMBEM_SHIFT_ROT=0):
 // the sparse-operator kernels of kernels_far.hip, which round differently -- there the choice is the same for all shards.
-int fmmbem_plan::m2m_pass(int p, bool shared, hipStream_t s) {
-  const auto& launches = shared ? m2m_shared_launch : m2m_launch;
-  const auto& rots = shared ? m2m_shared_rot : m2m_rot;
+int fmmbem_plan::m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const {
+  const auto& launches = shared ? g.m2m_shared_launch : g.m2m_launch;
+  const auto& rots = shared ? g.m2m_shared_rot : g.m2m_rot;
   for (size_t i = 0; i < launches.size(); ++i) {
     const auto [first, count] = launches[i];
     const ShiftRot& sr = rots[i];
-    if (shift_rot && shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * d.n_act <= lanes_max(p, true)) {
+    if (g.shift_rot && g.shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * dv.n_act <= g.lanes_max(p, true)) {
       ShiftLaneWork lw;
-      lw.src = up_rsrc; lw.cls = up_rcls; lw.tgt = up_rtgt; lw.unit_ptr = up_unit_ptr + sr.unit_first; lw.n_units = sr.n_units;
-      lw.class_tab = sl_up_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
-      lw.rot_c = sl_up_rc + sl_rot_off[p]; lw.rot_s = sl_up_rs + sl_rot_off[p]; lw.ax_c = sl_up_xc + sl_ax_off[p]; lw.ax_s = sl_up_xs + sl_ax_off[p];
-      HIP_TRY(launch_m2m_lanes(d, lw, p, s));
-    } else if (shift_rot && shift_rot_supported(p) && (shift_lanes || sr.level_boxes >= shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
+      lw.src = g.up_rsrc; lw.cls = g.up_rcls; lw.tgt = g.up_rtgt; lw.unit_ptr = g.up_unit_ptr + sr.unit_first; lw.n_units = sr.n_units;
+      lw.class_tab = g.sl_up_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
+      lw.rot_c = g.sl_up_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_up_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_up_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_up_xs + g.sl_ax_off[p];
+      HIP_TRY(launch_m2m_lanes(dv, lw, p, s));
+    } else if (g.shift_rot && shift_rot_supported(p) && (g.shift_lanes || sr.level_boxes >= g.shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
       RotWork w;
-      w.src = up_rsrc; w.cls = up_rcls; w.tgt = up_rtgt; w.rec = up_rec;
-      w.item_ptr = up_ritem + sr.item_first; w.n_items = sr.n_items;
-      w.stream = up_stream + shift_stream_off[p - 1];
-      HIP_TRY(launch_m2m_rot(d, w, p, s));
-    } else HIP_TRY(launch_m2m_level(d, up_ops[p - 1], p, first, count, s));
+      w.src = g.up_rsrc; w.cls = g.up_rcls; w.tgt = g.up_rtgt; w.rec = g.up_rec;
+      w.item_ptr = g.up_ritem + sr.item_first; w.n_items = sr.n_items;
+      w.stream = g.up_stream + g.shift_stream_off[p - 1];
+      HIP_TRY(launch_m2m_rot(dv, w, p, s));
+    } else HIP_TRY(launch_m2m_level(dv, g.up_ops[p - 1], p, first, count, s));
   }
   return FMMBEM_OK;
 }
-int fmmbem_plan::l2l_pass(int p, hipStream_t s) {
-  for (size_t i = 0; i < l2l_launch.size(); ++i) {
-    const auto [first, count] = l2l_launch[i];
-    const ShiftRot& sr = l2l_rot[i];
-    if (shift_rot && shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * d.n_act <= lanes_max(p, false)) {
+int fmmbem_plan::l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const {
+  for (size_t i = 0; i < g.l2l_launch.size(); ++i) {
+    const auto [first, count] = g.l2l_launch[i];
+    const ShiftRot& sr = g.l2l_rot[i];
+    if (g.shift_rot && g.shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * dv.n_act <= g.lanes_max(p, false)) {
       ShiftLaneWork lw;
-      lw.src = dn_rsrc + sr.pair_first; lw.cls = dn_rcls + sr.pair_first; lw.tgt = dn_rtgt + sr.pair_first; lw.n_units = sr.n_units;
-      lw.class_tab = sl_dn_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
-      lw.rot_c = sl_dn_rc + sl_rot_off[p]; lw.rot_s = sl_dn_rs + sl_rot_off[p]; lw.ax_c = sl_dn_xc + sl_ax_off[p]; lw.ax_s = sl_dn_xs + sl_ax_off[p];
-      HIP_TRY(launch_l2l_lanes(d, lw, p, s));
-    } else if (shift_rot && shift_rot_supported(p) && (shift_lanes || sr.level_boxes >= shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
+      lw.src = g.dn_rsrc + sr.pair_first; lw.cls = g.dn_rcls + sr.pair_first; lw.tgt = g.dn_rtgt + sr.pair_first; lw.n_units = sr.n_units;
+      lw.class_tab = g.sl_dn_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
+      lw.rot_c = g.sl_dn_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_dn_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_dn_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_dn_xs + g.sl_ax_off[p];
+      HIP_TRY(launch_l2l_lanes(dv, lw, p, s));
+    } else if (g.shift_rot && shift_rot_supported(p) && (g.shift_lanes || sr.level_boxes >= g.shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
       RotWork w;
-      w.src = dn_rsrc; w.cls = dn_rcls; w.tgt = dn_rtgt; w.rec = dn_rec;
-      w.item_ptr = dn_ritem + sr.item_first; w.n_items = sr.n_items;
-      w.stream = dn_stream + shift_stream_off[p - 1];
-      HIP_TRY(launch_l2l_rot(d, w, p, s));
-    } else HIP_TRY(launch_l2l_level(d, down_ops[p - 1], p, first, count, s));
+      w.src = g.dn_rsrc; w.cls = g.dn_rcls; w.tgt = g.dn_rtgt; w.rec = g.dn_rec;
+      w.item_ptr = g.dn_ritem + sr.item_first; w.n_items = sr.n_items;
+      w.stream = g.dn_stream + g.shift_stream_off[p - 1];
+      HIP_TRY(launch_l2l_rot(dv, w, p, s));
+    } else HIP_TRY(launch_l2l_level(dv, g.down_ops[p - 1], p, first, count, s));
   }
   return FMMBEM_OK;
 }
 
 // P2M of a dual plan: once per live slot, every source panel taken with that slot's flag (the moments of G, or of dG/dn with the
 // panel's normal) and that slot's table; the same kernels as a plan whose panels all carry the flag
-int fmmbem_plan::p2m_targets(int p, hipStream_t s) {
+template <class Launch>
+int fmmbem_plan::p2m_targets(const DevicePlan& dv, Launch&& launch) const {
   for (int f = 0; f < 2; ++f) {
     if (!has_bc[f]) continue;
-    DevicePlan dp = d;
+    DevicePlan dp = dv;
     dp.bc = bc_all[f];
     dp.n_act = 1; dp.act[0] = f;
-    if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
-    HIP_TRY(launch_p2m(dp, p, s));
+    if (dv.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
+    HIP_TRY(launch(dp));
+  }
+  return FMMBEM_OK;
+}
+
+// The result leaves the plan once, at the very end: the owned rows of y_tree (near + far field) scattered to the caller's
+// panel order (zeros elsewhere when the plan is a shard), or -- result_slices -- copied as they are, tree order, to the
+// head of d_y, for the caller's all-gather (fmmbem_plan_assemble_slices_device puts the gathered slices in panel order).
+// fold: L2P has stored the result at y[perm[i]] already
+int fmmbem_plan::deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream_t s) const {
+  if (fold) return FMMBEM_OK;
+  if (result_slices) {
+    HIP_TRY(hipMemcpyAsync(d_y, dv.yt + dv.row_begin * dv.dof, sizeof(double) * (size_t)(dv.row_end - dv.row_begin) * dv.dof,
+                           hipMemcpyDeviceToDevice, s));
+  } else if (targets) {                                // the target rows -> distinct points -> the targets as given
+    HIP_TRY(launch_scatter_y(dv, d_target_point ? y_points : d_y, s));
+    if (d_target_point) {
+      const int64_t nt = hp.n_targets;
+      hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, y_points, d_y, nt);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    if (hp.opt.shard_world > 1) HIP_TRY(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)hp.n * dv.dof, s));
+    HIP_TRY(launch_scatter_y(dv, d_y, s));
   }
   return FMMBEM_OK;
 }
@@ -1292,9 +1379,9 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   if (!on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   if ((phase < 2 && !d_x) || (phase != 1 && !d_y)) return fail(FMMBEM_ERR_INVALID, "null vector");
-  if (split_upward && phase == 0 && !near_only)
+  if (g.split_upward && phase == 0 && !near_only)
     return fail(FMMBEM_ERR_UNSUPPORTED, "plan shards the upward pass: use fmmbem_plan_upward_device / _downward_device");
-  if (phase != 0 && (!split_upward || (!xbuf && phase != 3))) return fail(FMMBEM_ERR_INVALID, "split execute needs shard_upward and an exchange buffer");
+  if (phase != 0 && (!g.split_upward || (!xbuf && phase != 3))) return fail(FMMBEM_ERR_INVALID, "split execute needs shard_upward and an exchange buffer");
   if (targets && (phase != 0 || result_slices)) return fail(FMMBEM_ERR_UNSUPPORTED, "a target plan runs whole executes only");
   DEVICE_SCOPE(opts.device);
   const int tm = timing;
@@ -1356,7 +1443,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
       if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
       HIP_TRY(end(3, s));
       HIP_TRY(begin(4, s));
-      TRY(m2m_pass(p, false, s));
+      TRY(m2m_pass(d, p, false, s));
       HIP_TRY(launch_xch_pack(d, p, reinterpret_cast<double2*>(xbuf), s));
       HIP_TRY(end(4, s));
       return FMMBEM_OK;
@@ -1372,36 +1459,13 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     // only added to by L2P -- they start from zero
     if (targets && zero_target_rows)
       HIP_TRY(hipMemsetAsync(d.yt + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), ns));
-    if (hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
+    if (g.hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
     else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
     else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
     HIP_TRY(end(1, ns));
     return FMMBEM_OK;
   };
-  // the result leaves the plan once, at the very end: the owned rows of y_tree (near + far field) scattered to the caller's
-  // panel order (zeros elsewhere when the plan is a shard), or -- result_slices -- copied as they are, tree order, to the
-  // head of d_y, for the caller's all-gather (fmmbem_plan_assemble_slices_device puts the gathered slices in panel order)
   const bool fold = l2p_delivers(near_only, phase);  // L2P stores into d_y: the scatter stage then brackets nothing
-  auto deliver = [&](hipStream_t ns) -> int {
-    HIP_TRY(begin(2, ns));
-    if (fold) {                                        // L2P has stored the result at y[perm[i]]
-    } else if (result_slices) {
-      HIP_TRY(hipMemcpyAsync(d_y, d.yt + d.row_begin * d.dof, sizeof(double) * (size_t)(d.row_end - d.row_begin) * d.dof,
-                             hipMemcpyDeviceToDevice, ns));
-    } else if (targets) {                              // the target rows -> distinct points -> the targets as given
-      HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : d_y, ns));
-      if (d_target_point) {
-        const int64_t nt = hp.n_targets;
-        hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ns, d_target_point, y_points, d_y, nt);
-        HIP_TRY(hipGetLastError());
-      }
-    } else {
-      if (hp.opt.shard_world > 1) HIP_TRY(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)hp.n * d.dof, ns));
-      HIP_TRY(launch_scatter_y(d, d_y, ns));
-    }
-    HIP_TRY(end(2, ns));
-    return FMMBEM_OK;
-  };
   if (phase == 3) {                                    // the near field of a split execute, while the caller's all-gather is in flight
     TRY(near_field(s));
     pending_mask = mask;
@@ -1415,19 +1479,19 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   if (!near_only) {
     if (phase == 0) {
       HIP_TRY(begin(3, s));
-      if (targets) TRY(p2m_targets(p, s));
+      if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); }));
       else if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
       HIP_TRY(end(3, s));
       HIP_TRY(begin(4, s));
-      TRY(m2m_pass(p, false, s));
+      TRY(m2m_pass(d, p, false, s));
       HIP_TRY(end(4, s));
     }
     HIP_TRY(begin(5, s));
     if (phase == 2) {                                  // the other shards' multipoles, then the boxes spanning shards
       HIP_TRY(launch_xch_unpack(d, p, reinterpret_cast<const double2*>(xbuf), s));
-      TRY(m2m_pass(p, true, s));
+      TRY(m2m_pass(d, p, true, s));
     }
-    const bool rot = use_rot(p);
+    const bool rot = g.use_rot(p);
     if (!rot) HIP_TRY(launch_mh_prep(d, p, s));      // the rotation kernel reads M itself
     HIP_TRY(end(5, s));
     HIP_TRY(begin(6, s));
@@ -1435,7 +1499,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     else HIP_TRY(launch_m2l(d, d_dev, p, s));
     HIP_TRY(end(6, s));
     HIP_TRY(begin(7, s));
-    TRY(l2l_pass(p, s));
+    TRY(l2l_pass(d, p, s));
     HIP_TRY(end(7, s));
     HIP_TRY(begin(8, s));
     if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s));
@@ -1446,7 +1510,9 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   return FMMBEM_OK;
   }));
   if (fold && graph_ok) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, d_y));   // takes the caller's pointer: after the graph, as the scatter
-  TRY(deliver(s));
+  HIP_TRY(begin(2, s));
+  TRY(deliver(d, d_y, fold, s));
+  HIP_TRY(end(2, s));
   last_p = p;
   last_near_f32 = near_f32 ? 1 : 0;
   if (tm) { ev_mask[ring] = mask; ++ev_count; }
@@ -1468,7 +1534,7 @@ static int batch_nv() {
 // the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch), and
 // the Stokes plans with the symmetric blocks that ask for it (fmmbem_options.stokes_batch_width)
 int fmmbem_plan::batch_width() const {
-  const bool one = on_device && !multi && opts.sparse_local && !hybrid && hp.opt.shard_world <= 1 && !split_upward && !result_slices &&
+  const bool one = on_device && !multi && opts.sparse_local && !g.hybrid && hp.opt.shard_world <= 1 && !g.split_upward && !result_slices &&
                    !d.near_f32;                      // float near field: vector by vector, each with the bits of its single execute
   if (!one) return 1;
   if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM)
@@ -1498,8 +1564,7 @@ int fmmbem_plan::batch_alloc(hipStream_t s) {
     // zero as the plan's own x_tree, y_tree and M (a target plan's x rows of the targets stay 0); on `s`, ahead of the batch
     ok = hipMemsetAsync(b.xt[j], 0, nt * sizeof(double), s) == hipSuccess && hipMemsetAsync(b.yt[j], 0, nt * sizeof(double), s) == hipSuccess &&
          hipMemsetAsync(b.M[j], 0, nm * sizeof(double2), s) == hipSuccess;
-    DevicePlan dj = d;
-    dj.xt = b.xt[j]; dj.yt = b.yt[j]; dj.M = b.M[j];
+    const DevicePlan dj = batch_view(b, j);
     ok = ok && hipMemcpy(b.dev[j], &dj, sizeof(DevicePlan), hipMemcpyHostToDevice) == hipSuccess;
   }
   if (!ok) {
@@ -1532,17 +1597,6 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
   BatchVecs bv{};
   bv.width = w;
   for (int j = 0; j < w; ++j) { bv.xt[j] = bat.xt[j]; bv.yt[j] = bat.yt[j]; bv.M[j] = bat.M[j]; }
-  // m2m_pass / l2l_pass and the M2L launchers read the plan's d / d_dev: pointed at vector j's buffers while its far field is
-  // issued (the launches take d by value), restored after
-  struct View {
-    fmmbem_plan& pl;
-    const DevicePlan keep;
-    const DevicePlan* keep_dev;
-    View(fmmbem_plan& q, int j) : pl(q), keep(q.d), keep_dev(q.d_dev) {
-      pl.d.xt = pl.bat.xt[j]; pl.d.yt = pl.bat.yt[j]; pl.d.M = pl.bat.M[j]; pl.d_dev = pl.bat.dev[j];
-    }
-    ~View() { pl.d = keep; pl.d_dev = keep_dev; }
-  };
   for (int j0 = 0; j0 < k; j0 += w) {
     const int nv = std::min(w, k - j0);
     bv.nv = nv;
@@ -1564,16 +1618,8 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
     if (set) HIP_TRY(hipEventRecord(set[2 * 1 + 1], s));
     if (!stokes) {
       if (set) HIP_TRY(hipEventRecord(set[2 * 3], s));
-      if (targets) {                                   // as p2m_targets: once per live slot
-        for (int f = 0; f < 2; ++f) {
-          if (!has_bc[f]) continue;
-          DevicePlan dp = d;
-          dp.bc = bc_all[f];
-          dp.n_act = 1; dp.act[0] = f;
-          if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
-          HIP_TRY(launch_p2m_multi(dp, bv, p, s));
-        }
-      } else HIP_TRY(launch_p2m_multi(d, bv, p, s));
+      if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m_multi(dp, bv, p, s); }));
+      else HIP_TRY(launch_p2m_multi(d, bv, p, s));
       if (set) HIP_TRY(hipEventRecord(set[2 * 3 + 1], s));
     }
     if (set) {
@@ -1582,29 +1628,19 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
     }
     for (int j = 0; j < nv; ++j) {
       double* yj = host ? sy : y + (size_t)(j0 + j) * ldy;
-      {
-        View view(*this, j);
-        if (stokes) HIP_TRY(launch_p2m_stokes(d, p, s));
-        TRY(m2m_pass(p, false, s));
-        const bool rot = use_rot(p);
-        if (!rot) HIP_TRY(launch_mh_prep(d, p, s));
-        if (rot) HIP_TRY(launch_m2l_rot(d, d_dev, p, s));
-        else HIP_TRY(launch_m2l(d, d_dev, p, s));
-        TRY(l2l_pass(p, s));
-        const bool fold = l2p_delivers(false, 0);
-        if (stokes) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s));
-        else if (fold) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, yj));
-        else HIP_TRY(launch_l2p(d, p, d.yt, s));
-        if (fold) {                                    // delivered by L2P
-        } else if (targets) {
-          HIP_TRY(launch_scatter_y(d, d_target_point ? y_points : yj, s));
-          if (d_target_point) {
-            const int64_t nt = hp.n_targets;
-            hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, y_points, yj, nt);
-            HIP_TRY(hipGetLastError());
-          }
-        } else HIP_TRY(launch_scatter_y(d, yj, s));
-      }
+      const DevicePlan dj = batch_view(bat, j);        // vector j's far field: the launchers of run() on its buffers
+      if (stokes) HIP_TRY(launch_p2m_stokes(dj, p, s));
+      TRY(m2m_pass(dj, p, false, s));
+      const bool rot = g.use_rot(p);
+      if (!rot) HIP_TRY(launch_mh_prep(dj, p, s));
+      if (rot) HIP_TRY(launch_m2l_rot(dj, bat.dev[j], p, s));
+      else HIP_TRY(launch_m2l(dj, bat.dev[j], p, s));
+      TRY(l2l_pass(dj, p, s));
+      const bool fold = l2p_delivers(false, 0);
+      if (stokes) HIP_TRY(launch_l2p_stokes(dj, p, dj.yt, s));
+      else if (fold) HIP_TRY(launch_l2p(dj, p, dj.yt, s, dj.perm, yj));
+      else HIP_TRY(launch_l2p(dj, p, dj.yt, s));
+      TRY(deliver(dj, yj, fold, s));
       if (host) HIP_TRY(hipMemcpyAsync(y + (size_t)(j0 + j) * ldy, sy, bytes_y, hipMemcpyDeviceToHost, s));
     }
   }
@@ -1668,72 +1704,48 @@ static bool same_geometry_options(const fmmbem_options& a, const fmmbem_options&
          a.near_f32_max_p == b.near_f32_max_p;
 }
 
-// live plans that hold a geometry, most recent first (a handful: operator, right-hand side, preconditioner plans).  ONE mutex: a
-// creation that finds its geometry here copies the holder's state under it (microseconds), fmmbem_plan_destroy takes it before it
-// deletes -- so a plan is never read while it goes away -- and the long part of the creation runs outside.
+// the geometries still alive, most recent first (a handful: operator, right-hand side, preconditioner plans).  The cache owns
+// nothing: an entry whose last plan is gone has expired and is dropped at the next insertion.  A creation that finds its geometry
+// here takes a reference under the mutex and reads only what no plan ever writes (PlanGeometry, the fingerprint): no live plan
+// is looked at, so it cannot race with an execute on another handle.
 static std::mutex g_cache_mu;
-static std::vector<fmmbem_plan*> g_cache;
+static std::vector<std::weak_ptr<PlanShared>> g_cache;
 
-static void geometry_cache_add(fmmbem_plan* p) {
+static void geometry_cache_add(const std::shared_ptr<PlanShared>& sh) {
   std::lock_guard<std::mutex> lock(g_cache_mu);
-  g_cache.insert(g_cache.begin(), p);
+  g_cache.erase(std::remove_if(g_cache.begin(), g_cache.end(), [](const std::weak_ptr<PlanShared>& w) { return w.expired(); }), g_cache.end());
+  g_cache.insert(g_cache.begin(), sh);
   if (g_cache.size() > 32) g_cache.resize(32);
 }
-static void geometry_cache_remove(fmmbem_plan* p) {
+static std::shared_ptr<PlanShared> geometry_cache_find(size_t n_panels, const uint64_t fp[2], const fmmbem_options& o) {
   std::lock_guard<std::mutex> lock(g_cache_mu);
-  g_cache.erase(std::remove(g_cache.begin(), g_cache.end(), p), g_cache.end());
+  for (const std::weak_ptr<PlanShared>& w : g_cache)
+    if (std::shared_ptr<PlanShared> sh = w.lock())
+      if ((size_t)sh->geo.gd.n == n_panels && sh->fingerprint[0] == fp[0] && sh->fingerprint[1] == fp[1] && same_geometry_options(sh->geo.opts, o)) return sh;
+  return nullptr;
 }
 
-// A plan of `base`'s panels with other boundary-condition flags: shares base's PlanShared, builds what the flags decide.
-int fmmbem_plan::like(const fmmbem_plan& base, const uint8_t* bc, fmmbem_plan** out) {
-  *out = nullptr;
-  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan(base));       // memberwise: d, the launch lists, the table pointers
-  if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
-  return like_finish(std::move(pl), bc, out);
-}
-
-// `pl`: a memberwise copy of a plan that holds the geometry (base may be gone by now: the shared block is reference counted)
-int fmmbem_plan::like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc, fmmbem_plan** out) {
+// A plan on a geometry that exists (`sh`: a base plan's, or one the cache recognised) with the options `o` and other
+// boundary-condition flags: a new plan with its own stream and events, which builds what the flags decide.
+int fmmbem_plan::like(std::shared_ptr<PlanShared> sh, const fmmbem_options& o, const uint8_t* bc, fmmbem_plan** out) {
   *out = nullptr;
   const double t0 = now_ms();
-  // ... and now everything that must NOT be shared with base (the copy constructor copied the handles): fresh or empty
-  pl->allocs.clear();
-  pl->alloc_list = &pl->allocs;
-  pl->ev.assign(pl->ev.size(), nullptr);
-  pl->graphs.clear();
-  pl->own_stream = nullptr; pl->hyb = HybridStreams{}; pl->d.ys = nullptr; pl->d.xt4 = nullptr;
-  pl->asm_ev[0] = pl->asm_ev[1] = nullptr;
-  pl->d_dev = nullptr; pl->stage_x = pl->stage_y = nullptr; pl->solver_ws = nullptr; pl->d_cut = nullptr;
-  pl->bat = BatchBufs{};
-  pl->binv = BlockInverse{};
-  pl->multi.reset();
-  pl->result_slices = false; pl->pending_mask = 0; pl->pending_near = false;
-  pl->timing = 0; pl->last_p = 0; pl->ev_count = 0;
-  for (auto& m : pl->ev_mask) m = 0;
-  pl->near_side_entries = 0;
-  pl->d.side_ptr = nullptr; pl->d.side_col = nullptr; pl->d.side_val = nullptr;
-  pl->d.p2m_tab = nullptr; pl->d.p2m_tab_g = nullptr;
-  pl->d.near_val = nullptr; pl->d.near_sym = nullptr; pl->d.near_f32 = nullptr; pl->last_near_f32 = 0;
-  pl->build_host_ms = 0;
-  DEVICE_SCOPE(pl->opts.device);
-  HIP_TRY(hipStreamCreateWithFlags(&pl->own_stream, hipStreamNonBlocking));
-  for (auto& e : pl->ev) HIP_TRY(hipEventCreate(&e));
+  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan(std::move(sh)));
+  if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
+  pl->opts = o;
+  TRY(pl->open_device());
   const HostPlan& h = pl->hp;
   std::vector<uint8_t> bc_tree((size_t)h.n, 0);
-  pl->has_bc[0] = pl->has_bc[1] = false;
   for (int64_t i = 0; i < h.n; ++i) {
     const uint8_t f = bc ? (bc[h.perm[(size_t)i]] ? 1 : 0) : 0;
     bc_tree[(size_t)i] = f;
     pl->has_bc[f] = true;
   }
-  const int rc = pl->to_device_bc(bc_tree.data());
-  if (rc != FMMBEM_OK) return rc;
+  TRY(pl->to_device_bc(bc_tree.data()));
   pl->build_host_ms = now_ms() - t0 - pl->build_assemble_ms;
-  if (!(std::getenv("FMMBEM_PLAN_SHARE") && std::atoi(std::getenv("FMMBEM_PLAN_SHARE")) == 0)) geometry_cache_add(pl.get());   // any holder of the geometry can stand in for the first
   *out = pl.release();
   return FMMBEM_OK;
 }
-
 
 // ---- one plan over several devices of ONE process (fmmbem_options.n_devices > 1; SURVEY.md section 8b "device list") ------
 // The reference's drivers build one plan in one process (examples/LaplaceBEM.cpp:209; FMM_plan.hpp:34-43).  This is that plan with
@@ -1746,9 +1758,8 @@ int fmmbem_plan::like_finish(std::unique_ptr<fmmbem_plan> pl, const uint8_t* bc,
 // every step on the shard's own stream, ordered by events: the host thread only enqueues.  xGMI is point to point, so plain peer
 // copies ARE the collective here (one link per peer, no ring); the same bits as a single plan (shards sum bitwise).
 // Not measured on more than one GPU (none has been available to this project); devices = {0, 0, ...} runs the whole path on one.
-struct ShardDeleter { void operator()(fmmbem_plan* p) const { fmmbem_plan_destroy(p); } };   // through the C entry point: the shards are known to the geometry cache
 struct MultiDevice {
-  std::vector<std::unique_ptr<fmmbem_plan, ShardDeleter>> shards;
+  std::vector<std::unique_ptr<fmmbem_plan>> shards;
   std::vector<int> dev;
   std::vector<double*> x, slice;                     // per shard, on its device: the replica of x, the result slice
   double* gathered = nullptr;                        // on dev[0]: world * chunk doubles
@@ -1779,15 +1790,19 @@ struct MultiDevice {
   }
 };
 
-static int multi_finish(fmmbem_plan* h, std::shared_ptr<MultiDevice> m) {
+// the handle over the shards of `m`: what the host-pointer execute and the solver need on the first device
+static int multi_finish(const fmmbem_options& opts, std::shared_ptr<MultiDevice> m, fmmbem_plan** out) {
   const int W = m->world();
   const fmmbem_plan& s0 = *m->shards[0];
+  std::unique_ptr<fmmbem_plan> h(new (std::nothrow) fmmbem_plan(s0.shared));
+  if (!h) return fail(FMMBEM_ERR_ALLOC, "plan");
+  h->opts = opts;
   const size_t nd = (size_t)s0.hp.n * s0.d.dof;
   m->cut.resize((size_t)W + 1);
   TRY(fmmbem_plan_shard_rows(m->shards[0].get(), m->cut.data()));
   for (int r = 0; r < W; ++r) m->chunk = std::max(m->chunk, (size_t)(m->cut[r + 1] - m->cut[r]) * s0.d.dof);
   m->chunk = std::max<size_t>(m->chunk, 1);
-  m->split = s0.split_upward;
+  m->split = s0.g.split_upward;
   m->x.assign(W, nullptr); m->slice.assign(W, nullptr); m->ev_up.assign(W, nullptr); m->ev_done.assign(W, nullptr);
   int prev = 0;
   (void)hipGetDevice(&prev);
@@ -1806,16 +1821,16 @@ static int multi_finish(fmmbem_plan* h, std::shared_ptr<MultiDevice> m) {
   HIP_TRY(hipSetDevice(m->dev[0]));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->gathered), sizeof(double) * m->chunk * (size_t)W));
   HIP_TRY(hipEventCreateWithFlags(&m->ev_x, hipEventDisableTiming));
-  // the handle itself: what the host-pointer execute and the solver need on the first device
   h->opts.device = m->dev[0];
   h->on_device = true;
-  h->d.dof = s0.d.dof; h->d.n = s0.d.n;
+  h->compose_d();                                    // the first shard's geometry, no flag side: the handle reads d.dof and d.n
   h->has_bc[0] = s0.has_bc[0]; h->has_bc[1] = s0.has_bc[1];
   HIP_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
   TRY(h->alloc(nd, &h->stage_x, true));
   TRY(h->alloc(nd, &h->stage_y, true));
   HIP_TRY(hipDeviceSynchronize());
   h->multi = std::move(m);
+  *out = h.release();
   return FMMBEM_OK;
 }
 
@@ -1847,12 +1862,7 @@ static int multi_create(const fmmbem_options* opts, const std::vector<int>& devi
     });
   for (auto& th : pool) th.join();
   for (int r = 0; r < W; ++r) if (rc[r] != FMMBEM_OK) return fail(rc[r], "shard " + std::to_string(r) + ": " + err[r]);
-  std::unique_ptr<fmmbem_plan> h(new (std::nothrow) fmmbem_plan(m->shards[0]->shared));
-  if (!h) return fail(FMMBEM_ERR_ALLOC, "plan");
-  h->opts = *opts;
-  TRY(multi_finish(h.get(), m));
-  *out = h.release();
-  return FMMBEM_OK;
+  return multi_finish(*opts, m, out);
 }
 
 // a multi-device plan of `base`'s panels with other flags: shard by shard (each shares its base shard's geometry)
@@ -1863,15 +1873,11 @@ static int multi_like(const fmmbem_plan& base, const uint8_t* bc, fmmbem_plan** 
   m->shards.resize(W);
   for (int r = 0; r < W; ++r) {
     fmmbem_plan* p = nullptr;
-    TRY(fmmbem_plan::like(*base.multi->shards[r], bc, &p));
+    const fmmbem_plan& sb = *base.multi->shards[r];
+    TRY(fmmbem_plan::like(sb.shared, sb.opts, bc, &p));
     m->shards[r].reset(p);
   }
-  std::unique_ptr<fmmbem_plan> h(new (std::nothrow) fmmbem_plan(m->shards[0]->shared));
-  if (!h) return fail(FMMBEM_ERR_ALLOC, "plan");
-  h->opts = base.opts;
-  TRY(multi_finish(h.get(), m));
-  *out = h.release();
-  return FMMBEM_OK;
+  return multi_finish(base.opts, m, out);
 }
 
 static int multi_xch(fmmbem_plan* h, int p, MultiDevice::Xch** out) {
@@ -2017,23 +2023,16 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   const bool share_on = !opts->host_only && !(std::getenv("FMMBEM_PLAN_SHARE") && std::atoi(std::getenv("FMMBEM_PLAN_SHARE")) == 0);
   if (share_on) {
     fingerprint_vertices(vertices, n_panels, fp);
-    std::unique_ptr<fmmbem_plan> copy;
-    {
-      std::lock_guard<std::mutex> lock(g_cache_mu);
-      for (const fmmbem_plan* p : g_cache)
-        if ((size_t)p->hp.n == n_panels && p->shared->fingerprint[0] == fp[0] && p->shared->fingerprint[1] == fp[1] && same_geometry_options(p->opts, *opts)) {
-          copy.reset(new (std::nothrow) fmmbem_plan(*p));
-          break;
-        }
-    }
-    if (copy) {
-      copy->opts.stokes_batch_width = opts->stokes_batch_width;     // no part of the geometry: the new plan's own
-      return fmmbem_plan::like_finish(std::move(copy), bc, out);
+    if (std::shared_ptr<PlanShared> sh = geometry_cache_find(n_panels, fp, *opts)) {
+      fmmbem_options o = sh->geo.opts;
+      o.stokes_batch_width = opts->stokes_batch_width;              // no part of the geometry: the new plan's own
+      return fmmbem_plan::like(std::move(sh), o, bc, out);
     }
   }
-  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan);
+  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan(std::make_shared<PlanShared>()));
   if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
-  pl->opts = *opts;
+  PlanGeometry& geo = pl->shared->geo;                  // written here and by to_device_near / to_device_far, then never again
+  pl->opts = geo.opts = *opts;
   pl->shared->fingerprint[0] = fp[0]; pl->shared->fingerprint[1] = fp[1];
   HostOptions ho;
   ho.p_max = opts->p_max; ho.quad_k = opts->quad_k; ho.theta = opts->theta; ho.ncrit = opts->ncrit;
@@ -2054,7 +2053,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
       pl->has_bc[0] = pl->hp.has_bc[0]; pl->has_bc[1] = pl->hp.has_bc[1];
       pl->create_vertices = vertices;
       try {
-        near_rc = pl->to_device(1);
+        near_rc = pl->to_device_near(geo);
       } catch (const std::bad_alloc&) {
         near_rc = fail(FMMBEM_ERR_ALLOC, "host allocation failed while tabulating operators");
       }
@@ -2077,15 +2076,16 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   if (!opts->host_only) {
     try {
       pl->create_vertices = ho.panels_on_device ? vertices : nullptr;
-      const int rc = pl->to_device(near_done ? 2 : 0);
+      int rc = near_done ? FMMBEM_OK : pl->to_device_near(geo);
       pl->create_vertices = nullptr;
+      if (rc == FMMBEM_OK) rc = pl->to_device_far(geo);
       if (rc != FMMBEM_OK) return rc;
     } catch (const std::bad_alloc&) {
       return fail(FMMBEM_ERR_ALLOC, "host allocation failed while tabulating operators");
     }
     // vertices are only needed on the device; keep the host copy small
     pl->hp.panels.vert.clear(); pl->hp.panels.vert.shrink_to_fit();
-    if (share_on) geometry_cache_add(pl.get());
+    if (share_on) geometry_cache_add(pl->shared);
   }
   *out = pl.release();
   return FMMBEM_OK;
@@ -2120,12 +2120,14 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   if (opts->l2l_rule != FMMBEM_L2L_COMPLETE) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: l2l_rule COMPLETE only");
   if (n_panels + n_targets > (size_t)INT32_MAX) return fail(FMMBEM_ERR_INVALID, "too many panels and targets");
   if (!opts->host_only) (void)order_tables();
-  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan);
+  std::unique_ptr<fmmbem_plan> pl(new (std::nothrow) fmmbem_plan(std::make_shared<PlanShared>()));
   if (!pl) return fail(FMMBEM_ERR_ALLOC, "plan");
+  PlanGeometry& geo = pl->shared->geo;
   pl->opts = *opts;
   pl->opts.near_stream_fraction = 1.0;                 // the hybrid near field is taken as 1 here
   pl->opts.near_f32_max_p = 0;                         // ... and the float near field as off
   pl->opts.shard_rank = 0; pl->opts.shard_world = 1; pl->opts.n_devices = 0;
+  geo.opts = pl->opts;
   pl->targets = true;
   HostOptions ho;
   ho.p_max = opts->p_max; ho.quad_k = opts->quad_k; ho.theta = opts->theta; ho.ncrit = opts->ncrit;
@@ -2141,9 +2143,9 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   pl->has_bc[0] = pl->hp.has_bc[0]; pl->has_bc[1] = pl->hp.has_bc[1];
   if (!opts->host_only) {
     try {
-      TRY(pl->to_device(0));
+      TRY(pl->to_device_near(geo));
+      TRY(pl->to_device_far(geo));
       DEVICE_SCOPE(opts->device);
-      pl->alloc_list = &pl->allocs;
       const HostPlan& h = pl->hp;
       for (int l = h.leaf_begin; l < h.leaf_end; ++l) pl->zero_target_rows = pl->zero_target_rows || h.near_ncols[l] == 0;
       bool coincide = false;
@@ -2219,13 +2221,10 @@ int fmmbem_plan_create_like(const fmmbem_plan* base, const uint8_t* bc, fmmbem_p
   TRY(target_plan_only(base, "fmmbem_plan_create_like"));
   if (!base->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "fmmbem_plan_create_like: the base plan was built host-only");
   if (base->multi) return multi_like(*base, bc, out);
-  return fmmbem_plan::like(*base, bc, out);
+  return fmmbem_plan::like(base->shared, base->opts, bc, out);
 }
 
-void fmmbem_plan_destroy(fmmbem_plan* plan) {
-  if (plan) geometry_cache_remove(plan);
-  delete plan;
-}
+void fmmbem_plan_destroy(fmmbem_plan* plan) { delete plan; }
 
 int fmmbem_plan_execute_device(fmmbem_plan* plan, int p, const double* d_x, double* d_y, void* stream) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
@@ -2431,7 +2430,7 @@ int fmmbem_plan_block_inverse_build(fmmbem_plan* plan) {
   if (plan->hp.opt.shard_world > 1 || plan->opts.shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "not on a shard of an operator");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, std::string(who) + "plan was built host-only; the blocks live on the device");
   if (plan->binv.built) return FMMBEM_OK;
-  if (plan->hybrid || (!plan->d.near_val && !plan->d.near_sym)) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "the plan stores no leaf blocks");
+  if (plan->g.hybrid || (!plan->d.near_val && !plan->d.near_sym)) return fail(FMMBEM_ERR_UNSUPPORTED, std::string(who) + "the plan stores no leaf blocks");
   const HostPlan& h = plan->hp;
   const int dof = plan->d.dof;
   // every leaf of a BLOCK_DIAGONAL plan is its own and only source (EvalDiagonalSparse.hpp:33-49)
@@ -2581,18 +2580,18 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
   o->m2l_classes = (int64_t)h.m2l_class_rep.size() / 2;
   o->owned_leaf_begin = h.leaf_begin; o->owned_leaf_end = h.leaf_end;
   o->owned_row_begin = h.row_begin; o->owned_row_end = h.row_end;
-  o->near_bytes = plan->near_bytes;
-  const bool long_items = plan->last_p > 0 && m2l_rot_long_items(plan->last_p) && plan->use_rot(plan->last_p);   // the cut the last execute ran
+  o->near_bytes = plan->g.near_bytes;
+  const bool long_items = plan->last_p > 0 && m2l_rot_long_items(plan->last_p) && plan->g.use_rot(plan->last_p);   // the cut the last execute ran
   o->m2l_items = (int64_t)(long_items ? h.rot_item_ptr_long : h.rot_item_ptr).size() - 1;
   o->m2l_passes = long_items ? h.rot_passes_long : h.rot_passes;
   o->near_side_entries = plan->near_side_entries;
-  o->near_recomputed_pairs = plan->near_recomputed_pairs;
-  o->near_f32_bytes = plan->d.near_f32 ? plan->near_f32_floats * (int64_t)sizeof(float) : 0;
+  o->near_recomputed_pairs = plan->g.near_recomputed_pairs;
+  o->near_f32_bytes = plan->d.near_f32 ? plan->g.near_f32_floats * (int64_t)sizeof(float) : 0;
   o->last_near_f32 = plan->last_near_f32;
   o->geometry_shared = (int32_t)plan->shared.use_count();
   o->n_devices = 1;
   o->expansion_slots = plan->on_device ? plan->d.nslots : (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 8 : 2);
-  o->m2l_kernel = plan->last_p > 0 ? (plan->use_rot(plan->last_p) ? 1 : plan->last_p <= 4 ? 3 : 2) : 0;
+  o->m2l_kernel = plan->last_p > 0 ? (plan->g.use_rot(plan->last_p) ? 1 : plan->last_p <= 4 ? 3 : 2) : 0;
   o->rot_nop_orders = (int64_t)rot_nop_orders_m2l() | ((int64_t)rot_nop_orders_m2m() << 16) | ((int64_t)rot_nop_orders_l2l() << 32);
   o->tree_coder_levels = h.tree_levels_max;
   o->expansions_active = (plan->has_bc[0] ? 1 : 0) | (plan->has_bc[1] ? 2 : 0);
@@ -2737,7 +2736,7 @@ int fmmbem_plan_get_near_row(const fmmbem_plan* plan, int64_t row, uint32_t* col
     if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "near values live on the device");
     if (!plan->opts.sparse_local) return fail(FMMBEM_ERR_INVALID, "matrix-free plan holds no near matrix");
     DEVICE_SCOPE(plan->opts.device);
-    if (!plan->near_rec_host.empty() && plan->near_rec_host[leaf]) {
+    if (!plan->g.near_rec_host.empty() && plan->g.near_rec_host[leaf]) {
       // hybrid plan, recomputed leaf: no block is stored -- the row is evaluated now, by the entry functions of the assembly
       const int ncp = h.near_ncols[leaf];
       std::vector<int> pcol((size_t)ncp);
@@ -2761,10 +2760,10 @@ int fmmbem_plan_get_near_row(const fmmbem_plan* plan, int64_t row, uint32_t* col
         for (int b = 0; b < dof; ++b) vals[dof * c + b] = blk[(size_t)c * dof * dof + comp * dof + b];
       return FMMBEM_OK;
     }
-    const int64_t off = plan->near_off_host[leaf];
+    const int64_t off = plan->g.near_off_host[leaf];
     if (plan->d.near_sym) {                            // Stokes, symmetric blocks: expand row `comp` of the panel row's 3x3 blocks
       const int ncp = h.near_ncols[leaf];
-      const int64_t soff = plan->sym_off_host[leaf];
+      const int64_t soff = plan->g.sym_off_host[leaf];
       std::vector<double> six((size_t)6 * ncp);
       HIP_TRY(hipMemcpy(six.data(), plan->d.near_sym + soff + (prow - h.box_body_begin[tb]) * 6 * ncp, sizeof(double) * six.size(), hipMemcpyDeviceToHost));
       const double *p0 = six.data(), *p1 = p0 + 2 * ncp, *p2 = p1 + 2 * ncp;      // (xx,xy) (xz,yy) (yz,zz) per source panel

@@ -501,9 +501,6 @@ class FMM_plan:
         plan's tree, lists and tables; builds only the near-matrix values, P2M moments and expansions.  The drivers'
         right-hand-side plan (examples/LaplaceBEM.cpp:218-232).  K: the kernel object the new plan reads its order from
         (default: this plan's)."""
-        import copy
-        other = copy.copy(self)
-        other._K = K if K is not None else self._K
         bcp = None
         if bc is not None:
             bc = np.ascontiguousarray(bc, dtype=np.uint8)
@@ -511,9 +508,10 @@ class FMM_plan:
                 raise ValueError("bc must have one flag per panel")
             bcp = bc.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        other._h = None
         _capi.check(_capi.lib().fmmbem_plan_create_like(self._h, bcp, C.byref(h)))
-        other._h = h
+        other = object.__new__(type(self))             # this plan's attributes with the new handle: never this plan's own
+        other.__dict__.update(self.__dict__, _h=h)
+        other._K = K if K is not None else self._K
         return other
 
     # ---- reference surface ----

@@ -229,3 +229,30 @@ print("ok")
 """ % ROOT
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+
+
+def test_like_with_a_wrong_bc_leaves_the_base_plan_whole():
+    """FMM_plan.like checks bc before there is a new object, and the new object never holds the base's handle: a refused like()
+    leaves nothing behind whose __del__ could destroy the base plan.  In a child process: the base's handle destroyed twice showed
+    as a crash when the interpreter exits (status -11), not as an exception."""
+    code = r"""
+import sys, numpy as np
+sys.path.insert(0, %r)
+import fmm_bem_relaxed_amd as fb
+v = fb.unit_sphere(3)
+assert len(v) == 128
+base = fb.FMM_plan(fb.LaplaceSphericalBEM(6, 3), v, host_only=True)
+perm = base.perm()
+try:
+    base.like(np.zeros(7, np.uint8))
+    raise SystemExit("like() took a bc of the wrong length")
+except ValueError:
+    pass
+import gc; gc.collect()
+assert base.stats()["n_panels"] == 128
+assert np.array_equal(base.perm(), perm) and sorted(perm) == list(range(128))
+base.close()
+print("ok")
+""" % ROOT
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout + r.stderr)

@@ -2,6 +2,8 @@
 (fmmbem_plan_create_like; fmmbem_plan_create recognises the geometry of a live plan by itself): the drivers' right-hand-side plan
 (examples/LaplaceBEM.cpp:218-232, StokesBEM.cpp:266-270) costs the near-matrix assembly and the P2M table, not a second tree build
 and traversal.  The shared plan must give the bits of an independent one, and either plan may be destroyed first."""
+import os
+
 import numpy as np
 import pytest
 
@@ -100,3 +102,150 @@ def test_shards_share_per_shard(fb):
         tot += a.execute(x)
         tot_nd += b.execute(x)
     assert np.array_equal(tot, whole) and np.array_equal(tot_nd, whole_nd)
+
+
+# ---- a plan is built on the shared geometry, never copied from a live plan: what a derived plan owns is its own ----
+# The mesh: two spheres of 2 048 + 512 panels -- at p_max = 8 four levels, 88 leaves, 2 913 M2L pairs, 83 M2M and 83 L2L operations:
+# the smallest found on which every stage of the chain does work (unit_sphere(5) alone gives no L2L).  Every reference is an
+# independent plan (FMMBEM_PLAN_SHARE=0), every comparison bit for bit.
+def _independent(fb, make):
+    keep = os.environ.get("FMMBEM_PLAN_SHARE")
+    os.environ["FMMBEM_PLAN_SHARE"] = "0"
+    try:
+        return make()
+    finally:
+        if keep is None:
+            del os.environ["FMMBEM_PLAN_SHARE"]
+        else:
+            os.environ["FMMBEM_PLAN_SHARE"] = keep
+
+
+@pytest.fixture(scope="module")
+def two(fb):
+    v = np.concatenate([fb.unit_sphere(5), fb.unit_sphere(4, center=(2.5, 0.0, 0.3))])
+    n = len(v)
+    assert n == 2560
+    d = {"v": v, "x": drand48(n, seed=11), "X": drand48(3 * n, seed=12).reshape(3, n),
+         "bc": {"pot": None, "mixed": (np.arange(n) % 3 == 0).astype(np.uint8), "nd": np.ones(n, dtype=np.uint8)}, "ref": {}}
+
+    def refs():
+        for name, bc in d["bc"].items():
+            p = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, bc=bc, p_max=8)
+            st = p.stats()
+            assert st["geometry_shared"] == 1 and st["l2l_ops"] > 0 and st["m2m_ops"] > 0 and st["m2l_pairs"] > 0
+            d["ref"][name] = (p.execute(d["x"]), p.execute_batch(d["X"]))
+            p.close()
+    _independent(fb, refs)
+    for a in d["ref"].values():
+        for b in a:
+            b.setflags(write=False)
+    return d
+
+
+def test_a_derived_plan_starts_clean_and_owns_its_own_state(fb, two):
+    """The base has a captured graph, recorded stage times, an order it last ran at and batch buffers; a plan made from it has
+    none of these, gives the bits of an independent plan, and neither plan's end touches the other."""
+    v, x, X, ref = two["v"], two["x"], two["X"], two["ref"]
+    base = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, p_max=8)
+    base.set_graphs(True)
+    for _ in range(3):                                  # launch by launch, captured, replayed
+        assert np.array_equal(base.execute(x), ref["pot"][0])
+    base.set_timing(True)                               # (timed executes go out launch by launch)
+    for _ in range(3):
+        assert np.array_equal(base.execute(x), ref["pot"][0])
+    assert base.batch_width() > 1                       # the batch allocates its buffers
+    assert np.array_equal(base.execute_batch(X), ref["pot"][1])
+    st = base.stats()
+    assert st["timed_executes"] > 0 and st["last_p"] == 8
+    like = base.like(two["bc"]["mixed"])
+    st = like.stats()
+    assert st["timed_executes"] == 0 and st["last_p"] == 0 and st["geometry_shared"] == 2
+    assert np.array_equal(like.execute(x), ref["mixed"][0])
+    assert np.array_equal(like.execute_batch(X), ref["mixed"][1])
+    assert np.array_equal(base.execute(x), ref["pot"][0])
+    like.close()
+    assert np.array_equal(base.execute(x), ref["pot"][0])
+    assert np.array_equal(base.execute_batch(X), ref["pot"][1])
+    second = base.like(two["bc"]["nd"])
+    base.close()
+    assert second.stats()["geometry_shared"] == 1
+    assert np.array_equal(second.execute(x), ref["nd"][0])
+    assert np.array_equal(second.execute_batch(X), ref["nd"][1])
+    second.close()
+
+
+@pytest.mark.parametrize("first", ["base", "like"])
+def test_a_derived_plan_has_no_block_inverse_until_it_builds_its_own(fb, first):
+    v = fb.unit_sphere(5)
+    n = len(v)
+    o = fb.FMMOptions()
+    o.local_evaluation, o.lazy_evaluation, o.sparse_local, o.block_diagonal = False, False, True, True
+    mixed = (np.arange(n) % 3 == 0).astype(np.uint8)
+    w = drand48(n, seed=13)
+    K = fb.LaplaceSphericalBEM(8, 3)
+
+    def refs():
+        out = []
+        for bc in (None, mixed):
+            p = fb.FMM_plan(K, v, o, bc=bc)
+            p.block_inverse_build()
+            out.append(p.block_inverse_apply(w))
+            p.close()
+        return out
+    ref_base, ref_like = _independent(fb, refs)
+    assert not np.array_equal(ref_base, ref_like)
+    base = fb.FMM_plan(K, v, o)
+    base.block_inverse_build()
+    assert base.block_inverse_bytes() > 0
+    like = base.like(mixed)
+    assert like.stats()["geometry_shared"] == 2 and like.block_inverse_bytes() == 0
+    with pytest.raises(fb.FmmBemError):
+        like.block_inverse_apply(w)
+    like.block_inverse_build()
+    assert like.block_inverse_bytes() == base.block_inverse_bytes()
+    assert np.array_equal(base.block_inverse_apply(w), ref_base) and np.array_equal(like.block_inverse_apply(w), ref_like)
+    (base if first == "base" else like).close()
+    if first == "base":
+        assert np.array_equal(like.block_inverse_apply(w), ref_like)
+        like.close()
+    else:
+        assert np.array_equal(base.block_inverse_apply(w), ref_base)
+        base.close()
+
+
+def test_the_cache_forgets_a_geometry_whose_plans_are_gone(fb, two):
+    """A plan created after the only holder of its geometry was closed builds its own.  (A geometry that lives on in a derived
+    plan after its first plan is closed is still recognised: `fourth` in the first test of this file.)  p_max = 9: a geometry
+    no other test of this process holds."""
+    v, x = two["v"], two["x"]
+    make = lambda: fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, p_max=9)
+
+    def ref():
+        p = make()
+        y = p.execute(x)
+        p.close()
+        return y
+    y_ref = _independent(fb, ref)
+    a = make()
+    assert a.stats()["geometry_shared"] == 1
+    a.close()
+    b = make()
+    assert b.stats()["geometry_shared"] == 1
+    assert np.array_equal(b.execute(x), y_ref)
+    c = make()                                          # ... and b's is recognised
+    assert b.stats()["geometry_shared"] == 2
+    assert np.array_equal(c.execute(x), y_ref)
+    b.close()
+    c.close()
+
+
+def test_a_batch_leaves_the_plan_as_it_was(fb, two):
+    """execute_batch runs vector j's far field on vector j's buffers; the plan's own are what a single execute uses afterwards."""
+    v, x, X, ref = two["v"], two["x"], two["X"], two["ref"]
+    p = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, bc=two["bc"]["mixed"], p_max=8)
+    assert p.batch_width() > 1
+    before = p.execute(x)
+    assert np.array_equal(before, ref["mixed"][0])
+    assert np.array_equal(p.execute_batch(X), ref["mixed"][1])
+    assert np.array_equal(p.execute(x), before)
+    p.close()
