@@ -32,6 +32,10 @@ hipError_t launch_scatter_y(const DevicePlan& d, double* y, hipStream_t s);
 hipError_t launch_assemble_slices(const DevicePlan& d, const double* slices, double* y, int world, const int64_t* d_cut, int64_t chunk,
                                   hipStream_t s);
 hipError_t launch_p2m(const DevicePlan& d, int p, hipStream_t s);
+// kernels_near.hip: launch_near_spmv and launch_p2m as ONE grid, the P2M workgroups queued behind the near field's -- bit for bit
+// the two launches; only the plans and orders at which those take near_spmv_pipe_kernel and p2m_stream_kernel (near_p2m_ok)
+bool near_p2m_ok(const DevicePlan& d, int p);
+hipError_t launch_near_p2m(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_p2m_table(const DevicePlan& d, double2* tab, hipStream_t s);
 hipError_t launch_p2m_table_grad(const DevicePlan& d, double2* tab, hipStream_t s);     // one-off: fills DevicePlan::p2m_tab's storage
 hipError_t launch_m2m_level(const DevicePlan& d, const ShiftOpDev& op, int p, int first, int count, hipStream_t s);

@@ -7,6 +7,7 @@
 //   scatter_y       y[perm[i]] = y_tree[i]        (EvalInteractionLazySparse.hpp:146-148)
 #include "device_launch.hpp"
 #include "near_entry.hpp"
+#include "p2m_stream.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1008,6 +1009,24 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_spmv_pipe_k
   __shared__ double part[1][kSpmvWaves][kColRows];
   const NearVecs<1> vecs{{d.xt}, {d.yt}};
   spmv_pipe_run<NearF64, kRows, kVecs, 1>(d, vecs, xs_all, part, blockIdx.x, gridDim.x, d.near_rec ? d.near_nitems_stream : d.near_nitems);
+}
+
+// near_spmv_pipe_kernel<kRows, kVecs> and the streaming P2M in ONE grid (launch_near_p2m).  The near field's workgroups are
+// exactly what is resident at once and finish over a window of tens of microseconds (the static deal leaves the heaviest one
+// largest item more than the lightest); P2M needs gather_x alone, is bound by the same HBM the draining workgroups free, and has
+// neither a barrier nor LDS of its own.  Workgroups are dispatched in order as slots free up, so the P2M workgroups behind the
+// near_grid near ones start CU by CU where those retire -- on the caller's stream, no fork.  The near branch is
+// near_spmv_pipe_kernel's line with near_grid as the stride, the P2M branch is p2m_stream_kernel's: the bits of both.
+template <int kRows, int kVecs>
+__global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_p2m_kernel(DevicePlan d, const int near_grid, const int P) {
+  extern __shared__ double xs_all[];
+  __shared__ double part[1][kSpmvWaves][kColRows];
+  if ((int)blockIdx.x < near_grid) {
+    const NearVecs<1> vecs{{d.xt}, {d.yt}};
+    spmv_pipe_run<NearF64, kRows, kVecs, 1>(d, vecs, xs_all, part, blockIdx.x, near_grid, d.near_nitems);
+  } else {
+    p2m_stream_run(d, P, (int)blockIdx.x - near_grid, (int)gridDim.x - near_grid);
+  }
 }
 
 constexpr int batch_occ(int nv) { return nv <= 2 ? 4 : nv <= 4 ? 2 : 1; }
@@ -2055,6 +2074,25 @@ hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s) {
   } else {
     hipLaunchKernelGGL((near_spmv_kernel<2, 4>), g, b, lds, s, d);
   }
+  return hipGetLastError();
+}
+
+// The near field and P2M as one launch (near_p2m_kernel): the plans where launch_near_spmv takes near_spmv_pipe_kernel and
+// launch_p2m takes p2m_stream_kernel at order p, both non-empty.  The caller (fmmbem_plan::run) rules out what it alone knows:
+// hybrid and float near fields, target plans, partial executes, stage timing.
+bool near_p2m_ok(const DevicePlan& d, int p) {
+  const char* se = std::getenv("FMMBEM_P2M_STREAM");                 // read per launch, as launch_p2m does
+  const bool stream_off = se && std::atoi(se) == 0;
+  return !d.near_rec && d.near_nitems > 0 && d.dof == 1 && d.max_runs <= kSpmvWaves * kWave &&
+         d.n_p2m > 0 && d.p2m_tab && d.n_act == 1 && p >= 1 && p <= 16 && p * (p + 1) / 2 > kWave / 2 && !stream_off;
+}
+
+hipError_t launch_near_p2m(const DevicePlan& d, int p, hipStream_t s) {
+  if (!near_p2m_ok(d, p)) return hipErrorInvalidValue;
+  const int near_grid = std::min(d.near_nitems, 256 * kSpmvOcc);     // launch_near_spmv's grid
+  const int nb = (d.n_p2m + 3) / 4, p2m_grid = nb < 256 * 8 ? nb : 256 * 8;   // launch_p2m's grid
+  const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
+  hipLaunchKernelGGL((near_p2m_kernel<2, 4>), dim3(near_grid + p2m_grid), dim3(kSpmvWaves * kWave), lds2, s, d, near_grid, p);
   return hipGetLastError();
 }
 

@@ -1474,14 +1474,26 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   }
   const bool near_here = !(phase == 2 && pending_near);
   pending_near = false;
-  TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0) + (fold ? 16 : 0), xbuf, [&](hipStream_t s) -> int {
-  if (near_here) TRY(near_field(s));
+  // The near field and P2M as ONE launch (launch_near_p2m: the P2M workgroups start where the near field's retire) on a whole
+  // execute whose near field is near_spmv_pipe_kernel and whose P2M is p2m_stream_kernel.  Stage timing keeps the two launches:
+  // its events bracket the near kernel alone.  FMMBEM_NEAR_P2M, read per launch: 0 = separate launches, 2 = one launch or
+  // FMMBEM_ERR_UNSUPPORTED (tests: proves which path ran), otherwise one launch where eligible.
+  const char* fuse_env = std::getenv("FMMBEM_NEAR_P2M");
+  const int fuse_mode = fuse_env ? std::atoi(fuse_env) : 1;
+  const bool fuse = fuse_mode != 0 && phase == 0 && !near_only && !targets && tm == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
+                    d.kernel != FMMBEM_KERNEL_STOKES_BEM && near_p2m_ok(d, p);
+  if (fuse_mode == 2 && !fuse) return fail(FMMBEM_ERR_UNSUPPORTED, "FMMBEM_NEAR_P2M=2: this execute does not take the combined near-field / P2M launch");
+  TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0) + (fold ? 16 : 0) + (fuse ? 32 : 0), xbuf, [&](hipStream_t s) -> int {
+  if (fuse) HIP_TRY(launch_near_p2m(d, p, s));
+  else if (near_here) TRY(near_field(s));
   if (!near_only) {
     if (phase == 0) {
+      if (!fuse) {
       HIP_TRY(begin(3, s));
       if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); }));
       else if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
       HIP_TRY(end(3, s));
+      }
       HIP_TRY(begin(4, s));
       TRY(m2m_pass(d, p, false, s));
       HIP_TRY(end(4, s));
