@@ -11,9 +11,8 @@ namespace fmmbem {
 hipError_t launch_near_assemble(const DevicePlan& d, hipStream_t s);
 hipError_t launch_gather_x(const DevicePlan& d, const double* x, hipStream_t s);
 hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s);
-// float near field (fmmbem_options.near_f32_max_p): which plans the float kernels serve; the copy of the stored values into
-// DevicePlan::near_f32 (after the assembly); the pass that streams it instead of launch_near_spmv
-bool near_f32_ok(int dof, int max_runs, bool stokes_sym);
+// float near field (fmmbem_options.near_f32_max_p; the plans it serves: near_f32_ok, launch_choice.hpp): the copy of the stored
+// values into DevicePlan::near_f32 (after the assembly); the pass that streams it instead of launch_near_spmv
 hipError_t launch_near_to_f32(const DevicePlan& d, hipStream_t s);
 hipError_t launch_near_spmv_f32(const DevicePlan& d, hipStream_t s);
 struct HybridStreams { hipStream_t recompute = nullptr; hipEvent_t fork = nullptr, join_recompute = nullptr; };
@@ -33,8 +32,8 @@ hipError_t launch_assemble_slices(const DevicePlan& d, const double* slices, dou
                                   hipStream_t s);
 hipError_t launch_p2m(const DevicePlan& d, int p, hipStream_t s);
 // kernels_near.hip: launch_near_spmv and launch_p2m as ONE grid, the P2M workgroups queued behind the near field's -- bit for bit
-// the two launches; only the plans and orders at which those take near_spmv_pipe_kernel and p2m_stream_kernel (near_p2m_ok)
-bool near_p2m_ok(const DevicePlan& d, int p);
+// the two launches; only the plans and orders at which those take near_spmv_pipe_kernel and p2m_stream_kernel (near_p2m_ok,
+// launch_choice.hpp)
 hipError_t launch_near_p2m(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_p2m_table(const DevicePlan& d, double2* tab, hipStream_t s);
 hipError_t launch_p2m_table_grad(const DevicePlan& d, double2* tab, hipStream_t s);     // one-off: fills DevicePlan::p2m_tab's storage
@@ -80,12 +79,10 @@ struct BatchVecs {                                     // per vector of the pass
   int width;                                           // slots allocated: 2, 4 or 8 (Stokes: 2, 3 or 4)
 };
 // the pipelined one-unknown SpMV (near_spmv_pipe_kernel) for nv vectors: bit for bit nv calls of launch_near_spmv; plans where
-// launch_near_spmv takes that kernel only (batch_near_ok)
-bool batch_near_ok(const DevicePlan& d);
+// launch_near_spmv takes that kernel only (batch_near_ok, launch_choice.hpp)
 hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s);
 // near_spmv_sym3 (Stokes, symmetric blocks) for nv = 2 .. 4 vectors: bit for bit nv calls of launch_near_spmv; the plans it serves
-// at a pass of `width` vectors (fmmbem_options.stokes_batch_width)
-bool batch_near_sym3_ok(const DevicePlan& d, int width);
+// at a pass of `width` vectors (fmmbem_options.stokes_batch_width; batch_near_sym3_ok, launch_choice.hpp)
 hipError_t launch_near_sym3_multi(const DevicePlan& d, const BatchVecs& b, hipStream_t s);
 // P2M for nv vectors: the streaming kernel once where launch_p2m streams (one live slot, p >= 8), else launch_p2m per vector
 hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s);

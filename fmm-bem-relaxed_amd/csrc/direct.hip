@@ -15,55 +15,11 @@
 #include "../../include/fmmbem.h"
 #include "device_launch.hpp"
 #include "host_plan.hpp"
+#include "status.hpp"
 
-namespace fmmbem {
-int fail(int code, const std::string& msg);            // plan.hip
-}
 using namespace fmmbem;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(e_ == hipErrorOutOfMemory ? FMMBEM_ERR_ALLOC : FMMBEM_ERR_HIP,                  \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                              \
-  } while (0)
-#define TRY(expr) do { int rc_ = (expr); if (rc_ != FMMBEM_OK) return rc_; } while (0)
-
-struct DeviceScope {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    err = hipGetDevice(&prev);
-    if (err != hipSuccess) { prev = -1; return; }
-    if (prev != dev) err = hipSetDevice(dev); else prev = -1;
-  }
-  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// device memory of one call, freed when the call returns
-struct Scratch {
-  std::vector<void*> v;
-  ~Scratch() { for (void* p : v) (void)hipFree(p); }
-  template <class T>
-  int alloc(size_t count, T** dst) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, count ? count * sizeof(T) : 1));
-    v.push_back(p);
-    *dst = static_cast<T*>(p);
-    return FMMBEM_OK;
-  }
-  template <class T>
-  int up(const T* src, size_t count, const T** dst) {
-    T* p = nullptr;
-    TRY(alloc(count, &p));
-    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = p;
-    return FMMBEM_OK;
-  }
-};
 
 bool all_finite(const double* v, size_t count) {
   for (size_t i = 0; i < count; ++i)
@@ -84,7 +40,7 @@ struct fmmbem_direct {
   double* part = nullptr;                              // [chunk][target][dof] partial sums, grown on demand
   size_t part_cap = 0;                                 // doubles
   ~fmmbem_direct() {
-    DeviceScope g(device);
+    DeviceGuard g(device);
     for (void* p : allocs) (void)hipFree(p);
     if (part) (void)hipFree(part);
     if (stream) (void)hipStreamDestroy(stream);
@@ -196,7 +152,7 @@ int fmmbem_direct_create(const fmmbem_options* opts, size_t n_sources, const dou
   std::unique_ptr<fmmbem_direct> h(new (std::nothrow) fmmbem_direct);
   if (!h) return fail(FMMBEM_ERR_ALLOC, "Direct handle");
   h->device = opts->device; h->n = (int64_t)n_sources;
-  DeviceScope guard(h->device);
+  DeviceGuard guard(h->device);
   HIP_TRY(guard.err);
   try {
     TRY(h->init(*opts, rule, fine, source_vertices));
@@ -213,7 +169,7 @@ int fmmbem_direct_apply_device(fmmbem_direct* direct, size_t n_targets, const do
   if (n_targets == 0) return fail(FMMBEM_ERR_INVALID, "Direct: no targets");
   if (!d_target_points && n_targets != (size_t)direct->n)
     return fail(FMMBEM_ERR_INVALID, "Direct: the symmetric form (no target points) takes n_targets = n_sources");
-  DeviceScope guard(direct->device);
+  DeviceGuard guard(direct->device);
   HIP_TRY(guard.err);
   return direct->apply(n_targets, d_target_points, d_target_bc, d_x, d_y, static_cast<hipStream_t>(stream));
 }
@@ -225,7 +181,7 @@ int fmmbem_direct_apply(fmmbem_direct* direct, size_t n_targets, const double* t
   if (!target_points && n_targets != (size_t)direct->n)
     return fail(FMMBEM_ERR_INVALID, "Direct: the symmetric form (no target points) takes n_targets = n_sources");
   if (target_points && !all_finite(target_points, 3 * n_targets)) return fail(FMMBEM_ERR_INVALID, "Direct: a target point is not finite");
-  DeviceScope guard(direct->device);
+  DeviceGuard guard(direct->device);
   HIP_TRY(guard.err);
   const size_t dof = (size_t)direct->d.dof;
   Scratch sc;

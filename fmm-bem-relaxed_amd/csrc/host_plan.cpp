@@ -1,5 +1,6 @@
 // host_plan.cpp -- see host_plan.hpp.  Host-only C++17; no device code here.
 #include "host_plan.hpp"
+#include "switches.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -19,6 +20,21 @@
 #include <unordered_map>
 
 namespace fmmbem {
+
+namespace {
+// FMMBEM_BUILD_TRACE: phase times of a build step on stderr (tuning aid)
+struct PhaseTrace {
+  const char* who; int width;
+  const bool on = sw::build_trace();
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "%s %-*s %8.2f ms\n", who, width, what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  }
+};
+}  // namespace
 
 // ---- host_parallel: a small persistent pool (host_plan.hpp) ----
 namespace {
@@ -335,7 +351,7 @@ bool build_tree(HostPlan& hp, unsigned L, const std::vector<double>& cen, double
   for (int k = 0; k < 3; ++k) hp.cell[k] = (ext_hi[k] - hp.pmin[k]) / std::ldexp(1.0, (int)L);
   // ---- Morton codes (Octree.hpp:118-129) ----
   std::vector<Coded> codes(n), scratch(n);
-  const bool serial = n < (1 << 15) || (std::getenv("FMMBEM_TREE_SERIAL") && std::atoi(std::getenv("FMMBEM_TREE_SERIAL")) != 0);
+  const bool serial = n < (1 << 15) || sw::tree_serial();
   par_shares(serial ? 1 : host_threads(n, 1 << 14), n, [&](int64_t i0, int64_t i1, int) {
     for (int64_t i = i0; i < i1; ++i) {
       Code s[3];
@@ -348,9 +364,7 @@ bool build_tree(HostPlan& hp, unsigned L, const std::vector<double>& cen, double
       codes[i] = {(Code)(spread3(s[0]) | (spread3(s[1]) << 1) | (spread3(s[2]) << 2)), (uint32_t)i};
     }
   });
-  const bool trace_t = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
-  auto tt = std::chrono::steady_clock::now();
-  auto tmark = [&](const char* w) { if (!trace_t) return; const auto now = std::chrono::steady_clock::now(); std::fprintf(stderr, "  build_tree %-20s %8.2f ms\n", w, std::chrono::duration<double, std::milli>(now - tt).count()); tt = now; };
+  PhaseTrace tmark{"  build_tree", 20};
   tmark("codes");
   std::vector<Code> key(1, (Code)1);
   hp.box_parent.assign(1, 0);
@@ -622,14 +636,7 @@ void fill_panel(PanelSoA& P, int64_t n, int64_t i, const double* v, const QuadRu
 
 std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double* vertices, const uint8_t* bc) {
   // FMMBEM_BUILD_TRACE=1: phase times of this function on stderr (tuning aid)
-  const bool trace = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!trace) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "host_plan %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
+  PhaseTrace mark{"host_plan", 28};
   opt = o;
   n = n_panels;
   if (n <= 0 || !vertices) return "no panels";
@@ -693,14 +700,7 @@ std::string HostPlan::build(const HostOptions& o, int64_t n_panels, const double
 // their panels themselves.
 std::string HostPlan::finish(const double* vertices, const uint8_t* bc) {
   const HostOptions& o = opt;
-  const bool trace = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!trace) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "host_plan %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
+  PhaseTrace mark{"host_plan", 28};
   // ---- leaves in tree order ----
   box_leaf_index.assign(nboxes, -1);
   for (int b = 0; b < nboxes; ++b)
@@ -1204,11 +1204,9 @@ void partition_leaves(const HostPlan& hp, int world, std::vector<int>& cut) {
 void HostPlan::build_rot_items() {
   constexpr int kLanes = 64, kSimds = 1024;
   constexpr int kItemsWanted = 4 * 1024;
-  int kRotItemPasses = 2, kRotLongMax = 16, kRotLongRounds = 0;   // rounds: 0 = by the rule below
-  if (const char* e = std::getenv("FMMBEM_ROT_LONG_ROUNDS")) kRotLongRounds = std::max(0, std::atoi(e));
+  int kRotLongRounds = sw::rot_long_rounds();   // 0 = by the rule below
   // the two knobs of the cut, for the test that ANY cut of the list gives the same bits (tests/test_gpu_parity.py)
-  if (const char* e = std::getenv("FMMBEM_ROT_ITEM_PASSES")) kRotItemPasses = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("FMMBEM_ROT_LONG_MAX")) kRotLongMax = std::max(1, std::atoi(e));
+  const int kRotItemPasses = sw::rot_item_passes(), kRotLongMax = sw::rot_long_max();
   rot_src.clear(); rot_cls.clear(); rot_tgt.clear(); rot_empty.clear();
   rot_item_ptr.assign(1, 0);
   rot_item_ptr_long.assign(1, 0);

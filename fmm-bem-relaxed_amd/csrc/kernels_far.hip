@@ -23,6 +23,7 @@
 // (j,k) outputs, Yh staged in LDS, Mh read through the scalar cache (wave-uniform), L accumulated
 // in registers over the whole source list and written once -- no atomics, fixed summation order.
 #include "device_launch.hpp"
+#include "launch_choice.hpp"
 #include "p2m_stream.hpp"
 #define FMMBEM_INLINE __attribute__((always_inline))
 
@@ -33,8 +34,7 @@ namespace fmmbem {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kPmaxDev = 16, kSmax = kPmaxDev * (kPmaxDev + 1) / 2;
+constexpr int kSmax = kPmaxDev * (kPmaxDev + 1) / 2;
 constexpr double kEps = 1e-12;                         // kernel/LaplaceSpherical.hpp:30
 
 // stored index -> (j,k), up to p = 16
@@ -110,7 +110,6 @@ __device__ __forceinline__ double from_upper_half(double v) {
   return __hiloint2double((int)b[1], (int)a[1]);
 }
 
-constexpr int kP2MWaves = 4;                          // independent leaves per workgroup
 struct D4 { double x, y, z, w; };
 typedef __attribute__((address_space(4))) D4 ConstD4;  // wave-uniform constants through the scalar cache
 
@@ -893,7 +892,6 @@ constexpr int kL2PLeaves = 8, kL2PWaves = 4;
 // SIMD; groups of at most 4 leaves (plan.hip asks l2p_group_leaves) halve it
 constexpr int kL2PLeavesStokes = 4;
 constexpr int kL2PUnrollMax = 12;                     // orders with an L2P kernel of their own (the orders of the rotation kernels)
-static bool l2p_generic() { const char* e = std::getenv("FMMBEM_L2P_GENERIC"); return e && std::atoi(e) != 0; }   // A/B runs
 // The Legendre step of the Laplace L2P, carried on q_n = rho^n P_n^m:  q_{n+1} = c1 (rho cos a) q_n - c2 rho^2 q_{n-1},
 // c1 = (2n+1)/(n-m+1), c2 = (n+m)/(n-m+1) (c1 = 2m+1, c2 = 0 on the diagonal n = m): the doubles fill_step_tables forms, and
 // kRecip[k] is the host's 1.0 / k.  With n and m known at compile time they fold to literals; the run-time kernel reads the
@@ -1160,63 +1158,45 @@ hipError_t upload_constants_once() {
 
 }  // namespace
 
-hipError_t launch_p2m_table(const DevicePlan& d, double2* tab, hipStream_t s) {
+// NTV records per panel; FMMBEM_P2M_TABLE_POINTS=0: the point-by-point kernel at every rule (A/B: the same records to <= 4e-16)
+template <int NTV>
+static hipError_t p2m_table_with(const DevicePlan& d, double2* tab, hipStream_t s) {
   if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
   if (d.n_p2m <= 0) return hipSuccess;
   const dim3 g(d.n_p2m < 256 * 32 ? d.n_p2m : 256 * 32), b(kWave);
-  // FMMBEM_P2M_TABLE_POINTS=0: the point-by-point kernel at every rule (A/B: the same records to <= 4e-16)
-  const bool pts = !(std::getenv("FMMBEM_P2M_TABLE_POINTS") && std::atoi(std::getenv("FMMBEM_P2M_TABLE_POINTS")) == 0);
-#define P2M_TABLE_CASE(NTV)                                                                             \
-  if (pts && d.nq == 1) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 1>), g, b, 0, s, d, tab);       \
-  else if (pts && d.nq == 3) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 3>), g, b, 0, s, d, tab);  \
-  else if (pts && d.nq == 4) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 4>), g, b, 0, s, d, tab);  \
-  else hipLaunchKernelGGL((p2m_table_kernel<NTV>), g, b, 0, s, d, tab)
-  if (d.kernel == 1) { P2M_TABLE_CASE(4); } else { P2M_TABLE_CASE(1); }
+  const bool pts = sw::p2m_table_points();
+  if (pts && d.nq == 1) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 1>), g, b, 0, s, d, tab);
+  else if (pts && d.nq == 3) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 3>), g, b, 0, s, d, tab);
+  else if (pts && d.nq == 4) hipLaunchKernelGGL((p2m_table_points_kernel<NTV, 4>), g, b, 0, s, d, tab);
+  else hipLaunchKernelGGL((p2m_table_kernel<NTV>), g, b, 0, s, d, tab);
   return hipGetLastError();
 }
-
-hipError_t launch_p2m_table_grad(const DevicePlan& d, double2* tab, hipStream_t s) {      // Stokes double layer: three gradient records per panel
-  if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
-  if (d.n_p2m <= 0) return hipSuccess;
-  const dim3 g(d.n_p2m < 256 * 32 ? d.n_p2m : 256 * 32), b(kWave);
-  const bool pts = !(std::getenv("FMMBEM_P2M_TABLE_POINTS") && std::atoi(std::getenv("FMMBEM_P2M_TABLE_POINTS")) == 0);
-  P2M_TABLE_CASE(3);
-#undef P2M_TABLE_CASE
-  return hipGetLastError();
-}
+hipError_t launch_p2m_table(const DevicePlan& d, double2* tab, hipStream_t s) { return d.kernel == 1 ? p2m_table_with<4>(d, tab, s) : p2m_table_with<1>(d, tab, s); }
+hipError_t launch_p2m_table_grad(const DevicePlan& d, double2* tab, hipStream_t s) { return p2m_table_with<3>(d, tab, s); }   // Stokes double layer: three gradient records per panel
 
 hipError_t launch_p2m(const DevicePlan& d, int p, hipStream_t s) {
   if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
-  if (d.n_p2m <= 0) return hipSuccess;
-  if (p < 1 || p > kPmaxDev) return hipErrorInvalidValue;
-  if (d.p2m_tab) {
-    const int nb = (d.n_p2m + 3) / 4;
-    const char* se = std::getenv("FMMBEM_P2M_STREAM");               // read per launch: tests switch it per plan
-    const bool stream_off = se && std::atoi(se) == 0;
-    if (d.n_act == 1 && p * (p + 1) / 2 > kWave / 2 && !stream_off)      // one expansion per box, more than 32 coefficients
-      hipLaunchKernelGGL(p2m_stream_kernel, dim3(nb < 256 * 8 ? nb : 256 * 8), dim3(4 * kWave), 0, s, d, p);
-    else
-      hipLaunchKernelGGL((p2m_apply_kernel<1>), dim3(nb < 256 * 16 ? nb : 256 * 16), dim3(4 * kWave), 0, s, d, p);
-    return hipGetLastError();
-  }
-  const int nblk = (d.n_p2m + kP2MWaves - 1) / kP2MWaves;
-  const dim3 g(nblk < 256 * 8 ? nblk : 256 * 8), b(kP2MWaves * kWave);
-  for (int a = 0; a < d.n_act; ++a) {
-    if (d.act[a] == 0) hipLaunchKernelGGL((p2m_kernel<0>), g, b, 0, s, d, p, 0, 0);
-    else hipLaunchKernelGGL((p2m_kernel<1>), g, b, 0, s, d, p, 0, 1);
-  }
+  const P2MForm f = p2m_form(d, p);
+  if (f == P2MForm::Empty) return hipSuccess;
+  if (f == P2MForm::Invalid) return hipErrorInvalidValue;
+  const dim3 g(p2m_grid(d, f));
+  if (f == P2MForm::Stream) hipLaunchKernelGGL(p2m_stream_kernel, g, dim3(4 * kWave), 0, s, d, p);
+  else if (f == P2MForm::Apply) hipLaunchKernelGGL((p2m_apply_kernel<1>), g, dim3(4 * kWave), 0, s, d, p);
+  else
+    for (int a = 0; a < d.n_act; ++a) {
+      if (d.act[a] == 0) hipLaunchKernelGGL((p2m_kernel<0>), g, dim3(kP2MWaves * kWave), 0, s, d, p, 0, 0);
+      else hipLaunchKernelGGL((p2m_kernel<1>), g, dim3(kP2MWaves * kWave), 0, s, d, p, 0, 1);
+    }
   return hipGetLastError();
 }
 
 hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipStream_t s) {
   if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
   if (b.nv < 1 || b.nv > b.width || b.width > kBatchMax) return hipErrorInvalidValue;
-  if (d.n_p2m <= 0) return hipSuccess;
-  if (p < 1 || p > kPmaxDev) return hipErrorInvalidValue;
-  const char* se = std::getenv("FMMBEM_P2M_STREAM");
-  const bool stream_off = se && std::atoi(se) == 0;
-  // exactly the case in which launch_p2m takes p2m_stream_kernel; elsewhere its own choice, once per vector
-  if (b.nv == 1 || !d.p2m_tab || d.n_act != 1 || p * (p + 1) / 2 <= kWave / 2 || stream_off) {
+  const P2MForm f = p2m_form(d, p);
+  if (f == P2MForm::Empty) return hipSuccess;
+  if (f == P2MForm::Invalid) return hipErrorInvalidValue;
+  if (b.nv == 1 || f != P2MForm::Stream) {            // only the streaming kernel takes several vectors
     for (int j = 0; j < b.nv; ++j) {
       DevicePlan dj = d;
       dj.xt = b.xt[j]; dj.M = b.M[j];
@@ -1227,8 +1207,7 @@ hipError_t launch_p2m_multi(const DevicePlan& d, const BatchVecs& b, int p, hipS
   // the kernel for 2, 4 or 8 vectors; slots nv .. of a short pass are the batch's scratch and their moments are never read
   const int nv = b.nv <= 2 ? 2 : b.nv <= 4 ? 4 : 8;
   if (nv > b.width) return hipErrorInvalidValue;
-  const int nb = (d.n_p2m + 3) / 4;
-  const dim3 g(nb < 256 * 8 ? nb : 256 * 8), t(4 * kWave);
+  const dim3 g(p2m_grid(d, f)), t(4 * kWave);
   if (nv == 2) hipLaunchKernelGGL(p2m_stream_multi_kernel<2>, g, t, 0, s, d, p, b);
   else if (nv == 4) hipLaunchKernelGGL(p2m_stream_multi_kernel<4>, g, t, 0, s, d, p, b);
   else hipLaunchKernelGGL(p2m_stream_multi_kernel<8>, g, t, 0, s, d, p, b);
@@ -1346,7 +1325,7 @@ hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s, cons
   const size_t lds = sizeof(double2) * (size_t)((3 * S + 1) / 2) + nw * per_wave;
   const dim3 grid(nblk < 256 * 8 ? nblk : 256 * 8), block(nw * kWave);
 #define L2P_CASE(PP) case PP: hipLaunchKernelGGL(l2p_kernel<PP>, grid, block, lds, s, d, p, y, store ? 1 : 0, perm, y_out); break;
-  switch (p <= kL2PUnrollMax && !l2p_generic() ? p : 0) {
+  switch (p <= kL2PUnrollMax && !sw::l2p_generic() ? p : 0) {
     L2P_CASE(1) L2P_CASE(2) L2P_CASE(3) L2P_CASE(4) L2P_CASE(5) L2P_CASE(6) L2P_CASE(7) L2P_CASE(8)
     L2P_CASE(9) L2P_CASE(10) L2P_CASE(11) L2P_CASE(12)
     default: hipLaunchKernelGGL(l2p_kernel<0>, grid, block, lds, s, d, p, y, store ? 1 : 0, perm, y_out);
@@ -1362,20 +1341,16 @@ hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s) {
   if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
   if (d.n_p2m <= 0) return hipSuccess;
   if (p < 1 || p > kPmaxDev) return hipErrorInvalidValue;
-  const int nb = (d.n_p2m + 3) / 4;
-  const int nblk_r = (d.n_p2m + kP2MWaves - 1) / kP2MWaves;
-  const dim3 gr(nblk_r < 256 * 8 ? nblk_r : 256 * 8), br(kP2MWaves * kWave);
-  if (d.p2m_tab_g) hipLaunchKernelGGL((p2m_apply_kernel<3>), dim3(nb < 256 * 16 ? nb : 256 * 16), dim3(4 * kWave), 0, s, d, p);
+  const dim3 ga(p2m_grid(d, P2MForm::Apply)), ba(4 * kWave), gr(p2m_grid(d, P2MForm::Recurrence)), br(kP2MWaves * kWave);
+  if (d.p2m_tab_g) hipLaunchKernelGGL((p2m_apply_kernel<3>), ga, ba, 0, s, d, p);
   else if (d.stokes_traction_targets)                  // no gradient records (FMMBEM_P2M_TABLE=0, or more than 16 GB of them): the recurrences, slot by slot
     for (int e = 0; e < 7; ++e) hipLaunchKernelGGL((p2m_kernel<1>), gr, br, 0, s, d, p, 5 + e, 4 + e);
   if (!d.stokes_velocity_targets) return hipGetLastError();
   if (d.p2m_tab) {
-    hipLaunchKernelGGL((p2m_apply_kernel<4>), dim3(nb < 256 * 16 ? nb : 256 * 16), dim3(4 * kWave), 0, s, d, p);
+    hipLaunchKernelGGL((p2m_apply_kernel<4>), ga, ba, 0, s, d, p);
     return hipGetLastError();
   }
-  const int nblk = (d.n_p2m + kP2MWaves - 1) / kP2MWaves;
-  const dim3 g(nblk < 256 * 8 ? nblk : 256 * 8), b(kP2MWaves * kWave);
-  for (int e = 0; e < 4; ++e) hipLaunchKernelGGL((p2m_kernel<0>), g, b, 0, s, d, p, e + 1, e);
+  for (int e = 0; e < 4; ++e) hipLaunchKernelGGL((p2m_kernel<0>), gr, br, 0, s, d, p, e + 1, e);
   return hipGetLastError();
 }
 
@@ -1395,7 +1370,7 @@ hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t 
     const dim3 grid(nblk < 256 * 8 ? nblk : 256 * 8), block(nw * kWave);
 #define L2PS_CASE(PP) case PP: if (trac) hipLaunchKernelGGL((l2p_stokes_kernel<true, PP>), grid, block, lds, s, d, p, y, store ? 1 : 0); \
                                else hipLaunchKernelGGL((l2p_stokes_kernel<false, PP>), grid, block, lds, s, d, p, y, store ? 1 : 0); break;
-    switch (p <= kL2PUnrollMax && !l2p_generic() ? p : 0) {
+    switch (p <= kL2PUnrollMax && !sw::l2p_generic() ? p : 0) {
       L2PS_CASE(1) L2PS_CASE(2) L2PS_CASE(3) L2PS_CASE(4) L2PS_CASE(5) L2PS_CASE(6) L2PS_CASE(7) L2PS_CASE(8)
       L2PS_CASE(9) L2PS_CASE(10) L2PS_CASE(11) L2PS_CASE(12)
       default: L2PS_CASE(0)

@@ -6,6 +6,7 @@
 //   near_spmv       y_tree = A_near * x_tree      (Matvec<>, include/Matvec.hpp:14-33) -- HBM-bound hot kernel
 //   scatter_y       y[perm[i]] = y_tree[i]        (EvalInteractionLazySparse.hpp:146-148)
 #include "device_launch.hpp"
+#include "launch_choice.hpp"
 #include "near_entry.hpp"
 #include "p2m_stream.hpp"
 
@@ -16,7 +17,6 @@ namespace fmmbem {
 
 namespace {
 
-constexpr int kWave = 64;
 typedef double dvec2 __attribute__((ext_vector_type(2)));   // native 16-B vector (nontemporal builtin needs it)
 
 __device__ inline double wave_sum(double v) {
@@ -705,10 +705,7 @@ __global__ void scatter_y_kernel(const uint32_t* __restrict__ perm, const double
 // This plain form serves Stokes (3 unknowns per panel, 2048-column chunks); one unknown per panel takes the pipelined
 // form further down.
 // ---------------------------------------------------------------------------------------------
-constexpr int kSpmvWaves = 4;
-constexpr int kSpmvChunk = 2048;                     // columns of x staged in LDS at a time (16 KiB)
-
-constexpr int kSpmvOcc = 5;                           // wavefronts per SIMD = workgroups per CU (82 VGPRs)
+// (kSpmvWaves, the chunk sizes and the workgroups per CU: launch_choice.hpp)
 constexpr int kColRows = 8;                           // work items with fewer rows split the COLUMNS over the wavefronts
 
 typedef float fvec4 __attribute__((ext_vector_type(4)));
@@ -720,7 +717,6 @@ struct NearVecs { const double* xt[NV]; double* yt[NV]; };
 // x chunk in LDS for the float rows: the four columns of 16-byte vector j live as two 16-byte pairs, columns 4j, 4j+1 at pair j of
 // the first half and 4j+2, 4j+3 at pair j of the second, so that the lanes of a wavefront read consecutive 16-byte slots
 // (columns in their natural order put the lanes 32 bytes apart: a 2-way bank conflict on every read)
-constexpr int kSpmvPipeChunk = 1024;                  // columns per x buffer of the pipelined form (2 x 8 KiB)
 __device__ __forceinline__ int f32_xpos(int c) { return ((c >> 1) & 1) * (kSpmvPipeChunk / 2) + ((c >> 2) << 1) + (c & 1); }
 
 // Element policies of the row loops: what a stored row is made of.  vec = a lane's nontemporal 16-byte load, 1 << kLog2Cols
@@ -1029,8 +1025,6 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSpmvOcc) void near_p2m_kernel(
   }
 }
 
-constexpr int batch_occ(int nv) { return nv <= 2 ? 4 : nv <= 4 ? 2 : 1; }
-
 template <int kRows, int kVecs, int NV>
 __global__ __launch_bounds__(kSpmvWaves * kWave, batch_occ(NV)) void near_spmv_pipe_multi_kernel(DevicePlan d, BatchVecs bv) {
   extern __shared__ double xs_all[];
@@ -1050,15 +1044,6 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, batch_occ(NV)) void near_spmv_p
 // near_spmv_sym3: the scheme of near_spmv_kernel with a PANEL row per wavefront step -- per source panel three 16-byte
 // vectors and the three x components from LDS feed nine FMAs into (y_x, y_y, y_z).
 // ---------------------------------------------------------------------------------------------
-#ifndef FMMBEM_SYM_OCC
-#define FMMBEM_SYM_OCC 5
-#endif
-#ifndef FMMBEM_SYM_CHUNK
-#define FMMBEM_SYM_CHUNK 1024
-#endif
-constexpr int kSymOcc = FMMBEM_SYM_OCC;               // workgroups per CU
-constexpr int kSymChunk = FMMBEM_SYM_CHUNK;           // source panels of x staged at a time (3 x 8 KiB)
-//
 // ONE loop, sym3_run<kRows, kVecs, NV>, serves two kernels that differ in NV alone, so the order of every sum is one text: chunks
 // of kSymChunk source panels with a later chunk added into y; the colsplit segments and the fixed sum ((p0 + p1) + p2) + p3 of
 // their parts; lane l taking the columns v0 + l, stepping by kVecs * 64; all kRows x kVecs x 3 loads issued before the first FMA;
@@ -1185,8 +1170,6 @@ __global__ __launch_bounds__(kSpmvWaves * kWave, kSymOcc) void near_spmv_sym3_ke
   const NearVecs<1> vecs{{d.xt}, {d.yt}};
   sym3_run<kRows, kVecs, 1>(d, vecs, xs, part);
 }
-
-constexpr int sym3_multi_occ(int nv) { return nv <= 2 ? 3 : nv == 3 ? 2 : 1; }   // workgroups per CU that 24 KiB of x per vector leave
 
 template <int kRows, int kVecs, int NV>
 __global__ __launch_bounds__(kSpmvWaves * kWave, sym3_multi_occ(NV)) void near_spmv_sym3_multi_kernel(DevicePlan d, BatchVecs bv) {
@@ -1931,31 +1914,23 @@ hipError_t launch_near_diag(const DevicePlan& d, const int* selfcol, double* out
   return hipGetLastError();
 }
 
-hipError_t launch_near_assemble(const DevicePlan& d, hipStream_t s) {
+// FMMBEM_ASM_COLS=0: the entry-per-thread kernel at every rule (A/B: the two give the same bits)
+static hipError_t near_assemble_with(const DevicePlan& d, hipStream_t s, void (*cols1)(DevicePlan), void (*cols3)(DevicePlan),
+                                     void (*cols4)(DevicePlan), void (*entries)(DevicePlan)) {
   const int nb = d.leaf_end - d.leaf_begin;
   if (nb <= 0) return hipSuccess;
   const size_t lds = ((size_t)kAsmChunk + 2 * (size_t)d.max_runs) * sizeof(int);
-  const dim3 g(nb < 256 * 8 ? nb : 256 * 8), b(256);
-  // FMMBEM_ASM_COLS=0: the entry-per-thread kernel at every rule (A/B: the two give the same bits)
-  const bool cols = !(std::getenv("FMMBEM_ASM_COLS") && std::atoi(std::getenv("FMMBEM_ASM_COLS")) == 0);
-  if (cols && d.nq == 1) hipLaunchKernelGGL(near_assemble_cols_kernel<1>, g, b, lds, s, d);
-  else if (cols && d.nq == 3) hipLaunchKernelGGL(near_assemble_cols_kernel<3>, g, b, lds, s, d);
-  else if (cols && d.nq == 4) hipLaunchKernelGGL(near_assemble_cols_kernel<4>, g, b, lds, s, d);
-  else hipLaunchKernelGGL(near_assemble_kernel, g, b, lds, s, d);
+  const bool cols = sw::asm_cols();
+  hipLaunchKernelGGL(cols && d.nq == 1 ? cols1 : cols && d.nq == 3 ? cols3 : cols && d.nq == 4 ? cols4 : entries,
+                     dim3(nb < 256 * 8 ? nb : 256 * 8), dim3(256), lds, s, d);
   return hipGetLastError();
 }
-
+hipError_t launch_near_assemble(const DevicePlan& d, hipStream_t s) {
+  return near_assemble_with(d, s, near_assemble_cols_kernel<1>, near_assemble_cols_kernel<3>, near_assemble_cols_kernel<4>, near_assemble_kernel);
+}
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s) {
-  const int nb = d.leaf_end - d.leaf_begin;
-  if (nb <= 0) return hipSuccess;
-  const size_t lds = ((size_t)kAsmChunk + 2 * (size_t)d.max_runs) * sizeof(int);
-  const dim3 g(nb < 256 * 8 ? nb : 256 * 8), b(256);
-  const bool cols = !(std::getenv("FMMBEM_ASM_COLS") && std::atoi(std::getenv("FMMBEM_ASM_COLS")) == 0);
-  if (cols && d.nq == 1) hipLaunchKernelGGL(near_assemble_stokes_cols_kernel<1>, g, b, lds, s, d);
-  else if (cols && d.nq == 3) hipLaunchKernelGGL(near_assemble_stokes_cols_kernel<3>, g, b, lds, s, d);
-  else if (cols && d.nq == 4) hipLaunchKernelGGL(near_assemble_stokes_cols_kernel<4>, g, b, lds, s, d);
-  else hipLaunchKernelGGL(near_assemble_stokes_kernel, g, b, lds, s, d);
-  return hipGetLastError();
+  return near_assemble_with(d, s, near_assemble_stokes_cols_kernel<1>, near_assemble_stokes_cols_kernel<3>,
+                            near_assemble_stokes_cols_kernel<4>, near_assemble_stokes_kernel);
 }
 
 hipError_t launch_near_matfree(const DevicePlan& d, hipStream_t s) {
@@ -2003,9 +1978,7 @@ hipError_t launch_gather_x(const DevicePlan& d, const double* x, hipStream_t s) 
 hipError_t launch_near_hybrid(const DevicePlan& d, hipStream_t s, const HybridStreams& hs) {
   if (!d.near_rec) return hipErrorInvalidValue;
   const bool stokes = d.dof == 3;
-  static const int kS3 = [] { const char* e = std::getenv("FMMBEM_HYB_WG_STREAM"); return e ? std::atoi(e) : 2; }();
-  static const int kS1 = [] { const char* e = std::getenv("FMMBEM_HYB_WG_STREAM"); return e ? std::atoi(e) : 3; }();
-  static const int kR = [] { const char* e = std::getenv("FMMBEM_HYB_WG_RECOMPUTE"); return e ? std::atoi(e) : 1; }();
+  const int kS3 = sw::hyb_wg_stream().value_or(2), kS1 = sw::hyb_wg_stream().value_or(3), kR = sw::hyb_wg_recompute().value_or(1);
   const dim3 b(kSpmvWaves * kWave);
   const bool flag1 = stokes ? d.stokes_traction_targets != 0 : (d.n_act > 1 || d.act[0] == 1);   // TRACTION / NORMAL_DERIV targets present
   const int n_stream = stokes ? d.sym_nitems : d.near_nitems_stream;
@@ -2017,7 +1990,7 @@ hipError_t launch_near_hybrid(const DevicePlan& d, hipStream_t s, const HybridSt
     if ((e = hipStreamWaitEvent(hs.recompute, hs.fork, 0)) != hipSuccess) return e;
     const dim3 g(std::min(d.rc_nitems, 256 * kR));
     if (stokes) {                                        // sources straight into LDS: two workgroups per CU
-      static const int kRg = [] { const char* e = std::getenv("FMMBEM_HYB_WG_RECOMPUTE"); return e ? std::atoi(e) : 2; }();
+      const int kRg = sw::hyb_wg_recompute().value_or(2);
       const dim3 gg(std::min(d.rc_nitems, 256 * kRg));
       const size_t ldsg = (size_t)2 * (flag1 ? 12 : 10) * kRcgChunk * 2 * sizeof(double) + (size_t)2 * 2 * kRcgTgt * 2 * sizeof(double) + 6 * (size_t)d.max_runs * sizeof(int);
       if (flag1) hipLaunchKernelGGL((near_recompute3g_kernel<true>), gg, b, ldsg, hs.recompute, d);
@@ -2031,13 +2004,13 @@ hipError_t launch_near_hybrid(const DevicePlan& d, hipStream_t s, const HybridSt
   }
   if (n_stream > 0) {
     if (stokes) {
-      const size_t lds3 = 3 * (size_t)kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
+      const size_t lds3 = near_lds(d, NearForm::Sym3);
       // beside the recompute kernel: two source-panel vectors in flight per lane instead of three (2.11 against 2.10 ms alone) --
       // 88 VGPRs or fewer, so that 2 x 168 (two recompute workgroups) + 2 x 88 fit the 512 registers of a SIMD
       if (d.rc_nitems > 0) hipLaunchKernelGGL((near_spmv_sym3_kernel<1, 2>), dim3(std::min(n_stream, 256 * kS3)), b, lds3, s, d);
       else hipLaunchKernelGGL((near_spmv_sym3_kernel<1, 3>), dim3(std::min(n_stream, 256 * kSymOcc)), b, lds3, s, d);
     } else {
-      const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
+      const size_t lds2 = near_lds(d, NearForm::Pipe);
       hipLaunchKernelGGL((near_spmv_pipe_kernel<2, 4>), dim3(std::min(n_stream, 256 * (d.rc_nitems > 0 ? kS1 : kSpmvOcc))), b, lds2, s, d);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -2052,67 +2025,41 @@ hipError_t launch_near_hybrid(const DevicePlan& d, hipStream_t s, const HybridSt
 }
 
 hipError_t launch_near_spmv(const DevicePlan& d, hipStream_t s) {
-  if (d.near_rec) return hipErrorInvalidValue;         // hybrid plans go through launch_near_hybrid
-  if (d.near_nitems <= 0) return hipSuccess;
-  if (d.dof == 3 && d.near_sym) {
-    const size_t lds3 = 3 * (size_t)kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
-    // panel rows x source-panel vectors in flight per wavefront, red blood cell N = 524 288 (ms): 1x3 2.10, 1x2 2.11, 1x1 2.15,
-    // 1x4 2.3-2.6, 2x2 3.39, 1x5 3.36, 4x1 4.14; 2x4, 4x2, 1x6 spill (7-9); the 9-value rows: 3.32
-    hipLaunchKernelGGL((near_spmv_sym3_kernel<1, 3>), dim3(std::min(d.sym_nitems, 256 * kSymOcc)), dim3(kSpmvWaves * kWave), lds3, s, d);
-    return hipGetLastError();
-  }
-  const size_t lds = (size_t)kSpmvChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
-  // rows x vectors in flight per wavefront measured at N = 1M (ms): 4x4 1.05,
-  // 2x4 0.99, 4x2 1.14, 8x2 1.21, 2x2 1.09, 4x1 1.09; plain (non-nontemporal) loads +25 %
-  // The grid is exactly what is resident at once (kSpmvOcc workgroups per CU): with one more per CU the stragglers
-  // start when the others finish (0.98 ms instead of 0.79 at N = 1M); occupancy 6 (80 VGPRs) and 2x2 loads at
+  const NearForm f = near_form(d);
+  if (f == NearForm::Hybrid) return hipErrorInvalidValue;         // hybrid plans go through launch_near_hybrid
+  if (f == NearForm::Empty) return hipSuccess;
+  const dim3 g(near_grid(d, f)), b(kSpmvWaves * kWave);
+  const size_t lds = near_lds(d, f);
+  // Sym3, panel rows x source-panel vectors in flight per wavefront, red blood cell N = 524 288 (ms): 1x3 2.10, 1x2 2.11, 1x1 2.15,
+  // 1x4 2.3-2.6, 2x2 3.39, 1x5 3.36, 4x1 4.14; 2x4, 4x2, 1x6 spill (7-9); the 9-value rows: 3.32
+  // Pipe and Plain, rows x vectors in flight per wavefront measured at N = 1M (ms): 4x4 1.05,
+  // 2x4 0.99, 4x2 1.14, 8x2 1.21, 2x2 1.09, 4x1 1.09; plain (non-nontemporal) loads +25 %; occupancy 6 (80 VGPRs) and 2x2 loads at
   // occupancy 8 measure within 3 % of this.
-  const dim3 g(std::min(d.near_nitems, 256 * kSpmvOcc)), b(kSpmvWaves * kWave);
-  if (d.dof == 1 && d.max_runs <= kSpmvWaves * kWave) {               // the pipelined form; a leaf with more runs than threads (never seen) takes the plain one
-    const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
-    hipLaunchKernelGGL((near_spmv_pipe_kernel<2, 4>), g, b, lds2, s, d);
-  } else {
-    hipLaunchKernelGGL((near_spmv_kernel<2, 4>), g, b, lds, s, d);
-  }
+  if (f == NearForm::Sym3) hipLaunchKernelGGL((near_spmv_sym3_kernel<1, 3>), g, b, lds, s, d);
+  else if (f == NearForm::Pipe) hipLaunchKernelGGL((near_spmv_pipe_kernel<2, 4>), g, b, lds, s, d);
+  else hipLaunchKernelGGL((near_spmv_kernel<2, 4>), g, b, lds, s, d);
   return hipGetLastError();
 }
 
-// The near field and P2M as one launch (near_p2m_kernel): the plans where launch_near_spmv takes near_spmv_pipe_kernel and
-// launch_p2m takes p2m_stream_kernel at order p, both non-empty.  The caller (fmmbem_plan::run) rules out what it alone knows:
-// hybrid and float near fields, target plans, partial executes, stage timing.
-bool near_p2m_ok(const DevicePlan& d, int p) {
-  const char* se = std::getenv("FMMBEM_P2M_STREAM");                 // read per launch, as launch_p2m does
-  const bool stream_off = se && std::atoi(se) == 0;
-  return !d.near_rec && d.near_nitems > 0 && d.dof == 1 && d.max_runs <= kSpmvWaves * kWave &&
-         d.n_p2m > 0 && d.p2m_tab && d.n_act == 1 && p >= 1 && p <= 16 && p * (p + 1) / 2 > kWave / 2 && !stream_off;
-}
-
+// The near field and P2M as one launch (near_p2m_kernel): the P2M workgroups queued behind the near field's
 hipError_t launch_near_p2m(const DevicePlan& d, int p, hipStream_t s) {
   if (!near_p2m_ok(d, p)) return hipErrorInvalidValue;
-  const int near_grid = std::min(d.near_nitems, 256 * kSpmvOcc);     // launch_near_spmv's grid
-  const int nb = (d.n_p2m + 3) / 4, p2m_grid = nb < 256 * 8 ? nb : 256 * 8;   // launch_p2m's grid
-  const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
-  hipLaunchKernelGGL((near_p2m_kernel<2, 4>), dim3(near_grid + p2m_grid), dim3(kSpmvWaves * kWave), lds2, s, d, near_grid, p);
+  const int near_wgs = near_grid(d, NearForm::Pipe);
+  hipLaunchKernelGGL((near_p2m_kernel<2, 4>), dim3(near_wgs + p2m_grid(d, P2MForm::Stream)), dim3(kSpmvWaves * kWave),
+                     near_lds(d, NearForm::Pipe), s, d, near_wgs, p);
   return hipGetLastError();
 }
 
-// ---- float near field: the plans it serves, the copy, the pass ----
-// Laplace through the pipelined kernel (a leaf with more runs than threads, never seen, keeps the FP64 kernels), Stokes through
-// the symmetric blocks
-bool near_f32_ok(int dof, int max_runs, bool stokes_sym) { return dof == 3 ? stokes_sym : dof == 1 && max_runs <= kSpmvWaves * kWave; }
-
+// ---- float near field (the plans it serves: near_f32_ok): the copy, the pass ----
 hipError_t launch_near_to_f32(const DevicePlan& d, hipStream_t s) {
   if (!d.near_f32 || !d.near_f32_off) return hipErrorInvalidValue;
   const int nl = d.leaf_end - d.leaf_begin;
   if (nl <= 0) return hipSuccess;
   const dim3 g(std::min(nl, 256 * 16)), b(kSpmvWaves * kWave);
-  if (d.dof == 3) {
-    if (!d.near_sym) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(near_sym_to_f32_kernel, g, b, 0, s, d);
-  } else {
-    if (!d.near_val) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(near_to_f32_kernel, g, b, 0, s, d);
-  }
+  const NearForm k = near_kernel(d);                  // the forms near_f32_ok admits
+  if (k == NearForm::Sym3) hipLaunchKernelGGL(near_sym_to_f32_kernel, g, b, 0, s, d);
+  else if (k == NearForm::Pipe && d.near_val) hipLaunchKernelGGL(near_to_f32_kernel, g, b, 0, s, d);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
@@ -2122,30 +2069,28 @@ hipError_t launch_near_to_f32(const DevicePlan& d, hipStream_t s) {
 //   Laplace, N = 1M (FP64 pass 0.70):     0: 2x4x4 0.505   1: 2x3x5 0.462 (default)   2: 2x2x5 0.472   3: 4x2x4 0.512
 //   Stokes, red blood cell N = 524 288 (FP64 pass 2.00):  0: 1x3x4 1.081 (default)   1: 1x2x5 1.098   2: 1x2x4 1.085   3: 1x4x4 1.078
 hipError_t launch_near_spmv_f32(const DevicePlan& d, hipStream_t s) {
-  if (d.near_rec || !d.near_f32 || !d.near_f32_off) return hipErrorInvalidValue;
-  if (d.near_nitems <= 0) return hipSuccess;
+  const NearForm f = near_form(d);
+  if (f == NearForm::Hybrid || !d.near_f32 || !d.near_f32_off) return hipErrorInvalidValue;
+  if (f == NearForm::Empty) return hipSuccess;
   const dim3 b(kSpmvWaves * kWave);
-  if (d.dof == 3) {
-    if (!d.near_sym) return hipErrorInvalidValue;
-    const size_t lds3 = 3 * (size_t)kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
-    static const int shape = [] { const char* e = std::getenv("FMMBEM_F32_SHAPE"); return e ? std::atoi(e) : 0; }();
+  if (f == NearForm::Sym3) {
+    const size_t lds3 = near_lds(d, f);
+    const int shape = sw::f32_shape().value_or(0);
     if (shape == 1) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 2, 5>), dim3(std::min(d.sym_nitems, 256 * 5)), b, lds3, s, d);
     else if (shape == 2) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 2, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
     else if (shape == 3) hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 4, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
     else hipLaunchKernelGGL((near_spmv_sym3_f32_kernel<1, 3, 4>), dim3(std::min(d.sym_nitems, 256 * 4)), b, lds3, s, d);
     return hipGetLastError();
   }
-  if (d.dof != 1 || !d.near_recs_f32 || d.max_runs > kSpmvWaves * kWave) return hipErrorInvalidValue;
-  const size_t lds2 = 2 * (size_t)kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
-  static const int shape = [] { const char* e = std::getenv("FMMBEM_F32_SHAPE"); return e ? std::atoi(e) : 1; }();
+  if (f != NearForm::Pipe || !d.near_recs_f32) return hipErrorInvalidValue;
+  const size_t lds2 = near_lds(d, f);
+  const int shape = sw::f32_shape().value_or(1);
   if (shape == 0) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 4, 4>), dim3(std::min(d.near_nitems, 256 * 4)), b, lds2, s, d);
   else if (shape == 2) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 2, 5>), dim3(std::min(d.near_nitems, 256 * 5)), b, lds2, s, d);
   else if (shape == 3) hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<4, 2, 4>), dim3(std::min(d.near_nitems, 256 * 4)), b, lds2, s, d);
   else hipLaunchKernelGGL((near_spmv_pipe_f32_kernel<2, 3, 5>), dim3(std::min(d.near_nitems, 256 * 5)), b, lds2, s, d);
   return hipGetLastError();
 }
-
-bool batch_near_ok(const DevicePlan& d) { return !d.near_rec && d.dof == 1 && d.max_runs <= kSpmvWaves * kWave; }
 
 // One pass over the matrix for b.nv vectors; a pass of one vector is launch_near_spmv itself.  The kernel is instantiated for 2,
 // 4 and 8 vectors; a pass of 3 runs the 4-vector kernel, the fourth slot being scratch of the batch buffers.
@@ -2162,9 +2107,9 @@ hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipSt
   if (d.near_nitems <= 0) return hipSuccess;
   const int nv = b.nv <= 2 ? 2 : b.nv <= 4 ? 4 : 8;
   if (nv > b.width) return hipErrorInvalidValue;
-  static const int shape = [] { const char* e = std::getenv("FMMBEM_BATCH_SHAPE"); return e ? std::atoi(e) : 0; }();
-  const size_t lds = 2 * (size_t)nv * kSpmvPipeChunk * sizeof(double) + 4 * (size_t)d.max_runs * sizeof(int);
-  const dim3 g(std::min(d.near_nitems, 256 * (nv == 2 ? batch_occ(2) : nv == 4 ? batch_occ(4) : batch_occ(8)))), t(kSpmvWaves * kWave);
+  const int shape = sw::batch_shape();
+  const size_t lds = near_lds(d, NearForm::Pipe, nv);
+  const dim3 g(near_grid(d, NearForm::Pipe, nv)), t(kSpmvWaves * kWave);
 #define BATCH_NEAR(R, V, NV)                                                                                                         \
   {                                                                                                                                  \
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(near_spmv_pipe_multi_kernel<R, V, NV>),        \
@@ -2182,13 +2127,7 @@ hipError_t launch_near_spmv_multi(const DevicePlan& d, const BatchVecs& b, hipSt
 }
 
 // ---- Stokes plans with the symmetric blocks (fmmbem_options.stokes_batch_width): near_spmv_sym3 for 2, 3 or 4 vectors ----
-// dynamic LDS of a pass of `width` vectors: the x images and the run descriptors (the column-split parts, 768 bytes per vector, are
-// static), within the 160 KiB of a CU
-constexpr size_t kSym3MultiLds = 156 * 1024;
-bool batch_near_sym3_ok(const DevicePlan& d, int width) {
-  return !d.near_rec && d.dof == 3 && d.near_sym && d.sym_items && width >= 2 && width <= 4 &&
-         (size_t)width * 3 * kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int) <= kSym3MultiLds;
-}
+// (batch_near_sym3_ok: the x images and the run descriptors fit kSym3MultiLds; the column-split parts, 768 bytes per vector, are static)
 
 // One pass over near_sym for b.nv vectors, each y bit for bit launch_near_spmv's; a pass of one vector is launch_near_spmv itself.
 // The kernel is instantiated for every count 2, 3, 4, so a short pass runs the instantiation of its own size and no slot is spare.
@@ -2203,8 +2142,8 @@ hipError_t launch_near_sym3_multi(const DevicePlan& d, const BatchVecs& b, hipSt
     return launch_near_spmv(d1, s);
   }
   if (d.near_nitems <= 0 || d.sym_nitems <= 0) return hipSuccess;
-  const size_t lds = (size_t)b.nv * 3 * kSymChunk * sizeof(double) + 2 * (size_t)d.max_runs * sizeof(int);
-  const dim3 g(std::min(d.sym_nitems, 256 * sym3_multi_occ(b.nv))), t(kSpmvWaves * kWave);
+  const size_t lds = near_lds(d, NearForm::Sym3, b.nv);
+  const dim3 g(near_grid(d, NearForm::Sym3, b.nv)), t(kSpmvWaves * kWave);
 #define SYM3_MULTI(R, V, NV)                                                                                                         \
   {                                                                                                                                  \
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(near_spmv_sym3_multi_kernel<R, V, NV>),        \

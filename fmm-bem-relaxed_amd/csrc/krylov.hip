@@ -16,9 +16,10 @@
 #include <vector>
 
 #include "../../include/fmmbem.h"
+#include "status.hpp"
+#include "switches.hpp"
 
 namespace fmmbem {
-int fail(int code, const std::string& msg);        // plan.hip: records the message for fmmbem_last_error
 struct SolverWs;
 // plan.hip: where a plan lives, how many unknowns it has, and the slot in which it keeps the workspace of the solver below
 // (freed with the plan through solver_ws_destroy)
@@ -349,21 +350,7 @@ namespace {
 
 using fmmbem::SolverWs;
 using fmmbem::fail;
-
-#define KRY_HIP(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess)                                                                                 \
-      return fail(e_ == hipErrorOutOfMemory ? FMMBEM_ERR_ALLOC : FMMBEM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define KRY_TRY(expr) do { int rc_ = (expr); if (rc_ != FMMBEM_OK) return rc_; } while (0)
-
-struct DevGuard {
-  int prev = 0;
-  bool on = false;
-  explicit DevGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) on = true; }
-  ~DevGuard() { if (on) (void)hipSetDevice(prev); }
-};
+using fmmbem::DeviceGuard;
 
 // FMMBEM_KRYLOV_FAIL_GROW=k (tests only): the k-th allocation of the solver workspace in this process fails once, as an
 // out-of-memory would -- the retry path of ensure_ws cannot be exercised otherwise without filling 288 GB
@@ -371,9 +358,9 @@ int grow(double** p, size_t doubles) {
   if (*p) (void)hipFree(*p);
   *p = nullptr;
   static int calls = 0;
-  static const int fail_at = [] { const char* e = std::getenv("FMMBEM_KRYLOV_FAIL_GROW"); return e ? std::atoi(e) : 0; }();
+  const int fail_at = fmmbem::sw::krylov_fail_grow();
   if (fail_at > 0 && ++calls == fail_at) return fail(FMMBEM_ERR_ALLOC, "solver workspace: allocation failure injected by FMMBEM_KRYLOV_FAIL_GROW");
-  KRY_HIP(hipMalloc(reinterpret_cast<void**>(p), sizeof(double) * std::max<size_t>(doubles, 1)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), sizeof(double) * std::max<size_t>(doubles, 1)));
   return FMMBEM_OK;
 }
 
@@ -394,22 +381,22 @@ int grow_ws(SolverWs* ws, int64_t n, int k, int vcols, int zcols) {
   const int64_t ld = (n + 1) & ~int64_t(1);                      // even stride: every vector of every system on a 16-byte boundary
   if (ws->n != n || ws->cap < k) {
     reset_ws(ws);
-    KRY_TRY(grow(&ws->w, (size_t)ld * k));
-    KRY_TRY(grow(&ws->z, (size_t)ld * k));
+    TRY(grow(&ws->w, (size_t)ld * k));
+    TRY(grow(&ws->z, (size_t)ld * k));
     ws->n = n; ws->ld = ld; ws->cap = k;
   }
   const size_t col = (size_t)ld * ws->cap;
-  if (ws->vcols < vcols) { ws->vcols = 0; KRY_TRY(grow(&ws->V, col * vcols)); ws->vcols = vcols; }
-  if (ws->zcols < zcols) { ws->zcols = 0; KRY_TRY(grow(&ws->Z, col * zcols)); ws->zcols = zcols; }
+  if (ws->vcols < vcols) { ws->vcols = 0; TRY(grow(&ws->V, col * vcols)); ws->vcols = vcols; }
+  if (ws->zcols < zcols) { ws->zcols = 0; TRY(grow(&ws->Z, col * zcols)); ws->zcols = zcols; }
   if (ws->hcap < vcols + 1) {
     const int hcap = vcols + 1;
     ws->hcap = 0;
-    KRY_TRY(grow(&ws->d_h, (size_t)hcap * ws->cap));
-    KRY_TRY(grow(&ws->d_y, (size_t)hcap * ws->cap));
-    KRY_TRY(grow(&ws->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap) * ws->cap));
+    TRY(grow(&ws->d_h, (size_t)hcap * ws->cap));
+    TRY(grow(&ws->d_y, (size_t)hcap * ws->cap));
+    TRY(grow(&ws->d_scratch, (size_t)fmmbem_mgs_scratch_doubles(hcap) * ws->cap));
     if (ws->h_pin) (void)hipHostFree(ws->h_pin);
     ws->h_pin = nullptr;
-    KRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_pin), sizeof(double) * 2 * (size_t)hcap * ws->cap, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ws->h_pin), sizeof(double) * 2 * (size_t)hcap * ws->cap, hipHostMallocDefault));
     ws->hcap = hcap;                                             // sizes are committed only once every buffer of the group exists
   }
   return FMMBEM_OK;
@@ -480,7 +467,7 @@ int check_block_inverse_args(const fmmbem_plan* plan, const fmmbem_preconditione
 // what a solve refuses before it touches anything
 int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem_preconditioner* M, int depth, int* device, int64_t* n,
                 int* plan_pmax, SolverWs*** slot) {
-  KRY_TRY(fmmbem::plan_solver_info(plan, device, n, plan_pmax, slot));
+  TRY(fmmbem::plan_solver_info(plan, device, n, plan_pmax, slot));
   if (depth > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "fmmbem_gmres: a preconditioner's inner solve cannot itself be preconditioned by a plan");
   if (so.restart < 1 || so.max_iters < 0 || so.max_p < 1 || !(so.residual > 0.0))
     return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: restart >= 1, max_iters >= 0, max_p >= 1, residual > 0 required");
@@ -489,13 +476,13 @@ int check_solve(fmmbem_plan* plan, const fmmbem_solver_options& so, const fmmbem
   if (kind == FMMBEM_PC_INNER_PLAN) {
     if (!M->inner_plan || M->inner_plan == plan) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner needs a plan of its own");
     int dv = 0, pm = 0; int64_t nn = 0; SolverWs** sl = nullptr;
-    KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
+    TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
     if (dv != *device || nn != *n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
   }
   if (kind == FMMBEM_PC_BLOCK_INVERSE) {
-    KRY_TRY(check_block_inverse_args(plan, M));
+    TRY(check_block_inverse_args(plan, M));
     int dv = 0, pm = 0; int64_t nn = 0; SolverWs** sl = nullptr;
-    KRY_TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
+    TRY(fmmbem::plan_solver_info(M->inner_plan, &dv, &nn, &pm, &sl));
     if (dv != *device || nn != *n) return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the preconditioner's plan must hold the same panels on the same device");
     if (!fmmbem::plan_block_inverse_built(M->inner_plan))
       return fail(FMMBEM_ERR_INVALID, "fmmbem_gmres: the block-inverse preconditioner's plan has no inverse built (fmmbem_plan_block_inverse_build)");
@@ -582,7 +569,7 @@ int batch_matvecs(fmmbem_plan* plan, int64_t n, int k, const std::vector<MatvecJ
           dx = dy = n;
         }
       }
-      KRY_TRY(fmmbem_plan_execute_batch_device(plan, jobs[a].p, (int)cnt, jobs[g[f]].x, (size_t)dx, jobs[g[f]].y, (size_t)dy, s));
+      TRY(fmmbem_plan_execute_batch_device(plan, jobs[a].p, (int)cnt, jobs[g[f]].x, (size_t)dx, jobs[g[f]].y, (size_t)dy, s));
       f += cnt;
     }
   }
@@ -621,8 +608,8 @@ struct Solver {
   int norm(int j, double* w, double a, const double* v, double* out) const {
     hipLaunchKernelGGL(axpy_norm_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, w, a, v, scratch(j));
     hipLaunchKernelGGL(mgs_finish_kernel, dim3(1), dim3(kThreads), 0, s, scratch(j), 0, ws->d_h);      // ncols = 0: row 0 is a norm
-    KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double), hipMemcpyDeviceToHost, s));
-    KRY_HIP(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     *out = ws->h_pin[0];
     return FMMBEM_OK;
   }
@@ -647,7 +634,7 @@ struct Solver {
       for (size_t a = 0; a < act.size();) {
         size_t cnt = 1;
         while (a + cnt < act.size() && act[a + cnt] == act[a] + (int)cnt) ++cnt;
-        KRY_TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, (int)cnt, Vc(c, act[a]), (size_t)ld, out + (int64_t)act[a] * ld, (size_t)ld, s));
+        TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, (int)cnt, Vc(c, act[a]), (size_t)ld, out + (int64_t)act[a] * ld, (size_t)ld, s));
         a += cnt;
       }
       return FMMBEM_OK;
@@ -660,7 +647,7 @@ struct Solver {
       v.push_back(Vc(c, j));
     }
     // one memset from the first to the last system of act: a system in between that has left has finished with its z
-    KRY_HIP(hipMemsetAsync(y.front(), 0, sizeof(double) * (size_t)((int64_t)(act.back() - act.front()) * ld + n), s));
+    HIP_TRY(hipMemsetAsync(y.front(), 0, sizeof(double) * (size_t)((int64_t)(act.back() - act.front()) * ld + n), s));
     return solve(M->inner_plan, M->inner, (int)act.size(), y.data(), v.data(), nullptr, nullptr, s, depth + 1);
   }
 
@@ -690,7 +677,7 @@ struct Solver {
       const std::vector<int> one(1, j);
       std::vector<const double*> z;
       for (int c = 0; c <= i; ++c) {           // x += y_c M(V_c): the inner solve again, column by column, as the reference
-        KRY_TRY(apply_pc(one, c, false, &z));
+        TRY(apply_pc(one, c, false, &z));
         hipLaunchKernelGGL(mgs_axpy_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, S.ar.sv[c], z[0]);
       }
       return FMMBEM_OK;
@@ -699,14 +686,14 @@ struct Solver {
     double* hy = ws->h_pin + (size_t)ws->hcap * (ws->cap + j);
     double* dy = ws->d_y + (size_t)ws->hcap * j;
     for (int c = 0; c <= i; ++c) hy[c] = S.ar.sv[c];
-    KRY_HIP(hipMemcpyAsync(dy, hy, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dy, hy, sizeof(double) * (size_t)(i + 1), hipMemcpyHostToDevice, s));
     if (kind == FMMBEM_PC_BLOCK_INVERSE && !so.flexible) {
       // M is linear and constant: x += M (sum_c y_c V_c), one pass over the inverses instead of one per column.  The sum is
       // formed in this system's w, which the Arnoldi column has finished with
-      KRY_HIP(hipMemsetAsync(wv(j), 0, sizeof(double) * (size_t)n, s));
+      HIP_TRY(hipMemsetAsync(wv(j), 0, sizeof(double) * (size_t)n, s));
       hipLaunchKernelGGL(update_x_kernel, dim3(grid), dim3(kThreads), 0, s, n, wv(j), Vc(0, j), ld * ws->cap, i + 1, dy, (const double*)nullptr);
       double* zj = ws->z + (int64_t)j * ld;
-      KRY_TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, 1, wv(j), (size_t)ld, zj, (size_t)ld, s));
+      TRY(fmmbem_plan_block_inverse_apply_device(M->inner_plan, 1, wv(j), (size_t)ld, zj, (size_t)ld, s));
       hipLaunchKernelGGL(mgs_axpy_kernel, dim3(grid), dim3(kThreads), 0, s, n, S.x, 1.0, zj);
       return FMMBEM_OK;
     }
@@ -723,7 +710,7 @@ struct Solver {
     for (int j = 0; j < k; ++j) {
       System& S = sys[j];
       if (S.log) { S.log->iterations = 0; S.log->residual = 0.0; }
-      KRY_TRY(norm(j, const_cast<double*>(S.b), 0.0, nullptr, &S.normb));      // scale residual by |b| (GMRES.hpp:162)
+      TRY(norm(j, const_cast<double*>(S.b), 0.0, nullptr, &S.normb));      // scale residual by |b| (GMRES.hpp:162)
       if (S.normb == 0.0) continue;            // b = 0: the reference divides by zero and stops on NaN; x = x0 is returned
       S.cur_p = std::min(so.initial_p > 0 ? so.initial_p : so.max_p, plan_pmax);
       live.push_back(j);
@@ -737,12 +724,12 @@ struct Solver {
     while (!live.empty()) {                    // outer (restart) loop, :166 -- the systems still running restart together
       jobs.clear();
       for (int j : live) jobs.push_back({sys[j].cur_p, sys[j].x, wv(j)});      // w = A x at each system's current order
-      KRY_TRY(batch_matvecs(plan, n, k, jobs, s));
+      TRY(batch_matvecs(plan, n, k, jobs, s));
       std::vector<int> act;
       for (int j : live) {
         System& S = sys[j];
         double beta = 0;
-        KRY_TRY(norm(j, wv(j), -1.0, S.b, &beta));                             // w -= b; beta = |w|
+        TRY(norm(j, wv(j), -1.0, S.b, &beta));                             // w -= b; beta = |w|
         if (beta == 0.0) { S.resid = 0.0; finish(j); continue; }               // x solves the system exactly
         hipLaunchKernelGGL(scale_kernel, dim3(sweep_grid(n)), dim3(kThreads), 0, s, n, wv(j), -1.0 / beta, Vc(0, j));   // V_0 = -w / beta
         S.ar.sv[0] = beta;
@@ -755,14 +742,14 @@ struct Solver {
         ++i;
         ++iter;
         for (int j : act) sys[j].cur_p = order_for(so, sys[j].resid, plan_pmax);
-        KRY_TRY(apply_pc(act, i, so.flexible != 0, &zs));
+        TRY(apply_pc(act, i, so.flexible != 0, &zs));
         jobs.clear();
         for (size_t a = 0; a < act.size(); ++a) jobs.push_back({sys[act[a]].cur_p, zs[a], wv(act[a])});
-        KRY_TRY(batch_matvecs(plan, n, k, jobs, s));
+        TRY(batch_matvecs(plan, n, k, jobs, s));
         // modified Gram-Schmidt against V_0..V_i, |w|, V_{i+1} = w / |w| (:203-212), then the columns to the host
         mgs_columns(act, i + 1);
-        KRY_HIP(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2) * act.size(), hipMemcpyDeviceToHost, s));
-        KRY_HIP(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(ws->h_pin, ws->d_h, sizeof(double) * (size_t)(i + 2) * act.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         std::vector<int> stay;
         for (size_t a = 0; a < act.size(); ++a) {
           const int j = act[a];
@@ -771,18 +758,18 @@ struct Solver {
           S.resid = S.ar.sv[i + 1] / S.normb;
           if (S.log && S.log->p && S.log->resid && iter <= S.log->capacity) { S.log->p[iter - 1] = S.cur_p; S.log->resid[iter - 1] = std::fabs(S.resid); }
           if (std::fabs(S.resid) > so.residual) { stay.push_back(j); continue; }
-          KRY_TRY(update(j, i));               // converged (or not a number): this system's solve ends here
+          TRY(update(j, i));               // converged (or not a number): this system's solve ends here
           finish(j);
         }
         act.swap(stay);
         if (act.empty() || !(i + 1 < R && i + 1 <= so.max_iters)) break;      // :221
       }
-      for (int j : act) KRY_TRY(update(j, i));
+      for (int j : act) TRY(update(j, i));
       if (iter < so.max_iters) { live.swap(act); continue; }
       for (int j : act) finish(j);
       break;
     }
-    KRY_HIP(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));
     return hipGetLastError() == hipSuccess ? FMMBEM_OK : fail(FMMBEM_ERR_HIP, "fmmbem_gmres: a launch failed");
   }
 };
@@ -792,11 +779,11 @@ int solve(fmmbem_plan* plan, const fmmbem_solver_options& so, int k, double* con
   int device = 0, plan_pmax = 0;
   int64_t n = 0;
   SolverWs** slot = nullptr;
-  KRY_TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
+  TRY(check_solve(plan, so, M, depth, &device, &n, &plan_pmax, &slot));
   // the inner loop runs while i + 1 < R and i + 1 <= max_iters (GMRES.hpp:221): at most min(R, max_iters + 1) columns
   const int most = (int)std::min<int64_t>(so.restart, (int64_t)so.max_iters + 1);
   SolverWs* ws = nullptr;
-  KRY_TRY(ensure_ws(slot, device, n, k, most + 1, so.flexible ? most : 0, &ws));
+  TRY(ensure_ws(slot, device, n, k, most + 1, so.flexible ? most : 0, &ws));
   Solver S{plan, so, M, s, depth, M ? M->kind : FMMBEM_PC_IDENTITY, plan_pmax, n, ws->ld, ws, {}};
   S.sys.reserve((size_t)k);
   for (int j = 0; j < k; ++j) S.sys.emplace_back(xs[j], bs[j], logs ? logs[j] : nullptr, so.restart);
@@ -825,11 +812,11 @@ int entry_args(const fmmbem_plan* plan, const fmmbem_solver_options* opts, int k
 // the device-pointer entry points; log->seconds is the wall time of the call, set even when the solve fails
 int gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* d_x, size_t ldx, const double* d_b, size_t ldb,
                  const fmmbem_preconditioner* M, fmmbem_solver_log* logs, void* stream, const char* who) {
-  KRY_TRY(entry_args(plan, opts, k, d_x, ldx, d_b, ldb, who));
-  KRY_TRY(check_block_inverse_args(plan, M));
+  TRY(entry_args(plan, opts, k, d_x, ldx, d_b, ldb, who));
+  TRY(check_block_inverse_args(plan, M));
   int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
-  DevGuard guard(device);
+  TRY(fmmbem::plan_solver_info(plan, &device, &n, &pm, &slot));
+  DeviceGuard guard(device);
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = solve_strided(plan, *opts, k, d_x, ldx, d_b, ldb, M, logs, static_cast<hipStream_t>(stream));
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -841,18 +828,18 @@ int gmres_device(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, do
 // per solve -- the only PCIe traffic of length n -- in buffers the workspace's reset / grow never touch
 int gmres_host(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, double* x, size_t ldx, const double* b, size_t ldb,
                const fmmbem_preconditioner* M, fmmbem_solver_log* logs, const char* who) {
-  KRY_TRY(entry_args(plan, opts, k, x, ldx, b, ldb, who));
-  KRY_TRY(check_block_inverse_args(plan, M));
+  TRY(entry_args(plan, opts, k, x, ldx, b, ldb, who));
+  TRY(check_block_inverse_args(plan, M));
   int device = 0, pm = 0; int64_t n = 0; SolverWs** slot = nullptr;
-  KRY_TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
-  DevGuard guard(device);
+  TRY(check_solve(plan, *opts, M, 0, &device, &n, &pm, &slot));          // bad options or preconditioner: before anything is staged
+  DeviceGuard guard(device);
   const auto t0 = std::chrono::steady_clock::now();
   SolverWs* ws = plan_ws(slot, device);
   const int64_t ld = (n + 1) & ~int64_t(1);
   const size_t bytes = sizeof(double) * (size_t)n;
   if (ws->xb_doubles < (size_t)2 * k * ld) {
     ws->xb_doubles = 0;
-    KRY_TRY(grow(&ws->d_xb, (size_t)2 * k * ld));
+    TRY(grow(&ws->d_xb, (size_t)2 * k * ld));
     ws->xb_doubles = (size_t)2 * k * ld;
   }
   double* d_x = ws->d_xb;
@@ -860,16 +847,16 @@ int gmres_host(fmmbem_plan* plan, const fmmbem_solver_options* opts, int k, doub
   fmmbem_preconditioner Md;
   const fmmbem_preconditioner* Mp = M;
   if (M && M->kind == FMMBEM_PC_DIAGONAL) {
-    if (!ws->d_recip) KRY_TRY(grow(&ws->d_recip, (size_t)n));                // n is the plan's: allocated once
-    KRY_HIP(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
+    if (!ws->d_recip) TRY(grow(&ws->d_recip, (size_t)n));                // n is the plan's: allocated once
+    HIP_TRY(hipMemcpy(ws->d_recip, M->reciprocals, bytes, hipMemcpyHostToDevice));
     Md = *M;
     Md.reciprocals = ws->d_recip;
     Mp = &Md;
   }
-  KRY_HIP(hipMemcpy2D(d_x, sizeof(double) * (size_t)ld, x, sizeof(double) * ldx, bytes, (size_t)k, hipMemcpyHostToDevice));
-  KRY_HIP(hipMemcpy2D(d_b, sizeof(double) * (size_t)ld, b, sizeof(double) * ldb, bytes, (size_t)k, hipMemcpyHostToDevice));
-  KRY_TRY(solve_strided(plan, *opts, k, d_x, (size_t)ld, d_b, (size_t)ld, Mp, logs, nullptr));
-  KRY_HIP(hipMemcpy2D(x, sizeof(double) * ldx, d_x, sizeof(double) * (size_t)ld, bytes, (size_t)k, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(d_x, sizeof(double) * (size_t)ld, x, sizeof(double) * ldx, bytes, (size_t)k, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy2D(d_b, sizeof(double) * (size_t)ld, b, sizeof(double) * ldb, bytes, (size_t)k, hipMemcpyHostToDevice));
+  TRY(solve_strided(plan, *opts, k, d_x, (size_t)ld, d_b, (size_t)ld, Mp, logs, nullptr));
+  HIP_TRY(hipMemcpy2D(x, sizeof(double) * ldx, d_x, sizeof(double) * (size_t)ld, bytes, (size_t)k, hipMemcpyDeviceToHost));
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (logs) for (int j = 0; j < k; ++j) logs[j].seconds = secs;
   return FMMBEM_OK;

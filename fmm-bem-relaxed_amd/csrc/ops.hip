@@ -23,60 +23,15 @@
 #include "m2l_layout.hpp"
 #include "m2l_rot.hpp"
 #include "shift_ops.hpp"
+#include "status.hpp"
+#include "switches.hpp"
 
-namespace fmmbem {
-int fail(int code, const std::string& msg);            // plan.hip
-}
 using namespace fmmbem;
 using namespace fmmbem::tables;
 
 namespace {
 
 constexpr int kMaxSlots = 12;
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(e_ == hipErrorOutOfMemory ? FMMBEM_ERR_ALLOC : FMMBEM_ERR_HIP,                  \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                              \
-  } while (0)
-#define TRY(expr) do { int rc_ = (expr); if (rc_ != FMMBEM_OK) return rc_; } while (0)
-
-struct DeviceScope {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    err = hipGetDevice(&prev);
-    if (err != hipSuccess) { prev = -1; return; }
-    if (prev != dev) err = hipSetDevice(dev); else prev = -1;
-  }
-  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// device memory of one call, freed when the call returns
-struct Scratch {
-  std::vector<void*> v;
-  ~Scratch() { for (void* p : v) (void)hipFree(p); }
-  template <class T>
-  int up(const T* src, size_t count, const T** dst) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, count ? count * sizeof(T) : 1));
-    v.push_back(p);
-    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = static_cast<const T*>(p);
-    return FMMBEM_OK;
-  }
-  template <class T>
-  int zeros(size_t count, T** dst, hipStream_t s) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, count ? count * sizeof(T) : 1));
-    v.push_back(p);
-    if (count) HIP_TRY(hipMemsetAsync(p, 0, count * sizeof(T), s));
-    *dst = static_cast<T*>(p);
-    return FMMBEM_OK;
-  }
-};
 
 }  // namespace
 
@@ -102,7 +57,7 @@ struct fmmbem_ops {
   DevicePlan* d_dev = nullptr;
   bool generic_ready = false;
   ~fmmbem_ops() {
-    DeviceScope g(device);
+    DeviceGuard g(device);
     for (void* p : allocs) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -295,7 +250,7 @@ int fmmbem_ops::panels(Scratch& sc, DevicePlan& d, size_t n, const double* verti
 int fmmbem_ops::shift(int op, int p, int n_slots, const double* src, double* tgt, const double tr[3]) {
   if (!src || !tgt || !tr) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (p < 1 || p > p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
-  DeviceScope guard(device);
+  DeviceGuard guard(device);
   HIP_TRY(guard.err);
   DevicePlan d = base;
   TRY(set_slots(d, n_slots));
@@ -307,7 +262,7 @@ int fmmbem_ops::shift(int op, int p, int n_slots, const double* src, double* tgt
   double r8[8];
   rot_record(tr, r8);
   // FMMBEM_OPS_GENERIC=1: the kernels of the orders above 12 at every order (tests)
-  const bool force_generic = std::getenv("FMMBEM_OPS_GENERIC") && std::atoi(std::getenv("FMMBEM_OPS_GENERIC")) != 0;
+  const bool force_generic = sw::ops_generic();
   const bool rot = !force_generic && p <= kRotPmax && m2l_rot_supported(p) && shift_rot_supported(p);
   if (rot) {
     HIP_TRY(hipMemcpy(rec, r8, sizeof(r8), hipMemcpyHostToDevice));
@@ -375,7 +330,7 @@ int fmmbem_ops_create(const fmmbem_options* opts, fmmbem_ops** out) {
     return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
   if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
   o->kernel = opts->kernel; o->p_max = opts->p_max; o->device = opts->device; o->mu = opts->mu;
-  DeviceScope guard(o->device);
+  DeviceGuard guard(o->device);
   HIP_TRY(guard.err);
   try {
     TRY(o->init());
@@ -401,7 +356,7 @@ int fmmbem_ops_p2m(fmmbem_ops* ops, int p, size_t n, const double* vertices, con
     for (size_t i = 0; i < n; ++i)
       if (bc[i]) return fail(FMMBEM_ERR_UNSUPPORTED, "Stokes P2M of a TRACTION source: the reference's stresslet moments (kernel/StokesSphericalBEM.hpp:438-466) "
                                                      "are not what this library's far field uses (include/fmmbem.h, FMMBEM_KERNEL_STOKES_BEM)");
-  DeviceScope guard(ops->device);
+  DeviceGuard guard(ops->device);
   HIP_TRY(guard.err);
   try {
     Scratch sc;
@@ -432,7 +387,7 @@ int fmmbem_ops_l2p(fmmbem_ops* ops, int p, const double* L, const double center[
     for (size_t i = 0; i < n; ++i)
       if (bc[i]) return fail(FMMBEM_ERR_UNSUPPORTED, "Stokes L2P at a TRACTION target reads the double layer's seven potentials, which the reference's "
                                                      "local_type does not hold (include/fmmbem.h, FMMBEM_KERNEL_STOKES_BEM)");
-  DeviceScope guard(ops->device);
+  DeviceGuard guard(ops->device);
   HIP_TRY(guard.err);
   try {
     Scratch sc;

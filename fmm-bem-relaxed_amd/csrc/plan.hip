@@ -26,9 +26,11 @@
 #include "device_launch.hpp"
 #include "host_plan.hpp"
 #include "host_tables.hpp"
+#include "launch_choice.hpp"
 #include "m2l_layout.hpp"
 #include "m2l_rot.hpp"
 #include "shift_ops.hpp"
+#include "status.hpp"
 
 using namespace fmmbem;
 using namespace fmmbem::tables;
@@ -37,7 +39,7 @@ namespace {
 thread_local std::string g_last_error;
 }
 namespace fmmbem {
-int fail(int code, const std::string& msg) {          // also used by mesh_io.cpp
+int fail(int code, const std::string& msg) {          // status.hpp; also used by mesh_io.cpp
   g_last_error = msg;
   return code;
 }
@@ -50,29 +52,6 @@ bool plan_block_inverse_built(const fmmbem_plan* plan);
 
 namespace {
 
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(e_ == hipErrorOutOfMemory ? FMMBEM_ERR_ALLOC : FMMBEM_ERR_HIP,                  \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                              \
-  } while (0)
-
-// The C ABI takes a device ordinal per plan; every entry point that touches the device switches to it and restores the
-// caller's current device on the way out (a process may hold plans on several devices, and torch keeps its own idea of
-// the current device).
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err != hipSuccess) { prev = -1; return; }
-    if (prev != dev) err = hipSetDevice(dev); else prev = -1;
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 #define DEVICE_SCOPE(dev)        \
   DeviceGuard device_guard_(dev); \
   HIP_TRY(device_guard_.err)
@@ -170,6 +149,7 @@ struct PlanGeometry {
   bool shift_lanes = true;
   int shift_lanes_max = -1;                           // FMMBEM_SHIFT_LANES_MAX: one threshold for both passes and all orders (sweeps)
   int lanes_max(int p, bool m2m) const { return shift_lanes_max >= 0 ? shift_lanes_max : !m2m ? 16384 : p == 10 ? 16384 : p == 9 ? 8192 : 2048; }
+  ShiftForm shift_form(const ShiftRot& sr, int p, int n_act, bool m2m) const;   // the kernel one level of M2M / L2L takes
   const int* up_unit_ptr = nullptr;
   const double *sl_up_class = nullptr, *sl_dn_class = nullptr, *sl_up_rc = nullptr, *sl_up_xc = nullptr, *sl_dn_rc = nullptr, *sl_dn_xc = nullptr;
   const int32_t *sl_up_rs = nullptr, *sl_up_xs = nullptr, *sl_dn_rs = nullptr, *sl_dn_xs = nullptr;
@@ -278,8 +258,7 @@ struct fmmbem_plan {
   bool result_slices = false;                                  // execute delivers the owned rows in tree order (fmmbem_plan_set_result_slices)
   bool l2p_delivers(bool near_only, int phase) const {         // (PlanGeometry::l2p_scatter)
     if (!g.l2p_scatter || result_slices || near_only || phase != 0) return false;
-    const char* e = std::getenv("FMMBEM_L2P_SCATTER");
-    return !(e && std::atoi(e) == 0);
+    return sw::l2p_scatter();
   }
   int64_t* d_cut = nullptr;                                    // tree-order row cuts of all shards, on the device
   int64_t near_side_entries = 0;                               // matrix-free plans: listed near-regime pairs (12 bytes each)
@@ -391,8 +370,6 @@ struct fmmbem_plan {
   }
 };
 
-#define TRY(expr) do { int rc_ = (expr); if (rc_ != FMMBEM_OK) return rc_; } while (0)
-
 // Work items largest first, equal ones in their given order: a stable radix sort on the (descending) key -- the comparison
 // sort of 60 000 items took 4-5 ms of every plan build
 template <class T, class KeyFn>
@@ -426,7 +403,7 @@ __global__ void expand_targets_kernel(const uint32_t* __restrict__ point, const 
 
 // phase times of a plan build on stderr (FMMBEM_BUILD_TRACE: tuning aid)
 struct BuildTrace {
-  const bool on = std::getenv("FMMBEM_BUILD_TRACE") != nullptr;
+  const bool on = sw::build_trace();
   double t_last = now_ms();
   void operator()(const char* what) {
     if (!on) return;
@@ -447,7 +424,7 @@ int fmmbem_plan::open_device() {
   HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
   ev.assign((size_t)kRing * 2 * kStages, nullptr);
   for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-  if (const char* ge = getenv("FMMBEM_GRAPH")) use_graphs = atoi(ge) != 0;
+  use_graphs = sw::graph(use_graphs);
   return FMMBEM_OK;
 }
 
@@ -542,11 +519,9 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
   std::vector<NearItem> near_recs_host;
   std::vector<int> near_recs_leaf;
   {
-    double f = opts.near_stream_fraction;
-    if (const char* e = std::getenv("FMMBEM_NEAR_STREAM_FRACTION")) f = std::atof(e);
+    double f = sw::near_stream_fraction(opts.near_stream_fraction);
     bool rule_ok = hp.rule.n <= (dof == 3 ? 4 : 3);               // the far-regime points of a source live in registers
     for (int q = 2; q < hp.rule.n; ++q) rule_ok = rule_ok && hp.rule.w[q] == hp.rule.w[1];      // K = 1, 3, 4: two distinct weights at most
-    const bool stokes_sym_on = !(std::getenv("FMMBEM_STOKES_SYM") && std::atoi(std::getenv("FMMBEM_STOKES_SYM")) == 0);
     // runs of consecutive source rows per leaf (the pipelined kernels prefetch an item's run descriptors one per thread): counted
     // by the shares of a few threads, as the runs themselves are filled in below
     std::vector<int> nruns_of(nl, 0);
@@ -560,7 +535,7 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
     });
     for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) max_runs_owned = std::max(max_runs_owned, nruns_of[l]);
     for (int l = 0; l < nl; ++l) run_ptr[l + 1] = run_ptr[l] + nruns_of[l];
-    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && rule_ok && (dof == 3 ? stokes_sym_on : max_runs_owned <= 256);
+    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && rule_ok && (dof == 3 ? sw::stokes_sym() : near_pipe_ok(dof, max_runs_owned));
     if (g.hybrid) {
       if (!(f >= 0.0)) f = 0.0;
       std::vector<int> order(nl);
@@ -607,7 +582,7 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
     max_runs = std::max(max_runs, (int)(run_ptr[l + 1] - run_ptr[l]));
   }
   d.max_runs = max_runs;
-  if (const char* e = getenv("FMMBEM_M2L_ROT")) { if (atoi(e) == 0) g.rot_max = 0; }
+  if (!sw::m2l_rot()) g.rot_max = 0;
   d.max_ncols = max_cols;
   g.near_bytes = total * (int64_t)sizeof(double);
   TRY(upload(leaf_row0, &d.leaf_row0)); TRY(upload(leaf_nrows, &d.leaf_nrows)); TRY(upload(hp.leaf_box, &d.leaf_box));
@@ -662,7 +637,7 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
       for (size_t i = 0; i < items.size(); ++i) near_recs_leaf[i] = items[i].leaf;
     }
   }
-  const bool stokes_sym = dof == 3 && opts.sparse_local && !(std::getenv("FMMBEM_STOKES_SYM") && std::atoi(std::getenv("FMMBEM_STOKES_SYM")) == 0);
+  const bool stokes_sym = dof == 3 && opts.sparse_local && sw::stokes_sym();
   g.near_total_doubles = (opts.sparse_local && !stokes_sym) ? total : 0;      // allocated in to_device_bc; matrix-free mode keeps no matrix
   if (!g.near_total_doubles) g.near_bytes = 0;
   {
@@ -968,11 +943,11 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
         for (int q = 1; q <= kShiftLanesPmax; ++q) { g.sl_rot_off[q] = ot.sl_rot_off[q]; g.sl_ax_off[q] = ot.sl_ax_off[q]; }
         TRY(upload(ot.urc, &g.sl_up_rc)); TRY(upload(ot.urs, &g.sl_up_rs)); TRY(upload(ot.uxc, &g.sl_up_xc)); TRY(upload(ot.uxs, &g.sl_up_xs));
         TRY(upload(ot.drc, &g.sl_dn_rc)); TRY(upload(ot.drs, &g.sl_dn_rs)); TRY(upload(ot.dxc, &g.sl_dn_xc)); TRY(upload(ot.dxs, &g.sl_dn_xs));
-        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES")) g.shift_lanes = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FMMBEM_SHIFT_LANES_MAX")) g.shift_lanes_max = std::atoi(e);
+        g.shift_lanes = sw::shift_lanes(g.shift_lanes);
+        g.shift_lanes_max = sw::shift_lanes_max(g.shift_lanes_max);
       }
-      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT")) g.shift_rot = std::atoi(e) != 0;
-      if (const char* e = std::getenv("FMMBEM_SHIFT_ROT_MIN")) g.shift_rot_min = std::atoi(e);
+      g.shift_rot = sw::shift_rot(g.shift_rot);
+      g.shift_rot_min = sw::shift_rot_min(g.shift_rot_min);
     }
     const cplx *pu = nullptr, *pd = nullptr;
     TRY(upload(up_tab, &pu)); TRY(upload(down_tab, &pd));
@@ -1172,7 +1147,7 @@ int fmmbem_plan::to_device_bc_end() {
   // P2M as a stored operator: every panel's moments about its leaf centre, at p_max (FMMBEM_P2M_TABLE=0, or more than
   // 16 GB of them: the recurrences are run every matvec instead)
   {
-    const char* e = std::getenv("FMMBEM_P2M_TABLE");
+    const bool table_on = sw::p2m_table();
     const size_t ntab = opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 4 : 1;
     // the panels of the leaves this plan runs P2M on: all of them, or -- upward pass sharded by owner -- the shard's own
     // rows only (0.9 GB at N = 1M, p_max = 10 for the whole mesh: one eighth of that per GPU on an 8-GPU node)
@@ -1184,7 +1159,7 @@ int fmmbem_plan::to_device_bc_end() {
     const size_t count = (size_t)(r1 - r0) * ntab * d.p2m_stride;
     const bool stokes = opts.kernel == FMMBEM_KERNEL_STOKES_BEM;
     const size_t count_g = (size_t)(r1 - r0) * 3 * d.p2m_stride;
-    if (stokes && fd.stokes_traction_targets && d.n_p2m > 0 && !(e && std::atoi(e) == 0) && count_g * sizeof(double2) <= ((size_t)16 << 30)) {
+    if (stokes && fd.stokes_traction_targets && d.n_p2m > 0 && table_on && count_g * sizeof(double2) <= ((size_t)16 << 30)) {
       // the double layer's gradient records; without them (switch, or more than 16 GB) its P2M runs the recurrences per matvec
       double2* tab = nullptr;
       TRY(alloc(count_g, &tab, true));
@@ -1194,7 +1169,7 @@ int fmmbem_plan::to_device_bc_end() {
       fd.p2m_tab_g = tab;
     }
     const bool want = !stokes || fd.stokes_velocity_targets;
-    if (want && !(e && std::atoi(e) == 0) && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
+    if (want && table_on && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
       for (int f = 0; f < 2; ++f) {                    // (a dual plan: the table of every live slot, all sources; else one table)
         if (targets && !has_bc[f]) continue;
         DevicePlan dt = d;
@@ -1292,20 +1267,27 @@ int fmmbem_plan::build_side_lists() {
 // One level of the upward / downward pass, p <= 12: the one-pair-per-WAVEFRONT kernel (kernels_shift.hip) for up to
 // shift_lanes_max pairs of this plan, the one-pair-per-LANE rotation kernel (kernels_m2l_rot.hip, ~20 us a pass whatever it holds)
 // above -- the two give the same bits, so every plan and every shard chooses by its own share.  p > 12 (and FMMBEM_SHIFT_ROT=0):
-// the sparse-operator kernels of kernels_far.hip, which round differently -- there the choice is the same for all shards.
+// the sparse-operator kernels of kernels_far.hip, which round differently -- there the choice is the same for all shards, and
+// beside the wavefront kernel never the sparse operators.
+ShiftForm PlanGeometry::shift_form(const ShiftRot& sr, int p, int n_act, bool m2m) const {
+  if (shift_rot && shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * n_act <= lanes_max(p, m2m)) return ShiftForm::Lanes;
+  if (shift_rot && shift_rot_supported(p) && (shift_lanes || sr.level_boxes >= shift_rot_min)) return ShiftForm::Rot;
+  return ShiftForm::Sparse;
+}
 int fmmbem_plan::m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const {
   const auto& launches = shared ? g.m2m_shared_launch : g.m2m_launch;
   const auto& rots = shared ? g.m2m_shared_rot : g.m2m_rot;
   for (size_t i = 0; i < launches.size(); ++i) {
     const auto [first, count] = launches[i];
     const ShiftRot& sr = rots[i];
-    if (g.shift_rot && g.shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * dv.n_act <= g.lanes_max(p, true)) {
+    const ShiftForm f = g.shift_form(sr, p, dv.n_act, true);
+    if (f == ShiftForm::Lanes) {
       ShiftLaneWork lw;
       lw.src = g.up_rsrc; lw.cls = g.up_rcls; lw.tgt = g.up_rtgt; lw.unit_ptr = g.up_unit_ptr + sr.unit_first; lw.n_units = sr.n_units;
       lw.class_tab = g.sl_up_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
       lw.rot_c = g.sl_up_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_up_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_up_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_up_xs + g.sl_ax_off[p];
       HIP_TRY(launch_m2m_lanes(dv, lw, p, s));
-    } else if (g.shift_rot && shift_rot_supported(p) && (g.shift_lanes || sr.level_boxes >= g.shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
+    } else if (f == ShiftForm::Rot) {
       RotWork w;
       w.src = g.up_rsrc; w.cls = g.up_rcls; w.tgt = g.up_rtgt; w.rec = g.up_rec;
       w.item_ptr = g.up_ritem + sr.item_first; w.n_items = sr.n_items;
@@ -1319,13 +1301,14 @@ int fmmbem_plan::l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const {
   for (size_t i = 0; i < g.l2l_launch.size(); ++i) {
     const auto [first, count] = g.l2l_launch[i];
     const ShiftRot& sr = g.l2l_rot[i];
-    if (g.shift_rot && g.shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * dv.n_act <= g.lanes_max(p, false)) {
+    const ShiftForm f = g.shift_form(sr, p, dv.n_act, false);
+    if (f == ShiftForm::Lanes) {
       ShiftLaneWork lw;
       lw.src = g.dn_rsrc + sr.pair_first; lw.cls = g.dn_rcls + sr.pair_first; lw.tgt = g.dn_rtgt + sr.pair_first; lw.n_units = sr.n_units;
       lw.class_tab = g.sl_dn_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
       lw.rot_c = g.sl_dn_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_dn_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_dn_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_dn_xs + g.sl_ax_off[p];
       HIP_TRY(launch_l2l_lanes(dv, lw, p, s));
-    } else if (g.shift_rot && shift_rot_supported(p) && (g.shift_lanes || sr.level_boxes >= g.shift_rot_min)) {   // beside the wavefront kernel never the sparse operators: they round differently
+    } else if (f == ShiftForm::Rot) {
       RotWork w;
       w.src = g.dn_rsrc; w.cls = g.dn_rcls; w.tgt = g.dn_rtgt; w.rec = g.dn_rec;
       w.item_ptr = g.dn_ritem + sr.item_first; w.n_items = sr.n_items;
@@ -1478,8 +1461,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   // execute whose near field is near_spmv_pipe_kernel and whose P2M is p2m_stream_kernel.  Stage timing keeps the two launches:
   // its events bracket the near kernel alone.  FMMBEM_NEAR_P2M, read per launch: 0 = separate launches, 2 = one launch or
   // FMMBEM_ERR_UNSUPPORTED (tests: proves which path ran), otherwise one launch where eligible.
-  const char* fuse_env = std::getenv("FMMBEM_NEAR_P2M");
-  const int fuse_mode = fuse_env ? std::atoi(fuse_env) : 1;
+  const int fuse_mode = sw::near_p2m();
   const bool fuse = fuse_mode != 0 && phase == 0 && !near_only && !targets && tm == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
                     d.kernel != FMMBEM_KERNEL_STOKES_BEM && near_p2m_ok(d, p);
   if (fuse_mode == 2 && !fuse) return fail(FMMBEM_ERR_UNSUPPORTED, "FMMBEM_NEAR_P2M=2: this execute does not take the combined near-field / P2M launch");
@@ -1534,15 +1516,6 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
 // ======================================= batched execute =======================================
 // Vectors per near-field pass on the fast path (FMMBEM_BATCH_NV = 2, 4 or 8 for sweeps).  ms per vector at N = 1M, k = 4 / 8,
 // p = 10 and 2 (tools/batch_time.py, profiles/r06b_batch_time.txt): 2 -> 1.24, 0.59; 4 -> 1.16, 0.56; 8 -> 1.29, 0.67.
-static int batch_nv() {
-  static const int nv = [] {
-    const char* e = std::getenv("FMMBEM_BATCH_NV");
-    const int v = e ? std::atoi(e) : 4;
-    return v == 2 || v == 8 ? v : 4;
-  }();
-  return nv;
-}
-
 // the plans whose near field is the pipelined one-unknown SpMV on one device (include/fmmbem.h, fmmbem_plan_execute_batch), and
 // the Stokes plans with the symmetric blocks that ask for it (fmmbem_options.stokes_batch_width)
 int fmmbem_plan::batch_width() const {
@@ -1551,13 +1524,13 @@ int fmmbem_plan::batch_width() const {
   if (!one) return 1;
   if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM)
     return !targets && opts.stokes_batch_width >= 2 && batch_near_sym3_ok(d, opts.stokes_batch_width) ? opts.stokes_batch_width : 1;
-  return !batch_near_ok(d) ? 1 : bat.width ? bat.width : batch_nv();
+  return !batch_near_ok(d) ? 1 : bat.width ? bat.width : sw::batch_nv();
 }
 
 // all or nothing: a failed allocation leaves the plan as it was (FMMBEM_ERR_ALLOC; single executes are unaffected)
 int fmmbem_plan::batch_alloc(hipStream_t s) {
   if (bat.width) return FMMBEM_OK;
-  const int w = opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? opts.stokes_batch_width : batch_nv();
+  const int w = opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? opts.stokes_batch_width : sw::batch_nv();
   const size_t nt = (size_t)hp.n * d.dof, nm = (size_t)hp.nboxes * d.nslots * d.s_max;
   BatchBufs b;
   std::vector<void*> got;
@@ -1828,7 +1801,7 @@ static int multi_finish(const fmmbem_options& opts, std::shared_ptr<MultiDevice>
     HIP_TRY(hipEventCreateWithFlags(&m->ev_up[r], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&m->ev_done[r], hipEventDisableTiming));
     m->shards[r]->result_slices = true;
-    m->shards[r]->use_graphs = !(std::getenv("FMMBEM_GRAPH") && std::atoi(std::getenv("FMMBEM_GRAPH")) == 0);   // a shard's chain is short: the host must stay ahead of W of them
+    m->shards[r]->use_graphs = sw::graph(true);   // a shard's chain is short: the host must stay ahead of W of them
   }
   HIP_TRY(hipSetDevice(m->dev[0]));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->gathered), sizeof(double) * m->chunk * (size_t)W));
@@ -1866,7 +1839,7 @@ static int multi_create(const fmmbem_options* opts, const std::vector<int>& devi
       fmmbem_options o = *opts;
       o.n_devices = 0; o.device = devices[r]; o.shard_rank = r; o.shard_world = W;
       o.shard_upward = opts->shard_upward == 0 ? 0 : 2;            // 0: every device repeats the upward pass; else: owners + selective exchange
-      if (std::getenv("FMMBEM_MULTI_UPWARD")) o.shard_upward = std::atoi(std::getenv("FMMBEM_MULTI_UPWARD")) ? 2 : 0;
+      o.shard_upward = sw::multi_upward(o.shard_upward != 0) ? 2 : 0;
       fmmbem_plan* p = nullptr;
       rc[r] = fmmbem_plan_create(&o, n_panels, vertices, bc, &p);
       if (rc[r] != FMMBEM_OK) err[r] = g_last_error;
@@ -1933,7 +1906,7 @@ static int multi_execute_device(fmmbem_plan* h, int p, const double* d_x, double
   // Every device's share of a phase is ISSUED by a thread of its own (host_parallel): one thread took 0.43 ms to issue a matvec
   // over eight devices -- as long as a shard's share of the work runs (FMMBEM_MULTI_ISSUE_THREADS=0: the one thread).  A phase's
   // events are all recorded when its fan-out returns, which is what the next phase waits on.
-  const bool threads = W > 1 && !(std::getenv("FMMBEM_MULTI_ISSUE_THREADS") && std::atoi(std::getenv("FMMBEM_MULTI_ISSUE_THREADS")) == 0);
+  const bool threads = W > 1 && sw::multi_issue_threads();
   std::vector<int> rcs((size_t)W, FMMBEM_OK);
   std::vector<std::string> errs((size_t)W);
   auto fan_out = [&](auto&& body) -> int {
@@ -2019,12 +1992,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
     // a device list: the options' own, or FMMBEM_DEVICES=0,1,2,... for callers that cannot say (the reference's unmodified drivers)
     std::vector<int> devices;
     if (opts->n_devices > 1) devices.assign(opts->devices, opts->devices + std::min(opts->n_devices, 8));
-    else if (opts->n_devices == 0 && opts->shard_world <= 1 && !opts->host_only) {
-      if (const char* e = std::getenv("FMMBEM_DEVICES")) {
-        for (const char* c = e; *c;) { char* end = nullptr; const long v = std::strtol(c, &end, 10); if (end == c) break; devices.push_back((int)v); c = *end ? end + 1 : end; }
-        if (devices.size() < 2) devices.clear();
-      }
-    }
+    else if (opts->n_devices == 0 && opts->shard_world <= 1 && !opts->host_only) devices = sw::devices();
     if (!devices.empty()) {
       if (opts->host_only) return fail(FMMBEM_ERR_INVALID, "a device list and host_only exclude each other");
       return multi_create(opts, devices, n_panels, vertices, bc, out);
@@ -2032,7 +2000,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   }
   if (!opts->host_only) (void)order_tables();             // the order tables start building now, beside the tree
   uint64_t fp[2] = {0, 0};
-  const bool share_on = !opts->host_only && !(std::getenv("FMMBEM_PLAN_SHARE") && std::atoi(std::getenv("FMMBEM_PLAN_SHARE")) == 0);
+  const bool share_on = !opts->host_only && sw::plan_share();
   if (share_on) {
     fingerprint_vertices(vertices, n_panels, fp);
     if (std::shared_ptr<PlanShared> sh = geometry_cache_find(n_panels, fp, *opts)) {
@@ -2052,14 +2020,14 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   ho.evaluator = opts->evaluator;
   ho.shard_upward = opts->shard_upward < 0 ? 0 : opts->shard_upward > 2 ? 2 : opts->shard_upward;
   ho.reference_l2l = opts->l2l_rule == FMMBEM_L2L_REFERENCE;
-  ho.panels_on_device = !opts->host_only && !(std::getenv("FMMBEM_PANELS_ON_HOST") && std::atoi(std::getenv("FMMBEM_PANELS_ON_HOST")) != 0);
+  ho.panels_on_device = !opts->host_only && !sw::panels_on_host();
   const double t0 = now_ms();
   // The near field goes to the device as soon as the host plan holds what it needs -- the panels' geometry, the leaves, the
   // near lists -- and its assembly runs on the GPU while the host builds the far-field lists (FMMBEM_BUILD_TWO_PHASE=0: after them)
   int near_rc = FMMBEM_OK;
   bool near_done = false;
   double near_ms = 0;
-  if (!opts->host_only && ho.panels_on_device && !(std::getenv("FMMBEM_BUILD_TWO_PHASE") && std::atoi(std::getenv("FMMBEM_BUILD_TWO_PHASE")) == 0))
+  if (!opts->host_only && ho.panels_on_device && sw::build_two_phase())
     ho.after_near_lists = [&]() -> std::string {
       const double t = now_ms();
       pl->has_bc[0] = pl->hp.has_bc[0]; pl->has_bc[1] = pl->hp.has_bc[1];

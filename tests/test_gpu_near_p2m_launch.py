@@ -159,3 +159,75 @@ def test_plans_that_keep_the_two_launches(fb, monkeypatch, kind):
     assert torch.equal(torch.from_numpy(pl.execute(x)), before)
     monkeypatch.setenv("FMMBEM_NEAR_P2M", "0")
     assert torch.equal(torch.from_numpy(pl.execute(x)), before)
+
+
+# ---- the edges of the eligibility rule (near form Pipe and P2M form Stream, launch_choice.hpp), each proved by FMMBEM_NEAR_P2M=2 ----
+
+def _refused(fb, pl, x, p):
+    with pytest.raises(fb.FmmBemError) as e:
+        _run(pl, x, p)
+    assert e.value.status == ERR_UNSUPPORTED
+
+
+def test_order_edge_of_the_streaming_p2m(fb, monkeypatch):
+    """p = 7 has 28 coefficients and keeps p2m_apply_kernel; p = 8 has 36, more than half a wavefront, and streams: on one plan
+    the first is refused, the second runs, and both give the bits of the two launches."""
+    v = _two_spheres(fb, 5)
+    x = np.random.default_rng(48).standard_normal(len(v))
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "0")
+    pl = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, _opts(fb, 64))
+    before = {p: _run(pl, x, p) for p in (7, 8)}
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "2")
+    _refused(fb, pl, x, 7)
+    assert _same(_run(pl, x, 8), before[8])
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "1")
+    assert _same(_run(pl, x, 7), before[7])
+
+
+def test_p2m_stream_switch_is_read_at_every_launch(fb, monkeypatch):
+    """FMMBEM_P2M_STREAM=0 takes the streaming P2M away from a live plan, so p = 10 is refused; unset again, p = 10 runs combined
+    on the same plan.  The plan and the near-field launcher read the switch at the same call, through the same function."""
+    v = _two_spheres(fb, 5)
+    x = np.random.default_rng(49).standard_normal(len(v))
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "0")
+    pl = fb.FMM_plan(fb.LaplaceSphericalBEM(10, 3), v, _opts(fb, 64))
+    before = _run(pl, x, 10)
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "2")
+    assert _same(_run(pl, x, 10), before)
+    monkeypatch.setenv("FMMBEM_P2M_STREAM", "0")
+    _refused(fb, pl, x, 10)
+    monkeypatch.delenv("FMMBEM_P2M_STREAM")
+    assert _same(_run(pl, x, 10), before)
+
+
+def test_float_near_field_keeps_the_two_launches(fb, monkeypatch):
+    """near_f32_max_p = 5: p = 4 streams the float copy (and is below the streaming P2M) and is refused; p = 8 takes the FP64
+    matrix and runs combined."""
+    v = _two_spheres(fb, 5)
+    x = np.random.default_rng(50).standard_normal(len(v))
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "0")
+    pl = fb.FMM_plan(fb.LaplaceSphericalBEM(8, 3), v, _opts(fb, 64), near_f32_max_p=5)
+    assert pl.stats()["near_f32_bytes"] > 0
+    before = {p: _run(pl, x, p) for p in (4, 8)}
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "2")
+    _refused(fb, pl, x, 4)
+    assert _same(_run(pl, x, 8), before[8])
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "1")
+    assert _same(_run(pl, x, 4), before[4])
+    assert pl.stats()["last_near_f32"] == 1
+
+
+def test_hybrid_plan_keeps_the_two_launches(fb, monkeypatch):
+    """near_stream_fraction = 0.5: the near field is launch_near_hybrid's two kernels, never near_spmv_pipe_kernel alone."""
+    v = _two_spheres(fb, 5)
+    x = np.random.default_rng(51).standard_normal(len(v))
+    o = _opts(fb, 64)
+    o.near_stream_fraction = 0.5
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "1")
+    pl = fb.FMM_plan(fb.LaplaceSphericalBEM(10, 3), v, o)
+    assert pl.stats()["near_recomputed_pairs"] > 0
+    before = _run(pl, x, 10)
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "2")
+    _refused(fb, pl, x, 10)
+    monkeypatch.setenv("FMMBEM_NEAR_P2M", "1")
+    assert _same(_run(pl, x, 10), before)
