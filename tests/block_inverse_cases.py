@@ -8,7 +8,7 @@ U = 2.0 ** -52
 
 
 def soup(seed, n, clusters, stretch, size_spread, sigma):
-    """tests/test_random_meshes.py::_soup with the spread of a cluster as a parameter (there 0.15): at sigma = 0.03 the panels
+    """tests/near_form_cases.py::_soup with the spread of a cluster as a parameter (there 0.15): at sigma = 0.03 the panels
     of a cluster sit within a few panel sizes of each other and the off-diagonal entries of a leaf block outgrow the diagonal"""
     rng = np.random.default_rng(seed)
     centres = rng.uniform(-1, 1, (clusters, 3)) * np.array([stretch, 1.0, 1.0 / stretch])

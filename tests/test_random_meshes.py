@@ -7,18 +7,7 @@ import pytest
 from hypothesis import HealthCheck, given, settings
 from hypothesis import strategies as st
 
-
-def _soup(seed, n, clusters, stretch, size_spread):
-    rng = np.random.default_rng(seed)
-    centres = rng.uniform(-1, 1, (clusters, 3)) * np.array([stretch, 1.0, 1.0 / stretch])
-    which = rng.integers(0, clusters, n)
-    c = centres[which] + rng.normal(0, 0.15, (n, 3))
-    h = 0.02 * np.exp(rng.uniform(-size_spread, size_spread, n))
-    e0, e1 = rng.normal(size=(n, 3)), rng.normal(size=(n, 3))
-    e0 /= np.linalg.norm(e0, axis=1, keepdims=True)
-    e1 -= (e1 * e0).sum(axis=1, keepdims=True) * e0
-    e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
-    return np.stack([c, c + h[:, None] * e0, c + h[:, None] * (0.3 * e0 + e1)], axis=1)
+from near_form_cases import _soup
 
 
 def _coverage(pl, n):
