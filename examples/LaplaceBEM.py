@@ -31,7 +31,7 @@ import fmm_bem_relaxed_amd as fb  # noqa: E402
 def print_help_and_exit():
     print("serialBEM : FMM-BEM for Potential problems\n\nUsage: LaplaceBEM.py <options>\n\nFMM/Treecode Options:\n"
           "-theta <double> : Set MAC theta for treecode evaluators\n"
-          "-eval {FMM,TREE} : Choose either FMM or treecode evaluator (only FMM is built)\n"
+          "-eval {FMM,TREE} : Choose either FMM or treecode evaluator\n"
           "-ncrit <int> : Maximum # of particles per Octree box\n\nProblem & Solver Options:\n"
           "-p <double> : Number of terms in the Multipole / Local expansions\n"
           "-k {1,3,4,7} : Number of Gauss integration points used per panel\n"
@@ -107,7 +107,7 @@ def main(argv):
     if len(argv) == 1:
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
-    second_kind, mesh, field, near_f32 = False, None, 0, 0
+    second_kind, mesh, field, near_f32, evaluator = False, None, 0, 0, "FMM"
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -118,8 +118,12 @@ def main(argv):
             i += 1; theta = float(argv[i]); print("theta = %s" % argv[i])
         elif a == "-recursions":
             i += 1; recursions = int(argv[i]); print("N = %i" % (2 * 4 ** recursions))
-        elif a == "-eval":
+        elif a == "-eval":                                 # FMMOptions.hpp:85-94 (the reference's driver prints no line for it)
             i += 1
+            if argv[i] in ("FMM", "TREE"):
+                evaluator = "TREECODE" if argv[i] == "TREE" else "FMM"
+            else:
+                print('[W]: Unknown evaluator type: "%s"' % argv[i])
         elif a == "-ncrit":
             i += 1; ncrit = int(argv[i]); print("ncrit = %s" % argv[i])
         elif a == "-printtree":
@@ -171,6 +175,7 @@ def main(argv):
     opts = fb.FMMOptions()
     opts.set_mac_theta(theta)
     opts.set_max_per_box(ncrit)
+    opts.evaluator = evaluator                                         # the solve plan and the right-hand-side plan (:209-232)
     bc = np.full(n, 1 if second_kind else 0, dtype=np.uint8)           # panels switch_BC() for the second kind (:190-191)
     K = fb.LaplaceSphericalBEM(p, k)
     plan = fb.FMM_plan(K, v, opts, bc=bc, p_max=p, near_f32_max_p=near_f32)    # the operator of the solve; the right-hand side stays FP64
@@ -233,6 +238,7 @@ def main(argv):
     print("relative error: %.3e" % math.sqrt(e / n))
     if field > 0:
         pts = sphere_points(field, 3.0)
+        opts.evaluator = "FMM"                             # plans over target points: the FMM evaluator only
         phi = exterior_fmm(fb, v, xs, np.ones(n), pts, p, k, opts)
         err = np.abs(phi - 1.0 / 3.0) / (1.0 / 3.0)
         print("field: %d points at r = 3, max error: %.4e, rms error: %.4e" % (field, float(err.max()), float(np.sqrt((err ** 2).mean()))))

@@ -16,6 +16,7 @@ PMAX = 16
 MAX_QUAD = 79          # FMMBEM_MAX_QUAD
 KERNEL_LAPLACE_BEM, KERNEL_STOKES_BEM = 0, 1
 EVAL_FMM, EVAL_LOCAL, EVAL_BLOCK_DIAGONAL = 0, 1, 2
+EVAL_TREECODE = 4                                      # 3 is no evaluator (FMMBEM_ERR_INVALID)
 L2L_COMPLETE, L2L_REFERENCE = 0, 1
 BC_POTENTIAL, BC_NORMAL_DERIV = 0, 1
 

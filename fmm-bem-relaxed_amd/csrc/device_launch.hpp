@@ -65,6 +65,17 @@ hipError_t launch_l2l_level(const DevicePlan& d, const ShiftOpDev& op, int p, in
 // y[i] += the far field of row i (tree order).  With perm: y_out[perm[i]] = y[i] + the far field instead, y left as it is --
 // the result scatter folded into L2P's store (Laplace only; the caller makes sure the L2P groups cover every row)
 hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s, const uint32_t* perm = nullptr, double* y_out = nullptr);
+// ---- treecode evaluator (FMMBEM_EVAL_TREECODE): the far field by M2P instead of M2L, L2L and L2P ----
+// Work of m2p_kernel, built once per geometry.  An item is up to 64 consecutive rows of one target leaf; the leaf's chain is the
+// boxes from the root down to the leaf itself that are the target of an M2L pair, and the sources of a chain box are its range of
+// DevicePlan::m2l_ptr / m2l_src, in list order.  Leaves whose chain is empty have no item.
+struct M2PWork {
+  const int *item_leaf = nullptr, *item_row = nullptr;   // [n_items] leaf index, first row of the item within the leaf
+  int n_items = 0;
+  const int *chain_ptr = nullptr, *chain_box = nullptr;  // [nleaves + 1] -> chain_box
+};
+// y[i] += (POTENTIAL row) or -= (NORMAL_DERIV row) the sum over the row's chain of M2P(M[source], centre[source], centroid i); Laplace
+hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, hipStream_t s);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

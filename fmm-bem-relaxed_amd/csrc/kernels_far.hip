@@ -1003,6 +1003,110 @@ __global__ __launch_bounds__(kL2PWaves * kWave) __attribute__((amdgpu_waves_per_
 }
 
 // ---------------------------------------------------------------------------------------------
+// M2P, the far field of the treecode evaluator (LaplaceSphericalBEM::M2P, kernel/LaplaceSphericalBEM.hpp:395-422, called for every
+// long-range pair by EvalInteractionLazySparse<Context, false>): lane = target row.  A wavefront takes one item of M2PWork -- up to 64
+// rows of one leaf -- and walks the leaf's chain of boxes from the root down; for every chain box its sources in list order,
+// kM2PBatch at a time: the active slots of their M are staged in the wavefront's LDS slice times w_m pref(n, m) (sG, as L2P stages
+// L), then every lane runs L2P's recurrence on q = rho^-(n+1) P_n^m at its own (rho, alpha, beta) about the source's centre
+// (evalLocal, kernel/LaplaceSpherical.hpp:491-524): the same seven operations per term with 1/rho in the place of rho.
+// Order of a row's sum: chain boxes from the root down, sources in list order, terms m-major; one sum per source, added to the
+// row's far field in a register, which joins y_tree once.  No atomics: a row belongs to one item.
+// (The term loop is l2p_kernel's, restated here.  As one function called by both kernels it changed the instruction order and the
+// registers of l2p_kernel at every order, and L2P is on the FMM path that the benchmark times: L2P's code stays as it was.)
+// ---------------------------------------------------------------------------------------------
+template <int PT>
+__global__ __launch_bounds__(kM2PWaves * kWave) void m2p_kernel(DevicePlan d, M2PWork w, const int Prt, double* __restrict__ y) {
+  extern __shared__ double2 m2p_lds[];                  // tables (3 S doubles), then [wave][source of the batch][active slot][S]
+  const int P = PT > 0 ? PT : Prt;
+  const int S = P * (P + 1) / 2, na = d.n_act, per = na * S;
+  double* sG = reinterpret_cast<double*>(m2p_lds);
+  double* sC1 = sG + S;
+  double* sC2 = sC1 + S;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
+  double2* Mw = m2p_lds + (3 * S + 1) / 2 + (size_t)wave * kM2PBatch * per;
+  if (wave == 0) fill_l2p_tables(d, P, S, lane, PT == 0, sG, sC1, sC2);
+  __syncthreads();
+  const int act0 = d.act[0], act1 = d.act[1];
+  for (int it = blockIdx.x * nwaves + wave; it < w.n_items; it += gridDim.x * nwaves) {
+    // one item per wavefront: its leaf, chain and sources are wave-uniform (scalar loads)
+    const int leaf = __builtin_amdgcn_readfirstlane(w.item_leaf[it]), r_in_leaf = __builtin_amdgcn_readfirstlane(w.item_row[it]) + lane;
+    const bool live = r_in_leaf < d.leaf_nrows[leaf];
+    const int64_t i = d.leaf_row0[leaf] + (live ? r_in_leaf : 0);   // idle lanes read the leaf's first row and store nothing
+    const int tb = d.bc[i] ? 1 : 0;
+    const double tx = d.cx[i], ty = d.cy[i], tz = d.cz[i];
+    const double2* Mt = Mw + (na == 2 ? tb : 0) * S;     // the slot is picked by the row's flag, as in L2P
+    double far = 0;
+    for (int c = w.chain_ptr[leaf], ce = w.chain_ptr[leaf + 1]; c < ce; ++c) {
+      const int box = w.chain_box[c];
+      for (int k0 = d.m2l_ptr[box], k1 = d.m2l_ptr[box + 1]; k0 < k1; k0 += kM2PBatch) {
+        const int nb = k1 - k0 < kM2PBatch ? k1 - k0 : kM2PBatch, T = nb * per;
+        wave_lds_sync();                                  // the previous batch's reads are done
+#pragma unroll 4
+        for (int e = lane; e < T; e += kWave) {
+          const int j = e / per, rem = e - j * per, a = rem / S, n = rem - a * S;
+          const double2 v = d.M[((size_t)d.m2l_src[k0 + j] * d.nslots + (a == 0 ? act0 : act1)) * d.s_max + n];
+          const double sc = sG[n];
+          Mw[e] = double2{v.x * sc, v.y * sc};
+        }
+        wave_lds_sync();
+        const int nbl = live ? nb : 0;                    // idle lanes of a short leaf take no source
+#pragma nounroll
+        for (int j = 0; j < nbl; ++j) {
+          const int src = d.m2l_src[k0 + j];
+          const Sph s = cart2sph(tx - d.box_center[3 * src], ty - d.box_center[3 * src + 1], tz - d.box_center[3 * src + 2]);
+          const double inv = 1.0 / s.rho;
+          const double z = inv * s.ca, inv2 = inv * inv;
+          const double2* Ms = Mt + (size_t)j * per;
+          double r = 0;
+          double pn = 1, rhom = inv, er = 1, ei = 0, fact = 1;
+          auto order = [&](int m, int& step, auto unrolled) FMMBEM_INLINE {
+            int tz_ = 0;                                  // keeps a coefficient's LDS read with its term (see l2p_kernel)
+            if constexpr (decltype(unrolled)::value) asm volatile("" : "+v"(tz_), "+v"(r));
+            const double2* Mm = Ms + tz_;
+            double q = pn * rhom, q1 = q;                 // rho^-(n+1) P_n^m and its predecessor
+            auto degree = [&](int n) FMMBEM_INLINE {
+              const double2 Mc = Mm[n * (n + 1) / 2 + m];  // the coefficient times w_m pref(n, m)
+              const double u = fma(Mc.x, er, -(Mc.y * ei));   // Re(M' e^{+i m beta})
+              r = fma(u, q, r);
+              double k1_, k2_;
+              if constexpr (decltype(unrolled)::value) { k1_ = l2p_c1(n, m); k2_ = l2p_c2(n, m); }
+              else { k1_ = sC1[step]; k2_ = sC2[step]; }
+              const double zq = z * q;
+              const double qn = n == m ? k1_ * zq : fma(k1_, zq, -(k2_ * (inv2 * q1)));
+              q1 = q;
+              q = qn;
+              ++step;
+            };
+            if constexpr (decltype(unrolled)::value) {
+#pragma unroll
+              for (int n = m; n < PT; ++n) degree(n);
+            } else {
+#pragma nounroll
+              for (int n = m; n < P; ++n) degree(n);
+            }
+            pn = -pn * fact * s.sa;
+            fact += 2;
+            rhom *= inv;
+            const double nr = er * s.cb - ei * s.sb, ni = er * s.sb + ei * s.cb;
+            er = nr; ei = ni;
+          };
+          int step = 0;
+          if constexpr (PT > 0) {
+#pragma unroll
+            for (int m = 0; m < PT; ++m) order(m, step, std::true_type{});
+          } else {
+#pragma nounroll
+            for (int m = 0; m < P; ++m) order(m, step, std::false_type{});
+          }
+          far += r;
+        }
+      }
+    }
+    if (live) y[i] += tb ? -far : far;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Stokes L2P: StokesSpherical::L2P (kernel/StokesSpherical.hpp:318-401) then the 1/(2 mu) of
 // StokesSphericalBEM::L2P (kernel/StokesSphericalBEM.hpp:512-522).  Lane = target panel; the leaf's four
 // harmonic potentials L[0..3] in LDS; per lane the potentials' values and spherical gradients are
@@ -1331,6 +1435,22 @@ hipError_t launch_l2p(const DevicePlan& d, int p, double* y, hipStream_t s, cons
     default: hipLaunchKernelGGL(l2p_kernel<0>, grid, block, lds, s, d, p, y, store ? 1 : 0, perm, y_out);
   }
 #undef L2P_CASE
+  return hipGetLastError();
+}
+
+hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, hipStream_t s) {
+  if (hipError_t e = upload_constants_once(); e != hipSuccess) return e;
+  if (w.n_items <= 0) return hipSuccess;
+  if (p < 1 || p > kPmaxDev || d.n_act < 1 || d.n_act > 2) return hipErrorInvalidValue;
+  const size_t lds = m2p_lds(d, p);                    // launch_choice.hpp
+  const dim3 grid(m2p_grid(d, p, w.n_items)), block(m2p_waves(d, p) * kWave);
+#define M2P_CASE(PP) case PP: hipLaunchKernelGGL(m2p_kernel<PP>, grid, block, lds, s, d, w, p, y); break;
+  switch (p <= kL2PUnrollMax ? p : 0) {
+    M2P_CASE(1) M2P_CASE(2) M2P_CASE(3) M2P_CASE(4) M2P_CASE(5) M2P_CASE(6) M2P_CASE(7) M2P_CASE(8)
+    M2P_CASE(9) M2P_CASE(10) M2P_CASE(11) M2P_CASE(12)
+    default: hipLaunchKernelGGL(m2p_kernel<0>, grid, block, lds, s, d, w, p, y);
+  }
+#undef M2P_CASE
   return hipGetLastError();
 }
 

@@ -83,6 +83,18 @@ inline int p2m_grid(const DevicePlan& d, P2MForm f) {
 // knows: hybrid and float near fields, target plans, partial executes, stage timing.
 inline bool near_p2m_ok(const DevicePlan& d, int p) { return near_form(d) == NearForm::Pipe && p2m_form(d, p) == P2MForm::Stream; }
 
+// ---------------------------------------- M2P (kernels_far.hip, the treecode's far field) ----------------------------------------
+constexpr int kM2PWaves = 4;                          // items (<= 64 rows of one leaf) per workgroup, one per wavefront
+constexpr int kM2PBatch = 4;                          // sources whose M is staged per LDS fill
+// a wavefront's LDS slice: the batch's sources x active slots x S coefficients (7 KB at p = 10, 17 KB at p = 16 with both slots);
+// fewer wavefronts per workgroup where four slices pass 48 KB, as L2P
+inline size_t m2p_wave_lds(const DevicePlan& d, int p) { return sizeof(double2) * (size_t)kM2PBatch * d.n_act * (p * (p + 1) / 2); }
+inline int m2p_waves(const DevicePlan& d, int p) { return (int)std::clamp<size_t>((48 * 1024) / m2p_wave_lds(d, p), 1, kM2PWaves); }
+inline size_t m2p_lds(const DevicePlan& d, int p) {   // the tables of fill_l2p_tables (3 S doubles), then the slices
+  return sizeof(double2) * (size_t)((3 * (p * (p + 1) / 2) + 1) / 2) + m2p_waves(d, p) * m2p_wave_lds(d, p);
+}
+inline int m2p_grid(const DevicePlan& d, int p, int n_items) { return std::min((n_items + m2p_waves(d, p) - 1) / m2p_waves(d, p), 256 * 8); }
+
 // one level of M2M or L2L: the one-pair-per-wavefront kernel, the rotation kernel, or the sparse operators (PlanGeometry::shift_form)
 enum class ShiftForm { Lanes, Rot, Sparse };
 

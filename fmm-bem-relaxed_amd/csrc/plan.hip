@@ -163,6 +163,7 @@ struct PlanGeometry {
   // panels, one shard, whose L2P groups cover every row (decided once, to_device_far).  FMMBEM_L2P_SCATTER=0 keeps the separate
   // kernel (read per execute, for A/B runs).  The same single rounded add either way: the same bits.
   bool l2p_scatter = false;
+  M2PWork m2p;                                                 // treecode plans (FMMBEM_EVAL_TREECODE): the far field's work, else empty
   std::vector<ShiftOpDev> up_ops, down_ops;                    // M2M / L2L operators, index p - 1
   // sizes of the stored near blocks (allocated per plan, to_device_bc_begin)
   int64_t near_total_doubles = 0, sym_total_doubles = 0;
@@ -248,6 +249,12 @@ struct fmmbem_plan {
   struct GraphEntry { int region, p; const void* buf; int runs; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;
   bool use_graphs = false;
+  // The treecode evaluator: an FMM plan up to and including M2M; the far field is then ONE stage, M2P from the multipoles into
+  // y_tree (launch_m2p on g.m2p), and the ordinary scatter delivers.  Of the FMM path's shortcuts it takes none that look past
+  // M2M: not L2P's folded scatter (l2p_delivers), not mh_prep or the rotation items (nothing reads Mh).  It also leaves the
+  // combined near-field / P2M launch alone and runs the two launches: the same M bit for bit, and the treecode's critical path is
+  // the M2P stage, not the near field's drain.
+  bool treecode() const { return opts.evaluator == FMMBEM_EVAL_TREECODE; }
   // the launchers of one stage on the DevicePlan given (the plan's d; a batch: vector j's view of it)
   int m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const;
   int l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const;
@@ -257,7 +264,7 @@ struct fmmbem_plan {
   bool pending_near = false;                                   // split execute: the near field already ran (fmmbem_plan_near_split_device)
   bool result_slices = false;                                  // execute delivers the owned rows in tree order (fmmbem_plan_set_result_slices)
   bool l2p_delivers(bool near_only, int phase) const {         // (PlanGeometry::l2p_scatter)
-    if (!g.l2p_scatter || result_slices || near_only || phase != 0) return false;
+    if (!g.l2p_scatter || result_slices || near_only || phase != 0 || treecode()) return false;   // a treecode runs no L2P
     return sw::l2p_scatter();
   }
   int64_t* d_cut = nullptr;                                    // tree-order row cuts of all shards, on the device
@@ -535,7 +542,7 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
     });
     for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) max_runs_owned = std::max(max_runs_owned, nruns_of[l]);
     for (int l = 0; l < nl; ++l) run_ptr[l + 1] = run_ptr[l] + nruns_of[l];
-    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && rule_ok && (dof == 3 ? sw::stokes_sym() : near_pipe_ok(dof, max_runs_owned));
+    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && opts.evaluator != FMMBEM_EVAL_TREECODE && rule_ok && (dof == 3 ? sw::stokes_sym() : near_pipe_ok(dof, max_runs_owned));
     if (g.hybrid) {
       if (!(f >= 0.0)) f = 0.0;
       std::vector<int> order(nl);
@@ -976,6 +983,23 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
     d.n_m2l_tgt = (int)tgt.size(); d.n_mh = (int)mh.size();
     TRY(upload(tgt, &d.m2l_tgt)); TRY(upload(mh, &d.mh_box));
     TRY(upload(hp.m2l_ptr, &d.m2l_ptr)); TRY(upload(hp.m2l_src, &d.m2l_src)); TRY(upload(hp.m2l_cls, &d.m2l_cls));
+    if (opts.evaluator == FMMBEM_EVAL_TREECODE) {
+      // M2P work (device_launch.hpp M2PWork): per leaf the boxes of its path that are the target of a pair, root first -- box_parent
+      // is read here and never on the device -- and the leaves that have any cut into items of up to 64 rows
+      std::vector<int> chain_ptr(hp.nleaves() + 1, 0), chain_box, item_leaf, item_row, path;
+      for (int l = 0; l < hp.nleaves(); ++l) {
+        path.clear();
+        for (int b = hp.leaf_box[l]; b >= 0; b = b > 0 ? hp.box_parent[b] : -1)
+          if (hp.m2l_ptr[b + 1] > hp.m2l_ptr[b]) path.push_back(b);
+        chain_box.insert(chain_box.end(), path.rbegin(), path.rend());
+        chain_ptr[l + 1] = (int)chain_box.size();
+        const int nr = hp.box_body_end[hp.leaf_box[l]] - hp.box_body_begin[hp.leaf_box[l]];
+        for (int r = 0; r < nr && !path.empty(); r += 64) { item_leaf.push_back(l); item_row.push_back(r); }
+      }
+      g.m2p.n_items = (int)item_leaf.size();
+      TRY(upload(item_leaf, &g.m2p.item_leaf)); TRY(upload(item_row, &g.m2p.item_row));
+      TRY(upload(chain_ptr, &g.m2p.chain_ptr)); TRY(upload(chain_box, &g.m2p.chain_box));
+    }
     mark("m2l lists upload");
     g.n_classes = (int64_t)hp.m2l_class_rep.size() / 2;
     const int R = 2 * pm;
@@ -1462,7 +1486,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   // its events bracket the near kernel alone.  FMMBEM_NEAR_P2M, read per launch: 0 = separate launches, 2 = one launch or
   // FMMBEM_ERR_UNSUPPORTED (tests: proves which path ran), otherwise one launch where eligible.
   const int fuse_mode = sw::near_p2m();
-  const bool fuse = fuse_mode != 0 && phase == 0 && !near_only && !targets && tm == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
+  const bool fuse = fuse_mode != 0 && phase == 0 && !near_only && !targets && !treecode() && tm == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
                     d.kernel != FMMBEM_KERNEL_STOKES_BEM && near_p2m_ok(d, p);
   if (fuse_mode == 2 && !fuse) return fail(FMMBEM_ERR_UNSUPPORTED, "FMMBEM_NEAR_P2M=2: this execute does not take the combined near-field / P2M launch");
   TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0) + (fold ? 16 : 0) + (fuse ? 32 : 0), xbuf, [&](hipStream_t s) -> int {
@@ -1479,6 +1503,12 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
       HIP_TRY(begin(4, s));
       TRY(m2m_pass(d, p, false, s));
       HIP_TRY(end(4, s));
+    }
+    if (treecode()) {                                  // (never a shard: phase 0) the far field as one stage, timed as stage 6
+      HIP_TRY(begin(6, s));
+      HIP_TRY(launch_m2p(d, g.m2p, p, d.yt, s));
+      HIP_TRY(end(6, s));
+      return FMMBEM_OK;
     }
     HIP_TRY(begin(5, s));
     if (phase == 2) {                                  // the other shards' multipoles, then the boxes spanning shards
@@ -1616,6 +1646,12 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
       const DevicePlan dj = batch_view(bat, j);        // vector j's far field: the launchers of run() on its buffers
       if (stokes) HIP_TRY(launch_p2m_stokes(dj, p, s));
       TRY(m2m_pass(dj, p, false, s));
+      if (treecode()) {                                // as run(): M2P into vector j's y_tree, then the scatter
+        HIP_TRY(launch_m2p(dj, g.m2p, p, dj.yt, s));
+        TRY(deliver(dj, yj, false, s));
+        if (host) HIP_TRY(hipMemcpyAsync(y + (size_t)(j0 + j) * ldy, sy, bytes_y, hipMemcpyDeviceToHost, s));
+        continue;
+      }
       const bool rot = g.use_rot(p);
       if (!rot) HIP_TRY(launch_mh_prep(dj, p, s));
       if (rot) HIP_TRY(launch_m2l_rot(dj, bat.dev[j], p, s));
@@ -1981,9 +2017,23 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   }
   if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
   if (opts->l2l_rule != FMMBEM_L2L_COMPLETE && opts->l2l_rule != FMMBEM_L2L_REFERENCE) return fail(FMMBEM_ERR_INVALID, "unknown l2l_rule");
-  if (opts->evaluator < FMMBEM_EVAL_FMM || opts->evaluator > FMMBEM_EVAL_BLOCK_DIAGONAL) return fail(FMMBEM_ERR_INVALID, "unknown evaluator");
+  const bool tree = opts->evaluator == FMMBEM_EVAL_TREECODE;
+  if (!tree && (opts->evaluator < FMMBEM_EVAL_FMM || opts->evaluator > FMMBEM_EVAL_BLOCK_DIAGONAL)) return fail(FMMBEM_ERR_INVALID, "unknown evaluator");
   if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
   if (opts->stokes_batch_width < 0 || opts->stokes_batch_width > 4) return fail(FMMBEM_ERR_INVALID, "stokes_batch_width outside 0..4");
+  // The treecode evaluator: M2P is built for the Laplace kernel, on one device, whole operator.  The hybrid and the float near
+  // field are taken as off (the options as the plan and the geometry cache then see them)
+  fmmbem_options tree_opts;
+  if (tree) {
+    if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "treecode evaluator: Laplace only (the Stokes M2P is not built)");
+    if (opts->shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "treecode evaluator: shard_world > 1 is not built");
+    if (opts->n_devices > 1 || (opts->n_devices == 0 && !opts->host_only && !sw::devices().empty()))
+      return fail(FMMBEM_ERR_UNSUPPORTED, "treecode evaluator: a device list (n_devices > 1 or FMMBEM_DEVICES) is not built");
+    tree_opts = *opts;
+    tree_opts.near_stream_fraction = 1.0;
+    tree_opts.near_f32_max_p = 0;
+    opts = &tree_opts;
+  }
   // The geometry of a live plan, recognised: same options, same panel count, same vertex bytes (two 64-bit hashes) -- only the
   // boundary-condition flags may differ.  The new plan then shares that plan's tree, lists and tables (PlanShared) and builds
   // only what the flags decide.  This is the drivers' second plan (examples/LaplaceBEM.cpp:218-232: the same panels with the
@@ -2017,7 +2067,7 @@ int fmmbem_plan_create(const fmmbem_options* opts, size_t n_panels, const double
   HostOptions ho;
   ho.p_max = opts->p_max; ho.quad_k = opts->quad_k; ho.theta = opts->theta; ho.ncrit = opts->ncrit;
   ho.shard_rank = opts->shard_rank; ho.shard_world = opts->shard_world < 1 ? 1 : opts->shard_world;
-  ho.evaluator = opts->evaluator;
+  ho.evaluator = tree ? (int)FMMBEM_EVAL_FMM : opts->evaluator;   // a treecode plan's tree and lists ARE the FMM plan's
   ho.shard_upward = opts->shard_upward < 0 ? 0 : opts->shard_upward > 2 ? 2 : opts->shard_upward;
   ho.reference_l2l = opts->l2l_rule == FMMBEM_L2L_REFERENCE;
   ho.panels_on_device = !opts->host_only && !sw::panels_on_host();
@@ -2571,7 +2621,7 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
   o->geometry_shared = (int32_t)plan->shared.use_count();
   o->n_devices = 1;
   o->expansion_slots = plan->on_device ? plan->d.nslots : (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 8 : 2);
-  o->m2l_kernel = plan->last_p > 0 ? (plan->g.use_rot(plan->last_p) ? 1 : plan->last_p <= 4 ? 3 : 2) : 0;
+  o->m2l_kernel = plan->last_p > 0 ? (plan->treecode() ? 4 : plan->g.use_rot(plan->last_p) ? 1 : plan->last_p <= 4 ? 3 : 2) : 0;
   o->rot_nop_orders = (int64_t)rot_nop_orders_m2l() | ((int64_t)rot_nop_orders_m2m() << 16) | ((int64_t)rot_nop_orders_l2l() << 32);
   o->tree_coder_levels = h.tree_levels_max;
   o->expansions_active = (plan->has_bc[0] ? 1 : 0) | (plan->has_bc[1] ? 2 : 0);
@@ -2810,6 +2860,7 @@ int fmmbem_plan_get_expansions(const fmmbem_plan* plan, int which, int p, double
   TRY(target_plan_only(plan, "fmmbem_plan_get_expansions"));
   if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
   if (!plan || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  if (which != 0 && plan->treecode()) return fail(FMMBEM_ERR_UNSUPPORTED, "a treecode plan holds no local expansions (M only)");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "expansions live on the device");
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   DEVICE_SCOPE(plan->opts.device);

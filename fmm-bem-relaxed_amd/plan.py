@@ -22,6 +22,9 @@ class FMMOptions:
 
     def __init__(self):
         self.lazy_evaluation = True     # FMMOptions.hpp:41
+        # FMMOptions.hpp:18,91 (`-eval FMM|TREE`): "FMM" or "TREECODE" -- with lazy_evaluation the far field by M2L, L2L and L2P, or
+        # every long-range pair by M2P (include/fmmbem.h FMMBEM_EVAL_TREECODE; Laplace, one device)
+        self.evaluator = "FMM"
         self.local_evaluation = False
         self.sparse_local = True        # examples/LaplaceBEM.cpp:81 forces it
         self.block_diagonal = False
@@ -417,8 +420,12 @@ class FMM_plan:
         opts = opts if opts is not None else FMMOptions()
         # executor/make_executor.hpp:24-60: lazy_evaluation wins, then local_evaluation, then block_diagonal; the
         # non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones
-        evaluator = _capi.EVAL_FMM
+        which = getattr(opts, "evaluator", "FMM")
+        if which not in ("FMM", "TREECODE"):
+            raise ValueError('FMMOptions.evaluator is "FMM" or "TREECODE"')
+        evaluator = _capi.EVAL_TREECODE if which == "TREECODE" else _capi.EVAL_FMM
         if not opts.lazy_evaluation:
+            evaluator = _capi.EVAL_FMM                 # local_evaluation and block_diagonal have no far field to choose
             if opts.local_evaluation:
                 evaluator = _capi.EVAL_LOCAL
             elif opts.block_diagonal:

@@ -71,7 +71,19 @@ typedef enum {
   FMMBEM_EVAL_FMM = 0,            /* EvalInteractionLazy(Sparse): near field + far field (the solver's operator)      */
   FMMBEM_EVAL_LOCAL = 1,          /* EvalLocal(Sparse): the near-field blocks only (Preconditioners::LocalInnerSolver,
                                    * examples/BEM/LocalPC.hpp:26-59)                                                  */
-  FMMBEM_EVAL_BLOCK_DIAGONAL = 2  /* EvalDiagonalSparse: every leaf with itself (examples/BEM/BlockDiagonalPC.hpp:16-60)  */
+  FMMBEM_EVAL_BLOCK_DIAGONAL = 2, /* EvalDiagonalSparse: every leaf with itself (examples/BEM/BlockDiagonalPC.hpp:16-60)  */
+  /* 3 is no evaluator and stays FMMBEM_ERR_INVALID (callers probe it as "no such evaluator") */
+  FMMBEM_EVAL_TREECODE = 4        /* EvalInteractionLazySparse<Context, false> (FMMOptions::TREECODE, `-eval TREE`): the FMM plan's
+                                   * lists, near field and upward pass; every long-range pair (source box, target box) is then
+                                   * evaluated by M2P at the bodies of the target box -- no L, L2L or L2P
+                                   * (executor/EvalInteractionLazySparse.hpp:269-283).  Laplace, fmmbem_plan_create / _create_like,
+                                   * sparse_local 0 or 1, host_only, on one device.  FMMBEM_ERR_UNSUPPORTED: Stokes, shard_world > 1,
+                                   * a device list (n_devices > 1 or FMMBEM_DEVICES), fmmbem_plan_create_targets.
+                                   * near_stream_fraction is taken as 1 and near_f32_max_p as 0 (accepted without effect), l2l_rule
+                                   * has no effect.  fmmbem_plan_get_expansions("L") returns FMMBEM_ERR_UNSUPPORTED: the plan holds
+                                   * no local expansions.  fmmbem_stats: the list counts are the FMM plan's (l2p_leaves and l2l_ops as
+                                   * built, though nothing runs on them); ms_m2l carries the M2P time, ms_mh, ms_l2l and ms_l2p are 0.
+                                   * The same bits on every run, graph replay and batch.                                       */
 } fmmbem_evaluator;
 
 /* Downward pass.  The reference's lazy evaluator queues L2L parent->child only for children that were not an M2L
@@ -176,7 +188,8 @@ typedef struct {
                                  * is the lane fill                                                   */
   int64_t near_side_entries;    /* matrix-free plans (sparse_local = 0): near-regime pairs evaluated once at creation and kept
                                  * (12 bytes each: column + value); 0 for assembled plans                */
-  int32_t m2l_kernel;           /* the M2L an execute at last_p took: 1 rotation kernel, 2 double sum, 3 double sum (lanes = sources) */
+  int32_t m2l_kernel;           /* the M2L an execute at last_p took: 1 rotation kernel, 2 double sum, 3 double sum (lanes = sources),
+                                 * 4 M2P (treecode) */
   int32_t expansion_slots;             /* slots per box in M and L (fmmbem_plan_get_expansions): Laplace 2, Stokes 8, 11 with TRACTION targets */
   int64_t rot_nop_orders;       /* build record: orders p of the rotation kernels that were compiled with a wait state in front of
                                  * every DPP FMA because the build's ISA check found the DPP hazard in their code (csrc/Makefile,
@@ -368,7 +381,8 @@ int fmmbem_kernel_entries(const fmmbem_options *opts, size_t n, const double *ta
  * and kernel/StokesSphericalBEM.hpp:391-530 define them (each "+=" into its last argument), for code that drives single operators
  * (tests/single_level.cpp, ExpansionTraits<K>::is_valid_fmm of include/KernelTraits.hpp:188-194).  Every call runs the SAME device
  * kernels a plan's matvec runs, on a two-box plan that holds just the call's operands (csrc/ops.hip); operands and results are
- * host buffers.  M2P (the treecode's operator) is not offered.
+ * host buffers.  M2P (the treecode's operator) runs inside a plan created with FMMBEM_EVAL_TREECODE and is
+ * not offered as a single operator.
  *   fmmbem_ops_create reads opts->kernel, p_max (1..16), quad_k, mu, device.  A handle is not thread-safe.
  *   An expansion: [slot][p (p + 1) / 2] complex as (re, im) pairs, coefficient (n, m >= 0) at n (n + 1) / 2 + m -- the reference's
  *   stored half (kernel/LaplaceSpherical.hpp:187-206).  fmmbem_ops_slots: the slots P2M writes and L2P reads -- Laplace 2

@@ -192,10 +192,11 @@ class FMMOptions {
   void print_tree(bool v) { printTree = v; }
   bool print_tree() const { return printTree; }
   // executor/make_executor.hpp:24-60: lazy_evaluation wins, then local_evaluation, then block_diagonal; the
-  // non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones
+  // non-lazy upward/interact/downward evaluators compute the same operator as the lazy ones.  evaluator == TREECODE picks the
+  // lazy evaluator's far field (EvalInteractionLazySparse<Context, false>: M2P for every long-range pair); local_evaluation and
+  // block_diagonal have no far field to pick.  The library refuses what it has no M2P for (a Stokes kernel, device lists).
   int c_evaluator() const {
-    if (evaluator != FMM) throw fmmbem::Error(FMMBEM_ERR_UNSUPPORTED, "the treecode evaluator is not built");
-    if (lazy_evaluation) return FMMBEM_EVAL_FMM;
+    if (lazy_evaluation) return evaluator == TREECODE ? FMMBEM_EVAL_TREECODE : FMMBEM_EVAL_FMM;
     return local_evaluation ? FMMBEM_EVAL_LOCAL : block_diagonal ? FMMBEM_EVAL_BLOCK_DIAGONAL : FMMBEM_EVAL_FMM;
   }
 };
@@ -261,7 +262,7 @@ class LaplaceSphericalBEM {
     return out;
   }
 
-  // ---- the single operators of kernel/LaplaceSphericalBEM.hpp:143-156, 307-476 (M2P, the treecode's, is not offered) ----
+  // ---- the single operators of kernel/LaplaceSphericalBEM.hpp:143-156, 307-476 (M2P, the treecode's, runs inside the plan and is not offered as a single operator) ----
   void init_multipole(multipole_type& M, const point_type&, unsigned) const { M.assign(2, std::vector<complex>((size_t)P * (P + 1) / 2, 0.)); }
   void init_local(local_type& L, const point_type&, unsigned) const { L.assign(2, std::vector<complex>((size_t)P * (P + 1) / 2, 0.)); }
   // M[0] += the G moments of a POTENTIAL source, M[1] += the dG/dn moments of a NORMAL_DERIV source (:323-344)
