@@ -13,7 +13,11 @@ against 6 pi mu, area and pointwise traction errors (:337-372).  All matvecs run
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
 
 -field N (not a flag of the reference): after the solve, the velocity of the single layer with the solved density on N points of the
-sphere of radius 3, summed on the device by fb.Direct (Stokes has no target plan); prints the largest and the mean magnitude.
+sphere of radius 3, summed on the device by fb.Direct; prints the largest and the mean magnitude.
+
+-field_fmm N (not a flag of the reference): the same velocity on the same N points by the FMM, through plan.field_plan
+(fmmbem_plan_create_field) at order p; prints "field (FMM): ..." in the format of the "field:" line and, given together with
+-field N, the relative L2 difference between the two.
 
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
@@ -54,6 +58,8 @@ def print_help_and_exit():
           "-block_inverse : (not a flag of the reference) GMRES preconditioned by the exact inverse of the leaf-diagonal blocks\n"
           "-stokes_batch <int> : (not a flag of the reference) vectors one near-field pass of a batch serves: 2, 3 or 4\n"
           "-resistance : (not a flag of the reference) the 3 x 3 translational resistance matrix, three solves in one batch\n"
+          "-field <int> : (not a flag of the reference) the solved layer's velocity on N points at r = 3, by the Direct sum\n"
+          "-field_fmm <int> : (not a flag of the reference) the same velocity by the FMM (plan.field_plan)\n"
           "-help : print this message")
     sys.exit(0)
 
@@ -81,7 +87,7 @@ def main(argv):
     recursions, p, k, kfine, cells, mu, p_min = 4, 8, 4, 19, 1, 1e-3, 5
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
-    rbc, near_f32, field = False, 0, 0
+    rbc, near_f32, field, field_fmm = False, 0, 0, 0
     stokes_batch, resistance = 0, False
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
@@ -138,6 +144,8 @@ def main(argv):
             resistance = True
         elif a == "-field":                                # not in the reference: the solved layer's velocity off the surface
             i += 1; field = int(argv[i])
+        elif a == "-field_fmm":                            # not in the reference: the same velocity through plan.field_plan
+            i += 1; field_fmm = int(argv[i])
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
@@ -226,12 +234,22 @@ def main(argv):
     print("\n\n\n\tdrag error per panel : %.5e, average panel area: %.5e" % (drag_error / n, area.sum() / n))
     print("\tArea error : %.5e" % (abs(area.sum() - analytical_area) / analytical_area))
     print("\n\nPOINTWISE ERRORS\n\terror: %.3e" % math.sqrt(e / e2))
+    u = None
     if field > 0:
         direct = fb.Direct(kernel(), v)
         u = direct.matvec_torch(x, torch.from_numpy(sphere_points(field, 3.0)).to(dev)).cpu().numpy()
         direct.close()
         mag = np.linalg.norm(u, axis=1)
         print("field: %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field, float(mag.max()), float(mag.mean())))
+    if field_fmm > 0:
+        fplan = plan.field_plan(sphere_points(field_fmm, 3.0))       # VELOCITY targets: the single layer
+        plan.kernel().set_p(p)                             # (the relaxed solve leaves the kernel at its last order)
+        uf = fplan.execute_torch(x).cpu().numpy()
+        fplan.close()
+        mag = np.linalg.norm(uf, axis=1)
+        print("field (FMM): %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field_fmm, float(mag.max()), float(mag.mean())))
+        if u is not None and field == field_fmm:
+            print("field (FMM) against field: relative L2 difference %.3e" % float(np.linalg.norm(uf - u) / np.linalg.norm(u)))
     if resistance:
         # unit translation e_j on every panel: the right-hand side 4 pi e_j (as b above), the force of the solved traction
         B = torch.zeros((3, n, 3), dtype=torch.float64, device=dev)

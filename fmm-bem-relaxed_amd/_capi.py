@@ -107,6 +107,7 @@ SYMBOLS = (
     "fmmbem_direct_create", "fmmbem_direct_apply", "fmmbem_direct_apply_device", "fmmbem_direct_chunk", "fmmbem_direct_destroy",
     "fmmbem_plan_block_inverse_build", "fmmbem_plan_block_inverse_apply_device", "fmmbem_plan_block_inverse_apply",
     "fmmbem_plan_block_inverse_bytes",
+    "fmmbem_plan_create_field",
 )
 
 
@@ -185,6 +186,7 @@ def lib():
     L.fmmbem_gmres_device.argtypes = [vp, C.POINTER(SolverOpts), vp, vp, C.POINTER(Preconditioner), C.POINTER(SolverLog), vp]
     L.fmmbem_plan_create_like.argtypes = [vp, vp, C.POINTER(vp)]
     L.fmmbem_plan_create_targets.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.fmmbem_plan_create_field.argtypes = [C.POINTER(Options), C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.fmmbem_plan_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
     L.fmmbem_plan_get_target_boxes.argtypes = [vp] * 8
     L.fmmbem_plan_get_target_perm.argtypes = [vp, vp, vp]

@@ -298,10 +298,12 @@ struct fmmbem_plan {
     for (void* p : {(void*)binv.dev.val, (void*)binv.dev.off, (void*)binv.dev.bad, (void*)binv.stage}) if (p) (void)hipFree(p);
     binv = BlockInverse{};
   }
-  // Dual plans (fmmbem_plan_create_targets): hp holds the source tree and the target tree as one plan (HostPlan::build_targets);
-  // x has hp.n_src entries, y hp.n_targets.  Every source feeds both expansions (the TARGET's flag picks the kernel): P2M runs once
-  // per live slot with the flags of all sources set to that slot's (bc_all[slot]) and that slot's moment table.
+  // Dual plans (fmmbem_plan_create_targets, fmmbem_plan_create_field): hp holds the source tree and the target tree as one plan
+  // (HostPlan::build_targets); x has hp.n_src x dof entries, y hp.n_targets x dof.  Every source feeds every live expansion group
+  // (the TARGET's flag picks the kernel).  Laplace: P2M runs once per live slot with the flags of all sources set to that slot's
+  // (bc_all[slot]) and that slot's moment table.  Stokes: the single plan's P2M as it is -- it never reads a source's flag.
   bool targets = false;
+  bool p2m_per_slot() const { return targets && opts.kernel != FMMBEM_KERNEL_STOKES_BEM; }
   bool zero_target_rows = false;                               // some target leaf has no near pair
   const uint8_t* bc_all[2] = {nullptr, nullptr};
   const double2* p2m_tab_slot[2] = {nullptr, nullptr};
@@ -402,10 +404,14 @@ __global__ void expand_csr_targets_kernel(const int* __restrict__ ptr, int nboxe
   for (int i = ptr[b]; i < ptr[b + 1]; ++i) tgt[i] = b;
 }
 
-// a target plan whose targets coincide: y[k] = y_points[point[k]] over the targets as given
-__global__ void expand_targets_kernel(const uint32_t* __restrict__ point, const double* __restrict__ yp, double* __restrict__ y, int64_t n) {
-  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (k < n) y[k] = yp[point[k]];
+// a target plan whose targets coincide: y[k] = y_points[point[k]] over the targets as given, dof unknowns per target (interleaved);
+// n: unknowns, one thread each
+__global__ void expand_targets_kernel(const uint32_t* __restrict__ point, const double* __restrict__ yp, double* __restrict__ y, int64_t n, int dof) {
+  const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (u < n) {
+    const int64_t k = u / dof;
+    y[u] = yp[(int64_t)point[k] * dof + (u - k * dof)];
+  }
 }
 
 // phase times of a plan build on stderr (FMMBEM_BUILD_TRACE: tuning aid)
@@ -1120,7 +1126,7 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
     HIP_TRY(hipMemcpy(dbc, bc_tree, (size_t)hp.n, hipMemcpyHostToDevice));
     fd.bc = dbc;
   }
-  for (int f = 0; targets && f < 2; ++f) {
+  for (int f = 0; p2m_per_slot() && f < 2; ++f) {
     uint8_t* all = nullptr;
     TRY(alloc((size_t)hp.n, &all, false));
     HIP_TRY(hipMemset(all, f, (size_t)hp.n));
@@ -1194,17 +1200,18 @@ int fmmbem_plan::to_device_bc_end() {
     }
     const bool want = !stokes || fd.stokes_velocity_targets;
     if (want && table_on && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
-      for (int f = 0; f < 2; ++f) {                    // (a dual plan: the table of every live slot, all sources; else one table)
-        if (targets && !has_bc[f]) continue;
+      const bool per_slot = p2m_per_slot();
+      for (int f = 0; f < 2; ++f) {                    // (a Laplace dual plan: the table of every live slot, all sources; else one table)
+        if (per_slot && !has_bc[f]) continue;
         DevicePlan dt = d;
-        if (targets) dt.bc = bc_all[f];
+        if (per_slot) dt.bc = bc_all[f];
         double2* tab = nullptr;
         TRY(alloc(count, &tab, true));
         HIP_TRY(hipDeviceSynchronize());               // the zero-fill ran on the NULL stream
         HIP_TRY(launch_p2m_table(dt, tab, own_stream));
         HIP_TRY(hipStreamSynchronize(own_stream));
         p2m_tab_slot[f] = tab;
-        if (!targets) break;
+        if (!per_slot) break;
       }
       fd.p2m_tab = p2m_tab_slot[0] ? p2m_tab_slot[0] : p2m_tab_slot[1];
     }
@@ -1343,7 +1350,7 @@ int fmmbem_plan::l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const {
   return FMMBEM_OK;
 }
 
-// P2M of a dual plan: once per live slot, every source panel taken with that slot's flag (the moments of G, or of dG/dn with the
+// P2M of a Laplace dual plan: once per live slot, every source panel taken with that slot's flag (the moments of G, or of dG/dn with the
 // panel's normal) and that slot's table; the same kernels as a plan whose panels all carry the flag
 template <class Launch>
 int fmmbem_plan::p2m_targets(const DevicePlan& dv, Launch&& launch) const {
@@ -1370,8 +1377,8 @@ int fmmbem_plan::deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream
   } else if (targets) {                                // the target rows -> distinct points -> the targets as given
     HIP_TRY(launch_scatter_y(dv, d_target_point ? y_points : d_y, s));
     if (d_target_point) {
-      const int64_t nt = hp.n_targets;
-      hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, y_points, d_y, nt);
+      const int64_t nt = hp.n_targets * dv.dof;
+      hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, y_points, d_y, nt, dv.dof);
       HIP_TRY(hipGetLastError());
     }
   } else {
@@ -1465,7 +1472,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
     // only added to by L2P -- they start from zero
     if (targets && zero_target_rows)
-      HIP_TRY(hipMemsetAsync(d.yt + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), ns));
+      HIP_TRY(hipMemsetAsync(d.yt + hp.n_src * d.dof, 0, sizeof(double) * (size_t)(hp.n - hp.n_src) * d.dof, ns));
     if (g.hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
     else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
     else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
@@ -1496,8 +1503,9 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     if (phase == 0) {
       if (!fuse) {
       HIP_TRY(begin(3, s));
-      if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); }));
-      else if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
+      if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s));       // (a field plan too: every source feeds every live group)
+      else if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); }));
+      else HIP_TRY(launch_p2m(d, p, s));
       HIP_TRY(end(3, s));
       }
       HIP_TRY(begin(4, s));
@@ -1606,8 +1614,8 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
   TRY(batch_alloc(s));
   const int w = bat.width;
   const bool stokes = d.dof == 3;                      // never a target plan (batch_width)
-  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n * d.dof);
-  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n * d.dof);
+  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n) * d.dof;
+  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n) * d.dof;
   double* sy = targets ? stage_y_targets : stage_y;
   BatchVecs bv{};
   bv.width = w;
@@ -1623,7 +1631,7 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
       if (targets) dg.n = hp.n_src;                  // the target rows of x_tree stay 0
       HIP_TRY(launch_gather_x(dg, xj, s));
       if (targets && zero_target_rows)
-        HIP_TRY(hipMemsetAsync(bat.yt[j] + hp.n_src, 0, sizeof(double) * (size_t)(hp.n - hp.n_src), s));
+        HIP_TRY(hipMemsetAsync(bat.yt[j] + hp.n_src * d.dof, 0, sizeof(double) * (size_t)(hp.n - hp.n_src) * d.dof, s));
     }
     // stage timing on: a pass is one record of the ring with two stages, its near-field pass (1) and its P2M (3); a Stokes pass
     // records its near-field pass alone (P2M runs per vector, below)
@@ -2132,17 +2140,20 @@ static int target_plan_only(const fmmbem_plan* plan, const char* what) {
   return FMMBEM_OK;
 }
 
-int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, const double* vertices, const uint8_t* bc,
-                               size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
-  (void)bc;       // the sources' flags do not enter: the target's flag picks the kernel (kernel/LaplaceSphericalBEM.hpp:273-297)
+// The one builder of dual plans.  field: fmmbem_plan_create_field, which takes the Stokes kernel too (dof = 3: the single Stokes
+// plan's near blocks, P2M, tree passes and L2P on the two trees); the four-argument form of the reference keeps refusing it.
+static int create_dual(bool field, const fmmbem_options* opts, size_t n_panels, const double* vertices,
+                       size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
   if (!opts || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
   *out = nullptr;
   if (!vertices || n_panels == 0) return fail(FMMBEM_ERR_INVALID, "no panels");
   if (!target_points || n_targets == 0) return fail(FMMBEM_ERR_INVALID, "no targets");
   if (opts->near_f32_max_p < 0 || opts->near_f32_max_p > 16) return fail(FMMBEM_ERR_INVALID, "near_f32_max_p outside 0..16");
   if (opts->stokes_batch_width < 0 || opts->stokes_batch_width > 4) return fail(FMMBEM_ERR_INVALID, "stokes_batch_width outside 0..4");
-  if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: Laplace only (Stokes velocity at points is not implemented)");
-  if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "unknown kernel id");
+  if (opts->kernel == FMMBEM_KERNEL_STOKES_BEM) {
+    if (!field) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: Laplace only (the Stokes field at points: fmmbem_plan_create_field)");
+    if (!(opts->mu > 0)) return fail(FMMBEM_ERR_INVALID, "Stokes: viscosity mu must be positive");
+  } else if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "unknown kernel id");
   if (opts->shard_world > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: shard_world > 1 is not implemented");
   if (opts->n_devices > 1) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: a device list is not implemented");
   if (opts->evaluator != FMMBEM_EVAL_FMM) return fail(FMMBEM_ERR_UNSUPPORTED, "target plans: the FMM evaluator only");
@@ -2180,11 +2191,12 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
       for (int l = h.leaf_begin; l < h.leaf_end; ++l) pl->zero_target_rows = pl->zero_target_rows || h.near_ncols[l] == 0;
       bool coincide = false;
       for (size_t k = 0; k < h.target_point.size() && !coincide; ++k) coincide = h.target_point[k] != (uint32_t)k;
+      const size_t dof = (size_t)geo.gd.dof;
       if (coincide) {
         TRY(pl->upload(h.target_point, &pl->d_target_point));
-        TRY(pl->alloc((size_t)(h.n - h.n_src), &pl->y_points, true));
+        TRY(pl->alloc((size_t)(h.n - h.n_src) * dof, &pl->y_points, true));
       }
-      TRY(pl->alloc((size_t)n_targets, &pl->stage_y_targets, true));
+      TRY(pl->alloc((size_t)n_targets * dof, &pl->stage_y_targets, true));
       HIP_TRY(hipDeviceSynchronize());
     } catch (const std::bad_alloc&) {
       return fail(FMMBEM_ERR_ALLOC, "host allocation failed while tabulating operators");
@@ -2193,6 +2205,17 @@ int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, cons
   }
   *out = pl.release();
   return FMMBEM_OK;
+}
+
+int fmmbem_plan_create_targets(const fmmbem_options* opts, size_t n_panels, const double* vertices, const uint8_t* bc,
+                               size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
+  (void)bc;       // the sources' flags do not enter: the target's flag picks the kernel (kernel/LaplaceSphericalBEM.hpp:273-297)
+  return create_dual(false, opts, n_panels, vertices, n_targets, target_points, target_bc, out);
+}
+
+int fmmbem_plan_create_field(const fmmbem_options* opts, size_t n_panels, const double* vertices,
+                             size_t n_targets, const double* target_points, const uint8_t* target_bc, fmmbem_plan** out) {
+  return create_dual(true, opts, n_panels, vertices, n_targets, target_points, target_bc, out);
 }
 
 int fmmbem_plan_target_info(const fmmbem_plan* plan, fmmbem_target_info* o) {
@@ -2376,10 +2399,11 @@ int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   if (plan->result_slices)         // the owned rows in tree order at the head of y are only meaningful to the device-side all-gather
     return fail(FMMBEM_ERR_INVALID, "plan delivers result slices (fmmbem_plan_set_result_slices): use the device entry points");
   DEVICE_SCOPE(plan->opts.device);
-  const size_t bytes = sizeof(double) * (size_t)plan->hp.n * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);
+  const size_t dof = plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
+  const size_t bytes = sizeof(double) * (size_t)plan->hp.n * dof;
   // a target plan: x over the panels, y over the targets
-  const size_t bytes_x = plan->targets ? sizeof(double) * (size_t)plan->hp.n_src : bytes;
-  const size_t bytes_y = plan->targets ? sizeof(double) * (size_t)plan->hp.n_targets : bytes;
+  const size_t bytes_x = plan->targets ? sizeof(double) * (size_t)plan->hp.n_src * dof : bytes;
+  const size_t bytes_y = plan->targets ? sizeof(double) * (size_t)plan->hp.n_targets * dof : bytes;
   double* sy = plan->targets ? plan->stage_y_targets : plan->stage_y;
   hipStream_t s = plan->own_stream;
   HIP_TRY(hipMemcpyAsync(plan->stage_x, x, bytes_x, hipMemcpyHostToDevice, s));
@@ -2396,8 +2420,8 @@ static int batch_args(const fmmbem_plan* plan, int k, const void* x, size_t ldx,
   if (k < 1) return fail(FMMBEM_ERR_INVALID, "batch of k < 1 vectors");
   if (!x || !y) return fail(FMMBEM_ERR_INVALID, "null vector");
   const size_t dof = plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
-  const size_t nx = plan->targets ? (size_t)plan->hp.n_src : (size_t)plan->hp.n * dof;
-  const size_t ny = plan->targets ? (size_t)plan->hp.n_targets : (size_t)plan->hp.n * dof;
+  const size_t nx = (plan->targets ? (size_t)plan->hp.n_src : (size_t)plan->hp.n) * dof;
+  const size_t ny = (plan->targets ? (size_t)plan->hp.n_targets : (size_t)plan->hp.n) * dof;
   if (ldx < nx || ldy < ny) return fail(FMMBEM_ERR_INVALID, "leading dimension shorter than a vector");
   return FMMBEM_OK;
 }
@@ -3030,6 +3054,5 @@ int fmmbem::plan_solver_info(fmmbem_plan* plan, int* device, int64_t* unknowns, 
 bool fmmbem::plan_block_inverse_built(const fmmbem_plan* plan) { return plan && plan->binv.built; }
 
 size_t fmmbem::plan_unknowns(const fmmbem_plan* plan) {
-  if (plan->targets) return (size_t)plan->hp.n_src;
-  return (size_t)plan->hp.n * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);
+  return (size_t)(plan->targets ? plan->hp.n_src : plan->hp.n) * (plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1);
 }

@@ -403,7 +403,8 @@ class FMM_plan:
 
     targets: the reference's FMM_plan(K, sources, targets, opts) (include/FMM_plan.hpp:45-55) -- (M, 3) points, or (M, 3, 3)
     triangles standing for their centroids; target_bc: M flags (default POTENTIAL).  execute then returns the M values
-    y_i = sum_j K(t_i, s_j) x_j, the target's flag picking G or dG/dn (fmmbem_plan_create_targets; Laplace only).
+    y_i = sum_j K(t_i, s_j) x_j, the target's flag picking G or dG/dn (fmmbem_plan_create_targets; Laplace only -- the field of
+    either kernel at points: field_plan).
 
     near_f32_max_p: not in the reference.  0: off; 1..16: executes at an order p <= this value stream a float copy of the
     assembled near matrix (fmmbem_options.near_f32_max_p); stats() reports near_f32_bytes (0: not active on this plan) and
@@ -480,28 +481,55 @@ class FMM_plan:
             bcp = bc.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
         self.n_targets = None
+        self._created_from = (v, o)                        # what field_plan builds its plan from
         if targets is None:
             if target_bc is not None:
                 raise ValueError("target_bc without targets")
             _capi.check(_capi.lib().fmmbem_plan_create(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), bcp, C.byref(h)))
         else:
-            t = np.asarray(targets, dtype=np.float64)
-            if t.ndim == 3 and t.shape[1:] == (3, 3):
-                t = (t[:, 0] + t[:, 1] + t[:, 2]) / 3          # a Panel target: its centre (LaplaceSphericalBEM.hpp:64-97)
-            if t.ndim != 2 or t.shape[1] != 3:
-                raise ValueError("targets must be (M, 3) points or (M, 3, 3) triangles")
-            t = np.ascontiguousarray(t)
-            tbcp = None
-            if target_bc is not None:
-                target_bc = np.ascontiguousarray(target_bc, dtype=np.uint8)
-                if target_bc.shape != (t.shape[0],):
-                    raise ValueError("target_bc must have one flag per target")
-                tbcp = target_bc.ctypes.data_as(C.c_void_p)
+            t, target_bc, tbcp = self._target_points(targets, target_bc)
             self._targets = (t, target_bc)                 # kept alive with the plan
             _capi.check(_capi.lib().fmmbem_plan_create_targets(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), bcp, t.shape[0],
                                                                t.ctypes.data_as(C.c_void_p), tbcp, C.byref(h)))
             self.n_targets = t.shape[0]
         self._h = h
+
+    @staticmethod
+    def _target_points(targets, target_bc):
+        t = np.asarray(targets, dtype=np.float64)
+        if t.ndim == 3 and t.shape[1:] == (3, 3):
+            t = (t[:, 0] + t[:, 1] + t[:, 2]) / 3              # a Panel target: its centre (LaplaceSphericalBEM.hpp:64-97)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("targets must be (M, 3) points or (M, 3, 3) triangles")
+        t = np.ascontiguousarray(t)
+        tbcp = None
+        if target_bc is not None:
+            target_bc = np.ascontiguousarray(target_bc, dtype=np.uint8)
+            if target_bc.shape != (t.shape[0],):
+                raise ValueError("target_bc must have one flag per target")
+            tbcp = target_bc.ctypes.data_as(C.c_void_p)
+        return t, target_bc, tbcp
+
+    def field_plan(self, points, target_bc=None):
+        """The field of a layer on this plan's panels at points of their own (fmmbem_plan_create_field), either kernel: a plan over
+        the same kernel object, panels and options whose execute takes (N,) -- Stokes (N, 3) -- charges and returns
+        y_i = sum_j K(t_i, s_j) x_j as (M,) -- Stokes (M, 3).  points: (M, 3), or (M, 3, 3) triangles standing for their centroids;
+        target_bc: M flags (default 0) -- the TARGET's flag picks the operator (Stokes: VELOCITY the single layer, TRACTION the double
+        layer with the source's normal), the panels' own flags do not enter.  execute_torch, execute_batch(_torch), set_graphs,
+        target_info, target_boxes, target_perm, pairs and boxes work as on a targets= plan.  FmmBemError (status 6) on a plan that is
+        itself a target plan, and on a treecode, LOCAL, BLOCK_DIAGONAL, matrix-free, sharded or device-list plan."""
+        if self.n_targets is not None:
+            raise _capi.FmmBemError(_capi.ERR_UNSUPPORTED, "field_plan: this plan is itself a plan over separate targets")
+        v, o = self._created_from
+        t, target_bc, tbcp = self._target_points(points, target_bc)
+        h = C.c_void_p()
+        _capi.check(_capi.lib().fmmbem_plan_create_field(C.byref(o), self.n, v.ctypes.data_as(C.c_void_p), t.shape[0],
+                                                         t.ctypes.data_as(C.c_void_p), tbcp, C.byref(h)))
+        other = object.__new__(type(self))                 # this plan's attributes with the new handle, as like()
+        other.__dict__.update(self.__dict__, _h=h)
+        other._targets = (t, target_bc)
+        other.n_targets = t.shape[0]
+        return other
 
     def like(self, bc, K=None):
         """A plan of the same panels and options with other boundary-condition flags (fmmbem_plan_create_like): shares this
@@ -534,10 +562,13 @@ class FMM_plan:
         want = (self.n,) if self.dof == 1 else (self.n, self.dof)
         if x.shape != want:
             raise ValueError("charges must have shape %r" % (want,))
-        y = np.empty(want if self.n_targets is None else (self.n_targets,))
+        y = np.empty(want if self.n_targets is None else self._target_shape())
         _capi.check(_capi.lib().fmmbem_plan_execute(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
                                                     y.ctypes.data_as(C.c_void_p)))
         return y
+
+    def _target_shape(self):
+        return (self.n_targets,) if self.dof == 1 else (self.n_targets, self.dof)
 
     def __call__(self, x, y):
         """Preconditioner-style operator()(x, y) adapter (examples/BEM/Preconditioner.hpp:11-15)."""
@@ -597,7 +628,7 @@ class FMM_plan:
         if x.device.index != self.device:
             raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
         if out is None:
-            out = torch.empty_like(x) if self.n_targets is None else x.new_empty(self.n_targets)
+            out = torch.empty_like(x) if self.n_targets is None else x.new_empty(self._target_shape())
         self.execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
@@ -610,9 +641,9 @@ class FMM_plan:
         if x.ndim != 1 + len(want) or x.shape[1:] != want or x.shape[0] < 1:
             raise ValueError("charges must have shape (k,) + %r with k >= 1" % (want,))
         k = x.shape[0]
-        y = np.empty((k,) + (want if self.n_targets is None else (self.n_targets,)))
+        y = np.empty((k,) + (want if self.n_targets is None else self._target_shape()))
         ldx = self.n * self.dof
-        ldy = ldx if self.n_targets is None else self.n_targets
+        ldy = ldx if self.n_targets is None else self.n_targets * self.dof
         _capi.check(_capi.lib().fmmbem_plan_execute_batch(self._h, self._K.P, k, x.ctypes.data_as(C.c_void_p), ldx,
                                                           y.ctypes.data_as(C.c_void_p), ldy))
         return y
@@ -630,7 +661,7 @@ class FMM_plan:
             raise ValueError("x must be a contiguous float64 CUDA tensor of shape (k, n * dof)")
         if x.device.index != self.device:
             raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
-        m = self.n * self.dof if self.n_targets is None else self.n_targets
+        m = (self.n if self.n_targets is None else self.n_targets) * self.dof
         if out is None:
             out = x.new_empty((x.shape[0], m))
         elif (out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (x.shape[0], m)

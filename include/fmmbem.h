@@ -254,6 +254,27 @@ int fmmbem_plan_get_target_boxes(const fmmbem_plan *plan, double *center, double
 /* tree_to_point: n_target_points, target-tree position -> distinct point; target_to_point: n_targets, given target -> distinct
  * point.  Either may be NULL. */
 int fmmbem_plan_get_target_perm(const fmmbem_plan *plan, uint32_t *tree_to_point, uint32_t *target_to_point);
+/* The FIELD PLAN: the field of a layer on the panels at points of their own,
+ *   y_i = sum_j K(t_i, s_j) x_j,  K = Kernel::operator()(target, source),
+ * for either kernel.  The TARGET's flag picks the operator; the source's normal enters, the panels' own flags do not (there is
+ * no bc argument).  target_points: n_targets x 3; target_bc: n_targets flags or NULL (all 0).
+ *   FMMBEM_KERNEL_LAPLACE_BEM: the plan of fmmbem_plan_create_targets(opts, n, v, NULL, m, pts, flags) -- one code path, the same
+ *     bits in every result.
+ *   FMMBEM_KERNEL_STOKES_BEM: x is n_panels x 3, y n_targets x 3, interleaved, in the caller's order.  Flag 0 (VELOCITY): the single
+ *     layer, eval_velocity_integral with 1/(2 mu) (kernel/StokesSphericalBEM.hpp:260-375), the four potentials of the far field.
+ *     Flag 1 (TRACTION): the double layer, eval_traction_integral (:160-258), the seven dipole potentials.  The live expansion
+ *     groups follow the targets' flags alone (8 slots without TRACTION targets, 11 with them); every source feeds every live
+ *     group.  The kernels are the single Stokes plan's: a target on a panel's centroid gets that plan's row, bit for bit.
+ * Coincident targets (same point, same flag) are one body of the target tree; the result goes back to every copy.
+ * Options as fmmbem_plan_create_targets: the FMM evaluator, sparse_local = 1, shard_world = 1, one device, l2l_rule COMPLETE
+ * (FMMBEM_ERR_UNSUPPORTED otherwise, as for an unknown kernel id); near_stream_fraction is taken as 1; near_f32_max_p and
+ * stokes_batch_width are accepted without effect (fmmbem_plan_batch_width is 1 on a Stokes field plan: a batch runs vector by
+ * vector, bit for bit the single executes).  host_only = 1 builds the lists; executing such a plan returns FMMBEM_ERR_UNSUPPORTED.
+ * The handle is a plan over separate targets in every respect: fmmbem_plan_target_info, _get_target_boxes, _get_target_perm,
+ * _get_perm, _get_boxes, _get_pairs, _stats, _set_timing, _set_graphs, _execute(_device) and _execute_batch(_device) take it as they
+ * take the handle of fmmbem_plan_create_targets; the calls of whole operators return FMMBEM_ERR_UNSUPPORTED and leave it usable. */
+int fmmbem_plan_create_field(const fmmbem_options *opts, size_t n_panels, const double *vertices, size_t n_targets,
+                             const double *target_points, const uint8_t *target_bc, fmmbem_plan **out);
 void fmmbem_plan_destroy(fmmbem_plan *plan);
 
 /* ---- the hot path ----------------------------------------------------------------------- */

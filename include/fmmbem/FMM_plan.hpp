@@ -546,6 +546,17 @@ class PlanAdapter {
     }
     create(p_max > 0 ? p_max : K.p());
   }
+  // Not in the reference: the FIELD of a layer on this plan's panels at points of their own (fmmbem_plan_create_field), either
+  // kernel -- execute(charges) of the returned plan gives points.size() values of result_type,
+  // result i = sum_j K(points[i], sources[j]) charges[j], the point's flag (flags[i] != 0: BC1, i.e. NORMAL_DERIV / TRACTION;
+  // default all BC0) picking the operator.  The returned plan owns its own handle, copies this plan's kernel, options and
+  // sources, and grows on set_p above its p_max as every plan here does.  Error(FMMBEM_ERR_UNSUPPORTED) on a plan that is itself
+  // a plan over targets, and for the option combinations fmmbem_plan_create_field refuses.
+  std::unique_ptr<PlanAdapter> field_plan(const std::vector<point_type>& points, const std::vector<unsigned char>& flags = {}) const {
+    if (has_targets_) throw Error(FMMBEM_ERR_UNSUPPORTED, "field_plan: this plan is itself a plan over separate targets");
+    if (!flags.empty() && flags.size() != points.size()) throw Error(FMMBEM_ERR_INVALID, "field_plan: one flag per point");
+    return std::unique_ptr<PlanAdapter>(new PlanAdapter(*this, points, flags));
+  }
   ~PlanAdapter() { fmmbem_plan_destroy(plan_); }
   PlanAdapter(const PlanAdapter&) = delete;
   PlanAdapter& operator=(const PlanAdapter&) = delete;
@@ -569,7 +580,7 @@ class PlanAdapter {
       if (c.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges[j].size() != number of panels");
     constexpr size_t dof = sizeof(charge_type) / sizeof(double);
     const size_t k = charges.size(), m = has_targets_ ? target_bc_.size() : n_;
-    const size_t ldx = n_ * dof, ldy = m * (has_targets_ ? 1 : dof);
+    const size_t ldx = n_ * dof, ldy = m * dof;
     std::vector<double> x(k * ldx), y(k * ldy);
     for (size_t j = 0; j < k; ++j) std::memcpy(x.data() + j * ldx, KernelBinding<Kernel>::in(charges[j]), ldx * sizeof(double));
     if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
@@ -592,6 +603,17 @@ class PlanAdapter {
   void reserve_order(int p) { if (p > p_max_) create(p); }
 
  private:
+  // the field plan of `base` (field_plan)
+  PlanAdapter(const PlanAdapter& base, const std::vector<point_type>& points, const std::vector<unsigned char>& flags)
+      : K(base.K), opts_(base.opts_), sources_(base.sources_), n_(base.n_), device_(base.device_), has_targets_(true), field_(true) {
+    points_.reserve(3 * points.size());
+    for (const point_type& t : points)
+      for (int c = 0; c < 3; ++c) points_.push_back(t[c]);
+    target_bc_.assign(points.size(), 0);
+    for (size_t i = 0; i < flags.size(); ++i) target_bc_[i] = flags[i] != 0;
+    create(base.p_max_);
+  }
+
   void create(int p_max) {
     std::vector<double> v(9 * n_);
     std::vector<uint8_t> bc(n_);
@@ -623,7 +645,9 @@ class PlanAdapter {
     o.stokes_batch_width = opts_.stokes_batch_width;
     sparse_ = o.sparse_local != 0;
     fmmbem_plan* fresh = nullptr;
-    if (has_targets_) {
+    if (field_) {                                            // refusals (matrix-free, LOCAL ...) are the library's to make
+      check(fmmbem_plan_create_field(&o, n_, v.data(), target_bc_.size(), points_.data(), target_bc_.data(), &fresh));
+    } else if (has_targets_) {
       o.sparse_local = 1;                                    // a target plan assembles its near field (the same sums)
       check(fmmbem_plan_create_targets(&o, n_, v.data(), bc.data(), target_bc_.size(), points_.data(), target_bc_.data(), &fresh));
     } else {
@@ -657,6 +681,7 @@ class PlanAdapter {
   int device_ = 0, p_max_ = 0;
   bool sparse_ = false;
   bool has_targets_ = false;
+  bool field_ = false;                                      // a field plan (field_plan): created by fmmbem_plan_create_field
   std::vector<double> points_;                              // the targets' centres, n_targets x 3
   std::vector<uint8_t> target_bc_;
   fmmbem_plan* plan_ = nullptr;
