@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 
 namespace fmmbem {
 
@@ -95,7 +96,32 @@ inline size_t m2p_lds(const DevicePlan& d, int p) {   // the tables of fill_l2p_
 }
 inline int m2p_grid(const DevicePlan& d, int p, int n_items) { return std::min((n_items + m2p_waves(d, p) - 1) / m2p_waves(d, p), 256 * 8); }
 
-// one level of M2M or L2L: the one-pair-per-wavefront kernel, the rotation kernel, or the sparse operators (PlanGeometry::shift_form)
+// ---------------------------------------- tree passes (kernels_shift.hip, kernels_m2l_rot.hip, kernels_far.hip) ----------------------------------------
+// One level of the upward / downward pass, p <= 12: the one-pair-per-WAVEFRONT kernel (kernels_shift.hip) for up to
+// shift_lanes_max pairs of this plan, the one-pair-per-LANE rotation kernel (kernels_m2l_rot.hip, ~20 us a pass whatever it holds)
+// above -- the two give the same bits, so every plan and every shard chooses by its own share.  p > 12 (and FMMBEM_SHIFT_ROT=0):
+// the sparse-operator kernels of kernels_far.hip, which round differently -- there the choice is the same for all shards, and
+// beside the wavefront kernel never the sparse operators.
 enum class ShiftForm { Lanes, Rot, Sparse };
+// one pair per WAVEFRONT (kernels_shift.hip, shift_lanes.hpp): the same bits as the one-pair-per-lane kernels, ~5 us for a
+// level of a few thousand pairs where a pass of those takes ~20 whatever it holds; LDS-bound above (N = 1M, p = 10, L2L: 5 800
+// pairs 10.6 us against 16-20, 21 000 pairs 26 against 19.5, 39 000 pairs 42 against 23.6).  A launch of up to shift_lanes_max
+// pairs takes it -- counted on THIS plan's share of the level: the two kernels give the same bits, so a shard may choose for
+// itself (FMMBEM_SHIFT_LANES=0: never; FMMBEM_SHIFT_LANES_MAX).  Pairs are counted per live expansion slot
+// (Stokes: four, config 4 at p = 8 with the slots uncounted: M2M 0.09 -> 0.18 ms)
+// Thresholds from tools/shift_lanes_sweep.sh (profiles/r04k_shift_lanes_sweep.txt; M2M / L2L ms for one GPU and one rank of eight):
+// L2L gains at every order up to 16 384 pair-slots; M2M -- whose wavefronts also walk or share a parent's children -- only at
+// p = 9, 10, elsewhere the rotation kernel's pass is short enough and only launches of <= 2 048 pair-slots go over.
+inline int lanes_max(int shift_lanes_max, int p, bool m2m) {      // shift_lanes_max >= 0: one threshold for both passes and all orders (sweeps)
+  return shift_lanes_max >= 0 ? shift_lanes_max : !m2m ? 16384 : p == 10 ? 16384 : p == 9 ? 8192 : 2048;
+}
+// pairs: of the launch on this plan; level_boxes: boxes of the child level in the whole tree; lanes_ok, rot_ok: what
+// shift_lanes_supported(p), shift_rot_supported(p) answer -- the kernels' translation units say which orders they hold
+inline ShiftForm shift_form(bool shift_rot, bool shift_lanes, int shift_lanes_max, int shift_rot_min, int pairs, int level_boxes,
+                            int p, int n_act, bool m2m, bool lanes_ok, bool rot_ok) {
+  if (shift_rot && shift_lanes && lanes_ok && (int64_t)pairs * n_act <= lanes_max(shift_lanes_max, p, m2m)) return ShiftForm::Lanes;
+  if (shift_rot && rot_ok && (shift_lanes || level_boxes >= shift_rot_min)) return ShiftForm::Rot;
+  return ShiftForm::Sparse;
+}
 
 }  // namespace fmmbem

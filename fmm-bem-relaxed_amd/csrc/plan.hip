@@ -127,35 +127,31 @@ static std::shared_future<std::shared_ptr<const OrderTables>> order_tables() {
 // (first, items, pairs) of one level launch of the rotation kernels (kernels_m2l_rot.hip with FMMBEM_ROT_OP = 1, 2)
 struct ShiftRot { int item_first = 0, n_items = 0, pairs = 0, level_boxes = 0, pair_first = 0, unit_first = 0, n_units = 0; };   // level_boxes: boxes of the child level in the WHOLE tree; units: parents (M2M) / pairs (L2L) of the one-pair-per-wavefront kernel
 
+// What one direction of the tree, M2M up or L2L down, reads on the device, and its level launches
+struct ShiftSide {
+  const int *rsrc = nullptr, *rcls = nullptr, *rtgt = nullptr; // the pairs (source box, class, target box) of all launches, launch after launch
+  const int* ritem = nullptr;                                  // the rotation kernel's items: pair ranges of at most one pass
+  const int* unit_ptr = nullptr;                               // up: first pair of every parent, per launch; down (a pair is a unit): null
+  const double *rec = nullptr, *stream = nullptr;              // class records; the rotation kernel's constant stream, all orders
+  const double *sl_class = nullptr, *sl_rc = nullptr, *sl_xc = nullptr;       // one pair per wavefront: class table, and the lanes'
+  const int32_t *sl_rs = nullptr, *sl_xs = nullptr;                           // four tables, all orders
+  std::vector<ShiftOpDev> ops;                                 // the sparse operators, index p - 1
+  std::vector<std::pair<int, int>> launch;                     // (first, count) per level
+  std::vector<ShiftRot> rot;                                   // the same launches for the rotation and wavefront kernels
+};
+
 // The device side of what depends on the GEOMETRY and the options only: written once by geometry creation (to_device_near,
 // to_device_far, and the options in fmmbem_plan_create*), never changed afterwards.  A plan reads it through a const reference.
 struct PlanGeometry {
   fmmbem_options opts{};                                       // as given to the creation: what same_geometry_options compares
   DevicePlan gd;                                               // the geometry's fields of a plan's DevicePlan (gd.n: the panel count)
-  std::vector<std::pair<int, int>> m2m_launch, l2l_launch;     // (first, count) per level
-  std::vector<std::pair<int, int>> m2m_shared_launch;          // sharded upward pass: parents spanning shards
-  std::vector<ShiftRot> m2m_rot, m2m_shared_rot, l2l_rot;      // the same launches for the rotation kernels
-  const int *up_rsrc = nullptr, *up_rcls = nullptr, *up_rtgt = nullptr, *up_ritem = nullptr;
-  const int *dn_rsrc = nullptr, *dn_rcls = nullptr, *dn_rtgt = nullptr, *dn_ritem = nullptr;
-  // one pair per WAVEFRONT (kernels_shift.hip, shift_lanes.hpp): the same bits as the one-pair-per-lane kernels, ~5 us for a
-  // level of a few thousand pairs where a pass of those takes ~20 whatever it holds; LDS-bound above (N = 1M, p = 10, L2L: 5 800
-  // pairs 10.6 us against 16-20, 21 000 pairs 26 against 19.5, 39 000 pairs 42 against 23.6).  A launch of up to shift_lanes_max
-  // pairs takes it -- counted on THIS plan's share of the level: the two kernels give the same bits, so a shard may choose for
-  // itself (FMMBEM_SHIFT_LANES=0: never; FMMBEM_SHIFT_LANES_MAX).  Pairs are counted per live expansion slot
-  // (Stokes: four, config 4 at p = 8 with the slots uncounted: M2M 0.09 -> 0.18 ms)
-  // Thresholds from tools/shift_lanes_sweep.sh (profiles/r04k_shift_lanes_sweep.txt; M2M / L2L ms for one GPU and one rank of eight):
-  // L2L gains at every order up to 16 384 pair-slots; M2M -- whose wavefronts also walk or share a parent's children -- only at
-  // p = 9, 10, elsewhere the rotation kernel's pass is short enough and only launches of <= 2 048 pair-slots go over.
-  bool shift_lanes = true;
-  int shift_lanes_max = -1;                           // FMMBEM_SHIFT_LANES_MAX: one threshold for both passes and all orders (sweeps)
-  int lanes_max(int p, bool m2m) const { return shift_lanes_max >= 0 ? shift_lanes_max : !m2m ? 16384 : p == 10 ? 16384 : p == 9 ? 8192 : 2048; }
-  ShiftForm shift_form(const ShiftRot& sr, int p, int n_act, bool m2m) const;   // the kernel one level of M2M / L2L takes
-  const int* up_unit_ptr = nullptr;
-  const double *sl_up_class = nullptr, *sl_dn_class = nullptr, *sl_up_rc = nullptr, *sl_up_xc = nullptr, *sl_dn_rc = nullptr, *sl_dn_xc = nullptr;
-  const int32_t *sl_up_rs = nullptr, *sl_up_xs = nullptr, *sl_dn_rs = nullptr, *sl_dn_xs = nullptr;
-  size_t sl_rot_off[kShiftLanesPmax + 1] = {}, sl_ax_off[kShiftLanesPmax + 1] = {};
-  const double *up_rec = nullptr, *dn_rec = nullptr, *up_stream = nullptr, *dn_stream = nullptr;
-  int shift_stream_off[12] = {};
+  ShiftSide up, down;                                          // M2M / L2L
+  std::vector<std::pair<int, int>> m2m_shared_launch;          // sharded upward pass: parents spanning shards (pairs and items in `up`)
+  std::vector<ShiftRot> m2m_shared_rot;
+  bool shift_lanes = true;                                     // this and shift_lanes_max, shift_rot_min, shift_rot: the switches of the tree-pass rule (launch_choice.hpp shift_form)
+  int shift_lanes_max = -1;                                    // FMMBEM_SHIFT_LANES_MAX
+  size_t sl_rot_off[kShiftLanesPmax + 1] = {}, sl_ax_off[kShiftLanesPmax + 1] = {};     // into a side's sl_rc, sl_rs / sl_xc, sl_xs, by order
+  int shift_stream_off[12] = {};                               // into a side's stream, index p - 1
   int shift_rot_min = 2048;                                    // boxes on a tree level from which the rotation kernels take it
   bool shift_rot = true;
   bool split_upward = false;                                   // P2M/M2M sharded by owner, multipoles all-gathered by the caller
@@ -164,7 +160,6 @@ struct PlanGeometry {
   // kernel (read per execute, for A/B runs).  The same single rounded add either way: the same bits.
   bool l2p_scatter = false;
   M2PWork m2p;                                                 // treecode plans (FMMBEM_EVAL_TREECODE): the far field's work, else empty
-  std::vector<ShiftOpDev> up_ops, down_ops;                    // M2M / L2L operators, index p - 1
   // sizes of the stored near blocks (allocated per plan, to_device_bc_begin)
   int64_t near_total_doubles = 0, sym_total_doubles = 0;
   int64_t near_bytes = 0;
@@ -247,6 +242,9 @@ struct fmmbem_plan {
   // then replayed on the caller's stream.  Off unless fmmbem_plan_set_graphs / FMMBEM_GRAPH=1: on this runtime dependent
   // launches already run back to back on the device (profiles/r03b), what a graph saves is host time per matvec.
   struct GraphEntry { int region, p; const void* buf; int runs; hipGraphExec_t exec; };
+  // a region: the upward half, or what the rest of an execute holds -- the downward half (else a whole execute), the near field
+  // already run (near_split), the near field alone, L2P's folded store, the combined near-field / P2M launch
+  enum : int { kRegionUpward = 1, kRegionDownward = 2, kRegionNearDone = 4, kRegionNearOnly = 8, kRegionFold = 16, kRegionFused = 32 };
   std::vector<GraphEntry> graphs;
   bool use_graphs = false;
   // The treecode evaluator: an FMM plan up to and including M2M; the far field is then ONE stage, M2P from the multipoles into
@@ -255,16 +253,41 @@ struct fmmbem_plan {
   // combined near-field / P2M launch alone and runs the two launches: the same M bit for bit, and the treecode's critical path is
   // the M2P stage, not the near field's drain.
   bool treecode() const { return opts.evaluator == FMMBEM_EVAL_TREECODE; }
+  // Whole: a matvec; Upward: the first half of a split execute (gather, P2M, M2M of owned boxes, pack -> xbuf); Downward: the
+  // rest (xbuf = the gathered multipoles); NearSplit: the near field of a split execute, between the two
+  enum class Phase { Whole, Upward, Downward, NearSplit };
+  enum class Stage { Gather, Spmv, Scatter, P2M, M2M, Mh, M2L, L2L, L2P };          // the order fmmbem_plan_stats reads
+  // Begin / end events around a stage (a kernel, or a level sequence) on its stream; by default none (timing off; a batch's far
+  // chains).  An event record is a packet of its own between two kernels (~5 us each on this part: a fully instrumented matvec is
+  // 85 us longer than a bare one), so a throughput measurement brackets the one kernel it needs (mode 2: the near field) alone.
+  struct StageMarks {
+    int mode = 0;                                              // fmmbem_plan::timing
+    hipEvent_t* set = nullptr;                                 // this execute's kStages (begin, end) pairs of the ring
+    unsigned mask = 0;                                         // stages recorded
+    bool rec(Stage i) const { return mode == 1 || (mode == 2 && i == Stage::Spmv); }
+    hipError_t begin(Stage i, hipStream_t st) { return rec(i) ? hipEventRecord(set[2 * (int)i], st) : hipSuccess; }
+    hipError_t end(Stage i, hipStream_t st) {
+      if (rec(i)) mask |= 1u << (int)i;
+      return rec(i) ? hipEventRecord(set[2 * (int)i + 1], st) : hipSuccess;
+    }
+  };
   // the launchers of one stage on the DevicePlan given (the plan's d; a batch: vector j's view of it)
-  int m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const;
-  int l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const;
+  enum class ShiftDir { Up, UpShared, Down };                  // M2M of the own boxes, of the parents spanning shards; L2L
+  int shift_pass(const DevicePlan& dv, int p, ShiftDir dir, hipStream_t s) const;
   template <class Launch> int p2m_targets(const DevicePlan& dv, Launch&& launch) const;
+  int p2m(const DevicePlan& dv, int p, StageMarks& tm, hipStream_t s) const;
+  enum class L2PTo { YTree, Perm, Caller };                    // add into y_tree; store y_out[perm[i]]; nothing here (a capture: the caller's pointer comes after)
+  int l2p(const DevicePlan& dv, int p, double* y_out, hipStream_t s) const;
+  int far_chain(const DevicePlan& dv, const DevicePlan* dv_dev, int p, bool m2m_own, const double* xch, L2PTo to, double* y_out,
+                StageMarks& tm, hipStream_t s) const;
   int deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream_t s) const;
+  size_t x_doubles() const { return (size_t)(targets ? hp.n_src : hp.n) * (opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1); }      // a target plan: x over the panels,
+  size_t y_doubles() const { return (size_t)(targets ? hp.n_targets : hp.n) * (opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1); }  // y over the targets
   unsigned pending_mask = 0;                                   // stages recorded by the upward half of a split execute
   bool pending_near = false;                                   // split execute: the near field already ran (fmmbem_plan_near_split_device)
   bool result_slices = false;                                  // execute delivers the owned rows in tree order (fmmbem_plan_set_result_slices)
-  bool l2p_delivers(bool near_only, int phase) const {         // (PlanGeometry::l2p_scatter)
-    if (!g.l2p_scatter || result_slices || near_only || phase != 0 || treecode()) return false;   // a treecode runs no L2P
+  bool l2p_delivers(bool near_only, Phase phase) const {       // (PlanGeometry::l2p_scatter)
+    if (!g.l2p_scatter || result_slices || near_only || phase != Phase::Whole || treecode()) return false;   // a treecode runs no L2P
     return sw::l2p_scatter();
   }
   int64_t* d_cut = nullptr;                                    // tree-order row cuts of all shards, on the device
@@ -346,8 +369,7 @@ struct fmmbem_plan {
   int to_device_bc_end();
   hipEvent_t asm_ev[2] = {nullptr, nullptr};                 // around the assembly, between to_device_bc_begin and _end
   static int like(std::shared_ptr<PlanShared> sh, const fmmbem_options& o, const uint8_t* bc, fmmbem_plan** out);
-  // phase 0: whole matvec; 1: upward half (gather, P2M, M2M of owned boxes, pack -> xbuf); 2: the rest (xbuf = gathered)
-  int run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, int phase = 0, double* xbuf = nullptr);
+  int run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, Phase phase = Phase::Whole, double* xbuf = nullptr);
   // Batched execute (fmmbem_plan_execute_batch).  Per vector of a pass: tree-order x and y, one multipole set, and a copy of d
   // pointing at them in device memory (the double-sum M2L reads the plan from there); allocated at the first batch call, kept
   // until destroy.  L, Mh and the target plans' y_points are shared: the vectors run the far field one after another.
@@ -818,15 +840,11 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
   TRY(upload(hp.m2m_parents, &d.m2m_parent)); TRY(upload(hp.l2l_children, &d.l2l_child));
   TRY(upload(hp.box_child_begin, &d.box_child_begin)); TRY(upload(hp.box_child_end, &d.box_child_end));
   TRY(upload(hp.box_parent, &d.box_parent));
-  for (size_t l = 0; l + 1 < hp.m2m_level_ptr.size(); ++l)
-    if (hp.m2m_level_ptr[l + 1] > hp.m2m_level_ptr[l])
-      g.m2m_launch.emplace_back(hp.m2m_level_ptr[l], hp.m2m_level_ptr[l + 1] - hp.m2m_level_ptr[l]);
-  for (size_t l = 0; l + 1 < hp.l2l_level_ptr.size(); ++l)
-    if (hp.l2l_level_ptr[l + 1] > hp.l2l_level_ptr[l])
-      g.l2l_launch.emplace_back(hp.l2l_level_ptr[l], hp.l2l_level_ptr[l + 1] - hp.l2l_level_ptr[l]);
-  for (size_t l = 0; l + 1 < hp.m2m_shared_ptr.size(); ++l)
-    if (hp.m2m_shared_ptr[l + 1] > hp.m2m_shared_ptr[l])
-      g.m2m_shared_launch.emplace_back(hp.m2m_shared_ptr[l], hp.m2m_shared_ptr[l + 1] - hp.m2m_shared_ptr[l]);
+  auto level_launches = [](const std::vector<int>& ptr, std::vector<std::pair<int, int>>& out) {       // the levels that hold anything
+    for (size_t l = 0; l + 1 < ptr.size(); ++l)
+      if (ptr[l + 1] > ptr[l]) out.emplace_back(ptr[l], ptr[l + 1] - ptr[l]);
+  };
+  level_launches(hp.m2m_level_ptr, g.up.launch); level_launches(hp.l2l_level_ptr, g.down.launch); level_launches(hp.m2m_shared_ptr, g.m2m_shared_launch);
   // sharded upward pass: who sends which multipoles
   g.split_upward = hp.opt.shard_upward && hp.opt.shard_world > 1;
   d.xch_rank = hp.opt.shard_rank; d.xch_world = g.split_upward ? hp.opt.shard_world : 0; d.xch_max = 0;
@@ -882,7 +900,7 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
     TRY(upload(up_cls, &d.up_cls)); TRY(upload(down_cls, &d.down_cls));
     // ---- M2M / L2L by rotation: pair lists per level launch, items, records, constant streams ----
     {
-      TRY(upload(up_rec_h, &g.up_rec)); TRY(upload(dn_rec_h, &g.dn_rec));
+      TRY(upload(up_rec_h, &g.up.rec)); TRY(upload(dn_rec_h, &g.down.rec));
       std::vector<int> rs, rc, rt, ri, len, uptr;
       auto level_boxes = [&](int l) { return l >= 0 && l < hp.nlevels ? hp.level_off[l + 1] - hp.level_off[l] : 0; };
       // items of the shifts: whole targets, ONE pass (at most 64 pairs) -- the shift kernels carry nothing between passes
@@ -895,56 +913,54 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
         }
         if (fill > 0) item_ptr.push_back(item_ptr.back() + fill);
       };
-      auto add_m2m = [&](const std::vector<std::pair<int, int>>& launches, std::vector<ShiftRot>& out) {
+      // The pairs of a side's launches, launch after launch, with each launch's items and ShiftRot.  unit(i) appends the pairs of
+      // entry i of the side's box list and returns the level of their CHILD boxes; units: the wavefront kernel walks a unit's
+      // pairs through uptr (M2M: a parent's children), else a pair is a unit (L2L)
+      auto add_launches = [&](const std::vector<std::pair<int, int>>& launches, std::vector<ShiftRot>& out, bool units, auto&& unit) {
         for (auto [first, count] : launches) {
           ShiftRot sr;
           sr.item_first = (int)ri.size();
-          const int base = (int)rs.size();
-          sr.pair_first = base;
-          sr.unit_first = (int)uptr.size();
+          const int base = sr.pair_first = (int)rs.size();
+          if (units) sr.unit_first = (int)uptr.size();
           sr.n_units = count;
           len.clear();
           for (int i = first; i < first + count; ++i) {
-            const int par = hp.m2m_parents[i];
-            uptr.push_back((int)rs.size());
-            for (int c = hp.box_child_begin[par]; c < hp.box_child_end[par]; ++c) { rs.push_back(c); rc.push_back(up_cls[c]); rt.push_back(par); }
-            len.push_back(hp.box_child_end[par] - hp.box_child_begin[par]);
+            const int before = (int)rs.size();
+            if (units) uptr.push_back(before);
+            const int child_level = unit(i);
+            if (i == first) sr.level_boxes = level_boxes(child_level);
+            len.push_back((int)rs.size() - before);
           }
-          uptr.push_back((int)rs.size());               // one past the level's last parent
+          if (units) uptr.push_back((int)rs.size());    // one past the level's last parent
           cut_single_pass(len, base, ri);
           sr.n_items = (int)ri.size() - sr.item_first - 1;
           sr.pairs = (int)rs.size() - base;
-          sr.level_boxes = count > 0 ? level_boxes(hp.box_level[hp.m2m_parents[first]] + 1) : 0;
           out.push_back(sr);
         }
       };
-      add_m2m(g.m2m_launch, g.m2m_rot);
-      add_m2m(g.m2m_shared_launch, g.m2m_shared_rot);
-      TRY(upload(rs, &g.up_rsrc)); TRY(upload(rc, &g.up_rcls)); TRY(upload(rt, &g.up_rtgt)); TRY(upload(ri, &g.up_ritem));
-      TRY(upload(uptr, &g.up_unit_ptr));
+      auto upload_pairs = [&](ShiftSide& sd) -> int {
+        TRY(upload(rs, &sd.rsrc)); TRY(upload(rc, &sd.rcls)); TRY(upload(rt, &sd.rtgt)); TRY(upload(ri, &sd.ritem));
+        return FMMBEM_OK;
+      };
+      auto m2m_unit = [&](int i) {
+        const int par = hp.m2m_parents[i];
+        for (int c = hp.box_child_begin[par]; c < hp.box_child_end[par]; ++c) { rs.push_back(c); rc.push_back(up_cls[c]); rt.push_back(par); }
+        return hp.box_level[par] + 1;
+      };
+      add_launches(g.up.launch, g.up.rot, true, m2m_unit);
+      add_launches(g.m2m_shared_launch, g.m2m_shared_rot, true, m2m_unit);
+      TRY(upload_pairs(g.up)); TRY(upload(uptr, &g.up.unit_ptr));
       rs.clear(); rc.clear(); rt.clear(); ri.clear();
-      for (auto [first, count] : g.l2l_launch) {
-        ShiftRot sr;
-        sr.item_first = (int)ri.size();
-        const int base = (int)rs.size();
-        sr.pair_first = base;
-        sr.n_units = count;
-        for (int i = first; i < first + count; ++i) {
-          const int c = hp.l2l_children[i];
-          rs.push_back(hp.box_parent[c]); rc.push_back(down_cls[c]); rt.push_back(c);
-        }
-        len.assign((size_t)count, 1);
-        cut_single_pass(len, base, ri);
-        sr.n_items = (int)ri.size() - sr.item_first - 1;
-        sr.pairs = count;
-        sr.level_boxes = count > 0 ? level_boxes(hp.box_level[hp.l2l_children[first]]) : 0;
-        g.l2l_rot.push_back(sr);
-      }
-      TRY(upload(rs, &g.dn_rsrc)); TRY(upload(rc, &g.dn_rcls)); TRY(upload(rt, &g.dn_rtgt)); TRY(upload(ri, &g.dn_ritem));
+      add_launches(g.down.launch, g.down.rot, false, [&](int i) {
+        const int c = hp.l2l_children[i];
+        rs.push_back(hp.box_parent[c]); rc.push_back(down_cls[c]); rt.push_back(c);
+        return hp.box_level[c];
+      });
+      TRY(upload_pairs(g.down));
       const std::shared_ptr<const OrderTables> otp = order_tables().get();      // (built on a thread of their own since plan_create began)
       const OrderTables& ot = *otp;
       for (int q = 1; q <= kRotPmax; ++q) g.shift_stream_off[q - 1] = ot.shift_off[q - 1];
-      TRY(upload(ot.ups, &g.up_stream)); TRY(upload(ot.dns, &g.dn_stream));
+      TRY(upload(ot.ups, &g.up.stream)); TRY(upload(ot.dns, &g.down.stream));
       {                                                // one pair per wavefront: class tables and the lanes' tables per order
         const int nclass = (int)up_rec_h.size() / 8, cs = sl_class_doubles(pm);
         std::vector<double> cu((size_t)nclass * cs), cd((size_t)nclass * cs);
@@ -952,10 +968,10 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
           sl_class_table(up_rec_h.data() + (size_t)c * 8, pm, kRotM2M, cu.data() + (size_t)c * cs);
           sl_class_table(dn_rec_h.data() + (size_t)c * 8, pm, kRotL2L, cd.data() + (size_t)c * cs);
         }
-        TRY(upload(cu, &g.sl_up_class)); TRY(upload(cd, &g.sl_dn_class));
+        TRY(upload(cu, &g.up.sl_class)); TRY(upload(cd, &g.down.sl_class));
         for (int q = 1; q <= kShiftLanesPmax; ++q) { g.sl_rot_off[q] = ot.sl_rot_off[q]; g.sl_ax_off[q] = ot.sl_ax_off[q]; }
-        TRY(upload(ot.urc, &g.sl_up_rc)); TRY(upload(ot.urs, &g.sl_up_rs)); TRY(upload(ot.uxc, &g.sl_up_xc)); TRY(upload(ot.uxs, &g.sl_up_xs));
-        TRY(upload(ot.drc, &g.sl_dn_rc)); TRY(upload(ot.drs, &g.sl_dn_rs)); TRY(upload(ot.dxc, &g.sl_dn_xc)); TRY(upload(ot.dxs, &g.sl_dn_xs));
+        TRY(upload(ot.urc, &g.up.sl_rc)); TRY(upload(ot.urs, &g.up.sl_rs)); TRY(upload(ot.uxc, &g.up.sl_xc)); TRY(upload(ot.uxs, &g.up.sl_xs));
+        TRY(upload(ot.drc, &g.down.sl_rc)); TRY(upload(ot.drs, &g.down.sl_rs)); TRY(upload(ot.dxc, &g.down.sl_xc)); TRY(upload(ot.dxs, &g.down.sl_xs));
         g.shift_lanes = sw::shift_lanes(g.shift_lanes);
         g.shift_lanes_max = sw::shift_lanes_max(g.shift_lanes_max);
       }
@@ -973,8 +989,8 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
       o.T = v.T; o.V = v.V; o.maxp = v.maxp;
       return FMMBEM_OK;
     };
-    g.up_ops.resize(pm); g.down_ops.resize(pm);
-    for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], g.up_ops[p - 1])); TRY(up_op(ops.down_v[p - 1], g.down_ops[p - 1])); }
+    g.up.ops.resize(pm); g.down.ops.resize(pm);
+    for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], g.up.ops[p - 1])); TRY(up_op(ops.down_v[p - 1], g.down.ops[p - 1])); }
   }
 
   mark("shift classes + operators");
@@ -1295,57 +1311,32 @@ int fmmbem_plan::build_side_lists() {
   return FMMBEM_OK;
 }
 
-// One level of the upward / downward pass, p <= 12: the one-pair-per-WAVEFRONT kernel (kernels_shift.hip) for up to
-// shift_lanes_max pairs of this plan, the one-pair-per-LANE rotation kernel (kernels_m2l_rot.hip, ~20 us a pass whatever it holds)
-// above -- the two give the same bits, so every plan and every shard chooses by its own share.  p > 12 (and FMMBEM_SHIFT_ROT=0):
-// the sparse-operator kernels of kernels_far.hip, which round differently -- there the choice is the same for all shards, and
-// beside the wavefront kernel never the sparse operators.
-ShiftForm PlanGeometry::shift_form(const ShiftRot& sr, int p, int n_act, bool m2m) const {
-  if (shift_rot && shift_lanes && shift_lanes_supported(p) && (int64_t)sr.pairs * n_act <= lanes_max(p, m2m)) return ShiftForm::Lanes;
-  if (shift_rot && shift_rot_supported(p) && (shift_lanes || sr.level_boxes >= shift_rot_min)) return ShiftForm::Rot;
-  return ShiftForm::Sparse;
-}
-int fmmbem_plan::m2m_pass(const DevicePlan& dv, int p, bool shared, hipStream_t s) const {
-  const auto& launches = shared ? g.m2m_shared_launch : g.m2m_launch;
-  const auto& rots = shared ? g.m2m_shared_rot : g.m2m_rot;
+// The upward / downward pass, level launch by level launch; each takes the kernel shift_form (launch_choice.hpp) names
+int fmmbem_plan::shift_pass(const DevicePlan& dv, int p, ShiftDir dir, hipStream_t s) const {
+  const bool m2m = dir != ShiftDir::Down;
+  const ShiftSide& sd = m2m ? g.up : g.down;
+  const auto& launches = dir == ShiftDir::UpShared ? g.m2m_shared_launch : sd.launch;
+  const auto& rots = dir == ShiftDir::UpShared ? g.m2m_shared_rot : sd.rot;
   for (size_t i = 0; i < launches.size(); ++i) {
     const auto [first, count] = launches[i];
     const ShiftRot& sr = rots[i];
-    const ShiftForm f = g.shift_form(sr, p, dv.n_act, true);
+    const ShiftForm f = shift_form(g.shift_rot, g.shift_lanes, g.shift_lanes_max, g.shift_rot_min, sr.pairs, sr.level_boxes, p, dv.n_act, m2m,
+                                   shift_lanes_supported(p), shift_rot_supported(p));
     if (f == ShiftForm::Lanes) {
       ShiftLaneWork lw;
-      lw.src = g.up_rsrc; lw.cls = g.up_rcls; lw.tgt = g.up_rtgt; lw.unit_ptr = g.up_unit_ptr + sr.unit_first; lw.n_units = sr.n_units;
-      lw.class_tab = g.sl_up_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
-      lw.rot_c = g.sl_up_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_up_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_up_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_up_xs + g.sl_ax_off[p];
-      HIP_TRY(launch_m2m_lanes(dv, lw, p, s));
+      const int at = m2m ? 0 : sr.pair_first;          // L2L shifts its pair arrays to the launch's first pair (unit u is pair u); M2M takes them unshifted
+      lw.src = sd.rsrc + at; lw.cls = sd.rcls + at; lw.tgt = sd.rtgt + at; lw.n_units = sr.n_units;
+      lw.unit_ptr = m2m ? sd.unit_ptr + sr.unit_first : nullptr;   // M2M walks a parent's pairs through its unit pointer (positions in the unshifted arrays); L2L has none
+      lw.class_tab = sd.sl_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
+      lw.rot_c = sd.sl_rc + g.sl_rot_off[p]; lw.rot_s = sd.sl_rs + g.sl_rot_off[p]; lw.ax_c = sd.sl_xc + g.sl_ax_off[p]; lw.ax_s = sd.sl_xs + g.sl_ax_off[p];
+      HIP_TRY(m2m ? launch_m2m_lanes(dv, lw, p, s) : launch_l2l_lanes(dv, lw, p, s));
     } else if (f == ShiftForm::Rot) {
       RotWork w;
-      w.src = g.up_rsrc; w.cls = g.up_rcls; w.tgt = g.up_rtgt; w.rec = g.up_rec;
-      w.item_ptr = g.up_ritem + sr.item_first; w.n_items = sr.n_items;
-      w.stream = g.up_stream + g.shift_stream_off[p - 1];
-      HIP_TRY(launch_m2m_rot(dv, w, p, s));
-    } else HIP_TRY(launch_m2m_level(dv, g.up_ops[p - 1], p, first, count, s));
-  }
-  return FMMBEM_OK;
-}
-int fmmbem_plan::l2l_pass(const DevicePlan& dv, int p, hipStream_t s) const {
-  for (size_t i = 0; i < g.l2l_launch.size(); ++i) {
-    const auto [first, count] = g.l2l_launch[i];
-    const ShiftRot& sr = g.l2l_rot[i];
-    const ShiftForm f = g.shift_form(sr, p, dv.n_act, false);
-    if (f == ShiftForm::Lanes) {
-      ShiftLaneWork lw;
-      lw.src = g.dn_rsrc + sr.pair_first; lw.cls = g.dn_rcls + sr.pair_first; lw.tgt = g.dn_rtgt + sr.pair_first; lw.n_units = sr.n_units;
-      lw.class_tab = g.sl_dn_class; lw.class_stride = sl_class_doubles(hp.opt.p_max); lw.p_max = hp.opt.p_max;
-      lw.rot_c = g.sl_dn_rc + g.sl_rot_off[p]; lw.rot_s = g.sl_dn_rs + g.sl_rot_off[p]; lw.ax_c = g.sl_dn_xc + g.sl_ax_off[p]; lw.ax_s = g.sl_dn_xs + g.sl_ax_off[p];
-      HIP_TRY(launch_l2l_lanes(dv, lw, p, s));
-    } else if (f == ShiftForm::Rot) {
-      RotWork w;
-      w.src = g.dn_rsrc; w.cls = g.dn_rcls; w.tgt = g.dn_rtgt; w.rec = g.dn_rec;
-      w.item_ptr = g.dn_ritem + sr.item_first; w.n_items = sr.n_items;
-      w.stream = g.dn_stream + g.shift_stream_off[p - 1];
-      HIP_TRY(launch_l2l_rot(dv, w, p, s));
-    } else HIP_TRY(launch_l2l_level(dv, g.down_ops[p - 1], p, first, count, s));
+      w.src = sd.rsrc; w.cls = sd.rcls; w.tgt = sd.rtgt; w.rec = sd.rec;
+      w.item_ptr = sd.ritem + sr.item_first; w.n_items = sr.n_items;
+      w.stream = sd.stream + g.shift_stream_off[p - 1];
+      HIP_TRY(m2m ? launch_m2m_rot(dv, w, p, s) : launch_l2l_rot(dv, w, p, s));
+    } else HIP_TRY(m2m ? launch_m2m_level(dv, sd.ops[p - 1], p, first, count, s) : launch_l2l_level(dv, sd.ops[p - 1], p, first, count, s));
   }
   return FMMBEM_OK;
 }
@@ -1362,6 +1353,59 @@ int fmmbem_plan::p2m_targets(const DevicePlan& dv, Launch&& launch) const {
     if (dv.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
     HIP_TRY(launch(dp));
   }
+  return FMMBEM_OK;
+}
+// P2M on the view given: a Stokes plan's (a field plan too: every source feeds every live group), a Laplace dual plan's slot by
+// slot, or the one launch
+int fmmbem_plan::p2m(const DevicePlan& dv, int p, StageMarks& tm, hipStream_t s) const {
+  auto one = [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); };
+  HIP_TRY(tm.begin(Stage::P2M, s));
+  if (dv.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(dv, p, s));
+  else if (targets) TRY(p2m_targets(dv, one));
+  else HIP_TRY(one(dv));
+  HIP_TRY(tm.end(Stage::P2M, s));
+  return FMMBEM_OK;
+}
+// L2P on the view given: y_tree += the far field; with y_out (Laplace, l2p_delivers) y_out[perm[i]] = y_tree[i] + the far field
+int fmmbem_plan::l2p(const DevicePlan& dv, int p, double* y_out, hipStream_t s) const {
+  if (dv.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_l2p_stokes(dv, p, dv.yt, s));
+  else HIP_TRY(launch_l2p(dv, p, dv.yt, s, y_out ? dv.perm : nullptr, y_out));
+  return FMMBEM_OK;
+}
+
+// The far field after P2M on the view given -- the plan's d and its device copy; a batch: vector j's -- for every caller: the same
+// launches in the same order, so the same bits.  m2m_own: M2M of the own boxes runs (not on the downward half of a split execute:
+// the upward half ran it); xch: the other shards' multipoles are unpacked from it, then the parents spanning shards (null: neither)
+int fmmbem_plan::far_chain(const DevicePlan& dv, const DevicePlan* dv_dev, int p, bool m2m_own, const double* xch, L2PTo to, double* y_out,
+                           StageMarks& tm, hipStream_t s) const {
+  if (m2m_own) {
+    HIP_TRY(tm.begin(Stage::M2M, s));
+    TRY(shift_pass(dv, p, ShiftDir::Up, s));
+    HIP_TRY(tm.end(Stage::M2M, s));
+  }
+  if (treecode()) {                                    // (never a shard) the far field as one stage, timed as M2L's
+    HIP_TRY(tm.begin(Stage::M2L, s));
+    HIP_TRY(launch_m2p(dv, g.m2p, p, dv.yt, s));
+    HIP_TRY(tm.end(Stage::M2L, s));
+    return FMMBEM_OK;
+  }
+  HIP_TRY(tm.begin(Stage::Mh, s));
+  if (xch) {
+    HIP_TRY(launch_xch_unpack(dv, p, reinterpret_cast<const double2*>(xch), s));
+    TRY(shift_pass(dv, p, ShiftDir::UpShared, s));
+  }
+  const bool rot = g.use_rot(p);
+  if (!rot) HIP_TRY(launch_mh_prep(dv, p, s));       // the rotation kernel reads M itself
+  HIP_TRY(tm.end(Stage::Mh, s));
+  HIP_TRY(tm.begin(Stage::M2L, s));
+  HIP_TRY(rot ? launch_m2l_rot(dv, dv_dev, p, s) : launch_m2l(dv, dv_dev, p, s));
+  HIP_TRY(tm.end(Stage::M2L, s));
+  HIP_TRY(tm.begin(Stage::L2L, s));
+  TRY(shift_pass(dv, p, ShiftDir::Down, s));
+  HIP_TRY(tm.end(Stage::L2L, s));
+  HIP_TRY(tm.begin(Stage::L2P, s));
+  if (to != L2PTo::Caller) TRY(l2p(dv, p, to == L2PTo::Perm ? y_out : nullptr, s));
+  HIP_TRY(tm.end(Stage::L2P, s));
   return FMMBEM_OK;
 }
 
@@ -1388,36 +1432,25 @@ int fmmbem_plan::deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream
   return FMMBEM_OK;
 }
 
-int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, int phase, double* xbuf) {
+int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, Phase phase, double* xbuf) {
   if (!on_device && targets) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
   if (!on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
   if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
-  if ((phase < 2 && !d_x) || (phase != 1 && !d_y)) return fail(FMMBEM_ERR_INVALID, "null vector");
-  if (g.split_upward && phase == 0 && !near_only)
+  const bool whole = phase == Phase::Whole, takes_x = whole || phase == Phase::Upward;
+  if ((takes_x && !d_x) || (phase != Phase::Upward && !d_y)) return fail(FMMBEM_ERR_INVALID, "null vector");
+  if (g.split_upward && whole && !near_only)
     return fail(FMMBEM_ERR_UNSUPPORTED, "plan shards the upward pass: use fmmbem_plan_upward_device / _downward_device");
-  if (phase != 0 && (!g.split_upward || (!xbuf && phase != 3))) return fail(FMMBEM_ERR_INVALID, "split execute needs shard_upward and an exchange buffer");
-  if (targets && (phase != 0 || result_slices)) return fail(FMMBEM_ERR_UNSUPPORTED, "a target plan runs whole executes only");
+  if (!whole && (!g.split_upward || (!xbuf && phase != Phase::NearSplit))) return fail(FMMBEM_ERR_INVALID, "split execute needs shard_upward and an exchange buffer");
+  if (targets && (!whole || result_slices)) return fail(FMMBEM_ERR_UNSUPPORTED, "a target plan runs whole executes only");
   DEVICE_SCOPE(opts.device);
-  const int tm = timing;
   const int64_t ring = ev_count % kRing;
-  hipEvent_t* set = tm ? &ev[(size_t)ring * 2 * kStages] : nullptr;
-  unsigned mask = phase >= 2 ? pending_mask : 0;
-  // stage i runs on stream st: begin/end events bracket exactly that kernel (or level sequence).  An event record is a
-  // packet of its own between two kernels (~5 us each on this part: a fully instrumented matvec is 85 us longer than a bare
-  // one), so a throughput measurement brackets the one kernel it needs (mode 2: the near field, stage 1) and nothing else.
-  auto rec = [&](int i) { return tm == 1 || (tm == 2 && i == 1); };
-  auto begin = [&](int i, hipStream_t st) -> hipError_t { return rec(i) ? hipEventRecord(set[2 * i], st) : hipSuccess; };
-  auto end = [&](int i, hipStream_t st) -> hipError_t {
-    if (!rec(i)) return hipSuccess;
-    mask |= 1u << i;
-    return hipEventRecord(set[2 * i + 1], st);
-  };
+  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, takes_x ? 0 : pending_mask};
   // Stage order of the reference (EvalInteractionLazySparse.hpp:120-168): near-field SpMV, then P2M, M2M, M2L, L2L, L2P, all on
   // the caller's stream.  (The near field on a second stream beside the far field was measured in rounds 1, 2 and 3 in five
   // variants and is slower every time -- beside the saturated memory system of the near field every dependent access of the
   // latency-bound far kernels takes 10-70x longer; profiles/r03d_overlap_near_far.txt, DESIGN.md section 9 -- and is gone.)
   // a region of the chain, launch by launch or as a graph (see GraphEntry)
-  const bool graph_ok = use_graphs && tm == 0;
+  const bool graph_ok = use_graphs && timing == 0;
   auto graphed = [&](int region, const void* buf, auto&& body) -> int {
     if (!graph_ok) return body(s);
     GraphEntry* ge = nullptr;
@@ -1442,33 +1475,29 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     HIP_TRY(hipGraphLaunch(ge->exec, s));
     return FMMBEM_OK;
   };
-  if (phase < 2) {
-    HIP_TRY(begin(0, s));
-    if (targets) {                                     // x: the source panels only (the target rows of x_tree stay 0)
-      DevicePlan dg = d;
-      dg.n = hp.n_src;
-      HIP_TRY(launch_gather_x(dg, d_x, s));
-    } else HIP_TRY(launch_gather_x(d, d_x, s));
-    HIP_TRY(end(0, s));
+  if (takes_x) {
+    HIP_TRY(tm.begin(Stage::Gather, s));
+    DevicePlan dg = d;
+    if (targets) dg.n = hp.n_src;                      // x: the source panels only (the target rows of x_tree stay 0)
+    HIP_TRY(launch_gather_x(dg, d_x, s));
+    HIP_TRY(tm.end(Stage::Gather, s));
   }
-  if (phase == 1) {                                    // upward half: my leaves, my boxes, pack what the others need
-    TRY(graphed(1, xbuf, [&](hipStream_t s) -> int {
-      HIP_TRY(begin(3, s));
-      if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s)); else HIP_TRY(launch_p2m(d, p, s));
-      HIP_TRY(end(3, s));
-      HIP_TRY(begin(4, s));
-      TRY(m2m_pass(d, p, false, s));
+  if (phase == Phase::Upward) {                        // upward half: my leaves, my boxes, pack what the others need
+    TRY(graphed(kRegionUpward, xbuf, [&](hipStream_t s) -> int {
+      TRY(p2m(d, p, tm, s));
+      HIP_TRY(tm.begin(Stage::M2M, s));
+      TRY(shift_pass(d, p, ShiftDir::Up, s));
       HIP_TRY(launch_xch_pack(d, p, reinterpret_cast<double2*>(xbuf), s));
-      HIP_TRY(end(4, s));
+      HIP_TRY(tm.end(Stage::M2M, s));
       return FMMBEM_OK;
     }));
-    pending_mask = mask;
+    pending_mask = tm.mask;
     pending_near = false;
     return FMMBEM_OK;
   }
   const bool near_f32 = d.near_f32 && p <= opts.near_f32_max_p;
   auto near_field = [&](hipStream_t ns) -> int {
-    HIP_TRY(begin(1, ns));
+    HIP_TRY(tm.begin(Stage::Spmv, ns));
     // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
     // only added to by L2P -- they start from zero
     if (targets && zero_target_rows)
@@ -1476,78 +1505,44 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
     if (g.hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
     else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
     else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
-    HIP_TRY(end(1, ns));
+    HIP_TRY(tm.end(Stage::Spmv, ns));
     return FMMBEM_OK;
   };
   const bool fold = l2p_delivers(near_only, phase);  // L2P stores into d_y: the scatter stage then brackets nothing
-  if (phase == 3) {                                    // the near field of a split execute, while the caller's all-gather is in flight
+  if (phase == Phase::NearSplit) {                     // the near field of a split execute, while the caller's all-gather is in flight
     TRY(near_field(s));
-    pending_mask = mask;
+    pending_mask = tm.mask;
     pending_near = true;
     return FMMBEM_OK;
   }
-  const bool near_here = !(phase == 2 && pending_near);
+  const bool near_here = !(phase == Phase::Downward && pending_near);
   pending_near = false;
   // The near field and P2M as ONE launch (launch_near_p2m: the P2M workgroups start where the near field's retire) on a whole
   // execute whose near field is near_spmv_pipe_kernel and whose P2M is p2m_stream_kernel.  Stage timing keeps the two launches:
   // its events bracket the near kernel alone.  FMMBEM_NEAR_P2M, read per launch: 0 = separate launches, 2 = one launch or
   // FMMBEM_ERR_UNSUPPORTED (tests: proves which path ran), otherwise one launch where eligible.
   const int fuse_mode = sw::near_p2m();
-  const bool fuse = fuse_mode != 0 && phase == 0 && !near_only && !targets && !treecode() && tm == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
+  const bool fuse = fuse_mode != 0 && whole && !near_only && !targets && !treecode() && timing == 0 && !g.hybrid && !near_f32 && opts.sparse_local &&
                     d.kernel != FMMBEM_KERNEL_STOKES_BEM && near_p2m_ok(d, p);
   if (fuse_mode == 2 && !fuse) return fail(FMMBEM_ERR_UNSUPPORTED, "FMMBEM_NEAR_P2M=2: this execute does not take the combined near-field / P2M launch");
-  TRY(graphed((phase == 2 ? 2 : 0) + (near_here ? 0 : 4) + (near_only ? 8 : 0) + (fold ? 16 : 0) + (fuse ? 32 : 0), xbuf, [&](hipStream_t s) -> int {
-  if (fuse) HIP_TRY(launch_near_p2m(d, p, s));
-  else if (near_here) TRY(near_field(s));
-  if (!near_only) {
-    if (phase == 0) {
-      if (!fuse) {
-      HIP_TRY(begin(3, s));
-      if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_p2m_stokes(d, p, s));       // (a field plan too: every source feeds every live group)
-      else if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m(dp, p, s); }));
-      else HIP_TRY(launch_p2m(d, p, s));
-      HIP_TRY(end(3, s));
-      }
-      HIP_TRY(begin(4, s));
-      TRY(m2m_pass(d, p, false, s));
-      HIP_TRY(end(4, s));
-    }
-    if (treecode()) {                                  // (never a shard: phase 0) the far field as one stage, timed as stage 6
-      HIP_TRY(begin(6, s));
-      HIP_TRY(launch_m2p(d, g.m2p, p, d.yt, s));
-      HIP_TRY(end(6, s));
-      return FMMBEM_OK;
-    }
-    HIP_TRY(begin(5, s));
-    if (phase == 2) {                                  // the other shards' multipoles, then the boxes spanning shards
-      HIP_TRY(launch_xch_unpack(d, p, reinterpret_cast<const double2*>(xbuf), s));
-      TRY(m2m_pass(d, p, true, s));
-    }
-    const bool rot = g.use_rot(p);
-    if (!rot) HIP_TRY(launch_mh_prep(d, p, s));      // the rotation kernel reads M itself
-    HIP_TRY(end(5, s));
-    HIP_TRY(begin(6, s));
-    if (rot) HIP_TRY(launch_m2l_rot(d, d_dev, p, s));
-    else HIP_TRY(launch_m2l(d, d_dev, p, s));
-    HIP_TRY(end(6, s));
-    HIP_TRY(begin(7, s));
-    TRY(l2l_pass(d, p, s));
-    HIP_TRY(end(7, s));
-    HIP_TRY(begin(8, s));
-    if (d.kernel == FMMBEM_KERNEL_STOKES_BEM) HIP_TRY(launch_l2p_stokes(d, p, d.yt, s));
-    else if (!fold) HIP_TRY(launch_l2p(d, p, d.yt, s));
-    else if (!graph_ok) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, d_y));
-    HIP_TRY(end(8, s));
-  }
-  return FMMBEM_OK;
+  const int region = (phase == Phase::Downward ? kRegionDownward : 0) | (near_here ? 0 : kRegionNearDone) | (near_only ? kRegionNearOnly : 0) |
+                     (fold ? kRegionFold : 0) | (fuse ? kRegionFused : 0);
+  // L2P's folded store takes the caller's pointer: a graph leaves it out, and it follows the replay, as the scatter does
+  const L2PTo to = !fold ? L2PTo::YTree : graph_ok ? L2PTo::Caller : L2PTo::Perm;
+  TRY(graphed(region, xbuf, [&](hipStream_t s) -> int {
+    if (fuse) HIP_TRY(launch_near_p2m(d, p, s));
+    else if (near_here) TRY(near_field(s));
+    if (near_only) return FMMBEM_OK;
+    if (whole && !fuse) TRY(p2m(d, p, tm, s));
+    return far_chain(d, d_dev, p, whole, whole ? nullptr : xbuf, to, d_y, tm, s);       // (Downward: the other shards' multipoles in xbuf)
   }));
-  if (fold && graph_ok) HIP_TRY(launch_l2p(d, p, d.yt, s, d.perm, d_y));   // takes the caller's pointer: after the graph, as the scatter
-  HIP_TRY(begin(2, s));
+  if (to == L2PTo::Caller) TRY(l2p(d, p, d_y, s));
+  HIP_TRY(tm.begin(Stage::Scatter, s));
   TRY(deliver(d, d_y, fold, s));
-  HIP_TRY(end(2, s));
+  HIP_TRY(tm.end(Stage::Scatter, s));
   last_p = p;
   last_near_f32 = near_f32 ? 1 : 0;
-  if (tm) { ev_mask[ring] = mask; ++ev_count; }
+  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
   return FMMBEM_OK;
 }
 
@@ -1604,19 +1599,18 @@ int fmmbem_plan::batch_alloc(hipStream_t s) {
 
 // The fast path: per pass of up to bat.width vectors the gathers, ONE near-field pass and one P2M pass (launch_near_spmv_multi,
 // launch_p2m_multi; a Stokes plan: launch_near_sym3_multi, and P2M with the single launcher per vector: there is no batched far
-// field), then M2M .. L2P and the delivery once per vector, with the launchers of run() on d pointing at that
-// vector's buffers.  The same kernels in the same order per vector as run(): the same bits.  host: x and y are host pointers,
-// staged through stage_x / stage_y(_targets) one vector at a time, in stream order.  With stage timing on, each pass records
-// its near-field and P2M passes (fmmbem_plan_stats ms_near, ms_p2m: means per pass).
+// field), then run()'s far chain (far_chain) and the delivery once per vector, on d pointing at that vector's buffers: the same
+// bits.  host: x and y are host pointers, staged through stage_x / stage_y(_targets) one vector at a time, in stream order.
+// With stage timing on, each pass records its near-field and P2M passes (fmmbem_plan_stats ms_near, ms_p2m: means per pass).
 int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y, size_t ldy, hipStream_t s, bool host) {
   if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   DEVICE_SCOPE(opts.device);
   TRY(batch_alloc(s));
   const int w = bat.width;
   const bool stokes = d.dof == 3;                      // never a target plan (batch_width)
-  const size_t bytes_x = sizeof(double) * (size_t)(targets ? hp.n_src : hp.n) * d.dof;
-  const size_t bytes_y = sizeof(double) * (size_t)(targets ? hp.n_targets : hp.n) * d.dof;
+  const size_t bytes_x = sizeof(double) * x_doubles(), bytes_y = sizeof(double) * y_doubles();
   double* sy = targets ? stage_y_targets : stage_y;
+  StageMarks no_marks;                                 // a vector's far chain records nothing
   BatchVecs bv{};
   bv.width = w;
   for (int j = 0; j < w; ++j) { bv.xt[j] = bat.xt[j]; bv.yt[j] = bat.yt[j]; bv.M[j] = bat.M[j]; }
@@ -1633,42 +1627,25 @@ int fmmbem_plan::run_batch(int p, int k, const double* x, size_t ldx, double* y,
       if (targets && zero_target_rows)
         HIP_TRY(hipMemsetAsync(bat.yt[j] + hp.n_src * d.dof, 0, sizeof(double) * (size_t)(hp.n - hp.n_src) * d.dof, s));
     }
-    // stage timing on: a pass is one record of the ring with two stages, its near-field pass (1) and its P2M (3); a Stokes pass
-    // records its near-field pass alone (P2M runs per vector, below)
-    hipEvent_t* set = timing ? &ev[(size_t)(ev_count % kRing) * 2 * kStages] : nullptr;
-    if (set) HIP_TRY(hipEventRecord(set[2 * 1], s));
+    // stage timing on (either mode): a pass is one record of the ring with two stages, its near-field pass and its P2M; a Stokes
+    // pass records its near-field pass alone (P2M runs per vector, below)
+    StageMarks pass{timing ? 1 : 0, timing ? &ev[(size_t)(ev_count % kRing) * 2 * kStages] : nullptr};
+    HIP_TRY(pass.begin(Stage::Spmv, s));
     if (stokes) HIP_TRY(launch_near_sym3_multi(d, bv, s)); else HIP_TRY(launch_near_spmv_multi(d, bv, s));
-    if (set) HIP_TRY(hipEventRecord(set[2 * 1 + 1], s));
+    HIP_TRY(pass.end(Stage::Spmv, s));
     if (!stokes) {
-      if (set) HIP_TRY(hipEventRecord(set[2 * 3], s));
+      HIP_TRY(pass.begin(Stage::P2M, s));
       if (targets) TRY(p2m_targets(d, [&](const DevicePlan& dp) { return launch_p2m_multi(dp, bv, p, s); }));
       else HIP_TRY(launch_p2m_multi(d, bv, p, s));
-      if (set) HIP_TRY(hipEventRecord(set[2 * 3 + 1], s));
+      HIP_TRY(pass.end(Stage::P2M, s));
     }
-    if (set) {
-      ev_mask[ev_count % kRing] = stokes ? (1u << 1) : (1u << 1) | (1u << 3);
-      ++ev_count;
-    }
+    if (timing) { ev_mask[ev_count % kRing] = pass.mask; ++ev_count; }
     for (int j = 0; j < nv; ++j) {
       double* yj = host ? sy : y + (size_t)(j0 + j) * ldy;
-      const DevicePlan dj = batch_view(bat, j);        // vector j's far field: the launchers of run() on its buffers
-      if (stokes) HIP_TRY(launch_p2m_stokes(dj, p, s));
-      TRY(m2m_pass(dj, p, false, s));
-      if (treecode()) {                                // as run(): M2P into vector j's y_tree, then the scatter
-        HIP_TRY(launch_m2p(dj, g.m2p, p, dj.yt, s));
-        TRY(deliver(dj, yj, false, s));
-        if (host) HIP_TRY(hipMemcpyAsync(y + (size_t)(j0 + j) * ldy, sy, bytes_y, hipMemcpyDeviceToHost, s));
-        continue;
-      }
-      const bool rot = g.use_rot(p);
-      if (!rot) HIP_TRY(launch_mh_prep(dj, p, s));
-      if (rot) HIP_TRY(launch_m2l_rot(dj, bat.dev[j], p, s));
-      else HIP_TRY(launch_m2l(dj, bat.dev[j], p, s));
-      TRY(l2l_pass(dj, p, s));
-      const bool fold = l2p_delivers(false, 0);
-      if (stokes) HIP_TRY(launch_l2p_stokes(dj, p, dj.yt, s));
-      else if (fold) HIP_TRY(launch_l2p(dj, p, dj.yt, s, dj.perm, yj));
-      else HIP_TRY(launch_l2p(dj, p, dj.yt, s));
+      const DevicePlan dj = batch_view(bat, j);        // vector j's far field: run()'s chain on its buffers and its device copy
+      if (stokes) TRY(p2m(dj, p, no_marks, s));
+      const bool fold = l2p_delivers(false, Phase::Whole);
+      TRY(far_chain(dj, bat.dev[j], p, true, nullptr, fold ? L2PTo::Perm : L2PTo::YTree, yj, no_marks, s));
       TRY(deliver(dj, yj, fold, s));
       if (host) HIP_TRY(hipMemcpyAsync(y + (size_t)(j0 + j) * ldy, sy, bytes_y, hipMemcpyDeviceToHost, s));
     }
@@ -1968,7 +1945,7 @@ static int multi_execute_device(fmmbem_plan* h, int p, const double* d_x, double
     HIP_TRY(hipStreamWaitEvent(sh.own_stream, m.ev_x, 0));
     HIP_TRY(hipMemcpyPeerAsync(m.x[r], m.dev[r], d_x, m.dev[0], sizeof(double) * nd, sh.own_stream));
     if (m.split) {
-      TRY(sh.run(p, m.x[r], nullptr, sh.own_stream, false, 1, xc->send[r]));
+      TRY(sh.run(p, m.x[r], nullptr, sh.own_stream, false, fmmbem_plan::Phase::Upward, xc->send[r]));
       HIP_TRY(hipEventRecord(m.ev_up[r], sh.own_stream));
     }
     return FMMBEM_OK;
@@ -1995,7 +1972,7 @@ static int multi_execute_device(fmmbem_plan* h, int p, const double* d_x, double
   TRY(fan_out([&](int q) -> int {                      // q's downward pass and near field, its slice home
     fmmbem_plan& sh = *m.shards[q];
     HIP_TRY(hipSetDevice(m.dev[q]));
-    if (m.split) TRY(sh.run(p, nullptr, m.slice[q], sh.own_stream, false, 2, xc->recv[q]));
+    if (m.split) TRY(sh.run(p, nullptr, m.slice[q], sh.own_stream, false, fmmbem_plan::Phase::Downward, xc->recv[q]));
     else TRY(sh.run(p, m.x[q], m.slice[q], sh.own_stream, false));
     const size_t rows = (size_t)(m.cut[q + 1] - m.cut[q]) * h->d.dof;
     if (rows) HIP_TRY(hipMemcpyPeerAsync(m.gathered + (size_t)q * m.chunk, m.dev[0], m.slice[q], m.dev[q], sizeof(double) * rows, sh.own_stream));
@@ -2285,6 +2262,17 @@ int fmmbem_plan_execute_device(fmmbem_plan* plan, int p, const double* d_x, doub
   return plan->run(p, d_x, d_y, static_cast<hipStream_t>(stream), false);
 }
 
+static int single_device_only(const fmmbem_plan* plan) {
+  return plan && plan->multi ? fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself") : FMMBEM_OK;
+}
+// The guard of the shard and split entry points: refuses a target plan, then the handle of a multi-device plan, then a null plan
+// (fmmbem_plan_exchange_doubles looks at its arguments before the multi-device check: it spells its own order with the pieces)
+static int shard_entry(const fmmbem_plan* plan, const char* what, const char* if_null = "null plan") {
+  TRY(target_plan_only(plan, what));
+  TRY(single_device_only(plan));
+  return plan ? FMMBEM_OK : fail(FMMBEM_ERR_INVALID, if_null);
+}
+
 // expansion slots an exchange carries per box, from the HOST lists (a host-only plan answers too): Laplace one per boundary
 // condition present; Stokes four potentials for velocity targets, seven for TRACTION targets (to_device, d.act)
 static int64_t active_slots(const fmmbem_plan* plan) {
@@ -2298,7 +2286,7 @@ static int64_t active_slots(const fmmbem_plan* plan) {
 int fmmbem_plan_exchange_doubles(const fmmbem_plan* plan, int p, size_t* per_shard) {
   TRY(target_plan_only(plan, "fmmbem_plan_exchange_doubles"));
   if (!plan || !per_shard) return fail(FMMBEM_ERR_INVALID, "null argument");
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
+  TRY(single_device_only(plan));
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   // from the host lists, so that a host-only plan (CPU tests of the N > 1 path) answers too
   const HostPlan& h = plan->hp;
@@ -2310,9 +2298,8 @@ int fmmbem_plan_exchange_doubles(const fmmbem_plan* plan, int p, size_t* per_sha
 }
 
 int fmmbem_plan_exchange_counts(const fmmbem_plan* plan, int p, int64_t* send_doubles, int64_t* recv_doubles) {
-  TRY(target_plan_only(plan, "fmmbem_plan_exchange_counts"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan || !send_doubles || !recv_doubles) return fail(FMMBEM_ERR_INVALID, "null argument");
+  TRY(shard_entry(plan, "fmmbem_plan_exchange_counts", "null argument"));
+  if (!send_doubles || !recv_doubles) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
   const HostPlan& h = plan->hp;
   const int W = h.opt.shard_world;
@@ -2328,24 +2315,18 @@ int fmmbem_plan_exchange_counts(const fmmbem_plan* plan, int p, int64_t* send_do
 }
 
 int fmmbem_plan_upward_device(fmmbem_plan* plan, int p, const double* d_x, double* d_send, void* stream) {
-  TRY(target_plan_only(plan, "fmmbem_plan_upward_device"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run(p, d_x, nullptr, static_cast<hipStream_t>(stream), false, 1, d_send);
+  TRY(shard_entry(plan, "fmmbem_plan_upward_device"));
+  return plan->run(p, d_x, nullptr, static_cast<hipStream_t>(stream), false, fmmbem_plan::Phase::Upward, d_send);
 }
 
 int fmmbem_plan_downward_device(fmmbem_plan* plan, int p, const double* d_recv, double* d_y, void* stream) {
-  TRY(target_plan_only(plan, "fmmbem_plan_downward_device"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run(p, nullptr, d_y, static_cast<hipStream_t>(stream), false, 2, const_cast<double*>(d_recv));
+  TRY(shard_entry(plan, "fmmbem_plan_downward_device"));
+  return plan->run(p, nullptr, d_y, static_cast<hipStream_t>(stream), false, fmmbem_plan::Phase::Downward, const_cast<double*>(d_recv));
 }
 
 int fmmbem_plan_near_split_device(fmmbem_plan* plan, double* d_y, void* stream) {
-  TRY(target_plan_only(plan, "fmmbem_plan_near_split_device"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run(plan->last_p > 0 ? plan->last_p : 1, nullptr, d_y, static_cast<hipStream_t>(stream), false, 3, nullptr);
+  TRY(shard_entry(plan, "fmmbem_plan_near_split_device"));
+  return plan->run(plan->last_p > 0 ? plan->last_p : 1, nullptr, d_y, static_cast<hipStream_t>(stream), false, fmmbem_plan::Phase::NearSplit, nullptr);
 }
 
 int fmmbem_plan_shard_rows(const fmmbem_plan* plan, int64_t* cut) {
@@ -2360,9 +2341,7 @@ int fmmbem_plan_shard_rows(const fmmbem_plan* plan, int64_t* cut) {
 }
 
 int fmmbem_plan_set_result_slices(fmmbem_plan* plan, int enabled) {
-  TRY(target_plan_only(plan, "fmmbem_plan_set_result_slices"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  TRY(shard_entry(plan, "fmmbem_plan_set_result_slices"));
   plan->result_slices = enabled != 0;
   return FMMBEM_OK;
 }
@@ -2386,7 +2365,7 @@ int fmmbem_plan_assemble_slices_device(fmmbem_plan* plan, const double* d_slices
 }
 
 int fmmbem_plan_near_device(fmmbem_plan* plan, const double* d_x, double* d_y, void* stream) {
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
+  TRY(single_device_only(plan));
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   return plan->run(1, d_x, d_y, static_cast<hipStream_t>(stream), true);
 }
@@ -2399,11 +2378,7 @@ int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   if (plan->result_slices)         // the owned rows in tree order at the head of y are only meaningful to the device-side all-gather
     return fail(FMMBEM_ERR_INVALID, "plan delivers result slices (fmmbem_plan_set_result_slices): use the device entry points");
   DEVICE_SCOPE(plan->opts.device);
-  const size_t dof = plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
-  const size_t bytes = sizeof(double) * (size_t)plan->hp.n * dof;
-  // a target plan: x over the panels, y over the targets
-  const size_t bytes_x = plan->targets ? sizeof(double) * (size_t)plan->hp.n_src * dof : bytes;
-  const size_t bytes_y = plan->targets ? sizeof(double) * (size_t)plan->hp.n_targets * dof : bytes;
+  const size_t bytes_x = sizeof(double) * plan->x_doubles(), bytes_y = sizeof(double) * plan->y_doubles();
   double* sy = plan->targets ? plan->stage_y_targets : plan->stage_y;
   hipStream_t s = plan->own_stream;
   HIP_TRY(hipMemcpyAsync(plan->stage_x, x, bytes_x, hipMemcpyHostToDevice, s));
@@ -2419,10 +2394,7 @@ static int batch_args(const fmmbem_plan* plan, int k, const void* x, size_t ldx,
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
   if (k < 1) return fail(FMMBEM_ERR_INVALID, "batch of k < 1 vectors");
   if (!x || !y) return fail(FMMBEM_ERR_INVALID, "null vector");
-  const size_t dof = plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
-  const size_t nx = (plan->targets ? (size_t)plan->hp.n_src : (size_t)plan->hp.n) * dof;
-  const size_t ny = (plan->targets ? (size_t)plan->hp.n_targets : (size_t)plan->hp.n) * dof;
-  if (ldx < nx || ldy < ny) return fail(FMMBEM_ERR_INVALID, "leading dimension shorter than a vector");
+  if (ldx < plan->x_doubles() || ldy < plan->y_doubles()) return fail(FMMBEM_ERR_INVALID, "leading dimension shorter than a vector");
   return FMMBEM_OK;
 }
 
@@ -2659,6 +2631,7 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
   }
   if (plan->on_device && plan->ev_count > 0) {
     // mean stage times over the recorded executes (waits for the recorded events)
+    using Stage = fmmbem_plan::Stage;
     constexpr int NS = fmmbem_plan::kStages, NR = fmmbem_plan::kRing;
     const int64_t have = plan->ev_count < NR ? plan->ev_count : NR;
     double sum[NS + 1] = {0};
@@ -2670,7 +2643,7 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
       const unsigned mask = plan->ev_mask[slot];
       int last = -1, first = -1;
       for (int k = 0; k < NS; ++k) if (mask & (1u << k)) { last = k; if (first < 0) first = k; }
-      if (mask & 4u) last = 2;                          // the delivery of the result (stage 2) is the last thing an execute does
+      if (mask & (1u << (int)Stage::Scatter)) last = (int)Stage::Scatter;     // the delivery of the result is the last thing an execute does
       if (last < 0) continue;
       float f = 0;
       for (int k = 0; k < NS; ++k) {
@@ -2685,9 +2658,10 @@ int fmmbem_plan_stats(const fmmbem_plan* plan, fmmbem_stats* o) {
     }
     if (used) {
       const double inv = 1.0 / double(used);
-      o->ms_gather = sum[0] * inv; o->ms_near = sum[1] * inv; o->ms_scatter = sum[2] * inv; o->ms_p2m = sum[3] * inv;
-      o->ms_m2m = sum[4] * inv; o->ms_mh = sum[5] * inv; o->ms_m2l = sum[6] * inv; o->ms_l2l = sum[7] * inv;
-      o->ms_l2p = sum[8] * inv; o->ms_total = sum[NS] * inv;
+      auto mean = [&](Stage k) { return sum[(int)k] * inv; };
+      o->ms_gather = mean(Stage::Gather); o->ms_near = mean(Stage::Spmv); o->ms_scatter = mean(Stage::Scatter); o->ms_p2m = mean(Stage::P2M);
+      o->ms_m2m = mean(Stage::M2M); o->ms_mh = mean(Stage::Mh); o->ms_m2l = mean(Stage::M2L); o->ms_l2l = mean(Stage::L2L);
+      o->ms_l2p = mean(Stage::L2P); o->ms_total = sum[NS] * inv;
       o->timed_executes = used;
     }
   }
@@ -2881,9 +2855,8 @@ int fmmbem_plan_get_diagonal(const fmmbem_plan* plan, double* out) {
 }
 
 int fmmbem_plan_get_expansions(const fmmbem_plan* plan, int which, int p, double* out) {
-  TRY(target_plan_only(plan, "fmmbem_plan_get_expansions"));
-  if (plan && plan->multi) return fail(FMMBEM_ERR_UNSUPPORTED, "not on a multi-device plan: it drives its shards itself");
-  if (!plan || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  TRY(shard_entry(plan, "fmmbem_plan_get_expansions", "null argument"));
+  if (!out) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (which != 0 && plan->treecode()) return fail(FMMBEM_ERR_UNSUPPORTED, "a treecode plan holds no local expansions (M only)");
   if (!plan->on_device) return fail(FMMBEM_ERR_NO_DEVICE, "expansions live on the device");
   if (p < 1 || p > plan->hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");

@@ -25,6 +25,8 @@ static const char* name(P2MForm f) {
   }
 }
 
+static const char* name(ShiftForm f) { return f == ShiftForm::Lanes ? "Lanes" : f == ShiftForm::Rot ? "Rot" : "Sparse"; }
+
 static double sym_vals[2];
 static uint8_t rec_flags[1];
 static double2 tab_recs[1];
@@ -53,6 +55,21 @@ static void p2m(const char* what, const DevicePlan& d, int p) {
   const P2MForm f = p2m_form(d, p);
   if (f == P2MForm::Empty || f == P2MForm::Invalid) std::printf("p2m %s %s\n", what, name(f));
   else std::printf("p2m %s %s grid=%d\n", what, name(f), p2m_grid(d, f));
+}
+
+// the tree-pass rule: the switches of a geometry and what the kernels' translation units answer for the order, all at their defaults
+struct ShiftSwitches { bool rot = true, lanes = true; int lanes_max = -1, rot_min = 2048; bool lanes_ok = true, rot_ok = true; };
+static void shift(const char* set, const ShiftSwitches& c, bool m2m, int p, int pairs, int n_act, int level_boxes = 0) {
+  std::printf("shift %s_%s_p%d_%dx%d_boxes%d %s\n", set, m2m ? "M2M" : "L2L", p, pairs, n_act, level_boxes,
+              name(shift_form(c.rot, c.lanes, c.lanes_max, c.rot_min, pairs, level_boxes, p, n_act, m2m, c.lanes_ok, c.rot_ok)));
+}
+// the hand-over from the wavefront kernel to the rotation kernel, per pass and order, in pair-slots
+static void shift_thresholds(const char* set, const ShiftSwitches& c) {
+  for (int d : {0, 1}) {
+    shift(set, c, true, 8, 2048 + d, 1); shift(set, c, true, 8, 512 + d, 4);
+    shift(set, c, true, 9, 8192 + d, 1); shift(set, c, true, 10, 16384 + d, 1); shift(set, c, true, 11, 2048 + d, 1);
+    shift(set, c, false, 3, 16384 + d, 1); shift(set, c, false, 10, 4096 + d, 4);
+  }
 }
 
 int main() {
@@ -105,5 +122,22 @@ int main() {
   std::printf("sym3_ok laplace %d\n", (int)batch_near_sym3_ok(laplace(), 2));
   d = stokes(); d.sym_items = nullptr; std::printf("sym3_ok no_items %d\n", (int)batch_near_sym3_ok(d, 2));
   std::printf("near_f32_ok %d%d%d%d\n", (int)near_f32_ok(1, 256, false), (int)near_f32_ok(1, 257, false), (int)near_f32_ok(3, 999, true), (int)near_f32_ok(3, 10, false));
+
+  ShiftSwitches c;
+  shift_thresholds("dflt", c);
+  for (bool m2m : {true, false}) shift("dflt", c, m2m, 10, 1 << 30, 4);     // 2^32 pair-slots: a 64-bit product, not 0
+  shift("dflt", c, true, 10, 1, 1, 0);
+  c = ShiftSwitches{}; c.lanes = false;
+  shift("lanes_off", c, true, 10, 1, 1, 2047); shift("lanes_off", c, true, 10, 1, 1, 2048);
+  c = ShiftSwitches{}; c.lanes_ok = false;
+  shift("lanes_unsupported", c, true, 10, 1, 1, 0);
+  c = ShiftSwitches{}; c.rot = false;
+  shift_thresholds("rot_off", c);
+  shift("rot_off", c, true, 10, 1, 1, 2048);
+  c = ShiftSwitches{}; c.lanes_ok = c.rot_ok = false;                       // p > 12
+  shift_thresholds("unsupported", c);
+  shift("unsupported", c, true, 10, 1, 1, 2048);
+  c = ShiftSwitches{}; c.lanes_max = 100;
+  for (int n : {100, 101}) { shift("max100", c, true, 10, n, 1); shift("max100", c, false, 3, n, 1); }
   return 0;
 }

@@ -4,7 +4,11 @@ written out from the launchers as they stood before the header existed (kernels_
   near grid   min(items, 256 * workgroups per CU): 5 for the single-vector kernels; 4, 2, 1 for the pipelined kernel at 2, 4, 8
               vectors; 3, 2, 1 for the symmetric Stokes kernel at 2, 3, 4
   near LDS    Pipe 2 * nv * 1024 * 8 + 4 * 4 * max_runs;  Sym3 nv * 3 * 1024 * 8 + 2 * 4 * max_runs;  Plain 2048 * 8 + 2 * 4 * max_runs
-  P2M grid    Stream min(ceil(leaves / 4), 2048);  Apply min(ceil(leaves / 4), 4096);  Recurrence min(ceil(leaves / 4), 2048)"""
+  P2M grid    Stream min(ceil(leaves / 4), 2048);  Apply min(ceil(leaves / 4), 4096);  Recurrence min(ceil(leaves / 4), 2048)
+  tree pass   the rule as it stood in plan.hip (PlanGeometry::shift_form): with FMMBEM_SHIFT_ROT on, the wavefront kernel up to
+              lanes_max pair-slots (pairs x live slots) where it is switched on and instantiated -- L2L 16 384; M2M 16 384 at
+              p = 10, 8 192 at p = 9, else 2 048; FMMBEM_SHIFT_LANES_MAX for all -- then the rotation kernel where instantiated
+              and (wavefront kernel switched on, or the child level has shift_rot_min = 2 048 boxes), else the sparse operators"""
 import os
 import subprocess
 
@@ -53,6 +57,31 @@ MULTI = {
 SYM3_OK = {"width=1": 0, "width=2": 1, "width=4": 1, "width=5": 0,
            "runs7680": 1,                               # 4 * 24 576 + 8 * 7 680 = 159 744 = 156 KiB exactly
            "runs7681": 0, "laplace": 0, "no_items": 0}
+# key: switches_pass_order_pairs x live slots_boxes of the child level
+SHIFT_THRESHOLDS = {
+    "M2M_p8_2048x1": "Lanes", "M2M_p8_2049x1": "Rot",
+    "M2M_p8_512x4": "Lanes", "M2M_p8_513x4": "Rot",          # Stokes: four live slots
+    "M2M_p9_8192x1": "Lanes", "M2M_p9_8193x1": "Rot",
+    "M2M_p10_16384x1": "Lanes", "M2M_p10_16385x1": "Rot",
+    "M2M_p11_2048x1": "Lanes", "M2M_p11_2049x1": "Rot",
+    "L2L_p3_16384x1": "Lanes", "L2L_p3_16385x1": "Rot",
+    "L2L_p10_4096x4": "Lanes", "L2L_p10_4097x4": "Rot",
+}
+SHIFT = {"dflt_%s_boxes0" % k: v for k, v in SHIFT_THRESHOLDS.items()}
+SHIFT.update({"rot_off_%s_boxes0" % k: "Sparse" for k in SHIFT_THRESHOLDS})          # FMMBEM_SHIFT_ROT=0
+SHIFT.update({"unsupported_%s_boxes0" % k: "Sparse" for k in SHIFT_THRESHOLDS})      # p > 12: neither kernel is instantiated
+SHIFT.update({
+    "dflt_M2M_p10_1073741824x4_boxes0": "Rot",              # 2^32 pair-slots: a 32-bit product would be 0 and say Lanes
+    "dflt_L2L_p10_1073741824x4_boxes0": "Rot",
+    "dflt_M2M_p10_1x1_boxes0": "Lanes",
+    "lanes_off_M2M_p10_1x1_boxes2047": "Sparse",            # FMMBEM_SHIFT_LANES=0: the level's size in the whole tree decides
+    "lanes_off_M2M_p10_1x1_boxes2048": "Rot",
+    "lanes_unsupported_M2M_p10_1x1_boxes0": "Rot",
+    "rot_off_M2M_p10_1x1_boxes2048": "Sparse",
+    "unsupported_M2M_p10_1x1_boxes2048": "Sparse",
+    "max100_M2M_p10_100x1_boxes0": "Lanes", "max100_M2M_p10_101x1_boxes0": "Rot",    # FMMBEM_SHIFT_LANES_MAX=100: both passes, all orders
+    "max100_L2L_p3_100x1_boxes0": "Lanes", "max100_L2L_p3_101x1_boxes0": "Rot",
+})
 
 
 @pytest.fixture(scope="module")
@@ -114,3 +143,9 @@ def test_multi_vector_grids_and_lds(exe):
 
 def test_stokes_batch_widths_and_the_lds_limit(exe):
     assert {k: int(v) for k, v in _table(_lines(exe)["sym3_ok"]).items()} == SYM3_OK
+
+
+def test_tree_pass_rule(exe):
+    got = _table(_lines(exe)["shift"])
+    assert len(got) == len(SHIFT) == 3 * 14 + 12
+    assert got == SHIFT
