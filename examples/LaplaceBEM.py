@@ -12,6 +12,8 @@ through a plan over those target points (FMM_plan(K, panels, targets=...), the r
 one more report line with its largest error against the exact exterior solution 1/|x|.
 -near_f32 P (not a flag of the reference): the operator's matvecs at orders p <= P stream the float copy of the near matrix
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
+-field_grad (not a flag of the reference): with -field N, one more line: the gradient of that formula at the same points
+(FMM_plan.execute_gradient on the two plans over them), its largest error against the exact -x/|x|^3 relative to 1/9.
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -fgmres -diagonal iterates on them; the same
 report lines as the other modes.
@@ -93,6 +95,19 @@ def exterior_fmm(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None):
     return out
 
 
+def exterior_fmm_gradient(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None):
+    """The gradient of the same formula at the points: (grad of the single layer of g_density - grad of the double layer of
+    dgdn_density) / 4 pi, by the gradient executes of the two plans over the points"""
+    m = len(points)
+    K = fb_.LaplaceSphericalBEM(p, k)
+    g = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.zeros(m, dtype=np.uint8))
+    d = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.ones(m, dtype=np.uint8))
+    out = (g.execute_gradient(g_density) - d.execute_gradient(dgdn_density)) / 4 / math.pi
+    g.close()
+    d.close()
+    return out
+
+
 def sphere_points(m, radius):
     """m points spread over a sphere (golden-angle spiral)"""
     i = np.arange(m) + 0.5
@@ -108,6 +123,7 @@ def main(argv):
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
     second_kind, mesh, field, near_f32, evaluator = False, None, 0, 0, "FMM"
+    field_grad = False
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -154,6 +170,8 @@ def main(argv):
             i += 1; mesh = argv[i]
         elif a == "-field":
             i += 1; field = int(argv[i])
+        elif a == "-field_grad":                           # not in the reference: FMM_plan.execute_gradient
+            field_grad = True
         elif a == "-block_inverse":                        # not in the reference: solver.BlockInverse
             solver, pc = "gmres", "block_inverse"
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
@@ -242,6 +260,12 @@ def main(argv):
         phi = exterior_fmm(fb, v, xs, np.ones(n), pts, p, k, opts)
         err = np.abs(phi - 1.0 / 3.0) / (1.0 / 3.0)
         print("field: %d points at r = 3, max error: %.4e, rms error: %.4e" % (field, float(err.max()), float(np.sqrt((err ** 2).mean()))))
+        if field_grad:
+            grad = exterior_fmm_gradient(fb, v, xs, np.ones(n), pts, p, k, opts)
+            exact_grad = -pts / np.linalg.norm(pts, axis=1)[:, None] ** 3
+            gerr = np.linalg.norm(grad - exact_grad, axis=1) / (1.0 / 9.0)
+            print("field gradient: %d points at r = 3, max error: %.4e, rms error: %.4e"
+                  % (field, float(gerr.max()), float(np.sqrt((gerr ** 2).mean()))))
     return it, res, math.sqrt(e / n), abs(outside - exact) / abs(exact)
 
 

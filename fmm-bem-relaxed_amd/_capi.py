@@ -108,6 +108,7 @@ SYMBOLS = (
     "fmmbem_plan_block_inverse_build", "fmmbem_plan_block_inverse_apply_device", "fmmbem_plan_block_inverse_apply",
     "fmmbem_plan_block_inverse_bytes",
     "fmmbem_plan_create_field",
+    "fmmbem_plan_execute_gradient", "fmmbem_plan_execute_gradient_device", "fmmbem_kernel_gradient_entries",
 )
 
 
@@ -213,6 +214,9 @@ def lib():
     L.fmmbem_plan_block_inverse_apply_device.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t, vp]
     L.fmmbem_plan_block_inverse_apply.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.fmmbem_plan_block_inverse_bytes.argtypes = [vp, i64p]
+    L.fmmbem_plan_execute_gradient.argtypes = [vp, i32, vp, vp]
+    L.fmmbem_plan_execute_gradient_device.argtypes = [vp, i32, vp, vp, vp]
+    L.fmmbem_kernel_gradient_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp, vp]
     _lib = L
     return L
 

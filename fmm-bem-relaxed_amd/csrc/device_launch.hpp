@@ -76,6 +76,14 @@ struct M2PWork {
 };
 // y[i] += (POTENTIAL row) or -= (NORMAL_DERIV row) the sum over the row's chain of M2P(M[source], centre[source], centroid i); Laplace
 hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, hipStream_t s);
+// ---- field gradient (kernels_grad.hip; Laplace plans over separate targets, whose target rows begin at n_src) ----
+// g_tree: 3 doubles per target row, tree order.  near: g_tree[row] = the near pairs' sum, every target row written (zeros where
+// the leaf has no near pair); l2p: g_tree[row] += (flag 0) or -= (flag 1) the gradient of the leaf's local expansion;
+// scatter: out[3 perm[row] ..] = g_tree[3 (row - n_src) ..]; entries: gamma for pairs laid out as launch_kernel_entries takes them
+hipError_t launch_near_grad(const DevicePlan& d, int64_t n_src, double* g_tree, hipStream_t s);
+hipError_t launch_l2p_grad(const DevicePlan& d, int p, int64_t n_src, double* g_tree, hipStream_t s);
+hipError_t launch_grad_scatter(const DevicePlan& d, int64_t n_src, const double* g_tree, double* out, hipStream_t s);
+hipError_t launch_grad_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

@@ -154,6 +154,60 @@ __device__ inline double laplace_entry(const DevicePlan& d, V3 t, int tbc, int64
   return deferred ? laplace_entry_near(d, t, tbc, j) : v;
 }
 
+// The gradient, with respect to the target point t, of the integrand the target's flag picks (include/fmmbem.h, "Field gradient"):
+// three doubles per (target point, source panel j).  The regimes are those of a NORMAL_DERIV target above: self (dist < 1e-8),
+// nearby (the 16-point rule on the vertices), else the K stored points; points in order, one running sum.  With dx = y_q - t:
+//   flag 0 (single layer, int G):        sum_q w_q A dx / |dx|^3;                                self: 2 pi n_j
+//   flag 1 (double layer, int dG/dn_y):  sum_q w_q A (-n_j / |dx|^3 + 3 (dx . n_j) dx / |dx|^5);  self: 0
+// so n_j . (flag 0) is the NORMAL_DERIV entry of the pair.  The ONE text of it: the matrix-free near kernel of the gradient execute
+// and fmmbem_kernel_gradient_entries (kernels_grad.hip) both call it: laplace_grad_from on a panel's fields, laplace_grad_entry on panel j of d.
+// (the arithmetic on a source panel handed over by its fields: quad(q) the stored point q, vert(a) vertex a, read only in the near regime)
+template <class Quad, class Vert>
+__device__ __forceinline__ V3 laplace_grad_from(V3 t, int tbc, V3 c, double A, V3 nrm, int nq, const double* qw, Quad&& quad, Vert&& vert) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  // The regime is decided by the expressions of laplace_far_from, dist < 1e-8 and sqrt(2 A) / dist >= 0.5, so that a pair is in the
+  // same regime there and here.  Most pairs are far from that boundary: with 8 A < 0.99 dist^2 the exact ratio is below 0.4975 and
+  // its few roundings cannot lift it to 0.5 (and dist^2 > 1e-15 is no self pair), so the square root and the division are skipped.
+  bool nearby = false;
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {
+    const double dist = sqrt(d2);
+    if (dist < 1e-8) {
+      const double s = tbc ? 0.0 : 2 * M_PI;
+      return {s * nrm.x, s * nrm.y, s * nrm.z};
+    }
+    nearby = sqrt(2 * A) / dist >= 0.5;
+  }
+  V3 g = {0, 0, 0};
+  auto point = [&](V3 y, double wA) {
+    const V3 dx = sub(y, t);
+    const double r2 = dx.x * dx.x + dx.y * dx.y + dx.z * dx.z;
+    const double ri = rsqrt(r2), ri2 = ri * ri;          // 1 / |dx|: one reciprocal square root per point, no division
+    const double f = wA * (ri * ri2);
+    if (tbc == 0) {
+      g.x += f * dx.x; g.y += f * dx.y; g.z += f * dx.z;
+    } else {
+      const double h = 3 * (dx.x * nrm.x + dx.y * nrm.y + dx.z * nrm.z) * ri2;
+      g.x += f * (h * dx.x - nrm.x); g.y += f * (h * dx.y - nrm.y); g.z += f * (h * dx.z - nrm.z);
+    }
+  };
+  if (nearby) {
+    const V3 v0 = vert(0), v1 = vert(1), v2 = vert(2);
+    for (int q = 0; q < 16; ++q)
+      point(V3{v0.x * kFine[q][0] + v1.x * kFine[q][1] + v2.x * kFine[q][2], v0.y * kFine[q][0] + v1.y * kFine[q][1] + v2.y * kFine[q][2],
+               v0.z * kFine[q][0] + v1.z * kFine[q][1] + v2.z * kFine[q][2]}, kFine[q][3] * A);
+  } else {
+    for (int q = 0; q < nq; ++q) point(quad(q), qw[q] * A);
+  }
+  return g;
+}
+__device__ inline V3 laplace_grad_entry(const DevicePlan& d, V3 t, int tbc, int64_t j) {
+  const int64_t N = d.n;
+  return laplace_grad_from(t, tbc, V3{d.cx[j], d.cy[j], d.cz[j]}, d.area[j], V3{d.nx[j], d.ny[j], d.nz[j]}, d.nq, d.qw,
+                           [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; },
+                           [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; });
+}
+
 // ---------------------------------------------------------------------------------------------
 // Stokes (velocity boundary condition): one near-matrix entry is the 3x3 block
 //   (1/2mu) int_source ( I/r + d d^T / r^3 ) dS,  d = target centroid - y

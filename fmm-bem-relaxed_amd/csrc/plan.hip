@@ -333,6 +333,11 @@ struct fmmbem_plan {
   const uint32_t* d_target_point = nullptr;                    // given target -> distinct point (only when some coincide)
   double* y_points = nullptr;                                  // the result per distinct point (only when some coincide)
   double* stage_y_targets = nullptr;                           // device staging of y for host-pointer execute
+  // Field gradient (fmmbem_plan_execute_gradient; Laplace dual plans): 3 doubles per target row in tree order, per distinct point
+  // (only when some targets coincide) and per given target (the host form's staging); allocated at the first gradient call
+  double *grad_tree = nullptr, *grad_points = nullptr, *stage_g = nullptr;
+  int grad_alloc();
+  int run_gradient(int p, const double* d_x, double* d_g, hipStream_t s);
 
   template <class T, class A>
   int upload(const std::vector<T, A>& v, const T** out) {
@@ -1546,6 +1551,55 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   return FMMBEM_OK;
 }
 
+// ======================================= field gradient =======================================
+int fmmbem_plan::grad_alloc() {
+  const size_t rows = (size_t)(hp.n - hp.n_src);
+  if (!grad_tree) TRY(alloc(3 * rows, &grad_tree, false));
+  if (d_target_point && !grad_points) TRY(alloc(3 * rows, &grad_points, false));
+  if (!stage_g) TRY(alloc(3 * (size_t)hp.n_targets, &stage_g, false));
+  return FMMBEM_OK;
+}
+
+// The gradient execute (include/fmmbem.h "Field gradient"): run()'s gather, P2M and far chain up to and including L2L on the plan's
+// own M and L -- the same launches in the same order, so the same L -- then the two kernels of kernels_grad.hip into grad_tree and
+// the delivery.  Launched plainly (never captured, never replayed; `graphs` is not touched), it writes x_tree, M, Mh and L, which
+// every potential execute writes afresh before it reads them, and leaves y_tree alone.
+int fmmbem_plan::run_gradient(int p, const double* d_x, double* d_g, hipStream_t s) {
+  if (!d_x || !d_g) return fail(FMMBEM_ERR_INVALID, "null vector");
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)");
+  if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: Laplace plans only");
+  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+  DEVICE_SCOPE(opts.device);
+  TRY(grad_alloc());
+  const int64_t ring = ev_count % kRing;
+  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
+  HIP_TRY(tm.begin(Stage::Gather, s));
+  DevicePlan dg = d;
+  dg.n = hp.n_src;                                     // x: the source panels only (the target rows of x_tree stay 0)
+  HIP_TRY(launch_gather_x(dg, d_x, s));
+  HIP_TRY(tm.end(Stage::Gather, s));
+  TRY(p2m(d, p, tm, s));
+  TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
+  HIP_TRY(tm.begin(Stage::Spmv, s));
+  HIP_TRY(launch_near_grad(d, hp.n_src, grad_tree, s));
+  HIP_TRY(tm.end(Stage::Spmv, s));
+  HIP_TRY(tm.begin(Stage::L2P, s));
+  HIP_TRY(launch_l2p_grad(d, p, hp.n_src, grad_tree, s));
+  HIP_TRY(tm.end(Stage::L2P, s));
+  HIP_TRY(tm.begin(Stage::Scatter, s));
+  HIP_TRY(launch_grad_scatter(d, hp.n_src, grad_tree, d_target_point ? grad_points : d_g, s));
+  if (d_target_point) {
+    const int64_t nt = hp.n_targets * 3;
+    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, grad_points, d_g, nt, 3);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(tm.end(Stage::Scatter, s));
+  last_p = p;
+  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
+  return FMMBEM_OK;
+}
+
 // ======================================= batched execute =======================================
 // Vectors per near-field pass on the fast path (FMMBEM_BATCH_NV = 2, 4 or 8 for sweeps).  ms per vector at N = 1M, k = 4 / 8,
 // p = 10 and 2 (tools/batch_time.py, profiles/r06b_batch_time.txt): 2 -> 1.24, 0.59; 4 -> 1.16, 0.56; 8 -> 1.29, 0.67.
@@ -2389,6 +2443,27 @@ int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   return FMMBEM_OK;
 }
 
+// ---- field gradient (include/fmmbem.h) ----
+int fmmbem_plan_execute_gradient_device(fmmbem_plan* plan, int p, const double* d_x, double* d_g, void* stream) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  return plan->run_gradient(p, d_x, d_g, static_cast<hipStream_t>(stream));
+}
+
+int fmmbem_plan_execute_gradient(fmmbem_plan* plan, int p, const double* x, double* g) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!x || !g) return fail(FMMBEM_ERR_INVALID, "null vector");
+  if (!plan->on_device || !plan->targets || plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM || p < 1 || p > plan->hp.opt.p_max)
+    return plan->run_gradient(p, x, g, nullptr);       // a refusal: it touches neither pointer
+  DEVICE_SCOPE(plan->opts.device);
+  TRY(plan->grad_alloc());
+  hipStream_t s = plan->own_stream;
+  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
+  TRY(plan->run_gradient(p, plan->stage_x, plan->stage_g, s));
+  HIP_TRY(hipMemcpyAsync(g, plan->stage_g, sizeof(double) * 3 * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
 // ---- batched execute (include/fmmbem.h) ----
 static int batch_args(const fmmbem_plan* plan, int k, const void* x, size_t ldx, const void* y, size_t ldy) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
@@ -2937,6 +3012,45 @@ int fmmbem_kernel_entries(const fmmbem_options* opts, size_t n, const double* ta
   frees.v.push_back(d_out);
   HIP_TRY(launch_kernel_entries(d, (int)n, d_out, nullptr));
   HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * n * per, hipMemcpyDeviceToHost));
+  return FMMBEM_OK;
+}
+
+int fmmbem_kernel_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
+                                   const double* source_vertices, double* out) {
+  if (!opts || !target_vertices || !source_vertices || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: the Laplace kernel only");
+  if (n == 0) return FMMBEM_OK;
+  if (n > ((size_t)1 << 30)) return fail(FMMBEM_ERR_INVALID, "too many pairs");
+  QuadRule rule;
+  if (!quad_rule(opts->quad_k, rule)) return fail(FMMBEM_ERR_INVALID, "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
+  if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
+  DEVICE_SCOPE(opts->device);
+  const int64_t N = 2 * (int64_t)n;                    // the layout of fmmbem_kernel_entries: panels [0, n) targets, [n, 2n) sources
+  PanelSoA P;
+  try {
+    alloc_panels(P, N, rule.n);
+  } catch (const std::bad_alloc&) {
+    return fail(FMMBEM_ERR_ALLOC, "host allocation failed");
+  }
+  for (size_t i = 0; i < n; ++i) {
+    fill_panel(P, N, (int64_t)i, target_vertices + 9 * i, rule, target_bc ? (target_bc[i] ? 1 : 0) : 0);
+    fill_panel(P, N, (int64_t)(n + i), source_vertices + 9 * i, rule, 0);
+  }
+  Scratch mem;
+  DevicePlan d{};
+  d.n = N; d.nq = rule.n; d.kernel = opts->kernel; d.dof = 1;
+  for (int q = 0; q < rule.n; ++q) d.qw[q] = rule.w[q];
+  TRY(mem.up(P.cx.data(), P.cx.size(), &d.cx)); TRY(mem.up(P.cy.data(), P.cy.size(), &d.cy)); TRY(mem.up(P.cz.data(), P.cz.size(), &d.cz));
+  TRY(mem.up(P.nx.data(), P.nx.size(), &d.nx)); TRY(mem.up(P.ny.data(), P.ny.size(), &d.ny)); TRY(mem.up(P.nz.data(), P.nz.size(), &d.nz));
+  TRY(mem.up(P.area.data(), P.area.size(), &d.area)); TRY(mem.up(P.quad.data(), P.quad.size(), &d.quad));
+  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert)); TRY(mem.up(P.bc.data(), P.bc.size(), &d.bc));
+  double* d_out = nullptr;
+  TRY(mem.alloc(3 * n, &d_out));
+  HIP_TRY(launch_grad_entries(d, (int)n, d_out, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
   return FMMBEM_OK;
 }
 

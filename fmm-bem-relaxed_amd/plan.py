@@ -264,6 +264,32 @@ def kernel_entries(K, targets, sources, target_bc=None, device=0):
     return out
 
 
+def kernel_gradient_entries(K, targets, sources, target_bc=None, device=0):
+    """gamma(target_i, source_i) of the field gradient for n pairs (fmmbem_kernel_gradient_entries): the gradient, with respect to
+    the target point, of the panel integral the target's flag picks, by the function FMM_plan.execute_gradient's near kernel calls.
+    targets, sources: (n, 3, 3) vertices -- the target POINT is the target panel's centroid; target_bc: n flags.  Laplace only.
+    Returns (n, 3)."""
+    t = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 9)
+    s = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 9)
+    if t.shape != s.shape:
+        raise ValueError("one source per target")
+    o = _capi.Options()
+    _capi.lib().fmmbem_options_default(C.byref(o))
+    o.quad_k, o.device = K.K, int(device)
+    if isinstance(K, StokesSphericalBEM):
+        o.kernel = _capi.KERNEL_STOKES_BEM                 # refused by the library (status 6)
+    bcp = None
+    if target_bc is not None:
+        target_bc = np.ascontiguousarray(target_bc, dtype=np.uint8)
+        if target_bc.shape != (len(t),):
+            raise ValueError("target_bc must have one flag per pair")
+        bcp = target_bc.ctypes.data_as(C.c_void_p)
+    out = np.empty((len(t), 3))
+    _capi.check(_capi.lib().fmmbem_kernel_gradient_entries(C.byref(o), len(t), t.ctypes.data_as(C.c_void_p), bcp,
+                                                           s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class Direct:
     """Direct::matvec (include/Direct.hpp:232-302) on the device: y_i = sum_j K(t_i, s_j) x_j over ALL the panels, every entry the
     one kernel_entries gives for that pair (fmmbem_direct_*, csrc/kernels_direct.hip).  Laplace and Stokes; no tree, no matrix.
@@ -630,6 +656,38 @@ class FMM_plan:
         if out is None:
             out = torch.empty_like(x) if self.n_targets is None else x.new_empty(self._target_shape())
         self.execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
+        return out
+
+    # ---- field gradient: grad of the Laplace field at the points of a targets= plan or a field plan (fmmbem_plan_execute_gradient) ----
+    def execute_gradient(self, charges):
+        """(N,) charges -> (M, 3): g_i = sum_j gamma(t_i, s_j) x_j at the kernel's current p, gamma the gradient with respect to the
+        target point of the integrand the target's flag picks (include/fmmbem.h, "Field gradient").  numpy in, numpy out (host).
+        FmmBemError (status 6) on a plan that is not over separate targets, on a Stokes plan and on a host-only plan."""
+        x = np.ascontiguousarray(charges, dtype=np.float64)
+        if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
+            raise ValueError("charges must have one value per panel")
+        g = np.empty((self.n if self.n_targets is None else self.n_targets, 3))
+        _capi.check(_capi.lib().fmmbem_plan_execute_gradient(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
+                                                             g.ctypes.data_as(C.c_void_p)))
+        return g
+
+    def execute_gradient_device(self, x_ptr, g_ptr, stream=0, p=None):
+        _capi.check(_capi.lib().fmmbem_plan_execute_gradient_device(self._h, self._K.P if p is None else int(p),
+                                                                    C.c_void_p(x_ptr), C.c_void_p(g_ptr), C.c_void_p(stream)))
+
+    def execute_gradient_torch(self, x, out=None, p=None):
+        """x: contiguous float64 CUDA tensor (N,), ORIGINAL panel order; returns (M, 3).  Runs on torch's current stream."""
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
+            raise ValueError("x must be a contiguous float64 CUDA tensor with one value per panel")
+        if x.device.index != self.device:
+            raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
+        shape = (self.n if self.n_targets is None else self.n_targets, 3)
+        if out is None:
+            out = x.new_empty(shape)
+        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
+        self.execute_gradient_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
     # ---- batched execute: k vectors, one near-field pass per batch_width() of them (fmmbem_plan_execute_batch) ----

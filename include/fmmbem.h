@@ -327,6 +327,34 @@ int fmmbem_plan_execute_batch_device(fmmbem_plan *plan, int p, int k, const doub
  * (also on a host-only plan). */
 int fmmbem_plan_batch_width(const fmmbem_plan *plan, int *width);
 
+/* ---- Field gradient: the gradient of the Laplace field at the points of a plan over separate targets ----------------------
+ * (no reference counterpart: the electric field, the velocity of a potential flow, the flux are -grad phi off the surface).
+ * On a Laplace plan of fmmbem_plan_create_targets or fmmbem_plan_create_field, for target i with point t_i,
+ *   g_i = sum_j gamma(t_i, s_j) x_j,   three doubles,
+ * gamma = the gradient WITH RESPECT TO THE TARGET POINT of the integrand the target's flag picks.  The rule is chosen as
+ * eval_dGdn chooses it for a NORMAL_DERIV target (kernel/LaplaceSphericalBEM.hpp:208-264): dist = |t - c_j|;
+ * nearby = sqrt(2 A_j) / dist >= 0.5; the 16-point rule on the vertices if nearby, else the K stored points.  With dx = y_q - t:
+ *   flag 0 (gradient of the single layer, int G):        gamma = sum_q w_q A_j dx / |dx|^3;  dist < 1e-8: gamma = 2 pi n_j, the
+ *     reference's self value of the derivative kernel -- so n_j . gamma(t, s_j) is, for every pair and regime, the entry K(t, s_j)
+ *     of a NORMAL_DERIV target;
+ *   flag 1 (gradient of the double layer, int dG/dn_y):  gamma = sum_q w_q A_j (-n_j / |dx|^3 + 3 (dx . n_j) dx / |dx|^5);
+ *     dist < 1e-8: gamma = 0.
+ * n_j is the panel normal as the plan holds it.  The far field is +- grad of the local expansion that the potential execute
+ * evaluates: the slot picked by the target's flag, + for flag 0 and - for flag 1, as its L2P adds the value.  The gradient of the
+ * representation formula is (g[flag 0 plan, density] - g[flag 1 plan, potential]) / (4 pi).
+ * x: n_panels doubles; g: n_targets x 3, interleaved, both in the caller's order; coincident targets each get their copy.
+ * The execute is the potential execute's gather, P2M, M2M, M2L and L2L, then two kernels of its own -- the near pairs matrix-free
+ * (a row's sum: the leaf's near list in order, panels ascending, quadrature points in order) and the gradient of L (terms
+ * m-major) -- and the delivery: the same bits every run.  Its buffers are allocated at the first gradient call
+ * (FMMBEM_ERR_ALLOC if that fails; the plan stays usable).  Checked in this order: a null plan or vector -> FMMBEM_ERR_INVALID;
+ * p outside 1..p_max -> _INVALID; a plan that is not over separate targets -> _UNSUPPORTED; a Stokes plan -> _UNSUPPORTED; a
+ * host-only plan -> _UNSUPPORTED; the handle stays usable.  A gradient execute is launched plainly, kernel by kernel, whatever
+ * fmmbem_plan_set_graphs says, and leaves the captured graphs of the potential execute as they are.  With stage timing on it is
+ * recorded as an execute: ms_near is the near kernel of the gradient, ms_l2p the gradient of L.  No batches.
+ * The host form takes HOST pointers and returns when g is written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_gradient(fmmbem_plan *plan, int p, const double *x, double *g);
+int fmmbem_plan_execute_gradient_device(fmmbem_plan *plan, int p, const double *d_x, double *d_g, void *stream);
+
 /* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
  * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES
  * iteration on that operator instead).  A BLOCK_DIAGONAL plan holds every leaf's self block assembled in HBM; build inverts
@@ -396,6 +424,11 @@ int fmmbem_plan_get_diagonal(const fmmbem_plan *plan, double *out);
  * (examples/BEM/Preconditioner.hpp:24-33) calls as K(*it, *it) on the panels of FMM_plan::source_begin(). */
 int fmmbem_kernel_entries(const fmmbem_options *opts, size_t n, const double *target_vertices, const uint8_t *target_bc,
                           const double *source_vertices, double *out);
+/* gamma(target, source) of the field gradient (see fmmbem_plan_execute_gradient) for n independent pairs, by the function the
+ * gradient execute's near kernel calls: the target POINT is the centroid of target_vertices' panel i, target_bc its flag (NULL:
+ * all 0).  Laplace only (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, device.  out: n x 3. */
+int fmmbem_kernel_gradient_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
+                                   const uint8_t *target_bc, const double *source_vertices, double *out /* n x 3 */);
 
 /* ---- the translation operators one at a time: the KernelSkeleton contract (kernel/KernelSkeleton.hpp:62-212) --------------
  * What the reference's kernel classes offer beside operator(): P2M, M2M, M2L, L2L, L2P as kernel/LaplaceSphericalBEM.hpp:307-476

@@ -589,6 +589,17 @@ class PlanAdapter {
     for (size_t j = 0; j < k; ++j) std::memcpy(KernelBinding<Kernel>::out(results[j]), y.data() + j * ldy, ldy * sizeof(double));
     return results;
   }
+  // Not in the reference: the gradient of the field at the targets of a plan over separate targets (the four-argument constructor
+  // or field_plan; fmmbem_plan_execute_gradient): result i = sum_j gamma(targets[i], sources[j]) charges[j], gamma the gradient
+  // with respect to the target point of the integrand the target's BC picks.  Laplace only: Error(FMMBEM_ERR_UNSUPPORTED) on a
+  // Stokes plan and on a plan over its own panels.
+  std::vector<Vec<3, double>> execute_gradient(const std::vector<charge_type>& charges) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
+    std::vector<Vec<3, double>> results(has_targets_ ? target_bc_.size() : charges.size());
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    check(fmmbem_plan_execute_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
+    return results;
+  }
   // preconditioner-style operator()(x, y) (examples/BEM/Preconditioner.hpp:11-15)
   void operator()(const std::vector<charge_type>& x, std::vector<result_type>& y) { y = execute(x); }
 
