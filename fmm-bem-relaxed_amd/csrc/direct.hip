@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/fmmbem.h"
+#include "device_allocs.hpp"
 #include "device_launch.hpp"
 #include "host_plan.hpp"
 #include "status.hpp"
@@ -35,32 +36,20 @@ struct fmmbem_direct {
   int device = 0;
   int64_t n = 0;
   DevicePlan d{};                                      // the source panels and the rules; nothing else is set
-  std::vector<void*> allocs;
+  DeviceAllocs mem;
   hipStream_t stream = nullptr;                        // the host form's stream
   double* part = nullptr;                              // [chunk][target][dof] partial sums, grown on demand
   size_t part_cap = 0;                                 // doubles
   ~fmmbem_direct() {
     DeviceGuard g(device);
-    for (void* p : allocs) (void)hipFree(p);
+    mem.free_all();
     if (part) (void)hipFree(part);
     if (stream) (void)hipStreamDestroy(stream);
   }
   template <class T>
-  int alloc(size_t count, T** out) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-    allocs.push_back(p);
-    *out = static_cast<T*>(p);
-    return FMMBEM_OK;
-  }
+  int alloc(size_t count, T** out) { return mem.alloc(count, out, false); }
   template <class T>
-  int upload(const std::vector<T>& v, const T** out) {
-    T* p = nullptr;
-    TRY(alloc(v.size(), &p));
-    if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = p;
-    return FMMBEM_OK;
-  }
+  int upload(const std::vector<T>& v, const T** out) { return mem.upload(v, out); }
   int init(const fmmbem_options& o, const QuadRule& rule, const QuadRule& fine, const double* vertices);
   int ensure_part(size_t doubles);
   int apply(size_t m, const double* d_pts, const uint8_t* d_bc, const double* d_x, double* d_y, hipStream_t s);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/fmmbem.h"
+#include "device_allocs.hpp"
 #include "device_launch.hpp"
 #include "host_plan.hpp"
 #include "host_tables.hpp"
@@ -41,13 +42,13 @@ struct fmmbem_ops {
   QuadRule rule;
   HarmonicTables T;
   DevicePlan base{};                                   // the constant fields: orders, tables, the two boxes' storage
-  std::vector<void*> allocs;
+  DeviceAllocs mem;
   hipStream_t stream = nullptr;
   // index lists of the one pair / the one leaf, uploaded once: ints[...]
   const int* ints = nullptr;
   enum { I_ZERO = 0, I_ONE = 1, I_PTR01 = 2, I_M2LPTR = 4, I_CHILD_BEGIN = 7, I_CHILD_END = 9, I_PARENT = 11, I_CLS = 13, I_COUNT = 16 };
+  std::shared_ptr<const OrderTables> ot;               // the tables of the order alone (host_tables.hpp), shared by the process
   const double *up_stream = nullptr, *dn_stream = nullptr;
-  int shift_stream_off[kRotPmax] = {};
   std::vector<ShiftOpDev> up_ops, down_ops;            // p > 12 only, built at the first call that needs them
   double2 *up_tab = nullptr, *down_tab = nullptr;      // [p_max^2], rewritten per call
   double* rec = nullptr;                               // [8] class record of the call's translation
@@ -58,27 +59,13 @@ struct fmmbem_ops {
   bool generic_ready = false;
   ~fmmbem_ops() {
     DeviceGuard g(device);
-    for (void* p : allocs) (void)hipFree(p);
+    mem.free_all();
     if (stream) (void)hipStreamDestroy(stream);
   }
+  template <class V, class T_>
+  int upload(const V& v, const T_** out) { return mem.upload(v, out); }
   template <class T_>
-  int upload(const std::vector<T_>& v, const T_** out) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T_)));
-    allocs.push_back(p);
-    if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T_), hipMemcpyHostToDevice));
-    *out = static_cast<const T_*>(p);
-    return FMMBEM_OK;
-  }
-  template <class T_>
-  int alloc(size_t count, T_** out) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T_)));
-    allocs.push_back(p);
-    HIP_TRY(hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T_)));
-    *out = static_cast<T_*>(p);
-    return FMMBEM_OK;
-  }
+  int alloc(size_t count, T_** out) { return mem.alloc(count, out, true); }
   int slots_p2m() const { return kernel == FMMBEM_KERNEL_STOKES_BEM ? 4 : 2; }
   int init();
   int ensure_generic();
@@ -101,21 +88,7 @@ int fmmbem_ops::init() {
   d.stokes_velocity_targets = 1; d.stokes_traction_targets = 0;
   HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   TRY(upload(T.A, &d.tabA)); TRY(upload(T.invA, &d.tabInvA)); TRY(upload(T.pref, &d.tabPref));
-  {
-    // the recurrences' per-step constants (the same table plan.hip uploads: {pref, c1, c2, 0} per (order, step), m-major)
-    const int smax = kPmax * (kPmax + 1) / 2;
-    std::vector<double> st((size_t)kPmax * (smax + 1) * 4, 0.0);
-    for (int p = 1; p <= kPmax; ++p) {
-      double* o = st.data() + (size_t)(p - 1) * (smax + 1) * 4;
-      for (int m = 0; m < p; ++m)
-        for (int n = m; n < p; ++n, o += 4) {
-          o[0] = T.pref[n * n + n + m];
-          o[1] = n == m ? (double)(2 * m + 1) : (double)(2 * n + 1) * (1.0 / (n - m + 1));
-          o[2] = n == m ? 0.0 : (double)(n + m) * (1.0 / (n - m + 1));
-        }
-    }
-    TRY(upload(st, &d.tabStep));
-  }
+  TRY(upload(step_table(T), &d.tabStep));
   TRY(alloc((size_t)2 * kMaxSlots * d.s_max, &d.M));
   TRY(alloc((size_t)2 * kMaxSlots * d.s_max, &d.L));
   TRY(alloc((size_t)2 * kMaxSlots * d.s_max, &d.Mh));
@@ -147,18 +120,10 @@ int fmmbem_ops::init() {
   d.rot_empty = ints + I_ZERO; d.n_rot_empty = 0;
   TRY(alloc(8, &rec));
   d.rot_cls_rec = rec;
-  {
-    // constant streams of the rotation kernels, every order they exist for
-    std::vector<double> all, ups, dns, one;
-    for (int p = 1; p <= kRotPmax; ++p) {
-      d.rot_tab_off[p - 1] = (int)all.size();
-      build_rot_stream(p, one); all.insert(all.end(), one.begin(), one.end());
-      shift_stream_off[p - 1] = (int)ups.size();
-      build_rot_stream(p, one, kRotM2M); ups.insert(ups.end(), one.begin(), one.end());
-      build_rot_stream(p, one, kRotL2L); dns.insert(dns.end(), one.begin(), one.end());
-    }
-    TRY(upload(all, &d.rot_tab)); TRY(upload(ups, &up_stream)); TRY(upload(dns, &dn_stream));
-  }
+  // constant streams of the rotation kernels, every order they exist for
+  ot = order_tables().get();
+  std::copy(ot->rot_off, ot->rot_off + kRotPmax, d.rot_tab_off);
+  TRY(upload(ot->rot_all, &d.rot_tab)); TRY(upload(ot->ups, &up_stream)); TRY(upload(ot->dns, &dn_stream));
   HIP_TRY(hipDeviceSynchronize());                     // the zero-fills ran on the NULL stream, which `stream` does not wait for
   return FMMBEM_OK;
 }
@@ -168,29 +133,15 @@ int fmmbem_ops::ensure_generic() {
   if (generic_ready) return FMMBEM_OK;
   DevicePlan& d = base;
   const int pm = p_max;
-  const ShiftOps ops = build_shift_ops(pm, T.A, kEps);
-  auto up_op = [&](const VOp& v, ShiftOpDev& o) -> int {
-    TRY(upload(v.src, &o.src)); TRY(upload(v.y, &o.y)); TRY(upload(v.real, &o.real));
-    TRY(upload(v.npiece, &o.npiece)); TRY(upload(v.piece, &o.piece));
-    o.T = v.T; o.V = v.V; o.maxp = v.maxp;
-    return FMMBEM_OK;
-  };
-  up_ops.resize(pm); down_ops.resize(pm);
-  for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], up_ops[p - 1])); TRY(up_op(ops.down_v[p - 1], down_ops[p - 1])); }
+  TRY(upload_shift_ops(mem, build_shift_ops(pm, T.A, kEps), up_ops, down_ops));
   TRY(alloc((size_t)d.p2_max, &up_tab)); TRY(alloc((size_t)d.p2_max, &down_tab));
   d.up_tab = up_tab; d.down_tab = down_tab;
   d.g_max = m2l_entries(pm);
   TRY(alloc((size_t)d.g_max, &gtab)); TRY(alloc((size_t)pm, &ztab));
   d.m2l_g = gtab; d.m2l_z = ztab;
-  std::vector<int32_t> lanes, scat, one;
-  for (int p = 1; p <= kPmax; ++p) {
-    if (!m2l_lane_map(p, one)) return fail(FMMBEM_ERR_INVALID, "internal: M2L lane dealing failed");
-    lanes.insert(lanes.end(), one.begin(), one.end());
-    m2l_scatter_map(p, one);
-    d.m2l_scat_off[p - 1] = (int)scat.size();
-    scat.insert(scat.end(), one.begin(), one.end());
-  }
-  TRY(upload(lanes, &d.m2l_lane)); TRY(upload(scat, &d.m2l_scat));
+  if (!ot->lanes_ok) return fail(FMMBEM_ERR_INVALID, "internal: M2L lane dealing failed");
+  std::copy(ot->scat_off, ot->scat_off + kPmax, d.m2l_scat_off);
+  TRY(upload(ot->lanes, &d.m2l_lane)); TRY(upload(ot->scat, &d.m2l_scat));
   TRY(alloc(1, &d_dev));
   HIP_TRY(hipDeviceSynchronize());
   generic_ready = true;
@@ -270,7 +221,7 @@ int fmmbem_ops::shift(int op, int p, int n_slots, const double* src, double* tgt
     else {
       RotWork w;
       w.src = ints + I_ZERO; w.cls = ints + I_ZERO; w.tgt = ints + I_ONE; w.item_ptr = ints + I_PTR01; w.n_items = 1;
-      w.rec = rec; w.stream = (op == 1 ? up_stream : dn_stream) + shift_stream_off[p - 1];
+      w.rec = rec; w.stream = (op == 1 ? up_stream : dn_stream) + ot->shift_off[p - 1];
       if (op == 1) HIP_TRY(launch_m2m_rot(d, w, p, stream)); else HIP_TRY(launch_l2l_rot(d, w, p, stream));
     }
   } else {
@@ -278,31 +229,19 @@ int fmmbem_ops::shift(int op, int p, int n_slots, const double* src, double* tgt
     d = base;                                          // ensure_generic filled in the tables' addresses
     TRY(set_slots(d, n_slots));
     const int pm = p_max;
-    const SphHost sp = cart2sph_host(tr);
     std::vector<cplx> h;
     if (op == 0) {
-      // Yh[r,c] = i^{|c|} EPS Y[r,c] / A[r,c] = Z^c gh[r,c]: the real part G (evalLocal to order 2 p_max at beta = 0) and the phases Z^m
-      const int R = 2 * pm;
-      harmonics(T, false, sp.rho, sp.alpha, 0.0, R, h);
       std::vector<double> g((size_t)d.g_max, 0.0);
-      for (int r = 0; r < R; ++r)
-        for (int cc = 0; cc <= r; ++cc) g[(size_t)r * (r + 1) / 2 + cc] = h[(size_t)r * (r + 1) / 2 + cc].real() * kEps / T.A[r * r + r + cc];
       std::vector<cplx> z((size_t)pm);
-      for (int m = 0; m < pm; ++m) z[(size_t)m] = i_pow(m) * std::exp(cplx(0, 1) * double(m * sp.beta));
+      m2l_class_rows(T, tr, pm, h, g.data(), z.data());
       HIP_TRY(hipMemcpy(gtab, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(ztab, z.data(), z.size() * sizeof(cplx), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(d_dev, &d, sizeof(DevicePlan), hipMemcpyHostToDevice));
       HIP_TRY(launch_mh_prep(d, p, stream));
       HIP_TRY(launch_m2l(d, d_dev, p, stream));
     } else {
-      // M2M: evalMultipole(rho, alpha, -beta) of the translation (LaplaceSpherical.hpp:253-254); L2L: (rho, alpha, +beta) (:383-384)
-      harmonics(T, true, sp.rho, sp.alpha, op == 1 ? -sp.beta : sp.beta, pm, h);
       std::vector<cplx> tab;
-      for (int n = 0; n < pm; ++n)
-        for (int m = -n; m <= n; ++m) {
-          const cplx y = h[(size_t)n * (n + 1) / 2 + std::abs(m)];
-          tab.push_back(m < 0 ? std::conj(y) : y);
-        }
+      shift_class_table(T, tr, op == 1, pm, h, tab);
       HIP_TRY(hipMemcpy(op == 1 ? up_tab : down_tab, tab.data(), tab.size() * sizeof(cplx), hipMemcpyHostToDevice));
       if (op == 1) HIP_TRY(launch_m2m_level(d, up_ops[p - 1], p, 0, 1, stream));
       else HIP_TRY(launch_l2l_level(d, down_ops[p - 1], p, 0, 1, stream));

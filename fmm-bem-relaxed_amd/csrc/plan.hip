@@ -12,23 +12,23 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
-#include <future>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/fmmbem.h"
 #include "blockinv.hpp"
+#include "device_allocs.hpp"
 #include "device_launch.hpp"
 #include "host_plan.hpp"
 #include "host_tables.hpp"
 #include "launch_choice.hpp"
 #include "m2l_layout.hpp"
 #include "m2l_rot.hpp"
+#include "plan_layout.hpp"
 #include "shift_ops.hpp"
 #include "status.hpp"
 
@@ -62,70 +62,6 @@ double now_ms() {
 }
 
 }  // namespace
-
-// the class tables of a plan are a few thousand independent rows of harmonics: a few threads take them in contiguous shares
-template <class F>
-static void parallel_rows(int64_t n, int64_t min_per_thread, F&& body) {
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency())), n / std::max<int64_t>(1, min_per_thread)));
-  if (nt <= 1) { body((int64_t)0, n); return; }
-  host_parallel(nt, [&](int t) { body(n * t / nt, n * (t + 1) / nt); });
-}
-
-// Tables that depend on the expansion ORDER alone -- the constant streams of the three rotation kernels, the lanes' tables of the
-// one-pair-per-wavefront shifts, the lane and scatter maps of the double-sum M2L: ~30 ms of host arithmetic that used to sit on
-// every plan's critical path.  Built once per process, on a thread of their own that fmmbem_plan_create starts BEFORE it builds
-// the tree; to_device waits for them where it uploads them.
-struct OrderTables {
-  std::vector<double> rot_all, ups, dns;
-  int rot_off[kRotPmax] = {}, shift_off[kRotPmax] = {};
-  std::vector<double> urc, uxc, drc, dxc;
-  std::vector<int32_t> urs, uxs, drs, dxs;
-  size_t sl_rot_off[kShiftLanesPmax + 1] = {}, sl_ax_off[kShiftLanesPmax + 1] = {};
-  std::vector<int32_t> lanes, scat;
-  int scat_off[kPmax] = {};
-  bool lanes_ok = true;
-};
-static std::shared_ptr<const OrderTables> build_order_tables() {
-  auto t = std::make_shared<OrderTables>();
-  std::vector<double> one;
-  for (int q = 1; q <= kRotPmax; ++q) {
-    t->rot_off[q - 1] = (int)t->rot_all.size();
-    build_rot_stream(q, one); t->rot_all.insert(t->rot_all.end(), one.begin(), one.end());
-    t->shift_off[q - 1] = (int)t->ups.size();
-    build_rot_stream(q, one, kRotM2M); t->ups.insert(t->ups.end(), one.begin(), one.end());
-    // both shifts have the same number of axial terms: one offset table serves the two streams
-    build_rot_stream(q, one, kRotL2L); t->dns.insert(t->dns.end(), one.begin(), one.end());
-  }
-  ShiftLaneTables lt;
-  for (int q = 1; q <= kShiftLanesPmax; ++q) {
-    t->sl_rot_off[q] = t->urc.size(); t->sl_ax_off[q] = t->uxc.size();
-    build_shift_lane_tables(q, kRotM2M, lt);
-    t->urc.insert(t->urc.end(), lt.rot_c.begin(), lt.rot_c.end()); t->urs.insert(t->urs.end(), lt.rot_s.begin(), lt.rot_s.end());
-    t->uxc.insert(t->uxc.end(), lt.ax_c.begin(), lt.ax_c.end()); t->uxs.insert(t->uxs.end(), lt.ax_s.begin(), lt.ax_s.end());
-    build_shift_lane_tables(q, kRotL2L, lt);
-    t->drc.insert(t->drc.end(), lt.rot_c.begin(), lt.rot_c.end()); t->drs.insert(t->drs.end(), lt.rot_s.begin(), lt.rot_s.end());
-    t->dxc.insert(t->dxc.end(), lt.ax_c.begin(), lt.ax_c.end()); t->dxs.insert(t->dxs.end(), lt.ax_s.begin(), lt.ax_s.end());
-  }
-  std::vector<int32_t> m;
-  for (int p = 1; p <= kPmax; ++p) {
-    if (!m2l_lane_map(p, m)) t->lanes_ok = false;
-    t->lanes.insert(t->lanes.end(), m.begin(), m.end());
-    m2l_scatter_map(p, m);
-    t->scat_off[p - 1] = (int)t->scat.size();
-    t->scat.insert(t->scat.end(), m.begin(), m.end());
-  }
-  return t;
-}
-static std::shared_future<std::shared_ptr<const OrderTables>> order_tables() {
-  static std::mutex mu;
-  static std::shared_future<std::shared_ptr<const OrderTables>> fut;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!fut.valid()) fut = std::async(std::launch::async, build_order_tables).share();
-  return fut;
-}
-
-// (first, items, pairs) of one level launch of the rotation kernels (kernels_m2l_rot.hip with FMMBEM_ROT_OP = 1, 2)
-struct ShiftRot { int item_first = 0, n_items = 0, pairs = 0, level_boxes = 0, pair_first = 0, unit_first = 0, n_units = 0; };   // level_boxes: boxes of the child level in the WHOLE tree; units: parents (M2M) / pairs (L2L) of the one-pair-per-wavefront kernel
 
 // What one direction of the tree, M2M up or L2L down, reads on the device, and its level launches
 struct ShiftSide {
@@ -186,15 +122,8 @@ struct PlanGeometry {
 struct PlanShared {
   HostPlan hp;
   PlanGeometry geo;
-  std::vector<void*> allocs;
-  int device = 0;
-  bool on_device = false;
+  DeviceAllocs allocs;                                         // (freed with the last plan, on the device they name)
   uint64_t fingerprint[2] = {0, 0};                            // of the vertex bytes (original order), 0 0: not taken
-  ~PlanShared() {
-    if (!on_device) return;
-    DeviceGuard guard(device);
-    for (void* p : allocs) (void)hipFree(p);
-  }
 };
 
 // The flag side of a plan's DevicePlan: what to_device_bc_begin / to_device_bc_end / build_side_lists decide and allocate, with
@@ -227,8 +156,8 @@ struct fmmbem_plan {
   const DevicePlan* d_dev = nullptr;                           // copy of d in device memory
   bool on_device = false;
   bool has_bc[2] = {false, false};                             // boundary-condition flags present among THIS plan's panels
-  std::vector<void*> allocs;                                   // what this plan alone owns: everything that depends on the flags
-  std::vector<void*>* alloc_list = &allocs;                    // where upload() / alloc() record: shared->allocs (geometry creation) or allocs
+  DeviceAllocs allocs;                                         // what this plan alone owns: everything that depends on the flags
+  DeviceAllocs* mem = &allocs;                                 // where upload() / alloc() record: shared->allocs (geometry creation) or allocs
   // every plan is built on a shared block: a new one (fmmbem_plan_create*), a live one (like()), a shard's (the handle of a
   // multi-device plan).  Never copied: what a plan owns has one owner.
   explicit fmmbem_plan(std::shared_ptr<PlanShared> sh) : shared(std::move(sh)), hp(shared->hp), g(shared->geo) {}
@@ -339,27 +268,11 @@ struct fmmbem_plan {
   int grad_alloc();
   int run_gradient(int p, const double* d_x, double* d_g, hipStream_t s);
 
-  template <class T, class A>
-  int upload(const std::vector<T, A>& v, const T** out) {
-    *out = nullptr;
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc(&p, bytes));
-    alloc_list->push_back(p);
-    if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T*>(p);
-    return FMMBEM_OK;
-  }
+  template <class V, class T>
+  int upload(const V& v, const T** out) { return mem->upload(v, out); }
   template <class T>
-  int alloc(size_t count, T** out, bool zero) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    HIP_TRY(hipMalloc(&p, bytes));
-    alloc_list->push_back(p);
-    if (zero) HIP_TRY(hipMemset(p, 0, bytes));
-    *out = static_cast<T*>(p);
-    return FMMBEM_OK;
-  }
+  int alloc(size_t count, T** out, bool zero) { return mem->alloc(count, out, zero); }
+  LayoutOptions layout_options() const;                      // the one place the layouts' options are filled in
   const double* create_vertices = nullptr;                   // fmmbem_plan_create: the caller's vertices while to_device_near runs (panel set-up on the device)
   // Geometry creation, the only writers of a PlanGeometry (-> shared).  to_device_near: the near field's share -- panels, leaves,
   // near lists, and the flag side's assembly LAUNCHED (to_device_bc_begin) -- as soon as the host plan holds them
@@ -395,7 +308,7 @@ struct fmmbem_plan {
     if (on_device) {
       DeviceGuard guard(opts.device);
       block_inverse_free();
-      for (void* p : allocs) (void)hipFree(p);
+      allocs.free_all();
       for (auto& e : ev) if (e) (void)hipEventDestroy(e);
       for (hipEvent_t e : asm_ev) if (e) (void)hipEventDestroy(e);      // a creation that failed between to_device_bc_begin and _end
       for (auto& ge : graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
@@ -405,24 +318,6 @@ struct fmmbem_plan {
     }
   }
 };
-
-// Work items largest first, equal ones in their given order: a stable radix sort on the (descending) key -- the comparison
-// sort of 60 000 items took 4-5 ms of every plan build
-template <class T, class KeyFn>
-static void stable_sort_largest_first(std::vector<T>& v, KeyFn key) {
-  if (v.size() < 2) return;
-  uint64_t kmax = 0;
-  for (const T& x : v) kmax = std::max<uint64_t>(kmax, (uint64_t)key(x));
-  std::vector<T> tmp(v.size());
-  constexpr int kBits = 11, kB = 1 << kBits;
-  for (int shift = 0; shift < 64 && (kmax >> shift) != 0; shift += kBits) {
-    size_t count[kB + 1] = {0};
-    for (const T& x : v) ++count[(((kmax - (uint64_t)key(x)) >> shift) & (kB - 1)) + 1];
-    for (int b = 0; b < kB; ++b) count[b + 1] += count[b];
-    for (const T& x : v) tmp[count[((kmax - (uint64_t)key(x)) >> shift) & (kB - 1)]++] = x;
-    v.swap(tmp);
-  }
-}
 
 // rot_tgt of a plan whose rotation pairs are its CSR lists: pair i belongs to the box b with m2l_ptr[b] <= i < m2l_ptr[b + 1]
 __global__ void expand_csr_targets_kernel(const int* __restrict__ ptr, int nboxes, int* __restrict__ tgt) {
@@ -461,6 +356,7 @@ int fmmbem_plan::open_device() {
   if (opts.device < 0 || opts.device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
   DEVICE_SCOPE(opts.device);
   on_device = true;
+  allocs.device = opts.device;
   HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
   ev.assign((size_t)kRing * 2 * kStages, nullptr);
   for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
@@ -468,12 +364,27 @@ int fmmbem_plan::open_device() {
   return FMMBEM_OK;
 }
 
+// what plan_layout.hpp takes from the options, the switches and the kernels' translation units
+LayoutOptions fmmbem_plan::layout_options() const {
+  LayoutOptions o;
+  o.dof = opts.kernel == FMMBEM_KERNEL_STOKES_BEM ? 3 : 1;
+  o.sparse_local = opts.sparse_local != 0;
+  o.treecode = treecode();
+  o.targets = targets;
+  o.near_stream_fraction = sw::near_stream_fraction(opts.near_stream_fraction);
+  o.stokes_sym = sw::stokes_sym();
+  o.m2l_rot = sw::m2l_rot();
+  o.near_f32_max_p = opts.near_f32_max_p;
+  o.rcg_item_rows = rcg_item_rows();
+  o.l2p_group_leaves = l2p_group_leaves(opts.kernel);
+  return o;
+}
+
 int fmmbem_plan::to_device_near(PlanGeometry& g) {
   TRY(open_device());
   DEVICE_SCOPE(opts.device);
-  shared->on_device = true;                            // from here on a creation that fails (an allocation, say the float near
-  shared->device = opts.device;                        // field's copy) frees the geometry's uploads with the plan: nothing stays behind
-  alloc_list = &shared->allocs;
+  shared->allocs.device = opts.device;                 // a creation that fails from here on (an allocation, say the float near field's
+  mem = &shared->allocs;                               // copy) frees the geometry's uploads with the plan: nothing stays behind
   BuildTrace mark;
   const HarmonicTables T;
   const int nl = hp.nleaves(), nb = hp.nboxes, pm = hp.opt.p_max;
@@ -542,237 +453,34 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
   }
 
   mark("panels: upload + geometry");
-  // leaves and the near block structure
-  std::vector<int> leaf_row0(nl), leaf_nrows(nl), near_stride(nl), run_row0, run_off;
-  std::vector<int64_t> near_off(nl, 0), run_ptr(nl + 1, 0);
-  int64_t total = 0;
-  int max_cols = 2, max_runs = 1;
-  for (int l = 0; l < nl; ++l) {
-    const int b = hp.leaf_box[l];
-    leaf_nrows[l] = hp.box_body_end[b] - hp.box_body_begin[b];
+  // leaves, the near block structure, the work items of every near-field form: decided in plan_layout.hpp, uploaded here
+  NearLayout L = near_layout(hp, layout_options());
+  g.hybrid = L.hybrid; g.near_recomputed_pairs = L.near_recomputed_pairs;
+  d.max_runs = L.max_runs; d.max_ncols = L.max_cols;
+  if (!layout_options().m2l_rot) g.rot_max = 0;
+  g.near_total_doubles = L.near_total_doubles; g.sym_total_doubles = L.sym_total_doubles;      // allocated per plan (to_device_bc_begin)
+  g.near_f32_floats = L.near_f32_floats; g.near_bytes = L.near_bytes;
+  TRY(upload(L.leaf_row0, &d.leaf_row0)); TRY(upload(L.leaf_nrows, &d.leaf_nrows)); TRY(upload(hp.leaf_box, &d.leaf_box));
+  TRY(upload(L.run_ptr, &d.near_ptr)); TRY(upload(L.run_row0, &d.near_run_row0)); TRY(upload(L.run_off, &d.near_run_off));
+  TRY(upload(hp.near_ncols, &d.near_ncols)); TRY(upload(L.near_stride, &d.near_stride)); TRY(upload(L.near_off, &d.near_off));
+  d.near_nitems = (int)L.items.size();
+  TRY(upload(L.items, &d.near_items)); TRY(upload(L.recs, &d.near_recs));
+  if (L.stokes_sym) {
+    d.sym_nitems = (int)L.sym_items.size();
+    TRY(upload(L.sym_items, &d.sym_items)); TRY(upload(L.sym_off, &d.near_sym_off));
   }
-  // Hybrid near field: the leaves that keep NO matrix.  Chosen on the WHOLE tree (every shard builds the same tree and reaches the
-  // same verdict for a leaf, so a shard's rows carry the bits of the single plan): the leaves with the most rows first -- a
-  // recomputed pair costs the same arithmetic wherever it sits, but the source panel's 128 bytes are read once per item and
-  // amortised over the item's rows -- until their pairs make up 1 - near_stream_fraction of all near pairs.
-  std::vector<uint8_t> rec(nl, 0);
-  std::vector<NearItem> near_recs_host;
-  std::vector<int> near_recs_leaf;
-  {
-    double f = sw::near_stream_fraction(opts.near_stream_fraction);
-    bool rule_ok = hp.rule.n <= (dof == 3 ? 4 : 3);               // the far-regime points of a source live in registers
-    for (int q = 2; q < hp.rule.n; ++q) rule_ok = rule_ok && hp.rule.w[q] == hp.rule.w[1];      // K = 1, 3, 4: two distinct weights at most
-    // runs of consecutive source rows per leaf (the pipelined kernels prefetch an item's run descriptors one per thread): counted
-    // by the shares of a few threads, as the runs themselves are filled in below
-    std::vector<int> nruns_of(nl, 0);
-    int max_runs_owned = 1;
-    parallel_rows(nl, 4096, [&](int64_t l0, int64_t l1) {
-      for (int64_t l = l0; l < l1; ++l) {
-        int c = 0;
-        for (int64_t i = hp.near_ptr[l]; i < hp.near_ptr[l + 1]; ++i) c += i == hp.near_ptr[l] || hp.near_src[i - 1] + 1 != hp.near_src[i];
-        nruns_of[l] = c;
-      }
-    });
-    for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) max_runs_owned = std::max(max_runs_owned, nruns_of[l]);
-    for (int l = 0; l < nl; ++l) run_ptr[l + 1] = run_ptr[l] + nruns_of[l];
-    g.hybrid = f < 1.0 && opts.sparse_local && hp.opt.evaluator == 0 && opts.evaluator != FMMBEM_EVAL_TREECODE && rule_ok && (dof == 3 ? sw::stokes_sym() : near_pipe_ok(dof, max_runs_owned));
-    if (g.hybrid) {
-      if (!(f >= 0.0)) f = 0.0;
-      std::vector<int> order(nl);
-      for (int l = 0; l < nl; ++l) order[l] = l;
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return leaf_nrows[a] > leaf_nrows[b]; });
-      double all = 0;
-      for (int l = 0; l < nl; ++l) all += (double)leaf_nrows[l] * hp.near_ncols[l];
-      double acc = 0;
-      for (int l : order) {
-        if (acc >= (1.0 - f) * all) break;
-        if (hp.near_ncols[l] > 8192) continue;        // a coarse leaf of an adaptive tree (10^4 columns): one item would run alone at the end
-        if (nruns_of[l] > 256) continue;
-        rec[l] = 1;
-        acc += (double)leaf_nrows[l] * hp.near_ncols[l];
-      }
-      g.near_recomputed_pairs = 0;
-      for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) if (rec[l]) g.near_recomputed_pairs += (int64_t)leaf_nrows[l] * hp.near_ncols[l];
-    }
+  if (L.f32) {
+    TRY(upload(L.off32, &d.near_f32_off));
+    if (dof == 1) TRY(upload(L.recs32, &d.near_recs_f32));
   }
-  run_row0.resize((size_t)run_ptr[nl]); run_off.resize((size_t)run_ptr[nl]);
-  parallel_rows(nl, 4096, [&](int64_t l0, int64_t l1) {
-    for (int64_t l = l0; l < l1; ++l) {
-      const int b = hp.leaf_box[l];
-      leaf_row0[l] = hp.box_body_begin[b];
-      near_stride[l] = (dof * hp.near_ncols[l] + 1) & ~1;      // in unknowns (dof per panel), rows 16-B aligned
-      // source leaves are ascending; leaves with consecutive indices own adjacent rows -> one run
-      int col = 0;
-      int64_t k = run_ptr[l];
-      for (int64_t i = hp.near_ptr[l]; i < hp.near_ptr[l + 1]; ++i) {
-        const int sl = hp.near_src[i], sb = hp.leaf_box[sl];
-        if (i == hp.near_ptr[l] || hp.near_src[i - 1] + 1 != sl) {
-          run_row0[(size_t)k] = hp.box_body_begin[sb];
-          run_off[(size_t)k] = col;
-          ++k;
-        }
-        col += hp.box_body_end[sb] - hp.box_body_begin[sb];
-      }
-    }
-  });
-  for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
-    near_off[l] = total;
-    if (!rec[l]) total += (int64_t)dof * leaf_nrows[l] * near_stride[l];
-    max_cols = std::max(max_cols, near_stride[l]);
-    max_runs = std::max(max_runs, (int)(run_ptr[l + 1] - run_ptr[l]));
-  }
-  d.max_runs = max_runs;
-  if (!sw::m2l_rot()) g.rot_max = 0;
-  d.max_ncols = max_cols;
-  g.near_bytes = total * (int64_t)sizeof(double);
-  TRY(upload(leaf_row0, &d.leaf_row0)); TRY(upload(leaf_nrows, &d.leaf_nrows)); TRY(upload(hp.leaf_box, &d.leaf_box));
-  TRY(upload(run_ptr, &d.near_ptr)); TRY(upload(run_row0, &d.near_run_row0)); TRY(upload(run_off, &d.near_run_off));
-  TRY(upload(hp.near_ncols, &d.near_ncols)); TRY(upload(near_stride, &d.near_stride)); TRY(upload(near_off, &d.near_off));
-  {
-    // SpMV work items: a leaf's row block, cut into row ranges of <= kItemBytes (256 KB) so that no workgroup is left
-    // streaming one coarse leaf alone (two-sphere N=1M: one leaf is 58 rows x 16 031 columns = 7.4 MB against
-    // a mean of 75 KB), dealt round-robin to the persistent workgroups largest first.  Ranges shorter than 8
-    // rows are processed with the columns split over the wavefronts instead of the rows.
-    constexpr int64_t kItemBytes = 256 << 10;          // two-sphere N = 1M (near ms): 64 KB 0.81, 128 0.72, 192 0.74, 256 0.705, 320 0.735, 384 0.72, 512 0.72
-    struct Item { int leaf, r0, nr; int64_t bytes; };
-    std::vector<Item> items;
-    // (a matrix-free plan runs the sweeps of kernels_near.hip over the same items, which count PANEL rows and pairs whatever
-    // the number of unknowns per panel)
-    const int idof = opts.sparse_local ? dof : 1;
-    for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
-      const int nr = idof * leaf_nrows[l];
-      const int64_t row_bytes = opts.sparse_local ? (int64_t)near_stride[l] * 8 : (int64_t)hp.near_ncols[l] * 8;
-      if (nr == 0 || row_bytes == 0) continue;
-      if (g.hybrid && (dof == 3 || rec[l])) continue;     // hybrid plans: Stokes builds its stream items below; a recomputed leaf has none
-      int per = (int)std::max<int64_t>(1, kItemBytes / row_bytes);
-      if (per >= 8) per &= ~7; else per = std::min(4, nr);
-      const int cnt = (nr + per - 1) / per;
-      per = (nr + cnt - 1) / cnt;
-      if (per >= 8) per = (per + 7) & ~7;
-      for (int r0 = 0; r0 < nr; r0 += per) { const int k = std::min(per, nr - r0); items.push_back({l, r0, k, k * row_bytes}); }
-    }
-    stable_sort_largest_first(items, [](const Item& a) { return a.bytes; });
-    std::vector<int4> packed(items.size());
-    for (size_t i = 0; i < items.size(); ++i) packed[i] = make_int4(items[i].leaf, items[i].r0, items[i].nr, items[i].nr < 8);
-    d.near_nitems = (int)packed.size();
-    TRY(upload(packed, &d.near_items));
-    std::vector<NearItem> recs(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-      const Item& it = items[i];
-      NearItem& q = recs[i];
-      q.val_off = near_off[it.leaf] + (int64_t)it.r0 * near_stride[it.leaf];
-      q.run_begin = run_ptr[it.leaf];
-      q.nruns = (int)(run_ptr[it.leaf + 1] - run_ptr[it.leaf]);
-      q.yrow = dof * leaf_row0[it.leaf] + it.r0;
-      q.nrows = it.nr;
-      q.ncols = dof * hp.near_ncols[it.leaf];
-      q.stride = near_stride[it.leaf];
-      q.colsplit = it.nr < 8;
-      q.pad[0] = q.pad[1] = 0;
-    }
-    TRY(upload(recs, &d.near_recs));
-    if (opts.near_f32_max_p > 0) {                      // the float near field lays the same items out again (below)
-      near_recs_host = recs;
-      near_recs_leaf.resize(items.size());
-      for (size_t i = 0; i < items.size(); ++i) near_recs_leaf[i] = items[i].leaf;
-    }
-  }
-  const bool stokes_sym = dof == 3 && opts.sparse_local && sw::stokes_sym();
-  g.near_total_doubles = (opts.sparse_local && !stokes_sym) ? total : 0;      // allocated in to_device_bc; matrix-free mode keeps no matrix
-  if (!g.near_total_doubles) g.near_bytes = 0;
-  {
-    // Stokes: the near blocks in their symmetric 6-value form, the only copy (FMMBEM_STOKES_SYM=0: the 9-value rows instead)
-    if (stokes_sym) {
-      std::vector<int64_t> sym_off(nl, 0);
-      int64_t sym_total = 0;
-      constexpr int64_t kItemBytes = 512 << 10;        // red blood cell N = 524 288 (near ms): 128 KB 2.06-2.08, 256 KB 2.06-2.09, 512 KB 2.01-2.03
-      struct Item { int leaf, r0, nr; int64_t bytes; };
-      std::vector<Item> items;
-      for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
-        const int nr = leaf_nrows[l], ncp = hp.near_ncols[l];
-        sym_off[l] = sym_total;
-        if (rec[l]) continue;                           // hybrid: no block, no stream item
-        sym_total += (int64_t)6 * nr * ncp;
-        const int64_t row_bytes = (int64_t)48 * ncp;
-        if (nr == 0 || row_bytes == 0) continue;
-          int per = (int)std::max<int64_t>(1, kItemBytes / row_bytes);
-        if (per >= 8) per &= ~7; else per = std::min(4, nr);
-        const int cnt = (nr + per - 1) / per;
-        per = (nr + cnt - 1) / cnt;
-        if (per >= 8) per = (per + 7) & ~7;
-        for (int r0 = 0; r0 < nr; r0 += per) { const int k = std::min(per, nr - r0); items.push_back({l, r0, k, k * row_bytes}); }
-      }
-      stable_sort_largest_first(items, [](const Item& a) { return a.bytes; });
-      std::vector<int4> packed(items.size());
-      for (size_t i = 0; i < items.size(); ++i) packed[i] = make_int4(items[i].leaf, items[i].r0, items[i].nr, items[i].nr < 8);
-      d.sym_nitems = (int)packed.size();
-      TRY(upload(packed, &d.sym_items));
-      TRY(upload(sym_off, &d.near_sym_off));
-      g.sym_total_doubles = std::max<int64_t>(sym_total, 1);          // allocated in to_device_bc
-      g.near_bytes = sym_total * (int64_t)sizeof(double);
-      g.sym_off_host = sym_off;
-    }
-  }
-  // Float near field: the layout of the copy (device_plan.hpp near_f32) -- per leaf offsets, and for the pipelined Laplace kernel
-  // the item records again with the offsets and strides of the float rows (near_recs itself is what the FP64 kernel reads)
-  g.near_f32_floats = 0;
-  // The option's premise is that the rounding of the entries hides under the truncation error of the far field.  An FMM plan whose
-  // leaves are ALL near one another (every leaf pair is a P2P pair: no M2L anywhere) has no far field: its result is exact at every
-  // order, relaxation changes nothing, and there is nothing for the float error to hide under -- such a plan (a few hundred panels)
-  // takes the option as 0.  The LOCAL / BLOCK_DIAGONAL evaluators are near-field operators by definition and keep it.
-  const bool f32_premise = hp.opt.evaluator != 0 || hp.near_ptr[nl] < (int64_t)nl * nl;
-  if (opts.near_f32_max_p > 0 && opts.sparse_local && !g.hybrid && !targets && hp.opt.shard_world <= 1 && g.near_bytes > 0 &&
-      f32_premise && near_f32_ok(dof, max_runs, stokes_sym)) {
-    std::vector<int64_t> off32(nl, 0);
-    int64_t total32 = 0;
-    for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
-      off32[l] = total32;
-      total32 += dof == 3 ? (int64_t)12 * leaf_nrows[l] * ((hp.near_ncols[l] + 1) / 2) : (int64_t)leaf_nrows[l] * ((hp.near_ncols[l] + 3) & ~3);
-    }
-    TRY(upload(off32, &d.near_f32_off));
-    if (dof == 1) {
-      std::vector<NearItem> recs32(near_recs_host);
-      for (NearItem& q : recs32) {
-        const int l = near_recs_leaf[(size_t)(&q - recs32.data())], s32 = (hp.near_ncols[l] + 3) & ~3;
-        q.val_off = off32[l] + (q.val_off - near_off[l]) / near_stride[l] * s32;
-        q.stride = s32;
-      }
-      TRY(upload(recs32, &d.near_recs_f32));
-    }
-    g.near_f32_floats = total32;
-  }
-  if (g.hybrid) {
-    // recompute items: ranges of <= 20 (Stokes: four wavefronts x five rows) or 32 (Laplace: x eight) panel rows of the recomputed
-    // leaves (kernels_near.hip near_recompute3 / near_recompute1)
-    struct RItem { int leaf, r0, nr; int64_t pairs; };
-    std::vector<RItem> ritems;
-    for (int l = hp.leaf_begin; l < hp.leaf_end; ++l) {
-      const int nr = leaf_nrows[l], ncp = hp.near_ncols[l];
-      if (!rec[l] || nr == 0 || ncp == 0) continue;
-      // Stokes, sources straight into LDS (near_recompute3g): a whole leaf of up to 60 rows is one item -- its source panels are
-      // loaded once; otherwise four wavefronts x five (Laplace: eight) rows
-      const int cap = dof == 3 ? rcg_item_rows() : 32;
-        const int cnt = (nr + cap - 1) / cap;
-      const int per = (nr + cnt - 1) / cnt;          // dealt evenly: the kernel gives a wavefront ceil(rows / 4) of an item's rows
-      for (int r0 = 0; r0 < nr; r0 += per) { const int k = std::min(per, nr - r0); ritems.push_back({l, r0, k, (int64_t)k * ncp}); }
-    }
-    stable_sort_largest_first(ritems, [](const RItem& a) { return a.pairs; });
+  if (L.hybrid) {
     // the side listing (mf_sweep COUNT / FILL) walks d.near_items: the recompute items, panel rows
-    std::vector<int4> rpacked(ritems.size());
-    std::vector<RcItem> rrecs(ritems.size());
-    for (size_t i = 0; i < ritems.size(); ++i) {
-      const RItem& it = ritems[i];
-      rpacked[i] = make_int4(it.leaf, it.r0, it.nr, 0);
-      RcItem& q = rrecs[i];
-      q.prow0 = leaf_row0[it.leaf] + it.r0; q.nrows = it.nr; q.ncp = hp.near_ncols[it.leaf];
-      q.run_begin = run_ptr[it.leaf]; q.nruns = (int)(run_ptr[it.leaf + 1] - run_ptr[it.leaf]); q.leaf = it.leaf; q.pad = 0;
-    }
-    d.near_nitems_stream = dof == 1 ? d.near_nitems : 0;   // (Laplace: the items built above are the streamed ones, near_recs)
-      d.near_nitems = (int)rpacked.size();
-    TRY(upload(rpacked, &d.near_items));
-    d.rc_nitems = (int)rrecs.size();
-    TRY(upload(rrecs, &d.rc_items));
-    TRY(upload(rec, &d.near_rec));
+    d.near_nitems_stream = dof == 1 ? d.near_nitems : 0;   // (Laplace: the items uploaded above are the streamed ones, near_recs)
+    d.near_nitems = (int)L.rc_items.size();
+    TRY(upload(L.rc_items, &d.near_items));
+    d.rc_nitems = (int)L.rc_recs.size();
+    TRY(upload(L.rc_recs, &d.rc_items));
+    TRY(upload(L.rec, &d.near_rec));
     if (dof == 3) {
       // packed per-panel records of near_recompute3g_kernel (its sources go straight into LDS, 16 bytes at a time)
       double *rs = nullptr, *rn = nullptr;
@@ -782,29 +490,13 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
       d.rc_src = rs; d.rc_nrm = rn;
     }
   }
-  g.near_rec_host = rec;
-  g.near_off_host = near_off;
+  g.near_rec_host = std::move(L.rec); g.near_off_host = std::move(L.near_off); g.sym_off_host = std::move(L.sym_off);      // (introspection)
 
   mark("near lists + items");
   // boxes, expansions, tables
   TRY(upload(hp.box_center, &d.box_center));
   TRY(upload(T.A, &d.tabA)); TRY(upload(T.invA, &d.tabInvA)); TRY(upload(T.pref, &d.tabPref));
-  {
-    // per-step constants of the harmonic recurrences in the m-major order P2M visits (n,m) at order p:
-    // pref = sqrt((n-m)!/(n+m)!) and the Legendre step P_{n+1}^m = c1 x P_n^m - c2 P_{n-1}^m (c1 = 2m+1, c2 = 0 at n = m)
-    const int smax = kPmax * (kPmax + 1) / 2;
-    std::vector<double> st((size_t)kPmax * (smax + 1) * 4, 0.0);
-    for (int p = 1; p <= kPmax; ++p) {
-      double* o = st.data() + (size_t)(p - 1) * (smax + 1) * 4;
-      for (int m = 0; m < p; ++m)
-        for (int n = m; n < p; ++n, o += 4) {
-          o[0] = T.pref[n * n + n + m];
-          o[1] = n == m ? (double)(2 * m + 1) : (double)(2 * n + 1) * (1.0 / (n - m + 1));
-          o[2] = n == m ? 0.0 : (double)(n + m) * (1.0 / (n - m + 1));
-        }
-    }
-    TRY(upload(st, &d.tabStep));
-  }
+  TRY(upload(step_table(T), &d.tabStep));
 
   mark("boxes + harmonic tables");
   return to_device_bc_begin(hp.panels.bc.data());    // the near-matrix assembly runs on the GPU from here, under the host work that follows
@@ -812,44 +504,23 @@ int fmmbem_plan::to_device_near(PlanGeometry& g) {
 
 int fmmbem_plan::to_device_far(PlanGeometry& g) {
   DEVICE_SCOPE(opts.device);
-  alloc_list = &shared->allocs;
+  mem = &shared->allocs;
   BuildTrace mark;
   const HarmonicTables T;
   const int nb = hp.nboxes, pm = hp.opt.p_max;
   DevicePlan& d = g.gd;
-  // far-field lists
-  std::vector<int> p2m_leaf, l2p_leaf;
-  for (int b : hp.p2m_leaves) p2m_leaf.push_back(hp.box_leaf_index[b]);
-  for (int b : hp.l2p_leaves) l2p_leaf.push_back(hp.box_leaf_index[b]);
-  d.n_p2m = (int)p2m_leaf.size(); d.n_l2p = (int)l2p_leaf.size();
-  TRY(upload(p2m_leaf, &d.p2m_leaf)); TRY(upload(l2p_leaf, &d.l2p_leaf));
-  {
-    // L2P work groups: a leaf of this tree holds ~19 panels, a third of a wavefront; consecutive leaves are packed until
-    // 64 rows or 8 leaves (Stokes: 4) (a leaf with more than 64 panels is a group of its own)
-    std::vector<int> grp(1, 0);
-    int rows = 0;
-    const int max_leaves = l2p_group_leaves(d.kernel);
-    for (size_t i = 0; i < l2p_leaf.size(); ++i) {
-      const int nr = hp.box_body_end[hp.leaf_box[l2p_leaf[i]]] - hp.box_body_begin[hp.leaf_box[l2p_leaf[i]]];
-      const int in_group = (int)i - grp.back();
-      if (in_group > 0 && (rows + nr > 64 || in_group == max_leaves)) { grp.push_back((int)i); rows = 0; }
-      rows += nr;
-    }
-    grp.push_back((int)l2p_leaf.size());
-    d.n_l2p_grp = l2p_leaf.empty() ? 0 : (int)grp.size() - 1;
-    TRY(upload(grp, &d.l2p_grp));
-    int64_t covered = 0;                               // the L2P leaves are distinct leaves: all rows are theirs when the counts agree
-    for (int lf : l2p_leaf) covered += hp.box_body_end[hp.leaf_box[lf]] - hp.box_body_begin[hp.leaf_box[lf]];
-    g.l2p_scatter = d.kernel == FMMBEM_KERNEL_LAPLACE_BEM && !targets && hp.opt.shard_world <= 1 && d.n_l2p > 0 && covered == (int64_t)hp.n;
-  }
+  // every list, record and class table of the far field: decided in plan_layout.hpp, uploaded here
+  FarLayout F = far_layout(hp, T, layout_options());
+  d.n_p2m = (int)F.p2m_leaf.size(); d.n_l2p = (int)F.l2p_leaf.size();
+  TRY(upload(F.p2m_leaf, &d.p2m_leaf)); TRY(upload(F.l2p_leaf, &d.l2p_leaf));
+  d.n_l2p_grp = F.n_l2p_grp;
+  TRY(upload(F.l2p_grp, &d.l2p_grp));
+  g.l2p_scatter = F.l2p_scatter;
   TRY(upload(hp.m2m_parents, &d.m2m_parent)); TRY(upload(hp.l2l_children, &d.l2l_child));
   TRY(upload(hp.box_child_begin, &d.box_child_begin)); TRY(upload(hp.box_child_end, &d.box_child_end));
   TRY(upload(hp.box_parent, &d.box_parent));
-  auto level_launches = [](const std::vector<int>& ptr, std::vector<std::pair<int, int>>& out) {       // the levels that hold anything
-    for (size_t l = 0; l + 1 < ptr.size(); ++l)
-      if (ptr[l + 1] > ptr[l]) out.emplace_back(ptr[l], ptr[l + 1] - ptr[l]);
-  };
-  level_launches(hp.m2m_level_ptr, g.up.launch); level_launches(hp.l2l_level_ptr, g.down.launch); level_launches(hp.m2m_shared_ptr, g.m2m_shared_launch);
+  g.up.launch = std::move(F.up.launch); g.down.launch = std::move(F.down.launch); g.m2m_shared_launch = std::move(F.shared_launch);
+  g.up.rot = std::move(F.up.rot); g.down.rot = std::move(F.down.rot); g.m2m_shared_rot = std::move(F.shared_rot);
   // sharded upward pass: who sends which multipoles
   g.split_upward = hp.opt.shard_upward && hp.opt.shard_world > 1;
   d.xch_rank = hp.opt.shard_rank; d.xch_world = g.split_upward ? hp.opt.shard_world : 0; d.xch_max = 0;
@@ -866,233 +537,82 @@ int fmmbem_plan::to_device_far(PlanGeometry& g) {
   }
 
   mark("far-field lists");
-  // parent<->child translation classes and their regular-harmonic tables
+  const std::shared_ptr<const OrderTables> otp = order_tables().get();      // (built on a thread of their own since plan_create began)
+  const OrderTables& ot = *otp;
+  // parent<->child translation classes; M2M / L2L by rotation: pair lists per level launch, items, records, constant streams
+  TRY(upload(F.up_cls, &d.up_cls)); TRY(upload(F.down_cls, &d.down_cls));
+  TRY(upload(F.up.rec, &g.up.rec)); TRY(upload(F.down.rec, &g.down.rec));
+  auto upload_pairs = [&](const SideLayout& from, ShiftSide& sd) -> int {
+    TRY(upload(from.src, &sd.rsrc)); TRY(upload(from.cls, &sd.rcls)); TRY(upload(from.tgt, &sd.rtgt)); TRY(upload(from.item, &sd.ritem));
+    return FMMBEM_OK;
+  };
+  TRY(upload_pairs(F.up, g.up)); TRY(upload(F.up_unit_ptr, &g.up.unit_ptr));
+  TRY(upload_pairs(F.down, g.down));
+  std::copy(ot.shift_off, ot.shift_off + kRotPmax, g.shift_stream_off);
+  TRY(upload(ot.ups, &g.up.stream)); TRY(upload(ot.dns, &g.down.stream));
+  // one pair per wavefront: class tables and the lanes' tables per order
+  TRY(upload(F.up.sl_class, &g.up.sl_class)); TRY(upload(F.down.sl_class, &g.down.sl_class));
+  std::copy(ot.sl_rot_off, ot.sl_rot_off + kShiftLanesPmax + 1, g.sl_rot_off);
+  std::copy(ot.sl_ax_off, ot.sl_ax_off + kShiftLanesPmax + 1, g.sl_ax_off);
+  TRY(upload(ot.urc, &g.up.sl_rc)); TRY(upload(ot.urs, &g.up.sl_rs)); TRY(upload(ot.uxc, &g.up.sl_xc)); TRY(upload(ot.uxs, &g.up.sl_xs));
+  TRY(upload(ot.drc, &g.down.sl_rc)); TRY(upload(ot.drs, &g.down.sl_rs)); TRY(upload(ot.dxc, &g.down.sl_xc)); TRY(upload(ot.dxs, &g.down.sl_xs));
+  g.shift_lanes = sw::shift_lanes(g.shift_lanes);
+  g.shift_lanes_max = sw::shift_lanes_max(g.shift_lanes_max);
+  g.shift_rot = sw::shift_rot(g.shift_rot);
+  g.shift_rot_min = sw::shift_rot_min(g.shift_rot_min);
   {
-    std::vector<int> up_cls(nb, 0), down_cls(nb, 0);
-    std::unordered_map<IVec3, int, IVec3Hash> seen;
-    std::vector<cplx> up_tab, down_tab, h;
-    std::vector<double> up_rec_h, dn_rec_h;              // records of the same classes for the rotation kernels
-    for (int b = 1; b < nb; ++b) {
-      const int par = hp.box_parent[b];
-      const int32_t v[3] = {hp.box_icoord[3 * par] - hp.box_icoord[3 * b], hp.box_icoord[3 * par + 1] - hp.box_icoord[3 * b + 1],
-                            hp.box_icoord[3 * par + 2] - hp.box_icoord[3 * b + 2]};
-      const IVec3 key = {v[0], v[1], v[2]};
-      auto [it, fresh] = seen.try_emplace(key, (int)seen.size());
-      if (fresh) {
-        double up[3], down[3];
-        for (int k = 0; k < 3; ++k) { up[k] = 0.5 * hp.cell[k] * double(v[k]); down[k] = -up[k]; }
-        up_rec_h.resize(up_rec_h.size() + 8); dn_rec_h.resize(dn_rec_h.size() + 8);
-        rot_record(up, up_rec_h.data() + up_rec_h.size() - 8); rot_record(down, dn_rec_h.data() + dn_rec_h.size() - 8);
-        // M2M: evalMultipole(rho, alpha, -beta) of (parent - child)   (LaplaceSpherical.hpp:253-254)
-        SphHost s = cart2sph_host(up);
-        harmonics(T, true, s.rho, s.alpha, -s.beta, pm, h);
-        for (int n = 0; n < pm; ++n)
-          for (int m = -n; m <= n; ++m) {
-            const cplx y = h[(size_t)n * (n + 1) / 2 + std::abs(m)];
-            up_tab.push_back(m < 0 ? std::conj(y) : y);
-          }
-        // L2L: evalMultipole(rho, alpha, +beta) of (child - parent)   (LaplaceSpherical.hpp:383-384)
-        s = cart2sph_host(down);
-        harmonics(T, true, s.rho, s.alpha, s.beta, pm, h);
-        for (int n = 0; n < pm; ++n)
-          for (int m = -n; m <= n; ++m) {
-            const cplx y = h[(size_t)n * (n + 1) / 2 + std::abs(m)];
-            down_tab.push_back(m < 0 ? std::conj(y) : y);
-          }
-      }
-      up_cls[b] = down_cls[b] = it->second;
-    }
-    TRY(upload(up_cls, &d.up_cls)); TRY(upload(down_cls, &d.down_cls));
-    // ---- M2M / L2L by rotation: pair lists per level launch, items, records, constant streams ----
-    {
-      TRY(upload(up_rec_h, &g.up.rec)); TRY(upload(dn_rec_h, &g.down.rec));
-      std::vector<int> rs, rc, rt, ri, len, uptr;
-      auto level_boxes = [&](int l) { return l >= 0 && l < hp.nlevels ? hp.level_off[l + 1] - hp.level_off[l] : 0; };
-      // items of the shifts: whole targets, ONE pass (at most 64 pairs) -- the shift kernels carry nothing between passes
-      auto cut_single_pass = [](const std::vector<int>& seg_len, int pair_base, std::vector<int>& item_ptr, int lanes = 64) {
-        item_ptr.push_back(pair_base);
-        int fill = 0;
-        for (int l : seg_len) {
-          if (fill + l > lanes) { item_ptr.push_back(item_ptr.back() + fill); fill = 0; }
-          fill += l;
-        }
-        if (fill > 0) item_ptr.push_back(item_ptr.back() + fill);
-      };
-      // The pairs of a side's launches, launch after launch, with each launch's items and ShiftRot.  unit(i) appends the pairs of
-      // entry i of the side's box list and returns the level of their CHILD boxes; units: the wavefront kernel walks a unit's
-      // pairs through uptr (M2M: a parent's children), else a pair is a unit (L2L)
-      auto add_launches = [&](const std::vector<std::pair<int, int>>& launches, std::vector<ShiftRot>& out, bool units, auto&& unit) {
-        for (auto [first, count] : launches) {
-          ShiftRot sr;
-          sr.item_first = (int)ri.size();
-          const int base = sr.pair_first = (int)rs.size();
-          if (units) sr.unit_first = (int)uptr.size();
-          sr.n_units = count;
-          len.clear();
-          for (int i = first; i < first + count; ++i) {
-            const int before = (int)rs.size();
-            if (units) uptr.push_back(before);
-            const int child_level = unit(i);
-            if (i == first) sr.level_boxes = level_boxes(child_level);
-            len.push_back((int)rs.size() - before);
-          }
-          if (units) uptr.push_back((int)rs.size());    // one past the level's last parent
-          cut_single_pass(len, base, ri);
-          sr.n_items = (int)ri.size() - sr.item_first - 1;
-          sr.pairs = (int)rs.size() - base;
-          out.push_back(sr);
-        }
-      };
-      auto upload_pairs = [&](ShiftSide& sd) -> int {
-        TRY(upload(rs, &sd.rsrc)); TRY(upload(rc, &sd.rcls)); TRY(upload(rt, &sd.rtgt)); TRY(upload(ri, &sd.ritem));
-        return FMMBEM_OK;
-      };
-      auto m2m_unit = [&](int i) {
-        const int par = hp.m2m_parents[i];
-        for (int c = hp.box_child_begin[par]; c < hp.box_child_end[par]; ++c) { rs.push_back(c); rc.push_back(up_cls[c]); rt.push_back(par); }
-        return hp.box_level[par] + 1;
-      };
-      add_launches(g.up.launch, g.up.rot, true, m2m_unit);
-      add_launches(g.m2m_shared_launch, g.m2m_shared_rot, true, m2m_unit);
-      TRY(upload_pairs(g.up)); TRY(upload(uptr, &g.up.unit_ptr));
-      rs.clear(); rc.clear(); rt.clear(); ri.clear();
-      add_launches(g.down.launch, g.down.rot, false, [&](int i) {
-        const int c = hp.l2l_children[i];
-        rs.push_back(hp.box_parent[c]); rc.push_back(down_cls[c]); rt.push_back(c);
-        return hp.box_level[c];
-      });
-      TRY(upload_pairs(g.down));
-      const std::shared_ptr<const OrderTables> otp = order_tables().get();      // (built on a thread of their own since plan_create began)
-      const OrderTables& ot = *otp;
-      for (int q = 1; q <= kRotPmax; ++q) g.shift_stream_off[q - 1] = ot.shift_off[q - 1];
-      TRY(upload(ot.ups, &g.up.stream)); TRY(upload(ot.dns, &g.down.stream));
-      {                                                // one pair per wavefront: class tables and the lanes' tables per order
-        const int nclass = (int)up_rec_h.size() / 8, cs = sl_class_doubles(pm);
-        std::vector<double> cu((size_t)nclass * cs), cd((size_t)nclass * cs);
-        for (int c = 0; c < nclass; ++c) {
-          sl_class_table(up_rec_h.data() + (size_t)c * 8, pm, kRotM2M, cu.data() + (size_t)c * cs);
-          sl_class_table(dn_rec_h.data() + (size_t)c * 8, pm, kRotL2L, cd.data() + (size_t)c * cs);
-        }
-        TRY(upload(cu, &g.up.sl_class)); TRY(upload(cd, &g.down.sl_class));
-        for (int q = 1; q <= kShiftLanesPmax; ++q) { g.sl_rot_off[q] = ot.sl_rot_off[q]; g.sl_ax_off[q] = ot.sl_ax_off[q]; }
-        TRY(upload(ot.urc, &g.up.sl_rc)); TRY(upload(ot.urs, &g.up.sl_rs)); TRY(upload(ot.uxc, &g.up.sl_xc)); TRY(upload(ot.uxs, &g.up.sl_xs));
-        TRY(upload(ot.drc, &g.down.sl_rc)); TRY(upload(ot.drs, &g.down.sl_rs)); TRY(upload(ot.dxc, &g.down.sl_xc)); TRY(upload(ot.dxs, &g.down.sl_xs));
-        g.shift_lanes = sw::shift_lanes(g.shift_lanes);
-        g.shift_lanes_max = sw::shift_lanes_max(g.shift_lanes_max);
-      }
-      g.shift_rot = sw::shift_rot(g.shift_rot);
-      g.shift_rot_min = sw::shift_rot_min(g.shift_rot_min);
-    }
     const cplx *pu = nullptr, *pd = nullptr;
-    TRY(upload(up_tab, &pu)); TRY(upload(down_tab, &pd));
+    TRY(upload(F.up_tab, &pu)); TRY(upload(F.down_tab, &pd));
     d.up_tab = reinterpret_cast<const double2*>(pu);
     d.down_tab = reinterpret_cast<const double2*>(pd);
-    const ShiftOps ops = build_shift_ops(pm, T.A, kEps);
-    auto up_op = [&](const VOp& v, ShiftOpDev& o) -> int {
-      TRY(upload(v.src, &o.src)); TRY(upload(v.y, &o.y)); TRY(upload(v.real, &o.real));
-      TRY(upload(v.npiece, &o.npiece)); TRY(upload(v.piece, &o.piece));
-      o.T = v.T; o.V = v.V; o.maxp = v.maxp;
-      return FMMBEM_OK;
-    };
-    g.up.ops.resize(pm); g.down.ops.resize(pm);
-    for (int p = 1; p <= pm; ++p) { TRY(up_op(ops.up_v[p - 1], g.up.ops[p - 1])); TRY(up_op(ops.down_v[p - 1], g.down.ops[p - 1])); }
   }
+  TRY(upload_shift_ops(*mem, build_shift_ops(pm, T.A, kEps), g.up.ops, g.down.ops));
 
   mark("shift classes + operators");
   // M2L: targets to run, sources whose Mh is needed, class tables Yh[r,c] = i^{|c|} EPS Y[r,c] / A[r,c]
-  {
-    std::vector<int> tgt, mh;
-    std::vector<uint8_t> is_src(nb, 0);
-    for (int b = 0; b < nb; ++b)
-      if (hp.has_L[b] && hp.owned_L[b]) tgt.push_back(b);
-    for (int s : hp.m2l_src) is_src[s] = 1;
-    for (int b = 0; b < nb; ++b) if (is_src[b]) mh.push_back(b);
-    d.n_m2l_tgt = (int)tgt.size(); d.n_mh = (int)mh.size();
-    TRY(upload(tgt, &d.m2l_tgt)); TRY(upload(mh, &d.mh_box));
-    TRY(upload(hp.m2l_ptr, &d.m2l_ptr)); TRY(upload(hp.m2l_src, &d.m2l_src)); TRY(upload(hp.m2l_cls, &d.m2l_cls));
-    if (opts.evaluator == FMMBEM_EVAL_TREECODE) {
-      // M2P work (device_launch.hpp M2PWork): per leaf the boxes of its path that are the target of a pair, root first -- box_parent
-      // is read here and never on the device -- and the leaves that have any cut into items of up to 64 rows
-      std::vector<int> chain_ptr(hp.nleaves() + 1, 0), chain_box, item_leaf, item_row, path;
-      for (int l = 0; l < hp.nleaves(); ++l) {
-        path.clear();
-        for (int b = hp.leaf_box[l]; b >= 0; b = b > 0 ? hp.box_parent[b] : -1)
-          if (hp.m2l_ptr[b + 1] > hp.m2l_ptr[b]) path.push_back(b);
-        chain_box.insert(chain_box.end(), path.rbegin(), path.rend());
-        chain_ptr[l + 1] = (int)chain_box.size();
-        const int nr = hp.box_body_end[hp.leaf_box[l]] - hp.box_body_begin[hp.leaf_box[l]];
-        for (int r = 0; r < nr && !path.empty(); r += 64) { item_leaf.push_back(l); item_row.push_back(r); }
-      }
-      g.m2p.n_items = (int)item_leaf.size();
-      TRY(upload(item_leaf, &g.m2p.item_leaf)); TRY(upload(item_row, &g.m2p.item_row));
-      TRY(upload(chain_ptr, &g.m2p.chain_ptr)); TRY(upload(chain_box, &g.m2p.chain_box));
-    }
-    mark("m2l lists upload");
-    g.n_classes = (int64_t)hp.m2l_class_rep.size() / 2;
-    const int R = 2 * pm;
-    d.g_max = m2l_entries(pm);
-    std::vector<double> gtab((size_t)g.n_classes * d.g_max);
-    std::vector<cplx> ztab((size_t)g.n_classes * pm);
-    parallel_rows(g.n_classes, 64, [&](int64_t c_begin, int64_t c_end) {
-    std::vector<cplx> h;
-    for (int64_t c = c_begin; c < c_end; ++c) {
-      // translation = c_target - c_source (executor/M2L.hpp:40), rebuilt from the exact integer class
-      // vector (half-cell units) so that the table does not depend on which pair was seen first
-      // (shards of one operator must produce bit-identical rows).
-      double tr[3];
-      for (int k = 0; k < 3; ++k) tr[k] = 0.5 * hp.cell[k] * double(hp.m2l_class_vec[3 * c + k]);
-      const SphHost sp = cart2sph_host(tr);
-      // Yh[r,c] = i^{|c|} EPS Y[r,c] / A[r,c] = Z^c gh[r,c]: tabulate the real part G (harmonics at beta = 0,
-      // evalLocal to order 2P) and the phases Z^m = i^m e^{i m beta} separately (kernels_m2l.hip header)
-      harmonics(T, false, sp.rho, sp.alpha, 0.0, R, h);
-      double* out = gtab.data() + (size_t)c * d.g_max;
-      for (int r = 0; r < R; ++r)
-        for (int cc = 0; cc <= r; ++cc)
-          out[r * (r + 1) / 2 + cc] = h[(size_t)r * (r + 1) / 2 + cc].real() * kEps / T.A[r * r + r + cc];
-      for (int m = 0; m < pm; ++m) ztab[(size_t)c * pm + m] = i_pow(m) * std::exp(cplx(0, 1) * double(m * sp.beta));
-    }
-    });
-    const cplx* pz = nullptr;
-    TRY(upload(gtab, &d.m2l_g));
-    TRY(upload(ztab, &pz));
-    d.m2l_z = reinterpret_cast<const double2*>(pz);
-    // lane -> output maps and table -> LDS scatter maps of the M2L kernel, every order up to p_max
-    const std::shared_ptr<const OrderTables> otp = order_tables().get();
-    if (!otp->lanes_ok) return fail(FMMBEM_ERR_INVALID, "internal: M2L lane dealing failed");
-    for (int p = 1; p <= kPmax; ++p) d.m2l_scat_off[p - 1] = otp->scat_off[p - 1];
-    TRY(upload(otp->lanes, &d.m2l_lane)); TRY(upload(otp->scat, &d.m2l_scat));
+  d.n_m2l_tgt = (int)F.m2l_tgt.size(); d.n_mh = (int)F.mh_box.size();
+  TRY(upload(F.m2l_tgt, &d.m2l_tgt)); TRY(upload(F.mh_box, &d.mh_box));
+  TRY(upload(hp.m2l_ptr, &d.m2l_ptr)); TRY(upload(hp.m2l_src, &d.m2l_src)); TRY(upload(hp.m2l_cls, &d.m2l_cls));
+  if (treecode()) {                                    // M2P work (device_launch.hpp M2PWork)
+    g.m2p.n_items = (int)F.m2p_item_leaf.size();
+    TRY(upload(F.m2p_item_leaf, &g.m2p.item_leaf)); TRY(upload(F.m2p_item_row, &g.m2p.item_row));
+    TRY(upload(F.m2p_chain_ptr, &g.m2p.chain_ptr)); TRY(upload(F.m2p_chain_box, &g.m2p.chain_box));
   }
+  mark("m2l lists upload");
+  g.n_classes = F.n_classes;
+  d.g_max = F.g_max;
+  {
+    const cplx* pz = nullptr;
+    TRY(upload(F.m2l_g, &d.m2l_g));
+    TRY(upload(F.m2l_z, &pz));
+    d.m2l_z = reinterpret_cast<const double2*>(pz);
+  }
+  // lane -> output maps and table -> LDS scatter maps of the M2L kernel, every order up to p_max
+  if (!ot.lanes_ok) return fail(FMMBEM_ERR_INVALID, "internal: M2L lane dealing failed");
+  std::copy(ot.scat_off, ot.scat_off + kPmax, d.m2l_scat_off);
+  TRY(upload(ot.lanes, &d.m2l_lane)); TRY(upload(ot.scat, &d.m2l_scat));
 
   mark("m2l class tables");
   // M2L by rotation (kernels_m2l_rot.hip): the owned pairs in CSR order by target, cut into items; class records; constants
-  {
-    d.n_rot_items = (int)hp.rot_item_ptr.size() - 1;
-    d.n_rot_empty = (int)hp.rot_empty.size();
-    if (hp.rot_alias) {
-      // one pair list for both M2L kernels; the target of pair i is the box whose CSR range holds i (written on the device)
-      d.rot_src = d.m2l_src; d.rot_cls = d.m2l_cls;
-      int* tgt = nullptr;
-      TRY(alloc(hp.m2l_src.size(), &tgt, false));
-      if (nb > 0) hipLaunchKernelGGL(expand_csr_targets_kernel, dim3((nb + 255) / 256), dim3(256), 0, own_stream, d.m2l_ptr, nb, tgt);
-      HIP_TRY(hipGetLastError());
-      d.rot_tgt = tgt;
-    } else {
-      TRY(upload(hp.rot_src, &d.rot_src)); TRY(upload(hp.rot_cls, &d.rot_cls)); TRY(upload(hp.rot_tgt, &d.rot_tgt));
-    }
-    TRY(upload(hp.rot_item_ptr, &d.rot_item_ptr)); TRY(upload(hp.rot_empty, &d.rot_empty));
-    d.n_rot_items_long = (int)hp.rot_item_ptr_long.size() - 1;
-    TRY(upload(hp.rot_item_ptr_long, &d.rot_item_ptr_long));
-    std::vector<double> rec((size_t)g.n_classes * 8, 0.0);
-    for (int64_t c = 0; c < g.n_classes; ++c) {
-      double tr[3];
-      for (int k = 0; k < 3; ++k) tr[k] = 0.5 * hp.cell[k] * double(hp.m2l_class_vec[3 * c + k]);
-      rot_record(tr, rec.data() + (size_t)c * 8);
-    }
-    TRY(upload(rec, &d.rot_cls_rec));
-    const std::shared_ptr<const OrderTables> otp = order_tables().get();
-    for (int p = 1; p <= kRotPmax; ++p) d.rot_tab_off[p - 1] = otp->rot_off[p - 1];
-    TRY(upload(otp->rot_all, &d.rot_tab));
+  d.n_rot_items = (int)hp.rot_item_ptr.size() - 1;
+  d.n_rot_empty = (int)hp.rot_empty.size();
+  if (hp.rot_alias) {
+    // one pair list for both M2L kernels; the target of pair i is the box whose CSR range holds i (written on the device)
+    d.rot_src = d.m2l_src; d.rot_cls = d.m2l_cls;
+    int* tgt = nullptr;
+    TRY(alloc(hp.m2l_src.size(), &tgt, false));
+    if (nb > 0) hipLaunchKernelGGL(expand_csr_targets_kernel, dim3((nb + 255) / 256), dim3(256), 0, own_stream, d.m2l_ptr, nb, tgt);
+    HIP_TRY(hipGetLastError());
+    d.rot_tgt = tgt;
+  } else {
+    TRY(upload(hp.rot_src, &d.rot_src)); TRY(upload(hp.rot_cls, &d.rot_cls)); TRY(upload(hp.rot_tgt, &d.rot_tgt));
   }
+  TRY(upload(hp.rot_item_ptr, &d.rot_item_ptr)); TRY(upload(hp.rot_empty, &d.rot_empty));
+  d.n_rot_items_long = (int)hp.rot_item_ptr_long.size() - 1;
+  TRY(upload(hp.rot_item_ptr_long, &d.rot_item_ptr_long));
+  TRY(upload(F.rot_cls_rec, &d.rot_cls_rec));
+  std::copy(ot.rot_off, ot.rot_off + kRotPmax, d.rot_tab_off);
+  TRY(upload(ot.rot_all, &d.rot_tab));
 
   mark("rotation lists");
   return to_device_bc_end();
@@ -1125,7 +645,7 @@ void fmmbem_plan::compose_d() {
 // tabulating and uploading the far-field operators.
 int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
   DEVICE_SCOPE(opts.device);
-  alloc_list = &allocs;
+  mem = &allocs;
   fd.n_act = 0;
   if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) {
     // StokesSphericalBEM: M[2][4] per box (kernel/StokesSphericalBEM.hpp:143-153).  The TARGET's flag picks the operator
@@ -1178,7 +698,7 @@ int fmmbem_plan::to_device_bc_begin(const uint8_t* bc_tree) {
 
 int fmmbem_plan::to_device_bc_end() {
   DEVICE_SCOPE(opts.device);
-  alloc_list = &allocs;
+  mem = &allocs;
   BuildTrace mark;
   const int dof = g.gd.dof, nb = hp.nboxes;
   TRY(alloc((size_t)nb * fd.nslots * g.gd.s_max, &fd.M, true));
@@ -1254,11 +774,7 @@ int fmmbem_plan::to_device_bc_end() {
   mark("near assembly (waited for)");
   compose_d();
   {                                                    // the plan itself, readable from the device
-    void* pd = nullptr;
-    HIP_TRY(hipMalloc(&pd, sizeof(DevicePlan)));
-    allocs.push_back(pd);
-    HIP_TRY(hipMemcpy(pd, &d, sizeof(DevicePlan), hipMemcpyHostToDevice));
-    d_dev = static_cast<const DevicePlan*>(pd);
+    TRY(allocs.upload(&d, 1, &d_dev));
   }
   return FMMBEM_OK;
 }
@@ -1292,26 +808,12 @@ int fmmbem_plan::build_side_lists() {
     HIP_TRY(hipStreamSynchronize(own_stream));
     fd.side_col = d_col; fd.side_val = d_val;
     near_side_entries = nside;
-    if (g.hybrid) {
-      // work items of near_side_items (kernels_near.hip): runs of consecutive rows that hold <= 256 listed entries together (a workgroup takes the
-      // entries one per thread, then a thread per row adds the row's products in entry order); a row of more than 256 is an item
-      // of its own, taken 256 at a time
-      std::vector<int4> sitems;
-      int64_t i = hp.row_begin;
-      while (i < hp.row_end) {
-        if (cnt[(size_t)i] == 0) { ++i; continue; }
-        int64_t j = i + 1;
-        while (j < hp.row_end && cnt[(size_t)j] > 0 && ptr[(size_t)j + 1] - ptr[(size_t)i] <= 256 && j - i < 256) ++j;
-        sitems.push_back(make_int4((int)ptr[(size_t)i], (int)ptr[(size_t)j], (int)i, (int)j));
-        i = j;
-      }
+    if (g.hybrid) {                                    // work items of near_side_items (kernels_near.hip)
+      const std::vector<int4> sitems = cut_side_items(cnt, ptr, hp.row_begin, hp.row_end);
       fd.side_nitems = (int)sitems.size();
       TRY(upload(sitems, &fd.side_items));
     }
-    for (void* tmp : {(void*)d_cnt, (void*)const_cast<int*>(d_row)}) {        // creation-time scratch
-      (void)hipFree(tmp);
-      allocs.erase(std::find(allocs.begin(), allocs.end(), tmp));
-    }
+    allocs.free_one(d_cnt); allocs.free_one(d_row);          // creation-time scratch
   }
   return FMMBEM_OK;
 }
@@ -1645,7 +1147,7 @@ int fmmbem_plan::batch_alloc(hipStream_t s) {
     (void)hipGetLastError();
     return fail(FMMBEM_ERR_ALLOC, "batch buffers: device allocation failed");
   }
-  for (void* q : got) allocs.push_back(q);           // this plan's alone, freed at destroy
+  for (void* q : got) allocs.list.push_back(q);           // this plan's alone, freed at destroy
   b.width = w;
   bat = b;
   return FMMBEM_OK;
