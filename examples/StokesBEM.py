@@ -19,6 +19,11 @@ sphere of radius 3, summed on the device by fb.Direct; prints the largest and th
 (fmmbem_plan_create_field) at order p; prints "field (FMM): ..." in the format of the "field:" line and, given together with
 -field N, the relative L2 difference between the two.
 
+-field_pressure (not a flag of the reference; with -field_fmm N): the pressure of the solved layer on the same N points by
+fplan.execute_pressure (fmmbem_plan_execute_pressure), in the library's scaling q = 4 pi p; prints "field pressure (FMM): ..." in the
+format of the "field (FMM):" line and, for the unit sphere, the largest deviation of q / (6 pi mu) from x / r^3 -- the exact pressure
+of a translating sphere, p = (3/2) mu a U.x / r^3 -- relative to 1/9.
+
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
 
@@ -60,6 +65,7 @@ def print_help_and_exit():
           "-resistance : (not a flag of the reference) the 3 x 3 translational resistance matrix, three solves in one batch\n"
           "-field <int> : (not a flag of the reference) the solved layer's velocity on N points at r = 3, by the Direct sum\n"
           "-field_fmm <int> : (not a flag of the reference) the same velocity by the FMM (plan.field_plan)\n"
+          "-field_pressure : (not a flag of the reference) with -field_fmm: the pressure on the same points (execute_pressure)\n"
           "-help : print this message")
     sys.exit(0)
 
@@ -88,7 +94,7 @@ def main(argv):
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
     rbc, near_f32, field, field_fmm = False, 0, 0, 0
-    stokes_batch, resistance = 0, False
+    stokes_batch, resistance, field_pressure = 0, False, False
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -146,10 +152,14 @@ def main(argv):
             i += 1; field = int(argv[i])
         elif a == "-field_fmm":                            # not in the reference: the same velocity through plan.field_plan
             i += 1; field_fmm = int(argv[i])
+        elif a == "-field_pressure":                       # not in the reference: the pressure through fplan.execute_pressure
+            field_pressure = True
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
     so.max_p, so.p_min, so.max_iters, so.restart = p, p_min, 100, 100
+    if field_pressure and field_fmm <= 0:
+        raise SystemExit("-field_pressure: needs -field_fmm N (the pressure is evaluated on the field plan's points)")
 
     if vert or face:
         print("reading mesh from %s, %s" % (vert, face))
@@ -245,11 +255,19 @@ def main(argv):
         fplan = plan.field_plan(sphere_points(field_fmm, 3.0))       # VELOCITY targets: the single layer
         plan.kernel().set_p(p)                             # (the relaxed solve leaves the kernel at its last order)
         uf = fplan.execute_torch(x).cpu().numpy()
+        q = fplan.execute_pressure_torch(x).cpu().numpy() if field_pressure else None
         fplan.close()
         mag = np.linalg.norm(uf, axis=1)
         print("field (FMM): %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field_fmm, float(mag.max()), float(mag.mean())))
         if u is not None and field == field_fmm:
             print("field (FMM) against field: relative L2 difference %.3e" % float(np.linalg.norm(uf - u) / np.linalg.norm(u)))
+        if q is not None:
+            print("field pressure (FMM): %d points at r = 3, max |q|: %.6e, mean |q|: %.6e" % (field_fmm, float(np.abs(q).max()), float(np.abs(q).mean())))
+            if not (rbc or mesh or vert or face):
+                # a sphere of radius a translating with U: p = (3/2) mu a U.x / r^3; q = 4 pi p and the solve's U is e_x
+                pts = sphere_points(field_fmm, 3.0)
+                dev_q = np.abs(q / (6 * math.pi * mu) - pts[:, 0] / 27.0).max() * 9.0
+                print("field pressure against the translating sphere's: largest deviation %.3e of 1/9" % float(dev_q))
     if resistance:
         # unit translation e_j on every panel: the right-hand side 4 pi e_j (as b above), the force of the solved traction
         B = torch.zeros((3, n, 3), dtype=torch.float64, device=dev)

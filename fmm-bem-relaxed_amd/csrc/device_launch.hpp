@@ -84,6 +84,14 @@ hipError_t launch_near_grad(const DevicePlan& d, int64_t n_src, double* g_tree, 
 hipError_t launch_l2p_grad(const DevicePlan& d, int p, int64_t n_src, double* g_tree, hipStream_t s);
 hipError_t launch_grad_scatter(const DevicePlan& d, int64_t n_src, const double* g_tree, double* out, hipStream_t s);
 hipError_t launch_grad_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
+// ---- field pressure (kernels_pressure.hip; Stokes field plans whose targets are all VELOCITY targets) ----
+// q_tree: one double per target row, tree order.  near: q_tree[row] = the near pairs' sum, every target row written (0 where the
+// leaf has no near pair); l2p: q_tree[row] -= d_x phi_0 + d_y phi_1 + d_z phi_2 of the leaf's local expansions (slots 0..2);
+// scatter: out[perm[row]] = q_tree[row - n_src]; entries: pi (3 doubles) for pairs laid out as launch_kernel_entries takes them
+hipError_t launch_near_pressure(const DevicePlan& d, int64_t n_src, double* q_tree, hipStream_t s);
+hipError_t launch_l2p_pressure(const DevicePlan& d, int p, int64_t n_src, double* q_tree, hipStream_t s);
+hipError_t launch_pressure_scatter(const DevicePlan& d, int64_t n_src, const double* q_tree, double* out, hipStream_t s);
+hipError_t launch_pressure_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

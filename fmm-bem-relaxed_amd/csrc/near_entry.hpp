@@ -372,6 +372,61 @@ __device__ inline void stokes_entry(const DevicePlan& d, V3 t, int tbc, int64_t 
     stokes_entry_near(d, t, tbc, j, out);
 }
 
+// The pressure of the single layer at a point t off the surface (include/fmmbem.h, "Field pressure"): three doubles per (target
+// point, source panel j), the row vector pi with q += pi . f_j:
+//   pi(t, s_j) = sum_q w_q A_j d_q / |d_q|^3,  d_q = t - y_q;   no mu, no 1/(2 mu)
+// The regimes are those of a VELOCITY target above -- dist < 1e-8: pi = 0 (the mean of the one-sided limits +-2 pi n_j of a flat
+// panel, its in-plane part neglected); sqrt(2 A) / dist >= 0.5: the K_fine rule on the vertices; else the K stored points -- and a
+// point with |d_q|^2 < 1e-8 contributes 0, as in stokeslet_point.  One reciprocal square root per point, no division.
+// In two parts like stokes_far_from / stokes_entry_near: stokes_pressure_far_from gives pi of a pair in the far regime (and the 0
+// of a self pair) from a source panel held in registers or LDS, or says `deferred`; stokes_pressure_near the K_fine rule on the
+// vertices of panel j.  The ONE text of pi: the near kernel of the pressure execute and fmmbem_kernel_pressure_entries
+// (kernels_pressure.hip) both call it.
+__device__ __forceinline__ void pressure_point(V3& out, double wA, V3 t, V3 pnt) {
+  const V3 dd = sub(t, pnt);
+  const double r2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
+  const double ri = rsqrt(r2);
+  const double f = r2 < 1e-8 ? 0.0 : wA * (ri * ri * ri);
+  out.x += f * dd.x; out.y += f * dd.y; out.z += f * dd.z;
+}
+template <class Quad>
+__device__ __forceinline__ bool stokes_pressure_far_from(const DevicePlan& d, V3 t, V3 c, double A, Quad&& quad, V3& out) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  out = {0, 0, 0};
+  // the regime by the expressions of stokes_far_from, dist < 1e-8 and sqrt(2 A) / dist >= 0.5; where 8 A < 0.99 dist^2 the exact
+  // ratio is below 0.4975 and its roundings cannot lift it to 0.5 (see laplace_grad_from): no square root, no division there
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {
+    const double dist = sqrt(d2);
+    if (dist < 1e-8) return false;
+    if (sqrt(2 * A) / dist >= 0.5) return true;
+  }
+  for (int q = 0; q < d.nq; ++q) pressure_point(out, d.qw[q] * A, t, quad(q));
+  return false;
+}
+__device__ inline void stokes_pressure_near(const DevicePlan& d, V3 t, int64_t j, double A, V3& out) {
+  const int64_t N = d.n;
+  const V3 v0 = {d.vert[0 * N + j], d.vert[1 * N + j], d.vert[2 * N + j]};
+  const V3 v1 = {d.vert[3 * N + j], d.vert[4 * N + j], d.vert[5 * N + j]};
+  const V3 v2 = {d.vert[6 * N + j], d.vert[7 * N + j], d.vert[8 * N + j]};
+  out = {0, 0, 0};
+  for (int q = 0; q < d.nqf; ++q) {
+    const V3 pt = {v0.x * d.qf[4 * q + 0] + v1.x * d.qf[4 * q + 1] + v2.x * d.qf[4 * q + 2],
+                   v0.y * d.qf[4 * q + 0] + v1.y * d.qf[4 * q + 1] + v2.y * d.qf[4 * q + 2],
+                   v0.z * d.qf[4 * q + 0] + v1.z * d.qf[4 * q + 1] + v2.z * d.qf[4 * q + 2]};
+    pressure_point(out, d.qf[4 * q + 3] * A, t, pt);
+  }
+}
+__device__ inline V3 stokes_pressure_entry(const DevicePlan& d, V3 t, int64_t j) {
+  const int64_t N = d.n;
+  const double A = d.area[j];
+  V3 out;
+  if (stokes_pressure_far_from(d, t, V3{d.cx[j], d.cy[j], d.cz[j]}, A,
+                               [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; }, out))
+    stokes_pressure_near(d, t, j, A, out);
+  return out;
+}
+
 }  // namespace
 
 }  // namespace fmmbem

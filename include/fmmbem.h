@@ -355,6 +355,35 @@ int fmmbem_plan_batch_width(const fmmbem_plan *plan, int *width);
 int fmmbem_plan_execute_gradient(fmmbem_plan *plan, int p, const double *x, double *g);
 int fmmbem_plan_execute_gradient_device(fmmbem_plan *plan, int p, const double *d_x, double *d_g, void *stream);
 
+/* ---- Field pressure: the pressure of the Stokes single layer at the points of a field plan ----------------------------------
+ * (no reference counterpart: the other half of a Stokes field off the surface).  On a Stokes plan of fmmbem_plan_create_field
+ * whose targets are all VELOCITY targets, for target i with point t_i,
+ *   q_i = sum_j pi(t_i, s_j) . x_j,   one double;  x_j the 3 components of panel j,
+ *   pi(t, s_j) = sum_q w_q A_j d_q / |d_q|^3,   d_q = t - y_q.
+ * Scaling: the plan's execute returns u' = (1/2mu) int (I/r + d d^T/r^3) f dS = 4 pi u; q is the pressure that belongs to that
+ * u': -grad q + mu lap u' = 0 off the surface.  The physical pressure is q / (4 pi), as the physical velocity is u' / (4 pi); there
+ * is no mu in pi.
+ * The rule is chosen as the velocity entry chooses it: dist = |t - c_j|; dist < 1e-8: pi = 0 -- the mean of the two one-sided
+ * limits +-2 pi n_j of a flat panel, with the in-plane part of its own integral neglected: the pressure jumps across the layer,
+ * and a point ON it is the caller's business; otherwise sqrt(2 A_j) / dist >= 0.5: the K_fine rule on the vertices; otherwise
+ * the K stored points.  A quadrature point with |d_q|^2 < 1e-8 contributes 0.
+ * The far field: q_i -= d_x phi_0 + d_y phi_1 + d_z phi_2 at t_i, phi_k the local expansion of the potential with charges f_k
+ * that the velocity execute holds after L2L (slot k of the leaf; unscaled: the 1/(2 mu) of the velocity's L2P does not enter;
+ * slot 3 is not read).  In the far regime, with the same K, pi is minus the flag-0 gamma of the field gradient above.
+ * x: n_panels x 3 doubles; q: n_targets doubles, both in the caller's order; coincident targets each get their copy.
+ * The execute is the velocity execute's gather, P2M, M2M, M2L and L2L, then two kernels of its own -- the near pairs matrix-free
+ * (a row's sum: the leaf's near list in order, panels ascending, quadrature points in order) and minus the divergence of the
+ * three expansions (terms m-major) -- and the delivery: the same bits every run.  Its buffers are allocated at the first pressure
+ * call (FMMBEM_ERR_ALLOC if that fails; the plan stays usable).  Checked in this order: a null plan or vector ->
+ * FMMBEM_ERR_INVALID; p outside 1..p_max -> _INVALID; a plan that is not over separate targets -> _UNSUPPORTED; a Laplace plan ->
+ * _UNSUPPORTED; a plan with any TRACTION target -> _UNSUPPORTED; a host-only plan -> _UNSUPPORTED; the handle stays usable and
+ * neither pointer is touched.  A pressure execute is launched plainly, kernel by kernel, whatever fmmbem_plan_set_graphs says,
+ * and leaves the captured graphs of the velocity execute as they are.  With stage timing on it is recorded as an execute:
+ * ms_near is the near kernel of the pressure, ms_l2p the divergence of L.  No batches.
+ * The host form takes HOST pointers and returns when q is written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_pressure(fmmbem_plan *plan, int p, const double *x /* n x 3 */, double *q /* n_targets */);
+int fmmbem_plan_execute_pressure_device(fmmbem_plan *plan, int p, const double *d_x, double *d_q, void *stream);
+
 /* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
  * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES
  * iteration on that operator instead).  A BLOCK_DIAGONAL plan holds every leaf's self block assembled in HBM; build inverts
@@ -429,6 +458,11 @@ int fmmbem_kernel_entries(const fmmbem_options *opts, size_t n, const double *ta
  * all 0).  Laplace only (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, device.  out: n x 3. */
 int fmmbem_kernel_gradient_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
                                    const uint8_t *target_bc, const double *source_vertices, double *out /* n x 3 */);
+/* pi(target, source) of the field pressure (see fmmbem_plan_execute_pressure) for n independent pairs, by the function the
+ * pressure execute's near kernel calls: the target POINT is the centroid of target_vertices' panel i.  Stokes only
+ * (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, quad_k_fine, device.  out: n x 3. */
+int fmmbem_kernel_pressure_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
+                                   const double *source_vertices, double *out /* n x 3 */);
 
 /* ---- the translation operators one at a time: the KernelSkeleton contract (kernel/KernelSkeleton.hpp:62-212) --------------
  * What the reference's kernel classes offer beside operator(): P2M, M2M, M2L, L2L, L2P as kernel/LaplaceSphericalBEM.hpp:307-476

@@ -600,6 +600,17 @@ class PlanAdapter {
     check(fmmbem_plan_execute_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
     return results;
   }
+  // Not in the reference: the pressure of the Stokes single layer at the points of a field plan whose points are all VELOCITY
+  // targets (field_plan; fmmbem_plan_execute_pressure): result i = sum_j pi(points[i], sources[j]) . charges[j], in the scaling of
+  // execute() -- q = 4 pi p, as execute() returns 4 pi u.  Error(FMMBEM_ERR_UNSUPPORTED) on a Laplace plan, on a plan over its own
+  // panels and on a field plan with a TRACTION target.
+  std::vector<double> execute_pressure(const std::vector<charge_type>& charges) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
+    std::vector<double> results(has_targets_ ? target_bc_.size() : charges.size());
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    check(fmmbem_plan_execute_pressure(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()));
+    return results;
+  }
   // preconditioner-style operator()(x, y) (examples/BEM/Preconditioner.hpp:11-15)
   void operator()(const std::vector<charge_type>& x, std::vector<result_type>& y) { y = execute(x); }
 
