@@ -24,6 +24,12 @@ fplan.execute_pressure (fmmbem_plan_execute_pressure), in the library's scaling 
 format of the "field (FMM):" line and, for the unit sphere, the largest deviation of q / (6 pi mu) from x / r^3 -- the exact pressure
 of a translating sphere, p = (3/2) mu a U.x / r^3 -- relative to 1/9.
 
+-field_stress (not a flag of the reference; with -field_fmm N): the velocity gradient of the solved layer on the same N points by
+fplan.execute_velocity_gradient (fmmbem_plan_execute_velocity_gradient), in the library's scaling G = 4 pi grad u, and the stress by
+fplan.execute_stress; prints "field velocity gradient (FMM): ..." and "field stress (FMM): ..." in the format of the "field (FMM):" line
+and, for the unit sphere, the largest deviation of G / 4 pi from the exact velocity gradient of a translating sphere, relative to that
+gradient's largest entry on the points.
+
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
 
@@ -66,6 +72,7 @@ def print_help_and_exit():
           "-field <int> : (not a flag of the reference) the solved layer's velocity on N points at r = 3, by the Direct sum\n"
           "-field_fmm <int> : (not a flag of the reference) the same velocity by the FMM (plan.field_plan)\n"
           "-field_pressure : (not a flag of the reference) with -field_fmm: the pressure on the same points (execute_pressure)\n"
+          "-field_stress : (not a flag of the reference) with -field_fmm: the velocity gradient and stress on the same points\n"
           "-help : print this message")
     sys.exit(0)
 
@@ -94,7 +101,7 @@ def main(argv):
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
     rbc, near_f32, field, field_fmm = False, 0, 0, 0
-    stokes_batch, resistance, field_pressure = 0, False, False
+    stokes_batch, resistance, field_pressure, field_stress = 0, False, False, False
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -154,12 +161,17 @@ def main(argv):
             i += 1; field_fmm = int(argv[i])
         elif a == "-field_pressure":                       # not in the reference: the pressure through fplan.execute_pressure
             field_pressure = True
+        elif a == "-field_stress":                         # not in the reference: fplan.execute_velocity_gradient / execute_stress
+            field_stress = True
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
     so.max_p, so.p_min, so.max_iters, so.restart = p, p_min, 100, 100
     if field_pressure and field_fmm <= 0:
         raise SystemExit("-field_pressure: needs -field_fmm N (the pressure is evaluated on the field plan's points)")
+
+    if field_stress and field_fmm <= 0:
+        raise SystemExit("-field_stress: needs -field_fmm N (the stress is evaluated on the field plan's points)")
 
     if vert or face:
         print("reading mesh from %s, %s" % (vert, face))
@@ -256,6 +268,8 @@ def main(argv):
         plan.kernel().set_p(p)                             # (the relaxed solve leaves the kernel at its last order)
         uf = fplan.execute_torch(x).cpu().numpy()
         q = fplan.execute_pressure_torch(x).cpu().numpy() if field_pressure else None
+        gu = fplan.execute_velocity_gradient_torch(x).cpu().numpy() if field_stress else None
+        sig = fplan.execute_stress(x.cpu().numpy()) if field_stress else None
         fplan.close()
         mag = np.linalg.norm(uf, axis=1)
         print("field (FMM): %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field_fmm, float(mag.max()), float(mag.mean())))
@@ -268,6 +282,25 @@ def main(argv):
                 pts = sphere_points(field_fmm, 3.0)
                 dev_q = np.abs(q / (6 * math.pi * mu) - pts[:, 0] / 27.0).max() * 9.0
                 print("field pressure against the translating sphere's: largest deviation %.3e of 1/9" % float(dev_q))
+        if gu is not None:
+            print("field velocity gradient (FMM): %d points at r = 3, max |G|: %.6e, mean |G|: %.6e" % (field_fmm, float(np.abs(gu).max()), float(np.abs(gu).mean())))
+            print("field stress (FMM): %d points at r = 3, max |sigma|: %.6e, mean |sigma|: %.6e" % (field_fmm, float(np.abs(sig).max()), float(np.abs(sig).mean())))
+            if not (rbc or mesh or vert or face):
+                # a unit sphere translating with e_x: u = 3/4 (e_x / r + x x_1 / r^3) + 1/4 (e_x / r^3 - 3 x x_1 / r^5); its gradient
+                # by central differences of that closed form (h = 1e-4: 1e-11 of it, far below the discretisation's error)
+                def u_exact(y):
+                    r = np.linalg.norm(y, axis=1)[:, None]
+                    ex = np.zeros_like(y)
+                    ex[:, 0] = 1
+                    return 0.75 * (ex / r + y * y[:, 0:1] / r ** 3) + 0.25 * (ex / r ** 3 - 3 * y * y[:, 0:1] / r ** 5)
+                pts = sphere_points(field_fmm, 3.0)
+                ge = np.empty((field_fmm, 3, 3))
+                for m_ in range(3):
+                    e_ = np.zeros(3)
+                    e_[m_] = 1e-4
+                    ge[:, :, m_] = (u_exact(pts + e_) - u_exact(pts - e_)) / 2e-4
+                dev_g = np.abs(gu / (4 * math.pi) - ge).max() / np.abs(ge).max()
+                print("field velocity gradient against the translating sphere's: largest deviation %.3e of its largest entry" % float(dev_g))
     if resistance:
         # unit translation e_j on every panel: the right-hand side 4 pi e_j (as b above), the force of the solved traction
         B = torch.zeros((3, n, 3), dtype=torch.float64, device=dev)

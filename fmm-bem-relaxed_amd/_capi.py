@@ -110,6 +110,7 @@ SYMBOLS = (
     "fmmbem_plan_create_field",
     "fmmbem_plan_execute_gradient", "fmmbem_plan_execute_gradient_device", "fmmbem_kernel_gradient_entries",
     "fmmbem_plan_execute_pressure", "fmmbem_plan_execute_pressure_device", "fmmbem_kernel_pressure_entries",
+    "fmmbem_plan_execute_velocity_gradient", "fmmbem_plan_execute_velocity_gradient_device", "fmmbem_kernel_velocity_gradient_entries",
 )
 
 
@@ -221,6 +222,9 @@ def lib():
     L.fmmbem_plan_execute_pressure.argtypes = [vp, i32, vp, vp]
     L.fmmbem_plan_execute_pressure_device.argtypes = [vp, i32, vp, vp, vp]
     L.fmmbem_kernel_pressure_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp]
+    L.fmmbem_plan_execute_velocity_gradient.argtypes = [vp, i32, vp, vp]
+    L.fmmbem_plan_execute_velocity_gradient_device.argtypes = [vp, i32, vp, vp, vp]
+    L.fmmbem_kernel_velocity_gradient_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp]
     _lib = L
     return L
 

@@ -92,6 +92,15 @@ hipError_t launch_near_pressure(const DevicePlan& d, int64_t n_src, double* q_tr
 hipError_t launch_l2p_pressure(const DevicePlan& d, int p, int64_t n_src, double* q_tree, hipStream_t s);
 hipError_t launch_pressure_scatter(const DevicePlan& d, int64_t n_src, const double* q_tree, double* out, hipStream_t s);
 hipError_t launch_pressure_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
+// ---- field velocity gradient (kernels_velgrad.hip; Stokes field plans whose targets are all VELOCITY targets) ----
+// g_tree: nine doubles per target row [k][m], tree order.  near: g_tree[row] = the near pairs' sums, every target row written
+// (zeros where the leaf has no near pair); l2p: g_tree[row] += (1 / 2 mu) [d_m phi_k - d_k phi_m - x_e d_k d_m phi_e + d_k d_m phi_3]
+// of the leaf's local expansions (slots 0..3; nothing at p = 1); scatter: out[perm[row]] = g_tree[row - n_src]; entries: Gamma
+// (27 doubles [k][m][e]) for pairs laid out as launch_kernel_entries takes them
+hipError_t launch_near_velgrad(const DevicePlan& d, int64_t n_src, double* g_tree, hipStream_t s);
+hipError_t launch_l2p_velgrad(const DevicePlan& d, int p, int64_t n_src, double* g_tree, hipStream_t s);
+hipError_t launch_velgrad_scatter(const DevicePlan& d, int64_t n_src, const double* g_tree, double* out, hipStream_t s);
+hipError_t launch_velgrad_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

@@ -427,6 +427,68 @@ __device__ inline V3 stokes_pressure_entry(const DevicePlan& d, V3 t, int64_t j)
   return out;
 }
 
+// The velocity gradient of the single layer at a point t off the surface (include/fmmbem.h, "Field velocity gradient"): per
+// (target point, source panel j) with charge f the nine doubles G[3 k + m] = d u'_k / d t_m WITHOUT the 1/(2 mu),
+//   G[k][m] += sum_q w_q A_j [ (-f_k d_m + delta_km s + d_k f_m) / r^3 - 3 s d_k d_m / r^5 ],   d = t - y_q,  s = d . f
+// ADDED to G: the near kernel of the gradient execute contracts every point with the panel's f in place, straight into a row's
+// nine sums; fmmbem_kernel_velocity_gradient_entries takes f = e_0, e_1, e_2 for the 27 numbers [k][m][e] (kernels_velgrad.hip).
+// The regimes and the shortcut of the regime test are the pressure's above (dist < 1e-8: nothing added); a point with
+// |d_q|^2 < 1e-8 adds 0.  One reciprocal square root per point, no division.  The ONE text of the tensor, in the two parts of
+// the pressure: stokes_velgrad_far_from adds a pair in the far regime (nothing for a self pair) or says `deferred`;
+// stokes_velgrad_near the K_fine rule on the vertices of panel j.
+__device__ __forceinline__ void velgrad_point(double (&G)[9], double wA, V3 t, V3 pnt, V3 f) {
+  const V3 dd = sub(t, pnt);
+  const double r2 = dd.x * dd.x + dd.y * dd.y + dd.z * dd.z;
+  const double ri = rsqrt(r2);
+  const double ri2 = ri * ri;
+  const double f3 = r2 < 1e-8 ? 0.0 : wA * (ri2 * ri);
+  const double f5 = r2 < 1e-8 ? 0.0 : 3 * (wA * (ri2 * ri)) * ri2;
+  const double s = dd.x * f.x + dd.y * f.y + dd.z * f.z;
+  const double a = f3 * s, b = f5 * s;
+  const double dv[3] = {dd.x, dd.y, dd.z}, fv[3] = {f.x, f.y, f.z};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+      G[3 * k + m] += f3 * (dv[k] * fv[m] - fv[k] * dv[m]) + (k == m ? a : 0.0) - b * dv[k] * dv[m];
+}
+template <class Quad>
+__device__ __forceinline__ bool stokes_velgrad_far_from(const DevicePlan& d, V3 t, V3 c, double A, Quad&& quad, V3 f, double (&G)[9]) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  // the regime by the expressions of stokes_pressure_far_from, with its shortcut: where 8 A < 0.99 dist^2 no square root, no division
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {
+    const double dist = sqrt(d2);
+    if (dist < 1e-8) return false;
+    if (sqrt(2 * A) / dist >= 0.5) return true;
+  }
+  for (int q = 0; q < d.nq; ++q) velgrad_point(G, d.qw[q] * A, t, quad(q), f);
+  return false;
+}
+__device__ inline void stokes_velgrad_near(const DevicePlan& d, V3 t, int64_t j, double A, V3 f, double (&G)[9]) {
+  const int64_t N = d.n;
+  const V3 v0 = {d.vert[0 * N + j], d.vert[1 * N + j], d.vert[2 * N + j]};
+  const V3 v1 = {d.vert[3 * N + j], d.vert[4 * N + j], d.vert[5 * N + j]};
+  const V3 v2 = {d.vert[6 * N + j], d.vert[7 * N + j], d.vert[8 * N + j]};
+  for (int q = 0; q < d.nqf; ++q) {
+    const V3 pt = {v0.x * d.qf[4 * q + 0] + v1.x * d.qf[4 * q + 1] + v2.x * d.qf[4 * q + 2],
+                   v0.y * d.qf[4 * q + 0] + v1.y * d.qf[4 * q + 1] + v2.y * d.qf[4 * q + 2],
+                   v0.z * d.qf[4 * q + 0] + v1.z * d.qf[4 * q + 1] + v2.z * d.qf[4 * q + 2]};
+    velgrad_point(G, d.qf[4 * q + 3] * A, t, pt, f);
+  }
+}
+// G = (1 / 2 mu) x the tensor of the pair (t, panel j) contracted with f: what fmmbem_kernel_velocity_gradient_entries returns
+__device__ inline void stokes_velgrad_entry(const DevicePlan& d, V3 t, int64_t j, V3 f, double (&G)[9]) {
+  const int64_t N = d.n;
+  const double A = d.area[j];
+  for (int c = 0; c < 9; ++c) G[c] = 0;
+  if (stokes_velgrad_far_from(d, t, V3{d.cx[j], d.cy[j], d.cz[j]}, A,
+                              [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; }, f, G))
+    stokes_velgrad_near(d, t, j, A, f, G);
+  const double sc = 1. / 2 / d.mu;
+  for (int c = 0; c < 9; ++c) G[c] *= sc;
+}
+
 }  // namespace
 
 }  // namespace fmmbem

@@ -274,6 +274,13 @@ struct fmmbem_plan {
   int pressure_refusal(int p) const;
   int pressure_alloc();
   int run_pressure(int p, const double* d_x, double* d_q, hipStream_t s);
+  // Field velocity gradient (fmmbem_plan_execute_velocity_gradient; the plans of the pressure): nine doubles per target row in tree
+  // order, per distinct point (only when some targets coincide) and per given target (the host form's staging); allocated at the
+  // first velocity-gradient call
+  double *vg_tree = nullptr, *vg_points = nullptr, *stage_vg = nullptr;
+  int velgrad_refusal(int p) const;
+  int velgrad_alloc();
+  int run_velocity_gradient(int p, const double* d_x, double* d_g, hipStream_t s);
 
   template <class V, class T>
   int upload(const V& v, const T** out) { return mem->upload(v, out); }
@@ -1157,6 +1164,62 @@ int fmmbem_plan::run_pressure(int p, const double* d_x, double* d_q, hipStream_t
   if (d_target_point) {
     const int64_t nt = hp.n_targets;
     hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, pres_points, d_q, nt, 1);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(tm.end(Stage::Scatter, s));
+  last_p = p;
+  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
+  return FMMBEM_OK;
+}
+
+// ======================================= field velocity gradient =======================================
+// the refusals of a velocity-gradient execute after the null checks, in the order include/fmmbem.h states them (the pressure's)
+int fmmbem_plan::velgrad_refusal(int p) const {
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: on a plan over separate targets only (fmmbem_plan_create_field)");
+  if (opts.kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: Stokes plans only");
+  if (has_bc[1]) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: VELOCITY targets only (the gradient of the double layer is not built)");
+  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan::velgrad_alloc() {
+  const size_t rows = (size_t)(hp.n - hp.n_src);
+  if (!vg_tree) TRY(alloc(9 * rows, &vg_tree, false));
+  if (d_target_point && !vg_points) TRY(alloc(9 * rows, &vg_points, false));
+  if (!stage_vg) TRY(alloc(9 * (size_t)hp.n_targets, &stage_vg, false));
+  return FMMBEM_OK;
+}
+
+// The velocity-gradient execute (include/fmmbem.h "Field velocity gradient"), after run_pressure and in its form: run()'s gather,
+// P2M and far chain up to and including L2L on the plan's own M and L, then the two kernels of kernels_velgrad.hip into vg_tree and
+// the delivery.  Launched plainly (never captured, never replayed; `graphs` is not touched), it writes x_tree, M, Mh and L, which
+// every potential execute writes afresh before it reads them, and leaves y_tree alone.
+int fmmbem_plan::run_velocity_gradient(int p, const double* d_x, double* d_g, hipStream_t s) {
+  if (!d_x || !d_g) return fail(FMMBEM_ERR_INVALID, "null vector");
+  TRY(velgrad_refusal(p));
+  DEVICE_SCOPE(opts.device);
+  TRY(velgrad_alloc());
+  const int64_t ring = ev_count % kRing;
+  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
+  HIP_TRY(tm.begin(Stage::Gather, s));
+  DevicePlan dg = d;
+  dg.n = hp.n_src;                                     // x: the source panels only (the target rows of x_tree stay 0)
+  HIP_TRY(launch_gather_x(dg, d_x, s));
+  HIP_TRY(tm.end(Stage::Gather, s));
+  TRY(p2m(d, p, tm, s));
+  TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
+  HIP_TRY(tm.begin(Stage::Spmv, s));
+  HIP_TRY(launch_near_velgrad(d, hp.n_src, vg_tree, s));
+  HIP_TRY(tm.end(Stage::Spmv, s));
+  HIP_TRY(tm.begin(Stage::L2P, s));
+  HIP_TRY(launch_l2p_velgrad(d, p, hp.n_src, vg_tree, s));
+  HIP_TRY(tm.end(Stage::L2P, s));
+  HIP_TRY(tm.begin(Stage::Scatter, s));
+  HIP_TRY(launch_velgrad_scatter(d, hp.n_src, vg_tree, d_target_point ? vg_points : d_g, s));
+  if (d_target_point) {
+    const int64_t nu = 9 * (int64_t)hp.n_targets;      // unknowns, one thread each
+    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, vg_points, d_g, nu, 9);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(tm.end(Stage::Scatter, s));
@@ -2049,6 +2112,26 @@ int fmmbem_plan_execute_pressure(fmmbem_plan* plan, int p, const double* x, doub
   return FMMBEM_OK;
 }
 
+// ---- field velocity gradient (include/fmmbem.h) ----
+int fmmbem_plan_execute_velocity_gradient_device(fmmbem_plan* plan, int p, const double* d_x, double* d_G, void* stream) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  return plan->run_velocity_gradient(p, d_x, d_G, static_cast<hipStream_t>(stream));
+}
+
+int fmmbem_plan_execute_velocity_gradient(fmmbem_plan* plan, int p, const double* x, double* G) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!x || !G) return fail(FMMBEM_ERR_INVALID, "null vector");
+  TRY(plan->velgrad_refusal(p));                       // a refusal touches neither pointer
+  DEVICE_SCOPE(plan->opts.device);
+  TRY(plan->velgrad_alloc());
+  hipStream_t s = plan->own_stream;
+  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
+  TRY(plan->run_velocity_gradient(p, plan->stage_x, plan->stage_vg, s));
+  HIP_TRY(hipMemcpyAsync(G, plan->stage_vg, sizeof(double) * 9 * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
 // ---- batched execute (include/fmmbem.h) ----
 static int batch_args(const fmmbem_plan* plan, int k, const void* x, size_t ldx, const void* y, size_t ldy) {
   if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
@@ -2677,6 +2760,47 @@ int fmmbem_kernel_pressure_entries(const fmmbem_options* opts, size_t n, const d
   TRY(mem.alloc(3 * n, &d_out));
   HIP_TRY(launch_pressure_entries(d, (int)n, d_out, nullptr));
   HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  return FMMBEM_OK;
+}
+
+int fmmbem_kernel_velocity_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices,
+                                            const double* source_vertices, double* out) {
+  if (!opts || !target_vertices || !source_vertices || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  if (opts->kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: the Stokes kernel only");
+  if (n == 0) return FMMBEM_OK;
+  if (n > ((size_t)1 << 26)) return fail(FMMBEM_ERR_INVALID, "too many pairs");
+  QuadRule rule, fine;
+  if (!quad_rule(opts->quad_k, rule)) return fail(FMMBEM_ERR_INVALID, "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)");
+  if (!quad_rule(opts->quad_k_fine, fine)) return fail(FMMBEM_ERR_INVALID, "invalid K_fine (valid: 1 3 4 7 13 17 19 25 79)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
+  if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
+  DEVICE_SCOPE(opts->device);
+  const int64_t N = 2 * (int64_t)n;                    // the layout of fmmbem_kernel_entries: panels [0, n) targets, [n, 2n) sources
+  PanelSoA P;
+  std::vector<double> qf((size_t)fine.n * 4);
+  try {
+    alloc_panels(P, N, rule.n);
+  } catch (const std::bad_alloc&) {
+    return fail(FMMBEM_ERR_ALLOC, "host allocation failed");
+  }
+  for (size_t i = 0; i < n; ++i) {
+    fill_panel(P, N, (int64_t)i, target_vertices + 9 * i, rule, 0);
+    fill_panel(P, N, (int64_t)(n + i), source_vertices + 9 * i, rule, 0);
+  }
+  for (int q = 0; q < fine.n; ++q) { for (int k = 0; k < 3; ++k) qf[4 * q + k] = fine.pts[q][k]; qf[4 * q + 3] = fine.w[q]; }
+  Scratch mem;
+  DevicePlan d{};
+  d.n = N; d.nq = rule.n; d.nqf = fine.n; d.kernel = opts->kernel; d.dof = 3; d.mu = opts->mu;
+  for (int q = 0; q < rule.n; ++q) d.qw[q] = rule.w[q];
+  TRY(mem.up(P.cx.data(), P.cx.size(), &d.cx)); TRY(mem.up(P.cy.data(), P.cy.size(), &d.cy)); TRY(mem.up(P.cz.data(), P.cz.size(), &d.cz));
+  TRY(mem.up(P.area.data(), P.area.size(), &d.area)); TRY(mem.up(P.quad.data(), P.quad.size(), &d.quad));
+  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert)); TRY(mem.up(qf.data(), qf.size(), &d.qf));
+  double* d_out = nullptr;
+  TRY(mem.alloc(27 * n, &d_out));
+  HIP_TRY(launch_velgrad_entries(d, (int)n, d_out, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 27 * n, hipMemcpyDeviceToHost));
   return FMMBEM_OK;
 }
 

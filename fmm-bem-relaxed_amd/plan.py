@@ -309,6 +309,26 @@ def kernel_pressure_entries(K, targets, sources, device=0):
     return out
 
 
+def kernel_velocity_gradient_entries(K, targets, sources, device=0):
+    """Gamma(target_i, source_i) of the field velocity gradient for n pairs (fmmbem_kernel_velocity_gradient_entries): the tensor
+    with G[k][m] += sum_e Gamma[k][m][e] x_j[e], the 1/(2 mu) included, by the function FMM_plan.execute_velocity_gradient's near
+    kernel calls.  targets, sources: (n, 3, 3) vertices -- the target POINT is the target panel's centroid.  Stokes only.
+    Returns (n, 3, 3, 3)."""
+    t = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 9)
+    s = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 9)
+    if t.shape != s.shape:
+        raise ValueError("one source per target")
+    o = _capi.Options()
+    _capi.lib().fmmbem_options_default(C.byref(o))
+    o.quad_k, o.device = K.K, int(device)
+    if isinstance(K, StokesSphericalBEM):
+        o.kernel, o.mu, o.quad_k_fine = _capi.KERNEL_STOKES_BEM, K.Mu, K.K_fine
+    out = np.empty((len(t), 3, 3, 3))
+    _capi.check(_capi.lib().fmmbem_kernel_velocity_gradient_entries(C.byref(o), len(t), t.ctypes.data_as(C.c_void_p),
+                                                                    s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class Direct:
     """Direct::matvec (include/Direct.hpp:232-302) on the device: y_i = sum_j K(t_i, s_j) x_j over ALL the panels, every entry the
     one kernel_entries gives for that pair (fmmbem_direct_*, csrc/kernels_direct.hip).  Laplace and Stokes; no tree, no matrix.
@@ -745,6 +765,49 @@ class FMM_plan:
             raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
         self.execute_pressure_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
+
+    # ---- field velocity gradient and stress of the Stokes single layer at the points of a field plan ----
+    def execute_velocity_gradient(self, traction):
+        """(N, 3) or (3N,) traction density -> (M, 3, 3): G_i[k][m] = d u'_k / d t_m at the kernel's current p, u' what execute
+        returns (include/fmmbem.h, "Field velocity gradient"; the physical gradient is G / 4 pi).  numpy in, numpy out (host).
+        FmmBemError (status 6) on a plan that is not over separate targets, on a Laplace plan, on a plan with a TRACTION target and
+        on a host-only plan."""
+        x = np.ascontiguousarray(traction, dtype=np.float64)
+        if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
+            raise ValueError("charges must have dof values per panel")
+        g = np.empty((self._pressure_rows(), 3, 3))
+        _capi.check(_capi.lib().fmmbem_plan_execute_velocity_gradient(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
+                                                                      g.ctypes.data_as(C.c_void_p)))
+        return g
+
+    def execute_velocity_gradient_device(self, x_ptr, g_ptr, stream=0, p=None):
+        _capi.check(_capi.lib().fmmbem_plan_execute_velocity_gradient_device(self._h, self._K.P if p is None else int(p),
+                                                                             C.c_void_p(x_ptr), C.c_void_p(g_ptr), C.c_void_p(stream)))
+
+    def execute_velocity_gradient_torch(self, x, out=None, p=None):
+        """x: contiguous float64 CUDA tensor with 3 values per panel, ORIGINAL panel order; returns (M, 3, 3).  Runs on torch's
+        current stream."""
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
+            raise ValueError("x must be a contiguous float64 CUDA tensor with dof values per panel")
+        if x.device.index != self.device:
+            raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
+        shape = (self._pressure_rows(), 3, 3)
+        if out is None:
+            out = x.new_empty(shape)
+        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
+        self.execute_velocity_gradient_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
+        return out
+
+    def execute_stress(self, traction):
+        """(N, 3) or (3N,) traction density -> (M, 3, 3): sigma_i[k][m] = -q_i delta_km + mu (G_i[k][m] + G_i[m][k]), q of
+        execute_pressure and G of execute_velocity_gradient, in their scaling: the physical stress is the result / 4 pi.  TWO
+        executes, one pressure and one gradient, and each runs the far chain (gather, P2M, M2M, M2L, L2L); an execute that fuses
+        them is not built."""
+        q = self.execute_pressure(traction)
+        g = self.execute_velocity_gradient(traction)
+        return -q[:, None, None] * np.eye(3)[None] + self._K.Mu * (g + g.transpose(0, 2, 1))
 
     # ---- batched execute: k vectors, one near-field pass per batch_width() of them (fmmbem_plan_execute_batch) ----
     def execute_batch(self, charges):

@@ -384,6 +384,38 @@ int fmmbem_plan_execute_gradient_device(fmmbem_plan *plan, int p, const double *
 int fmmbem_plan_execute_pressure(fmmbem_plan *plan, int p, const double *x /* n x 3 */, double *q /* n_targets */);
 int fmmbem_plan_execute_pressure_device(fmmbem_plan *plan, int p, const double *d_x, double *d_q, void *stream);
 
+/* ---- Field velocity gradient: the gradient of the Stokes single layer's velocity at the points of a field plan ---------------
+ * (no reference counterpart: with the pressure above it gives the stress sigma = -p I + mu (grad u + grad u^T) off the surface).
+ * On a Stokes plan of fmmbem_plan_create_field whose targets are all VELOCITY targets, for target i with point t_i,
+ *   G_i[k][m] = d u'_k / d t_m,   nine doubles, row-major,
+ * u' what the plan's execute returns there: u' = (1/2mu) int (I/r + d d^T/r^3) f dS = 4 pi u.  The scaling is execute's, the
+ * 1/(2 mu) included; the physical gradient is G / (4 pi).
+ * Near pairs: with d = t - y_q and s = d . f_j,
+ *   G[k][m] += (1/2mu) sum_q w_q A_j [ (-f_k d_m + delta_km s + d_k f_m) / r^3 - 3 s d_k d_m / r^5 ].
+ * The rule is chosen as the pressure chooses it: dist = |t - c_j|; dist < 1e-8: the pair contributes 0 -- the gradient jumps
+ * across the layer, and a point ON it is the caller's business; otherwise sqrt(2 A_j) / dist >= 0.5: the K_fine rule on the
+ * vertices; otherwise the K stored points.  A quadrature point with |d_q|^2 < 1e-8 contributes 0.
+ * The far field: with phi_0..phi_3 the four local expansions of the leaf after L2L and x the target's own coordinates,
+ *   G[k][m] += (1/2mu) [ d_m phi_k - d_k phi_m - x_e d_k d_m phi_e + d_k d_m phi_3 ].
+ * The second derivatives are first derivatives of the expansions of order p - 1 that d_x phi, d_y phi, d_z phi are, their
+ * coefficients linear in L: no second derivative by the spherical chain rule, one division by sin(alpha) per row.  An order p
+ * execute has the Hessian terms of degrees below p - 1 only: at p = 1 the far half is 0, at p = 2 only its antisymmetric part is
+ * not.  Both halves are trace-free term by term (every quadrature point's tensor, every R_nm harmonic): G[0][0] + G[1][1] +
+ * G[2][2] is rounding-level.
+ * x: n_panels x 3 doubles; G: n_targets x 9 doubles, both in the caller's order; coincident targets each get their copy.
+ * The execute is the velocity execute's gather, P2M, M2M, M2L and L2L, then two kernels of its own -- the near pairs matrix-free
+ * (a row's nine sums: the leaf's near list in order, panels ascending, quadrature points in order) and the far field above (terms
+ * m-major) -- and the delivery: the same bits every run.  Its buffers are allocated at the first call (FMMBEM_ERR_ALLOC if that
+ * fails; the plan stays usable).  Checked in this order: a null plan or vector -> FMMBEM_ERR_INVALID; p outside 1..p_max ->
+ * _INVALID; a plan that is not over separate targets -> _UNSUPPORTED; a Laplace plan -> _UNSUPPORTED; a plan with any TRACTION
+ * target -> _UNSUPPORTED; a host-only plan -> _UNSUPPORTED; the handle stays usable and neither pointer is touched.  It is
+ * launched plainly, kernel by kernel, whatever fmmbem_plan_set_graphs says, and leaves the captured graphs of the velocity
+ * execute as they are.  With stage timing on it is recorded as an execute: ms_near is the near kernel of the gradient, ms_l2p its
+ * far-field kernel.  No batches.  fmmbem_plan_execute_gradient goes on refusing Stokes plans.
+ * The host form takes HOST pointers and returns when G is written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_velocity_gradient(fmmbem_plan *plan, int p, const double *x /* n x 3 */, double *G /* n_targets x 9 */);
+int fmmbem_plan_execute_velocity_gradient_device(fmmbem_plan *plan, int p, const double *d_x, double *d_G, void *stream);
+
 /* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
  * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES
  * iteration on that operator instead).  A BLOCK_DIAGONAL plan holds every leaf's self block assembled in HBM; build inverts
@@ -463,6 +495,12 @@ int fmmbem_kernel_gradient_entries(const fmmbem_options *opts, size_t n, const d
  * (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, quad_k_fine, device.  out: n x 3. */
 int fmmbem_kernel_pressure_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
                                    const double *source_vertices, double *out /* n x 3 */);
+/* Gamma(target, source) of the field velocity gradient (see fmmbem_plan_execute_velocity_gradient) for n independent pairs, by
+ * the function the execute's near kernel calls, with f left open: G[k][m] += sum_e out[k][m][e] f_e, the 1/(2 mu) included.  The
+ * target POINT is the centroid of target_vertices' panel i.  Stokes only (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel,
+ * mu, quad_k, quad_k_fine, device.  out: n x 27, [k][m][e]. */
+int fmmbem_kernel_velocity_gradient_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
+                                            const double *source_vertices, double *out /* n x 27 */);
 
 /* ---- the translation operators one at a time: the KernelSkeleton contract (kernel/KernelSkeleton.hpp:62-212) --------------
  * What the reference's kernel classes offer beside operator(): P2M, M2M, M2L, L2L, L2P as kernel/LaplaceSphericalBEM.hpp:307-476

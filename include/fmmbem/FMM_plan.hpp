@@ -17,6 +17,7 @@
 // the device, and without a HIP device the constructor throws.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -610,6 +611,29 @@ class PlanAdapter {
     if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
     check(fmmbem_plan_execute_pressure(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()));
     return results;
+  }
+  // Not in the reference: the gradient of that velocity at the points of a field plan whose points are all VELOCITY targets
+  // (fmmbem_plan_execute_velocity_gradient): result i is G[k][m] = d u'_k / d t_m, nine doubles row-major, u' what execute() returns
+  // (the physical gradient is G / 4 pi).  The refusals are execute_pressure's.
+  std::vector<std::array<double, 9>> execute_velocity_gradient(const std::vector<charge_type>& charges) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
+    std::vector<std::array<double, 9>> results(has_targets_ ? target_bc_.size() : charges.size());
+    if (K.p() > p_max_) create(K.p());
+    check(fmmbem_plan_execute_velocity_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
+    return results;
+  }
+  // Not in the reference: the stress sigma[k][m] = -q delta_km + mu (G[k][m] + G[m][k]) from one execute_pressure and one
+  // execute_velocity_gradient, in their scaling (the physical stress is the result / 4 pi).  Two executes: each runs the far chain.
+  std::vector<std::array<double, 9>> execute_stress(const std::vector<charge_type>& charges) {
+    const std::vector<double> q = execute_pressure(charges);
+    std::vector<std::array<double, 9>> g = execute_velocity_gradient(charges);
+    for (size_t i = 0; i < g.size(); ++i) {
+      std::array<double, 9> s;
+      for (int k = 0; k < 3; ++k)
+        for (int m = 0; m < 3; ++m) s[3 * k + m] = -q[i] * (k == m ? 1.0 : 0.0) + K.Mu * (g[i][3 * k + m] + g[i][3 * m + k]);
+      g[i] = s;
+    }
+    return g;
   }
   // preconditioner-style operator()(x, y) (examples/BEM/Preconditioner.hpp:11-15)
   void operator()(const std::vector<charge_type>& x, std::vector<result_type>& y) { y = execute(x); }
