@@ -76,31 +76,20 @@ struct M2PWork {
 };
 // y[i] += (POTENTIAL row) or -= (NORMAL_DERIV row) the sum over the row's chain of M2P(M[source], centre[source], centroid i); Laplace
 hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, hipStream_t s);
-// ---- field gradient (kernels_grad.hip; Laplace plans over separate targets, whose target rows begin at n_src) ----
-// g_tree: 3 doubles per target row, tree order.  near: g_tree[row] = the near pairs' sum, every target row written (zeros where
-// the leaf has no near pair); l2p: g_tree[row] += (flag 0) or -= (flag 1) the gradient of the leaf's local expansion;
-// scatter: out[3 perm[row] ..] = g_tree[3 (row - n_src) ..]; entries: gamma for pairs laid out as launch_kernel_entries takes them
-hipError_t launch_near_grad(const DevicePlan& d, int64_t n_src, double* g_tree, hipStream_t s);
-hipError_t launch_l2p_grad(const DevicePlan& d, int p, int64_t n_src, double* g_tree, hipStream_t s);
-hipError_t launch_grad_scatter(const DevicePlan& d, int64_t n_src, const double* g_tree, double* out, hipStream_t s);
-hipError_t launch_grad_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
-// ---- field pressure (kernels_pressure.hip; Stokes field plans whose targets are all VELOCITY targets) ----
-// q_tree: one double per target row, tree order.  near: q_tree[row] = the near pairs' sum, every target row written (0 where the
-// leaf has no near pair); l2p: q_tree[row] -= d_x phi_0 + d_y phi_1 + d_z phi_2 of the leaf's local expansions (slots 0..2);
-// scatter: out[perm[row]] = q_tree[row - n_src]; entries: pi (3 doubles) for pairs laid out as launch_kernel_entries takes them
-hipError_t launch_near_pressure(const DevicePlan& d, int64_t n_src, double* q_tree, hipStream_t s);
-hipError_t launch_l2p_pressure(const DevicePlan& d, int p, int64_t n_src, double* q_tree, hipStream_t s);
-hipError_t launch_pressure_scatter(const DevicePlan& d, int64_t n_src, const double* q_tree, double* out, hipStream_t s);
-hipError_t launch_pressure_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
-// ---- field velocity gradient (kernels_velgrad.hip; Stokes field plans whose targets are all VELOCITY targets) ----
-// g_tree: nine doubles per target row [k][m], tree order.  near: g_tree[row] = the near pairs' sums, every target row written
-// (zeros where the leaf has no near pair); l2p: g_tree[row] += (1 / 2 mu) [d_m phi_k - d_k phi_m - x_e d_k d_m phi_e + d_k d_m phi_3]
-// of the leaf's local expansions (slots 0..3; nothing at p = 1); scatter: out[perm[row]] = g_tree[row - n_src]; entries: Gamma
-// (27 doubles [k][m][e]) for pairs laid out as launch_kernel_entries takes them
-hipError_t launch_near_velgrad(const DevicePlan& d, int64_t n_src, double* g_tree, hipStream_t s);
-hipError_t launch_l2p_velgrad(const DevicePlan& d, int p, int64_t n_src, double* g_tree, hipStream_t s);
-hipError_t launch_velgrad_scatter(const DevicePlan& d, int64_t n_src, const double* g_tree, double* out, hipStream_t s);
-hipError_t launch_velgrad_entries(const DevicePlan& d, int m, double* out, hipStream_t s);
+// ---- field quantities (kernels_field.hip; plans over separate targets, whose target rows begin at n_src) ----
+// Gradient: Laplace plans, 3 doubles per target row; Pressure (1) and VelocityGradient (9, [k][m]): Stokes field plans whose targets
+// are all VELOCITY targets.  tree: width doubles per target row, tree order.
+// near: tree[row] = the near pairs' sums, every target row written (zeros where the leaf has no near pair);
+// l2p: tree[row] += what the quantity reads of the leaf's local expansions -- + (flag 0) or - (flag 1) the gradient of the row's
+//      slot; - (d_x phi_0 + d_y phi_1 + d_z phi_2) of slots 0..2; (1 / 2 mu) [d_m phi_k - d_k phi_m - x_e d_k d_m phi_e + d_k d_m phi_3]
+//      of slots 0..3 (nothing at p = 1);
+// scatter: out[width perm[row] ..] = tree[width (row - n_src) ..];
+// entries: gamma (3 doubles), pi (3) or Gamma (27, [k][m][e]) for pairs laid out as launch_kernel_entries takes them
+enum class FieldQuantity { Gradient, Pressure, VelocityGradient };
+hipError_t launch_near_field(FieldQuantity q, const DevicePlan& d, int64_t n_src, double* tree, hipStream_t s);
+hipError_t launch_l2p_field(FieldQuantity q, const DevicePlan& d, int p, int64_t n_src, double* tree, hipStream_t s);
+hipError_t launch_field_scatter(FieldQuantity q, const DevicePlan& d, int64_t n_src, const double* tree, double* out, hipStream_t s);
+hipError_t launch_field_entries(FieldQuantity q, const DevicePlan& d, int m, double* out, hipStream_t s);
 hipError_t launch_near_assemble_stokes(const DevicePlan& d, hipStream_t s);
 hipError_t launch_p2m_stokes(const DevicePlan& d, int p, hipStream_t s);
 hipError_t launch_l2p_stokes(const DevicePlan& d, int p, double* y, hipStream_t s);

@@ -262,25 +262,14 @@ struct fmmbem_plan {
   const uint32_t* d_target_point = nullptr;                    // given target -> distinct point (only when some coincide)
   double* y_points = nullptr;                                  // the result per distinct point (only when some coincide)
   double* stage_y_targets = nullptr;                           // device staging of y for host-pointer execute
-  // Field gradient (fmmbem_plan_execute_gradient; Laplace dual plans): 3 doubles per target row in tree order, per distinct point
-  // (only when some targets coincide) and per given target (the host form's staging); allocated at the first gradient call
-  double *grad_tree = nullptr, *grad_points = nullptr, *stage_g = nullptr;
-  int grad_alloc();
-  int run_gradient(int p, const double* d_x, double* d_g, hipStream_t s);
-  // Field pressure (fmmbem_plan_execute_pressure; Stokes field plans of VELOCITY targets): one double per target row in tree order,
-  // per distinct point (only when some targets coincide) and per given target (the host form's staging); allocated at the first
-  // pressure call
-  double *pres_tree = nullptr, *pres_points = nullptr, *stage_q = nullptr;
-  int pressure_refusal(int p) const;
-  int pressure_alloc();
-  int run_pressure(int p, const double* d_x, double* d_q, hipStream_t s);
-  // Field velocity gradient (fmmbem_plan_execute_velocity_gradient; the plans of the pressure): nine doubles per target row in tree
-  // order, per distinct point (only when some targets coincide) and per given target (the host form's staging); allocated at the
-  // first velocity-gradient call
-  double *vg_tree = nullptr, *vg_points = nullptr, *stage_vg = nullptr;
-  int velgrad_refusal(int p) const;
-  int velgrad_alloc();
-  int run_velocity_gradient(int p, const double* d_x, double* d_g, hipStream_t s);
+  // Field quantities (fmmbem_plan_execute_gradient, _pressure, _velocity_gradient; kField below): per quantity its width in doubles
+  // per target row in tree order, per distinct point (only when some targets coincide) and per given target (the host form's
+  // staging); each quantity's buffers are allocated at its first call
+  struct FieldBuffers { double *tree = nullptr, *points = nullptr, *stage = nullptr; };
+  FieldBuffers field[3];
+  int field_refusal(FieldQuantity q, int p) const;
+  int field_alloc(FieldQuantity q);
+  int run_field(FieldQuantity q, int p, const double* d_x, double* d_out, hipStream_t s);
 
   template <class V, class T>
   int upload(const V& v, const T** out) { return mem->upload(v, out); }
@@ -1067,27 +1056,62 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   return FMMBEM_OK;
 }
 
-// ======================================= field gradient =======================================
-int fmmbem_plan::grad_alloc() {
-  const size_t rows = (size_t)(hp.n - hp.n_src);
-  if (!grad_tree) TRY(alloc(3 * rows, &grad_tree, false));
-  if (d_target_point && !grad_points) TRY(alloc(3 * rows, &grad_points, false));
-  if (!stage_g) TRY(alloc(3 * (size_t)hp.n_targets, &stage_g, false));
+// ======================================= field quantities =======================================
+// What the three field executes differ in (include/fmmbem.h "Field gradient", "Field pressure", "Field velocity gradient"): the
+// doubles per target, the plans a quantity accepts and the texts of its refusals, the doubles per pair and the most pairs of its
+// fmmbem_kernel_*_entries call.  Indexed by FieldQuantity, as the plan's buffers and the launchers of kernels_field.hip are.
+struct FieldRow {
+  int width;
+  bool stokes;                                         // Stokes plans only / Laplace plans only
+  const char *needs_targets, *needs_kernel;
+  const char* no_double_layer;                         // VELOCITY targets only; null: the target's flag picks the integrand
+  int entry_width;
+  size_t max_pairs;
+  const char* entries_kernel;
+};
+static const FieldRow kField[3] = {
+    {3, false, "the field gradient: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)",
+     "the field gradient: Laplace plans only", nullptr, 3, (size_t)1 << 30, "the field gradient: the Laplace kernel only"},
+    {1, true, "the field pressure: on a plan over separate targets only (fmmbem_plan_create_field)", "the field pressure: Stokes plans only",
+     "the field pressure: VELOCITY targets only (the pressure of the double layer is not built)", 3, (size_t)1 << 30,
+     "the field pressure: the Stokes kernel only"},
+    {9, true, "the field velocity gradient: on a plan over separate targets only (fmmbem_plan_create_field)",
+     "the field velocity gradient: Stokes plans only",
+     "the field velocity gradient: VELOCITY targets only (the gradient of the double layer is not built)", 27, (size_t)1 << 26,
+     "the field velocity gradient: the Stokes kernel only"},
+};
+
+// the refusals of a field execute after the null checks, in the order include/fmmbem.h states them
+int fmmbem_plan::field_refusal(FieldQuantity q, int p) const {
+  const FieldRow& row = kField[(int)q];
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, row.needs_targets);
+  if ((opts.kernel == FMMBEM_KERNEL_STOKES_BEM) != row.stokes) return fail(FMMBEM_ERR_UNSUPPORTED, row.needs_kernel);
+  if (row.no_double_layer && has_bc[1]) return fail(FMMBEM_ERR_UNSUPPORTED, row.no_double_layer);
+  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
   return FMMBEM_OK;
 }
 
-// The gradient execute (include/fmmbem.h "Field gradient"): run()'s gather, P2M and far chain up to and including L2L on the plan's
-// own M and L -- the same launches in the same order, so the same L -- then the two kernels of kernels_grad.hip into grad_tree and
-// the delivery.  Launched plainly (never captured, never replayed; `graphs` is not touched), it writes x_tree, M, Mh and L, which
-// every potential execute writes afresh before it reads them, and leaves y_tree alone.
-int fmmbem_plan::run_gradient(int p, const double* d_x, double* d_g, hipStream_t s) {
-  if (!d_x || !d_g) return fail(FMMBEM_ERR_INVALID, "null vector");
-  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
-  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)");
-  if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: Laplace plans only");
-  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+int fmmbem_plan::field_alloc(FieldQuantity q) {
+  const size_t rows = (size_t)(hp.n - hp.n_src), w = (size_t)kField[(int)q].width;
+  FieldBuffers& b = field[(int)q];
+  if (!b.tree) TRY(alloc(w * rows, &b.tree, false));
+  if (d_target_point && !b.points) TRY(alloc(w * rows, &b.points, false));
+  if (!b.stage) TRY(alloc(w * (size_t)hp.n_targets, &b.stage, false));
+  return FMMBEM_OK;
+}
+
+// A field execute: run()'s gather, P2M and far chain up to and including L2L on the plan's own M and L -- the same launches in the
+// same order, so the same L -- then the quantity's two kernels of kernels_field.hip into its tree buffer and the delivery.
+// Launched plainly (never captured, never replayed; `graphs` is not touched), it writes x_tree, M, Mh and L, which every potential
+// execute writes afresh before it reads them, and leaves y_tree alone.
+int fmmbem_plan::run_field(FieldQuantity q, int p, const double* d_x, double* d_out, hipStream_t s) {
+  if (!d_x || !d_out) return fail(FMMBEM_ERR_INVALID, "null vector");
+  TRY(field_refusal(q, p));
   DEVICE_SCOPE(opts.device);
-  TRY(grad_alloc());
+  TRY(field_alloc(q));
+  const int width = kField[(int)q].width;
+  const FieldBuffers& b = field[(int)q];
   const int64_t ring = ev_count % kRing;
   StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
   HIP_TRY(tm.begin(Stage::Gather, s));
@@ -1098,128 +1122,16 @@ int fmmbem_plan::run_gradient(int p, const double* d_x, double* d_g, hipStream_t
   TRY(p2m(d, p, tm, s));
   TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
   HIP_TRY(tm.begin(Stage::Spmv, s));
-  HIP_TRY(launch_near_grad(d, hp.n_src, grad_tree, s));
+  HIP_TRY(launch_near_field(q, d, hp.n_src, b.tree, s));
   HIP_TRY(tm.end(Stage::Spmv, s));
   HIP_TRY(tm.begin(Stage::L2P, s));
-  HIP_TRY(launch_l2p_grad(d, p, hp.n_src, grad_tree, s));
+  HIP_TRY(launch_l2p_field(q, d, p, hp.n_src, b.tree, s));
   HIP_TRY(tm.end(Stage::L2P, s));
   HIP_TRY(tm.begin(Stage::Scatter, s));
-  HIP_TRY(launch_grad_scatter(d, hp.n_src, grad_tree, d_target_point ? grad_points : d_g, s));
+  HIP_TRY(launch_field_scatter(q, d, hp.n_src, b.tree, d_target_point ? b.points : d_out, s));
   if (d_target_point) {
-    const int64_t nt = hp.n_targets * 3;
-    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, grad_points, d_g, nt, 3);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(tm.end(Stage::Scatter, s));
-  last_p = p;
-  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
-  return FMMBEM_OK;
-}
-
-// ======================================= field pressure =======================================
-// the refusals of a pressure execute after the null checks, in the order include/fmmbem.h states them
-int fmmbem_plan::pressure_refusal(int p) const {
-  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
-  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the field pressure: on a plan over separate targets only (fmmbem_plan_create_field)");
-  if (opts.kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field pressure: Stokes plans only");
-  if (has_bc[1]) return fail(FMMBEM_ERR_UNSUPPORTED, "the field pressure: VELOCITY targets only (the pressure of the double layer is not built)");
-  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
-  return FMMBEM_OK;
-}
-
-int fmmbem_plan::pressure_alloc() {
-  const size_t rows = (size_t)(hp.n - hp.n_src);
-  if (!pres_tree) TRY(alloc(rows, &pres_tree, false));
-  if (d_target_point && !pres_points) TRY(alloc(rows, &pres_points, false));
-  if (!stage_q) TRY(alloc((size_t)hp.n_targets, &stage_q, false));
-  return FMMBEM_OK;
-}
-
-// The pressure execute (include/fmmbem.h "Field pressure"), after run_gradient: run()'s gather, P2M and far chain up to and
-// including L2L on the plan's own M and L -- the same launches in the same order, so the same L -- then the two kernels of
-// kernels_pressure.hip into pres_tree and the delivery.  Launched plainly (never captured, never replayed; `graphs` is not touched),
-// it writes x_tree, M, Mh and L, which every potential execute writes afresh before it reads them, and leaves y_tree alone.
-int fmmbem_plan::run_pressure(int p, const double* d_x, double* d_q, hipStream_t s) {
-  if (!d_x || !d_q) return fail(FMMBEM_ERR_INVALID, "null vector");
-  TRY(pressure_refusal(p));
-  DEVICE_SCOPE(opts.device);
-  TRY(pressure_alloc());
-  const int64_t ring = ev_count % kRing;
-  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
-  HIP_TRY(tm.begin(Stage::Gather, s));
-  DevicePlan dg = d;
-  dg.n = hp.n_src;                                     // x: the source panels only (the target rows of x_tree stay 0)
-  HIP_TRY(launch_gather_x(dg, d_x, s));
-  HIP_TRY(tm.end(Stage::Gather, s));
-  TRY(p2m(d, p, tm, s));
-  TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
-  HIP_TRY(tm.begin(Stage::Spmv, s));
-  HIP_TRY(launch_near_pressure(d, hp.n_src, pres_tree, s));
-  HIP_TRY(tm.end(Stage::Spmv, s));
-  HIP_TRY(tm.begin(Stage::L2P, s));
-  HIP_TRY(launch_l2p_pressure(d, p, hp.n_src, pres_tree, s));
-  HIP_TRY(tm.end(Stage::L2P, s));
-  HIP_TRY(tm.begin(Stage::Scatter, s));
-  HIP_TRY(launch_pressure_scatter(d, hp.n_src, pres_tree, d_target_point ? pres_points : d_q, s));
-  if (d_target_point) {
-    const int64_t nt = hp.n_targets;
-    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_target_point, pres_points, d_q, nt, 1);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(tm.end(Stage::Scatter, s));
-  last_p = p;
-  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
-  return FMMBEM_OK;
-}
-
-// ======================================= field velocity gradient =======================================
-// the refusals of a velocity-gradient execute after the null checks, in the order include/fmmbem.h states them (the pressure's)
-int fmmbem_plan::velgrad_refusal(int p) const {
-  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
-  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: on a plan over separate targets only (fmmbem_plan_create_field)");
-  if (opts.kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: Stokes plans only");
-  if (has_bc[1]) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: VELOCITY targets only (the gradient of the double layer is not built)");
-  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
-  return FMMBEM_OK;
-}
-
-int fmmbem_plan::velgrad_alloc() {
-  const size_t rows = (size_t)(hp.n - hp.n_src);
-  if (!vg_tree) TRY(alloc(9 * rows, &vg_tree, false));
-  if (d_target_point && !vg_points) TRY(alloc(9 * rows, &vg_points, false));
-  if (!stage_vg) TRY(alloc(9 * (size_t)hp.n_targets, &stage_vg, false));
-  return FMMBEM_OK;
-}
-
-// The velocity-gradient execute (include/fmmbem.h "Field velocity gradient"), after run_pressure and in its form: run()'s gather,
-// P2M and far chain up to and including L2L on the plan's own M and L, then the two kernels of kernels_velgrad.hip into vg_tree and
-// the delivery.  Launched plainly (never captured, never replayed; `graphs` is not touched), it writes x_tree, M, Mh and L, which
-// every potential execute writes afresh before it reads them, and leaves y_tree alone.
-int fmmbem_plan::run_velocity_gradient(int p, const double* d_x, double* d_g, hipStream_t s) {
-  if (!d_x || !d_g) return fail(FMMBEM_ERR_INVALID, "null vector");
-  TRY(velgrad_refusal(p));
-  DEVICE_SCOPE(opts.device);
-  TRY(velgrad_alloc());
-  const int64_t ring = ev_count % kRing;
-  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
-  HIP_TRY(tm.begin(Stage::Gather, s));
-  DevicePlan dg = d;
-  dg.n = hp.n_src;                                     // x: the source panels only (the target rows of x_tree stay 0)
-  HIP_TRY(launch_gather_x(dg, d_x, s));
-  HIP_TRY(tm.end(Stage::Gather, s));
-  TRY(p2m(d, p, tm, s));
-  TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
-  HIP_TRY(tm.begin(Stage::Spmv, s));
-  HIP_TRY(launch_near_velgrad(d, hp.n_src, vg_tree, s));
-  HIP_TRY(tm.end(Stage::Spmv, s));
-  HIP_TRY(tm.begin(Stage::L2P, s));
-  HIP_TRY(launch_l2p_velgrad(d, p, hp.n_src, vg_tree, s));
-  HIP_TRY(tm.end(Stage::L2P, s));
-  HIP_TRY(tm.begin(Stage::Scatter, s));
-  HIP_TRY(launch_velgrad_scatter(d, hp.n_src, vg_tree, d_target_point ? vg_points : d_g, s));
-  if (d_target_point) {
-    const int64_t nu = 9 * (int64_t)hp.n_targets;      // unknowns, one thread each
-    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, vg_points, d_g, nu, 9);
+    const int64_t nu = width * (int64_t)hp.n_targets;  // unknowns, one thread each
+    hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, b.points, d_out, nu, width);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(tm.end(Stage::Scatter, s));
@@ -2071,65 +1983,44 @@ int fmmbem_plan_execute(fmmbem_plan* plan, int p, const double* x, double* y) {
   return FMMBEM_OK;
 }
 
-// ---- field gradient (include/fmmbem.h) ----
+// ---- field quantities (include/fmmbem.h) ----
+static int field_execute_device(fmmbem_plan* plan, FieldQuantity q, int p, const double* d_x, double* d_out, void* stream) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  return plan->run_field(q, p, d_x, d_out, static_cast<hipStream_t>(stream));
+}
+
+static int field_execute(fmmbem_plan* plan, FieldQuantity q, int p, const double* x, double* out) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!x || !out) return fail(FMMBEM_ERR_INVALID, "null vector");
+  TRY(plan->field_refusal(q, p));                      // a refusal touches neither pointer
+  DEVICE_SCOPE(plan->opts.device);
+  TRY(plan->field_alloc(q));
+  double* stage = plan->field[(int)q].stage;
+  hipStream_t s = plan->own_stream;
+  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
+  TRY(plan->run_field(q, p, plan->stage_x, stage, s));
+  HIP_TRY(hipMemcpyAsync(out, stage, sizeof(double) * kField[(int)q].width * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
 int fmmbem_plan_execute_gradient_device(fmmbem_plan* plan, int p, const double* d_x, double* d_g, void* stream) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run_gradient(p, d_x, d_g, static_cast<hipStream_t>(stream));
+  return field_execute_device(plan, FieldQuantity::Gradient, p, d_x, d_g, stream);
 }
-
 int fmmbem_plan_execute_gradient(fmmbem_plan* plan, int p, const double* x, double* g) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  if (!x || !g) return fail(FMMBEM_ERR_INVALID, "null vector");
-  if (!plan->on_device || !plan->targets || plan->opts.kernel == FMMBEM_KERNEL_STOKES_BEM || p < 1 || p > plan->hp.opt.p_max)
-    return plan->run_gradient(p, x, g, nullptr);       // a refusal: it touches neither pointer
-  DEVICE_SCOPE(plan->opts.device);
-  TRY(plan->grad_alloc());
-  hipStream_t s = plan->own_stream;
-  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
-  TRY(plan->run_gradient(p, plan->stage_x, plan->stage_g, s));
-  HIP_TRY(hipMemcpyAsync(g, plan->stage_g, sizeof(double) * 3 * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FMMBEM_OK;
+  return field_execute(plan, FieldQuantity::Gradient, p, x, g);
 }
-
-// ---- field pressure (include/fmmbem.h) ----
 int fmmbem_plan_execute_pressure_device(fmmbem_plan* plan, int p, const double* d_x, double* d_q, void* stream) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run_pressure(p, d_x, d_q, static_cast<hipStream_t>(stream));
+  return field_execute_device(plan, FieldQuantity::Pressure, p, d_x, d_q, stream);
 }
-
 int fmmbem_plan_execute_pressure(fmmbem_plan* plan, int p, const double* x, double* q) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  if (!x || !q) return fail(FMMBEM_ERR_INVALID, "null vector");
-  TRY(plan->pressure_refusal(p));                      // a refusal touches neither pointer
-  DEVICE_SCOPE(plan->opts.device);
-  TRY(plan->pressure_alloc());
-  hipStream_t s = plan->own_stream;
-  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
-  TRY(plan->run_pressure(p, plan->stage_x, plan->stage_q, s));
-  HIP_TRY(hipMemcpyAsync(q, plan->stage_q, sizeof(double) * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FMMBEM_OK;
+  return field_execute(plan, FieldQuantity::Pressure, p, x, q);
 }
-
-// ---- field velocity gradient (include/fmmbem.h) ----
 int fmmbem_plan_execute_velocity_gradient_device(fmmbem_plan* plan, int p, const double* d_x, double* d_G, void* stream) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  return plan->run_velocity_gradient(p, d_x, d_G, static_cast<hipStream_t>(stream));
+  return field_execute_device(plan, FieldQuantity::VelocityGradient, p, d_x, d_G, stream);
 }
-
 int fmmbem_plan_execute_velocity_gradient(fmmbem_plan* plan, int p, const double* x, double* G) {
-  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
-  if (!x || !G) return fail(FMMBEM_ERR_INVALID, "null vector");
-  TRY(plan->velgrad_refusal(p));                       // a refusal touches neither pointer
-  DEVICE_SCOPE(plan->opts.device);
-  TRY(plan->velgrad_alloc());
-  hipStream_t s = plan->own_stream;
-  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
-  TRY(plan->run_velocity_gradient(p, plan->stage_x, plan->stage_vg, s));
-  HIP_TRY(hipMemcpyAsync(G, plan->stage_vg, sizeof(double) * 9 * (size_t)plan->hp.n_targets, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return FMMBEM_OK;
+  return field_execute(plan, FieldQuantity::VelocityGradient, p, x, G);
 }
 
 // ---- batched execute (include/fmmbem.h) ----
@@ -2683,21 +2574,26 @@ int fmmbem_kernel_entries(const fmmbem_options* opts, size_t n, const double* ta
   return FMMBEM_OK;
 }
 
-int fmmbem_kernel_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
-                                   const double* source_vertices, double* out) {
+// The pair functions of the field quantities for n independent pairs, in the layout of fmmbem_kernel_entries: panels [0, n) the
+// targets, [n, 2n) the sources.  Laplace: the normals and the flags go up; Stokes: the fine rule.
+static int field_entries(FieldQuantity q, const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
+                         const double* source_vertices, double* out) {
+  const FieldRow& row = kField[(int)q];
   if (!opts || !target_vertices || !source_vertices || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
-  if (opts->kernel != FMMBEM_KERNEL_LAPLACE_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field gradient: the Laplace kernel only");
+  if (opts->kernel != (row.stokes ? FMMBEM_KERNEL_STOKES_BEM : FMMBEM_KERNEL_LAPLACE_BEM)) return fail(FMMBEM_ERR_UNSUPPORTED, row.entries_kernel);
   if (n == 0) return FMMBEM_OK;
-  if (n > ((size_t)1 << 30)) return fail(FMMBEM_ERR_INVALID, "too many pairs");
-  QuadRule rule;
+  if (n > row.max_pairs) return fail(FMMBEM_ERR_INVALID, "too many pairs");
+  QuadRule rule, fine;
   if (!quad_rule(opts->quad_k, rule)) return fail(FMMBEM_ERR_INVALID, "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)");
+  if (row.stokes && !quad_rule(opts->quad_k_fine, fine)) return fail(FMMBEM_ERR_INVALID, "invalid K_fine (valid: 1 3 4 7 13 17 19 25 79)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
   if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
   DEVICE_SCOPE(opts->device);
-  const int64_t N = 2 * (int64_t)n;                    // the layout of fmmbem_kernel_entries: panels [0, n) targets, [n, 2n) sources
+  const int64_t N = 2 * (int64_t)n;
   PanelSoA P;
+  std::vector<double> qf((size_t)fine.n * 4);
   try {
     alloc_panels(P, N, rule.n);
   } catch (const std::bad_alloc&) {
@@ -2707,101 +2603,39 @@ int fmmbem_kernel_gradient_entries(const fmmbem_options* opts, size_t n, const d
     fill_panel(P, N, (int64_t)i, target_vertices + 9 * i, rule, target_bc ? (target_bc[i] ? 1 : 0) : 0);
     fill_panel(P, N, (int64_t)(n + i), source_vertices + 9 * i, rule, 0);
   }
+  for (int k = 0; k < fine.n; ++k) { for (int c = 0; c < 3; ++c) qf[4 * k + c] = fine.pts[k][c]; qf[4 * k + 3] = fine.w[k]; }
   Scratch mem;
   DevicePlan d{};
-  d.n = N; d.nq = rule.n; d.kernel = opts->kernel; d.dof = 1;
-  for (int q = 0; q < rule.n; ++q) d.qw[q] = rule.w[q];
+  d.n = N; d.nq = rule.n; d.kernel = opts->kernel; d.dof = row.stokes ? 3 : 1;
+  for (int k = 0; k < rule.n; ++k) d.qw[k] = rule.w[k];
   TRY(mem.up(P.cx.data(), P.cx.size(), &d.cx)); TRY(mem.up(P.cy.data(), P.cy.size(), &d.cy)); TRY(mem.up(P.cz.data(), P.cz.size(), &d.cz));
-  TRY(mem.up(P.nx.data(), P.nx.size(), &d.nx)); TRY(mem.up(P.ny.data(), P.ny.size(), &d.ny)); TRY(mem.up(P.nz.data(), P.nz.size(), &d.nz));
   TRY(mem.up(P.area.data(), P.area.size(), &d.area)); TRY(mem.up(P.quad.data(), P.quad.size(), &d.quad));
-  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert)); TRY(mem.up(P.bc.data(), P.bc.size(), &d.bc));
+  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert));
+  if (row.stokes) {
+    d.nqf = fine.n; d.mu = opts->mu;
+    TRY(mem.up(qf.data(), qf.size(), &d.qf));
+  } else {
+    TRY(mem.up(P.nx.data(), P.nx.size(), &d.nx)); TRY(mem.up(P.ny.data(), P.ny.size(), &d.ny)); TRY(mem.up(P.nz.data(), P.nz.size(), &d.nz));
+    TRY(mem.up(P.bc.data(), P.bc.size(), &d.bc));
+  }
   double* d_out = nullptr;
-  TRY(mem.alloc(3 * n, &d_out));
-  HIP_TRY(launch_grad_entries(d, (int)n, d_out, nullptr));
-  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  TRY(mem.alloc(row.entry_width * n, &d_out));
+  HIP_TRY(launch_field_entries(q, d, (int)n, d_out, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * row.entry_width * n, hipMemcpyDeviceToHost));
   return FMMBEM_OK;
 }
 
+int fmmbem_kernel_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
+                                   const double* source_vertices, double* out) {
+  return field_entries(FieldQuantity::Gradient, opts, n, target_vertices, target_bc, source_vertices, out);
+}
 int fmmbem_kernel_pressure_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const double* source_vertices,
                                    double* out) {
-  if (!opts || !target_vertices || !source_vertices || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
-  if (opts->kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field pressure: the Stokes kernel only");
-  if (n == 0) return FMMBEM_OK;
-  if (n > ((size_t)1 << 30)) return fail(FMMBEM_ERR_INVALID, "too many pairs");
-  QuadRule rule, fine;
-  if (!quad_rule(opts->quad_k, rule)) return fail(FMMBEM_ERR_INVALID, "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)");
-  if (!quad_rule(opts->quad_k_fine, fine)) return fail(FMMBEM_ERR_INVALID, "invalid K_fine (valid: 1 3 4 7 13 17 19 25 79)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
-  if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
-  DEVICE_SCOPE(opts->device);
-  const int64_t N = 2 * (int64_t)n;                    // the layout of fmmbem_kernel_entries: panels [0, n) targets, [n, 2n) sources
-  PanelSoA P;
-  std::vector<double> qf((size_t)fine.n * 4);
-  try {
-    alloc_panels(P, N, rule.n);
-  } catch (const std::bad_alloc&) {
-    return fail(FMMBEM_ERR_ALLOC, "host allocation failed");
-  }
-  for (size_t i = 0; i < n; ++i) {
-    fill_panel(P, N, (int64_t)i, target_vertices + 9 * i, rule, 0);
-    fill_panel(P, N, (int64_t)(n + i), source_vertices + 9 * i, rule, 0);
-  }
-  for (int q = 0; q < fine.n; ++q) { for (int k = 0; k < 3; ++k) qf[4 * q + k] = fine.pts[q][k]; qf[4 * q + 3] = fine.w[q]; }
-  Scratch mem;
-  DevicePlan d{};
-  d.n = N; d.nq = rule.n; d.nqf = fine.n; d.kernel = opts->kernel; d.dof = 3; d.mu = opts->mu;
-  for (int q = 0; q < rule.n; ++q) d.qw[q] = rule.w[q];
-  TRY(mem.up(P.cx.data(), P.cx.size(), &d.cx)); TRY(mem.up(P.cy.data(), P.cy.size(), &d.cy)); TRY(mem.up(P.cz.data(), P.cz.size(), &d.cz));
-  TRY(mem.up(P.area.data(), P.area.size(), &d.area)); TRY(mem.up(P.quad.data(), P.quad.size(), &d.quad));
-  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert)); TRY(mem.up(qf.data(), qf.size(), &d.qf));
-  double* d_out = nullptr;
-  TRY(mem.alloc(3 * n, &d_out));
-  HIP_TRY(launch_pressure_entries(d, (int)n, d_out, nullptr));
-  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  return FMMBEM_OK;
+  return field_entries(FieldQuantity::Pressure, opts, n, target_vertices, nullptr, source_vertices, out);
 }
-
 int fmmbem_kernel_velocity_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices,
                                             const double* source_vertices, double* out) {
-  if (!opts || !target_vertices || !source_vertices || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
-  if (opts->kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the field velocity gradient: the Stokes kernel only");
-  if (n == 0) return FMMBEM_OK;
-  if (n > ((size_t)1 << 26)) return fail(FMMBEM_ERR_INVALID, "too many pairs");
-  QuadRule rule, fine;
-  if (!quad_rule(opts->quad_k, rule)) return fail(FMMBEM_ERR_INVALID, "invalid quadrature key (valid: 1 3 4 7 13 17 19 25 79)");
-  if (!quad_rule(opts->quad_k_fine, fine)) return fail(FMMBEM_ERR_INVALID, "invalid K_fine (valid: 1 3 4 7 13 17 19 25 79)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FMMBEM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU execution path)");
-  if (opts->device < 0 || opts->device >= ndev) return fail(FMMBEM_ERR_INVALID, "device ordinal out of range");
-  DEVICE_SCOPE(opts->device);
-  const int64_t N = 2 * (int64_t)n;                    // the layout of fmmbem_kernel_entries: panels [0, n) targets, [n, 2n) sources
-  PanelSoA P;
-  std::vector<double> qf((size_t)fine.n * 4);
-  try {
-    alloc_panels(P, N, rule.n);
-  } catch (const std::bad_alloc&) {
-    return fail(FMMBEM_ERR_ALLOC, "host allocation failed");
-  }
-  for (size_t i = 0; i < n; ++i) {
-    fill_panel(P, N, (int64_t)i, target_vertices + 9 * i, rule, 0);
-    fill_panel(P, N, (int64_t)(n + i), source_vertices + 9 * i, rule, 0);
-  }
-  for (int q = 0; q < fine.n; ++q) { for (int k = 0; k < 3; ++k) qf[4 * q + k] = fine.pts[q][k]; qf[4 * q + 3] = fine.w[q]; }
-  Scratch mem;
-  DevicePlan d{};
-  d.n = N; d.nq = rule.n; d.nqf = fine.n; d.kernel = opts->kernel; d.dof = 3; d.mu = opts->mu;
-  for (int q = 0; q < rule.n; ++q) d.qw[q] = rule.w[q];
-  TRY(mem.up(P.cx.data(), P.cx.size(), &d.cx)); TRY(mem.up(P.cy.data(), P.cy.size(), &d.cy)); TRY(mem.up(P.cz.data(), P.cz.size(), &d.cz));
-  TRY(mem.up(P.area.data(), P.area.size(), &d.area)); TRY(mem.up(P.quad.data(), P.quad.size(), &d.quad));
-  TRY(mem.up(P.vert.data(), P.vert.size(), &d.vert)); TRY(mem.up(qf.data(), qf.size(), &d.qf));
-  double* d_out = nullptr;
-  TRY(mem.alloc(27 * n, &d_out));
-  HIP_TRY(launch_velgrad_entries(d, (int)n, d_out, nullptr));
-  HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * 27 * n, hipMemcpyDeviceToHost));
-  return FMMBEM_OK;
+  return field_entries(FieldQuantity::VelocityGradient, opts, n, target_vertices, nullptr, source_vertices, out);
 }
 
 int fmmbem_mesh_unit_sphere(int recursions, double* vertices, size_t* n_panels) {

@@ -697,108 +697,79 @@ class FMM_plan:
         self.execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
-    # ---- field gradient: grad of the Laplace field at the points of a targets= plan or a field plan (fmmbem_plan_execute_gradient) ----
-    def execute_gradient(self, charges):
-        """(N,) charges -> (M, 3): g_i = sum_j gamma(t_i, s_j) x_j at the kernel's current p, gamma the gradient with respect to the
-        target point of the integrand the target's flag picks (include/fmmbem.h, "Field gradient").  numpy in, numpy out (host).
-        FmmBemError (status 6) on a plan that is not over separate targets, on a Stokes plan and on a host-only plan."""
+    # ---- field quantities at the points of a targets= plan or a field plan (include/fmmbem.h): the Laplace gradient, the pressure and
+    # the velocity gradient of the Stokes single layer.  One form each for numpy (host), raw device pointers and torch ----
+    def _field_rows(self):
+        return self.n if self.n_targets is None else self.n_targets
+
+    def _field_host(self, symbol, charges, tail, per):
         x = np.ascontiguousarray(charges, dtype=np.float64)
         if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
-            raise ValueError("charges must have one value per panel")
-        g = np.empty((self.n if self.n_targets is None else self.n_targets, 3))
-        _capi.check(_capi.lib().fmmbem_plan_execute_gradient(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
-                                                             g.ctypes.data_as(C.c_void_p)))
-        return g
+            raise ValueError("charges must have %s per panel" % per)
+        out = np.empty((self._field_rows(),) + tail)
+        _capi.check(getattr(_capi.lib(), symbol)(self._h, self._K.P, x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
 
-    def execute_gradient_device(self, x_ptr, g_ptr, stream=0, p=None):
-        _capi.check(_capi.lib().fmmbem_plan_execute_gradient_device(self._h, self._K.P if p is None else int(p),
-                                                                    C.c_void_p(x_ptr), C.c_void_p(g_ptr), C.c_void_p(stream)))
+    def _field_device(self, symbol, x_ptr, out_ptr, stream, p):
+        _capi.check(getattr(_capi.lib(), symbol)(self._h, self._K.P if p is None else int(p), C.c_void_p(x_ptr), C.c_void_p(out_ptr),
+                                                 C.c_void_p(stream)))
 
-    def execute_gradient_torch(self, x, out=None, p=None):
-        """x: contiguous float64 CUDA tensor (N,), ORIGINAL panel order; returns (M, 3).  Runs on torch's current stream."""
+    def _field_torch(self, execute_device, x, out, p, tail, per):
         import torch
         if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
-            raise ValueError("x must be a contiguous float64 CUDA tensor with one value per panel")
+            raise ValueError("x must be a contiguous float64 CUDA tensor with %s per panel" % per)
         if x.device.index != self.device:
             raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
-        shape = (self.n if self.n_targets is None else self.n_targets, 3)
+        shape = (self._field_rows(),) + tail
         if out is None:
             out = x.new_empty(shape)
         elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
             raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
-        self.execute_gradient_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
+        execute_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
         return out
 
-    # ---- field pressure: the pressure of the Stokes single layer at the points of a field plan (fmmbem_plan_execute_pressure) ----
-    def _pressure_rows(self):
-        return self.n if self.n_targets is None else self.n_targets
+    def execute_gradient(self, charges):
+        """(N,) charges -> (M, 3): g_i = sum_j gamma(t_i, s_j) x_j at the kernel's current p, gamma the gradient with respect to the
+        target point of the integrand the target's flag picks (include/fmmbem.h, "Field gradient").  numpy in, numpy out (host).
+        FmmBemError (status 6) on a plan that is not over separate targets, on a Stokes plan and on a host-only plan."""
+        return self._field_host("fmmbem_plan_execute_gradient", charges, (3,), "one value")
+
+    def execute_gradient_device(self, x_ptr, g_ptr, stream=0, p=None):
+        self._field_device("fmmbem_plan_execute_gradient_device", x_ptr, g_ptr, stream, p)
+
+    def execute_gradient_torch(self, x, out=None, p=None):
+        """x: contiguous float64 CUDA tensor (N,), ORIGINAL panel order; returns (M, 3).  Runs on torch's current stream."""
+        return self._field_torch(self.execute_gradient_device, x, out, p, (3,), "one value")
 
     def execute_pressure(self, charges):
         """(N, 3) or (3N,) traction density -> (M,): q_i = sum_j pi(t_i, s_j) . x_j at the kernel's current p, the pressure that
         belongs to the velocity execute returns (include/fmmbem.h, "Field pressure"; the physical pressure is q / 4 pi).  numpy in,
         numpy out (host).  FmmBemError (status 6) on a plan that is not over separate targets, on a Laplace plan, on a plan with a
         TRACTION target and on a host-only plan."""
-        x = np.ascontiguousarray(charges, dtype=np.float64)
-        if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
-            raise ValueError("charges must have dof values per panel")
-        q = np.empty(self._pressure_rows())
-        _capi.check(_capi.lib().fmmbem_plan_execute_pressure(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
-                                                             q.ctypes.data_as(C.c_void_p)))
-        return q
+        return self._field_host("fmmbem_plan_execute_pressure", charges, (), "dof values")
 
     def execute_pressure_device(self, x_ptr, q_ptr, stream=0, p=None):
-        _capi.check(_capi.lib().fmmbem_plan_execute_pressure_device(self._h, self._K.P if p is None else int(p),
-                                                                    C.c_void_p(x_ptr), C.c_void_p(q_ptr), C.c_void_p(stream)))
+        self._field_device("fmmbem_plan_execute_pressure_device", x_ptr, q_ptr, stream, p)
 
     def execute_pressure_torch(self, x, out=None, p=None):
         """x: contiguous float64 CUDA tensor with 3 values per panel, ORIGINAL panel order; returns (M,).  Runs on torch's current
         stream."""
-        import torch
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
-            raise ValueError("x must be a contiguous float64 CUDA tensor with dof values per panel")
-        if x.device.index != self.device:
-            raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
-        shape = (self._pressure_rows(),)
-        if out is None:
-            out = x.new_empty(shape)
-        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
-            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
-        self.execute_pressure_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
-        return out
+        return self._field_torch(self.execute_pressure_device, x, out, p, (), "dof values")
 
-    # ---- field velocity gradient and stress of the Stokes single layer at the points of a field plan ----
     def execute_velocity_gradient(self, traction):
         """(N, 3) or (3N,) traction density -> (M, 3, 3): G_i[k][m] = d u'_k / d t_m at the kernel's current p, u' what execute
         returns (include/fmmbem.h, "Field velocity gradient"; the physical gradient is G / 4 pi).  numpy in, numpy out (host).
         FmmBemError (status 6) on a plan that is not over separate targets, on a Laplace plan, on a plan with a TRACTION target and
         on a host-only plan."""
-        x = np.ascontiguousarray(traction, dtype=np.float64)
-        if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
-            raise ValueError("charges must have dof values per panel")
-        g = np.empty((self._pressure_rows(), 3, 3))
-        _capi.check(_capi.lib().fmmbem_plan_execute_velocity_gradient(self._h, self._K.P, x.ctypes.data_as(C.c_void_p),
-                                                                      g.ctypes.data_as(C.c_void_p)))
-        return g
+        return self._field_host("fmmbem_plan_execute_velocity_gradient", traction, (3, 3), "dof values")
 
     def execute_velocity_gradient_device(self, x_ptr, g_ptr, stream=0, p=None):
-        _capi.check(_capi.lib().fmmbem_plan_execute_velocity_gradient_device(self._h, self._K.P if p is None else int(p),
-                                                                             C.c_void_p(x_ptr), C.c_void_p(g_ptr), C.c_void_p(stream)))
+        self._field_device("fmmbem_plan_execute_velocity_gradient_device", x_ptr, g_ptr, stream, p)
 
     def execute_velocity_gradient_torch(self, x, out=None, p=None):
         """x: contiguous float64 CUDA tensor with 3 values per panel, ORIGINAL panel order; returns (M, 3, 3).  Runs on torch's
         current stream."""
-        import torch
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
-            raise ValueError("x must be a contiguous float64 CUDA tensor with dof values per panel")
-        if x.device.index != self.device:
-            raise ValueError("x lives on cuda:%s but the plan was built on device %d" % (x.device.index, self.device))
-        shape = (self._pressure_rows(), 3, 3)
-        if out is None:
-            out = x.new_empty(shape)
-        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
-            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
-        self.execute_velocity_gradient_device(x.data_ptr(), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream, p)
-        return out
+        return self._field_torch(self.execute_velocity_gradient_device, x, out, p, (3, 3), "dof values")
 
     def execute_stress(self, traction):
         """(N, 3) or (3N,) traction density -> (M, 3, 3): sigma_i[k][m] = -q_i delta_km + mu (G_i[k][m] + G_i[m][k]), q of
