@@ -30,6 +30,11 @@ fplan.execute_stress; prints "field velocity gradient (FMM): ..." and "field str
 and, for the unit sphere, the largest deviation of G / 4 pi from the exact velocity gradient of a translating sphere, relative to that
 gradient's largest entry on the points.
 
+-field_direct (not a flag of the reference; with -field_fmm N and -field_pressure and/or -field_stress): the same quantities on the same
+N points summed over all panels on the device by fb.Direct (pressure_torch, velocity_gradient_torch); after the "field pressure (FMM):"
+and the "field velocity gradient (FMM):" line prints "... against Direct: relative L2 difference ...", the distance of the FMM's value
+from the sum it approximates.
+
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -diagonal iterates on them; the same report lines.
 
@@ -73,6 +78,7 @@ def print_help_and_exit():
           "-field_fmm <int> : (not a flag of the reference) the same velocity by the FMM (plan.field_plan)\n"
           "-field_pressure : (not a flag of the reference) with -field_fmm: the pressure on the same points (execute_pressure)\n"
           "-field_stress : (not a flag of the reference) with -field_fmm: the velocity gradient and stress on the same points\n"
+          "-field_direct : (not a flag of the reference) with -field_fmm and -field_pressure / -field_stress: their difference from the Direct sum\n"
           "-help : print this message")
     sys.exit(0)
 
@@ -101,7 +107,7 @@ def main(argv):
     theta, ncrit = 0.5, 64
     mesh = vert = face = None
     rbc, near_f32, field, field_fmm = False, 0, 0, 0
-    stokes_batch, resistance, field_pressure, field_stress = 0, False, False, False
+    stokes_batch, resistance, field_pressure, field_stress, field_direct = 0, False, False, False, False
     so = fb.SolverOptions()
     solver, pc = "gmres", "identity"
     i = 1
@@ -163,6 +169,8 @@ def main(argv):
             field_pressure = True
         elif a == "-field_stress":                         # not in the reference: fplan.execute_velocity_gradient / execute_stress
             field_stress = True
+        elif a == "-field_direct":                         # not in the reference: those quantities against fb.Direct's all-pairs sums
+            field_direct = True
         elif a == "-disable_sparse":
             raise SystemExit("-disable_sparse: the Stokes near field is only built in assembled form")
         i += 1                                             # unknown arguments are ignored, as the reference does (:207-211)
@@ -172,6 +180,9 @@ def main(argv):
 
     if field_stress and field_fmm <= 0:
         raise SystemExit("-field_stress: needs -field_fmm N (the stress is evaluated on the field plan's points)")
+
+    if field_direct and (field_fmm <= 0 or not (field_pressure or field_stress)):
+        raise SystemExit("-field_direct: needs -field_fmm N and -field_pressure and/or -field_stress (it compares those quantities with the Direct sum)")
 
     if vert or face:
         print("reading mesh from %s, %s" % (vert, face))
@@ -271,12 +282,21 @@ def main(argv):
         gu = fplan.execute_velocity_gradient_torch(x).cpu().numpy() if field_stress else None
         sig = fplan.execute_stress(x.cpu().numpy()) if field_stress else None
         fplan.close()
+        q_direct = gu_direct = None
+        if field_direct:
+            direct = fb.Direct(kernel(), v)
+            pts_d = torch.from_numpy(sphere_points(field_fmm, 3.0)).to(dev)
+            q_direct = direct.pressure_torch(x, pts_d).cpu().numpy() if field_pressure else None
+            gu_direct = direct.velocity_gradient_torch(x, pts_d).cpu().numpy() if field_stress else None
+            direct.close()
         mag = np.linalg.norm(uf, axis=1)
         print("field (FMM): %d points at r = 3, max |u|: %.6e, mean |u|: %.6e" % (field_fmm, float(mag.max()), float(mag.mean())))
         if u is not None and field == field_fmm:
             print("field (FMM) against field: relative L2 difference %.3e" % float(np.linalg.norm(uf - u) / np.linalg.norm(u)))
         if q is not None:
             print("field pressure (FMM): %d points at r = 3, max |q|: %.6e, mean |q|: %.6e" % (field_fmm, float(np.abs(q).max()), float(np.abs(q).mean())))
+            if q_direct is not None:
+                print("field pressure (FMM) against Direct: relative L2 difference %.3e" % float(np.linalg.norm(q - q_direct) / np.linalg.norm(q_direct)))
             if not (rbc or mesh or vert or face):
                 # a sphere of radius a translating with U: p = (3/2) mu a U.x / r^3; q = 4 pi p and the solve's U is e_x
                 pts = sphere_points(field_fmm, 3.0)
@@ -284,6 +304,8 @@ def main(argv):
                 print("field pressure against the translating sphere's: largest deviation %.3e of 1/9" % float(dev_q))
         if gu is not None:
             print("field velocity gradient (FMM): %d points at r = 3, max |G|: %.6e, mean |G|: %.6e" % (field_fmm, float(np.abs(gu).max()), float(np.abs(gu).mean())))
+            if gu_direct is not None:
+                print("field velocity gradient (FMM) against Direct: relative L2 difference %.3e" % float(np.linalg.norm(gu - gu_direct) / np.linalg.norm(gu_direct)))
             print("field stress (FMM): %d points at r = 3, max |sigma|: %.6e, mean |sigma|: %.6e" % (field_fmm, float(np.abs(sig).max()), float(np.abs(sig).mean())))
             if not (rbc or mesh or vert or face):
                 # a unit sphere translating with e_x: u = 3/4 (e_x / r + x x_1 / r^3) + 1/4 (e_x / r^3 - 3 x x_1 / r^5); its gradient

@@ -105,6 +105,8 @@ SYMBOLS = (
     "fmmbem_plan_execute_batch", "fmmbem_plan_execute_batch_device", "fmmbem_plan_batch_width",
     "fmmbem_gmres_batch_device", "fmmbem_gmres_batch",
     "fmmbem_direct_create", "fmmbem_direct_apply", "fmmbem_direct_apply_device", "fmmbem_direct_chunk", "fmmbem_direct_destroy",
+    "fmmbem_direct_gradient", "fmmbem_direct_gradient_device", "fmmbem_direct_pressure", "fmmbem_direct_pressure_device",
+    "fmmbem_direct_velocity_gradient", "fmmbem_direct_velocity_gradient_device",
     "fmmbem_plan_block_inverse_build", "fmmbem_plan_block_inverse_apply_device", "fmmbem_plan_block_inverse_apply",
     "fmmbem_plan_block_inverse_bytes",
     "fmmbem_plan_create_field",
@@ -209,6 +211,12 @@ def lib():
     L.fmmbem_direct_create.argtypes = [C.POINTER(Options), C.c_size_t, vp, C.POINTER(vp)]
     L.fmmbem_direct_apply.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     L.fmmbem_direct_apply_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.fmmbem_direct_gradient.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    L.fmmbem_direct_gradient_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+    for fn in (L.fmmbem_direct_pressure, L.fmmbem_direct_velocity_gradient):
+        fn.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    for fn in (L.fmmbem_direct_pressure_device, L.fmmbem_direct_velocity_gradient_device):
+        fn.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     L.fmmbem_direct_chunk.argtypes = []
     L.fmmbem_direct_destroy.argtypes = [vp]
     L.fmmbem_direct_destroy.restype = None

@@ -118,6 +118,12 @@ int64_t direct_chunks(int64_t n_sources);              // partial sums per targe
 // point i = (tx, ty, tz)[i * tstride]; tbc null: flags 0; part: direct_chunks(d.n) * m * d.dof doubles of scratch; y: m * d.dof
 hipError_t launch_direct(const DevicePlan& d, int64_t m, const double* tx, const double* ty, const double* tz, int tstride,
                          const uint8_t* tbc, const double* x, double* part, double* y, hipStream_t s);
+// the field quantities at points: out_i = sum_j (q's pair function)(t_i, panel j) x_j, W = direct_field_width(q) doubles per target
+// (3, 1, 9).  pts: m x 3; tbc (Gradient only) null: flags 0; x: d.n * d.dof; part: direct_chunks(d.n) * m * W doubles of scratch;
+// out: m * W.  Gradient takes a Laplace d, the other two a Stokes d (hipErrorInvalidValue otherwise).
+int direct_field_width(FieldQuantity q);
+hipError_t launch_direct_field(FieldQuantity q, const DevicePlan& d, int64_t m, const double* pts, const uint8_t* tbc, const double* x,
+                               double* part, double* out, hipStream_t s);
 
 
 }  // namespace fmmbem

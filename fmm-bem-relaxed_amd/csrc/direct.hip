@@ -2,6 +2,7 @@
 // A handle owns a DevicePlan that holds ONLY the source panels, in the caller's order -- built the way ops.hip builds its two-box
 // plan, with the panels' derived geometry from panel_setup_kernel (identity permutation), so centroids, normals, areas and quadrature
 // points carry the bits a plan's carry.  No tree, no permutation, no matrix.  The sum itself is kernels_direct.hip.
+// fmmbem_direct_{gradient,pressure,velocity_gradient}: the field quantities at points summed the same way, over one routine.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,7 +53,9 @@ struct fmmbem_direct {
   int upload(const std::vector<T>& v, const T** out) { return mem.upload(v, out); }
   int init(const fmmbem_options& o, const QuadRule& rule, const QuadRule& fine, const double* vertices);
   int ensure_part(size_t doubles);
-  int apply(size_t m, const double* d_pts, const uint8_t* d_bc, const double* d_x, double* d_y, hipStream_t s);
+  // q null: the operator, width = d.dof; else the field quantity *q at points, width = direct_field_width(*q)
+  int apply(size_t m, int width, const FieldQuantity* q, const double* d_pts, const uint8_t* d_bc, const double* d_x, double* d_y,
+            hipStream_t s);
 };
 
 int fmmbem_direct::init(const fmmbem_options& o, const QuadRule& rule, const QuadRule& fine, const double* vertices) {
@@ -104,20 +107,86 @@ int fmmbem_direct::ensure_part(size_t doubles) {
   return FMMBEM_OK;
 }
 
-int fmmbem_direct::apply(size_t m, const double* d_pts, const uint8_t* d_bc, const double* d_x, double* d_y, hipStream_t s) {
-  const size_t per_target = (size_t)direct_chunks(n) * (size_t)d.dof;
+int fmmbem_direct::apply(size_t m, int width, const FieldQuantity* q, const double* d_pts, const uint8_t* d_bc, const double* d_x, double* d_y,
+                         hipStream_t s) {
+  const size_t per_target = (size_t)direct_chunks(n) * (size_t)width;
   size_t slab = m;
   if (per_target * m > kPartCap) slab = std::max<size_t>(256, kPartCap / per_target / 256 * 256);
   TRY(ensure_part(per_target * std::min(m, slab)));
   for (size_t off = 0; off < m; off += slab) {
     const size_t mm = std::min(slab, m - off);
+    if (q) {
+      HIP_TRY(launch_direct_field(*q, d, (int64_t)mm, d_pts + 3 * off, d_bc ? d_bc + off : nullptr, d_x, part, d_y + off * width, s));
+      continue;
+    }
     const double *tx = d_pts ? d_pts + 3 * off : d.cx + off, *ty = d_pts ? tx + 1 : d.cy + off, *tz = d_pts ? tx + 2 : d.cz + off;
     HIP_TRY(launch_direct(d, (int64_t)mm, tx, ty, tz, d_pts ? 3 : 1, d_bc ? d_bc + off : nullptr, d_x, part, d_y + off * d.dof, s));
   }
   return FMMBEM_OK;
 }
 
+namespace {
+
+// fmmbem_direct_{gradient,pressure,velocity_gradient}{,_device}: the checks in the header's order, then the sum.  host: the pointers
+// are the caller's host arrays (the points are read, the result is copied back); else device pointers, asynchronous on s.
+int direct_field(fmmbem_direct* direct, FieldQuantity q, bool host, size_t n_targets, const double* pts, const uint8_t* bc, const double* x,
+                 double* out, hipStream_t s) {
+  static const char* const kName[3] = {"gradient", "pressure", "velocity gradient"};
+  const char* name = kName[(int)q];
+  if (!direct || !pts || !x || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
+  if (n_targets == 0) return fail(FMMBEM_ERR_INVALID, std::string("Direct ") + name + ": no targets");
+  const bool laplace = direct->d.dof == 1;
+  if (q == FieldQuantity::Gradient && !laplace)
+    return fail(FMMBEM_ERR_UNSUPPORTED, "Direct gradient: the gradient of the Laplace field needs a handle of the Laplace kernel (this one is Stokes: "
+                                        "fmmbem_direct_velocity_gradient is its gradient)");
+  if (q != FieldQuantity::Gradient && laplace)
+    return fail(FMMBEM_ERR_UNSUPPORTED, std::string("Direct ") + name + ": the " + name + " of the single layer needs a handle of the Stokes kernel "
+                                        "(this one is Laplace: fmmbem_direct_gradient is its gradient)");
+  if (host && !all_finite(pts, 3 * n_targets)) return fail(FMMBEM_ERR_INVALID, std::string("Direct ") + name + ": a target point is not finite");
+  DeviceGuard guard(direct->device);
+  HIP_TRY(guard.err);
+  const int width = direct_field_width(q);
+  if (!host) return direct->apply(n_targets, width, &q, pts, bc, x, out, s);
+  Scratch sc;
+  const double *d_pts = nullptr, *d_x = nullptr;
+  const uint8_t* d_bc = nullptr;
+  double* d_out = nullptr;
+  TRY(sc.up(pts, 3 * n_targets, &d_pts));
+  if (bc) TRY(sc.up(bc, n_targets, &d_bc));
+  TRY(sc.up(x, (size_t)direct->n * (size_t)direct->d.dof, &d_x));
+  TRY(sc.alloc(n_targets * width, &d_out));
+  TRY(direct->apply(n_targets, width, &q, d_pts, d_bc, d_x, d_out, direct->stream));
+  HIP_TRY(hipStreamSynchronize(direct->stream));
+  HIP_TRY(hipMemcpy(out, d_out, n_targets * width * sizeof(double), hipMemcpyDeviceToHost));
+  return FMMBEM_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int fmmbem_direct_gradient(fmmbem_direct* direct, size_t n_targets, const double* target_points, const uint8_t* target_bc, const double* x,
+                           double* g) {
+  return direct_field(direct, FieldQuantity::Gradient, true, n_targets, target_points, target_bc, x, g, nullptr);
+}
+int fmmbem_direct_gradient_device(fmmbem_direct* direct, size_t n_targets, const double* d_target_points, const uint8_t* d_target_bc,
+                                  const double* d_x, double* d_g, void* stream) {
+  return direct_field(direct, FieldQuantity::Gradient, false, n_targets, d_target_points, d_target_bc, d_x, d_g, static_cast<hipStream_t>(stream));
+}
+int fmmbem_direct_pressure(fmmbem_direct* direct, size_t n_targets, const double* target_points, const double* x, double* q) {
+  return direct_field(direct, FieldQuantity::Pressure, true, n_targets, target_points, nullptr, x, q, nullptr);
+}
+int fmmbem_direct_pressure_device(fmmbem_direct* direct, size_t n_targets, const double* d_target_points, const double* d_x, double* d_q,
+                                  void* stream) {
+  return direct_field(direct, FieldQuantity::Pressure, false, n_targets, d_target_points, nullptr, d_x, d_q, static_cast<hipStream_t>(stream));
+}
+int fmmbem_direct_velocity_gradient(fmmbem_direct* direct, size_t n_targets, const double* target_points, const double* x, double* G) {
+  return direct_field(direct, FieldQuantity::VelocityGradient, true, n_targets, target_points, nullptr, x, G, nullptr);
+}
+int fmmbem_direct_velocity_gradient_device(fmmbem_direct* direct, size_t n_targets, const double* d_target_points, const double* d_x,
+                                           double* d_G, void* stream) {
+  return direct_field(direct, FieldQuantity::VelocityGradient, false, n_targets, d_target_points, nullptr, d_x, d_G, static_cast<hipStream_t>(stream));
+}
 
 int fmmbem_direct_create(const fmmbem_options* opts, size_t n_sources, const double* source_vertices, fmmbem_direct** out) {
   if (out) *out = nullptr;
@@ -160,7 +229,7 @@ int fmmbem_direct_apply_device(fmmbem_direct* direct, size_t n_targets, const do
     return fail(FMMBEM_ERR_INVALID, "Direct: the symmetric form (no target points) takes n_targets = n_sources");
   DeviceGuard guard(direct->device);
   HIP_TRY(guard.err);
-  return direct->apply(n_targets, d_target_points, d_target_bc, d_x, d_y, static_cast<hipStream_t>(stream));
+  return direct->apply(n_targets, direct->d.dof, nullptr, d_target_points, d_target_bc, d_x, d_y, static_cast<hipStream_t>(stream));
 }
 
 int fmmbem_direct_apply(fmmbem_direct* direct, size_t n_targets, const double* target_points, const uint8_t* target_bc, const double* x,
@@ -181,7 +250,7 @@ int fmmbem_direct_apply(fmmbem_direct* direct, size_t n_targets, const double* t
   if (target_bc) TRY(sc.up(target_bc, n_targets, &d_bc));
   TRY(sc.up(x, (size_t)direct->n * dof, &d_x));
   TRY(sc.alloc(n_targets * dof, &d_y));
-  TRY(direct->apply(n_targets, d_pts, d_bc, d_x, d_y, direct->stream));
+  TRY(direct->apply(n_targets, direct->d.dof, nullptr, d_pts, d_bc, d_x, d_y, direct->stream));
   HIP_TRY(hipStreamSynchronize(direct->stream));
   HIP_TRY(hipMemcpy(y, d_y, n_targets * dof * sizeof(double), hipMemcpyDeviceToHost));
   return FMMBEM_OK;

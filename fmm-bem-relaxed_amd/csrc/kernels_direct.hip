@@ -4,7 +4,8 @@
 //                    ascending j:  acc = fma(K_ij, x_j, acc)  (Stokes: three accumulators, the 3x3 block applied to x_j in column
 //                    order 0, 1, 2); the partial sum goes to part[chunk][target].  K_ij is laplace_entry / stokes_entry of
 //                    near_entry.hpp as it stands -- every regime, the self term, the K_fine rule and 1/(2 mu) live there.
-//   direct_reduce    y_i = part[0][i] + part[1][i] + ...  in ascending chunk order.
+//   direct_reduce    y_i = part[0][i] + part[1][i] + ...  in ascending chunk order, over m * W doubles (W = dof, or a quantity's width).
+//   direct_field_partial   the same shape for the field quantities at points (gradient, pressure, velocity gradient), below.
 // No atomics, no cross-lane reduction, and the chunk length is a compile-time constant: a result's bits depend on the inputs only,
 // not on the number of targets of the call, the launch shape or the run.  All regimes run in ONE pass (profiles/r11a_direct_resources.md
 // has the compiler's resource report: no scratch, and the occupancy it leaves).
@@ -71,6 +72,65 @@ __global__ __launch_bounds__(kDirectBlock) void direct_reduce_kernel(const doubl
   y[k] = s;
 }
 
+// The field quantities at points (include/fmmbem.h, "Direct sum: field quantities"): the shape of direct_partial_kernel over the
+// quantity's pair function of near_entry.hpp, W = 3, 1 or 9 sums per lane.
+//   Gradient           g = laplace_grad_entry;  acc_c = fma(g_c, x_j, acc_c), c = 0, 1, 2
+//   Pressure           pi = stokes_pressure_entry;  acc = fma(pi_x, x_j0, acc), then pi_y x_j1, then pi_z x_j2
+//   VelocityGradient   stokes_velgrad_far_from / stokes_velgrad_near add the pair, contracted with f = x_j, straight into the nine
+//                      sums (the 27 numbers are never formed); the chunk's partial is stored times 1 / (2 mu) -- with one source and
+//                      x = e_e the operations of stokes_velgrad_entry
+// The K_fine and 16-point rules run in place under the lane mask: a row's order does not depend on a pair's regime.  Points are
+// the caller's (m, 3) array; part is [chunk][target][W].  profiles/r28a_direct_field_resources.md has the compiler's report.
+constexpr int field_width(FieldQuantity q) { return q == FieldQuantity::Gradient ? 3 : q == FieldQuantity::Pressure ? 1 : 9; }
+
+template <FieldQuantity Q>
+__global__ __launch_bounds__(kDirectBlock) void direct_field_partial_kernel(DevicePlan d, int64_t m, const double* __restrict__ pts,
+                                                                            const uint8_t* __restrict__ tbc, const double* __restrict__ x,
+                                                                            double* __restrict__ part) {
+  constexpr int W = field_width(Q);
+  const int64_t i = (int64_t)blockIdx.x * kDirectBlock + threadIdx.x;
+  if (i >= m) return;
+  const V3 t = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+  const int64_t N = d.n;
+  const int64_t j0 = (int64_t)blockIdx.y * kDirectChunk;
+  const int64_t j1 = j0 + kDirectChunk < N ? j0 + kDirectChunk : N;
+  double acc[W];
+#pragma unroll
+  for (int a = 0; a < W; ++a) acc[a] = 0;
+  double* out = part + ((int64_t)blockIdx.y * m + i) * W;
+  if constexpr (Q == FieldQuantity::Gradient) {
+    const int flag = tbc ? (tbc[i] ? 1 : 0) : 0;
+    for (int64_t j = j0; j < j1; ++j) {
+      const V3 g = laplace_grad_entry(d, t, flag, j);
+      const double xj = x[j];
+      acc[0] = __builtin_fma(g.x, xj, acc[0]);
+      acc[1] = __builtin_fma(g.y, xj, acc[1]);
+      acc[2] = __builtin_fma(g.z, xj, acc[2]);
+    }
+#pragma unroll
+    for (int a = 0; a < W; ++a) out[a] = acc[a];
+  } else if constexpr (Q == FieldQuantity::Pressure) {
+    for (int64_t j = j0; j < j1; ++j) {
+      const V3 pi = stokes_pressure_entry(d, t, j);
+      acc[0] = __builtin_fma(pi.x, x[3 * j], acc[0]);
+      acc[0] = __builtin_fma(pi.y, x[3 * j + 1], acc[0]);
+      acc[0] = __builtin_fma(pi.z, x[3 * j + 2], acc[0]);
+    }
+    out[0] = acc[0];
+  } else {
+    for (int64_t j = j0; j < j1; ++j) {
+      const double A = d.area[j];
+      const V3 f = {x[3 * j], x[3 * j + 1], x[3 * j + 2]};
+      if (stokes_velgrad_far_from(d, t, V3{d.cx[j], d.cy[j], d.cz[j]}, A,
+                                  [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; }, f, acc))
+        stokes_velgrad_near(d, t, j, A, f, acc);
+    }
+    const double sc = 1. / 2 / d.mu;
+#pragma unroll
+    for (int a = 0; a < W; ++a) out[a] = acc[a] * sc;
+  }
+}
+
 }  // namespace
 
 int direct_chunk() { return kDirectChunk; }
@@ -92,6 +152,36 @@ hipError_t launch_direct(const DevicePlan& d, int64_t m, const double* tx, const
     hipLaunchKernelGGL(direct_reduce_kernel<1>, dim3((unsigned)gr), block, 0, s, part, (int)nchunks, m, y);
   }
   return hipGetLastError();
+}
+
+int direct_field_width(FieldQuantity q) { return field_width(q); }
+
+namespace {
+
+template <FieldQuantity Q>
+hipError_t launch_direct_field_as(const DevicePlan& d, int64_t m, const double* pts, const uint8_t* tbc, const double* x, double* part,
+                                  double* out, hipStream_t s) {
+  constexpr int W = field_width(Q);
+  const int64_t nchunks = direct_chunks(d.n);
+  const int64_t gx = (m + kDirectBlock - 1) / kDirectBlock, gr = (m * W + kDirectBlock - 1) / kDirectBlock;
+  if (nchunks > 65535 || gx > 0x7fffffff || gr > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(direct_field_partial_kernel<Q>, dim3((unsigned)gx, (unsigned)nchunks), dim3(kDirectBlock), 0, s, d, m, pts, tbc, x, part);
+  hipLaunchKernelGGL(direct_reduce_kernel<W>, dim3((unsigned)gr), dim3(kDirectBlock), 0, s, part, (int)nchunks, m, out);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_direct_field(FieldQuantity q, const DevicePlan& d, int64_t m, const double* pts, const uint8_t* tbc, const double* x,
+                               double* part, double* out, hipStream_t s) {
+  if (m <= 0 || d.n <= 0) return hipSuccess;
+  if ((q == FieldQuantity::Gradient) != (d.dof == 1)) return hipErrorInvalidValue;    // x holds d.dof values per panel
+  switch (q) {
+    case FieldQuantity::Gradient: return launch_direct_field_as<FieldQuantity::Gradient>(d, m, pts, tbc, x, part, out, s);
+    case FieldQuantity::Pressure: return launch_direct_field_as<FieldQuantity::Pressure>(d, m, pts, tbc, x, part, out, s);
+    case FieldQuantity::VelocityGradient: return launch_direct_field_as<FieldQuantity::VelocityGradient>(d, m, pts, tbc, x, part, out, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace fmmbem

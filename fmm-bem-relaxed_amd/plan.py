@@ -335,7 +335,9 @@ class Direct:
 
     panels: (N, 3, 3) source triangles; they carry no flags -- the TARGET's flag picks the operator (Laplace G / dG/dn; Stokes
     velocity / the double layer with the source's normal).  The order of addition is fixed (chunks of .chunk sources, ascending),
-    so a result's bits do not depend on how many targets a call holds.
+    so a result's bits do not depend on how many targets a call holds.  The same handle sums the field quantities at points:
+    gradient (Laplace), pressure, velocity_gradient and stress (Stokes) -- what FMM_plan.execute_gradient / execute_pressure /
+    execute_velocity_gradient / execute_stress approximate.
     """
 
     def __init__(self, K, panels, device=0):
@@ -420,6 +422,81 @@ class Direct:
             self._h, m, None if targets is None else vp(targets.data_ptr()), None if target_bc is None else vp(target_bc.data_ptr()),
             vp(x.data_ptr()), vp(out.data_ptr()), vp(torch.cuda.current_stream(x.device).cuda_stream)))
         return out
+
+    # ---- the field quantities at points (include/fmmbem.h, "Direct sum: field quantities"): the all-pairs sums that
+    # FMM_plan.execute_gradient / execute_pressure / execute_velocity_gradient approximate, every pair's value the one
+    # kernel_gradient_entries / kernel_pressure_entries / kernel_velocity_gradient_entries gives, the order of addition fixed ----
+    def _field_host(self, symbol, x, targets, target_bc, tail, flags):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        want = (self.n,) if self.dof == 1 else (self.n, 3)
+        if x.shape != want:
+            raise ValueError("x must have shape %r" % (want,))
+        if targets is None:
+            raise ValueError("targets must be (M, 3) points or (M, 3, 3) triangles (the field quantities have no symmetric form)")
+        t, bc, m = self._targets(targets, target_bc)
+        out = np.empty((m,) + tail)
+        vp = C.c_void_p
+        args = [self._h, m, t.ctypes.data_as(vp)] + ([None if bc is None else bc.ctypes.data_as(vp)] if flags else [])
+        _capi.check(getattr(_capi.lib(), symbol)(*args, x.ctypes.data_as(vp), out.ctypes.data_as(vp)))
+        return out
+
+    def _field_torch(self, symbol, x, targets, target_bc, out, tail, flags):
+        import torch
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or x.numel() != self.n * self.dof:
+            raise ValueError("x must be a contiguous float64 CUDA tensor with dof values per panel")
+        if x.device.index != self.device:
+            raise ValueError("x lives on cuda:%s but the Direct sum was built on device %d" % (x.device.index, self.device))
+        if (targets is None or targets.dtype != torch.float64 or targets.device != x.device or not targets.is_contiguous()
+                or targets.dim() != 2 or targets.shape[1] != 3):
+            raise ValueError("targets must be a contiguous float64 tensor (M, 3) on x's device")
+        m = targets.shape[0]
+        if target_bc is not None and (target_bc.dtype != torch.uint8 or target_bc.device != x.device or not target_bc.is_contiguous()
+                                      or tuple(target_bc.shape) != (m,)):
+            raise ValueError("target_bc must be a contiguous uint8 tensor (M,) on x's device")
+        shape = (m,) + tail
+        if out is None:
+            out = x.new_empty(shape)
+        elif out.dtype != torch.float64 or out.device != x.device or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise ValueError("out must be a contiguous float64 tensor of shape %r on x's device" % (shape,))
+        vp = C.c_void_p
+        args = [self._h, m, vp(targets.data_ptr())] + ([None if target_bc is None else vp(target_bc.data_ptr())] if flags else [])
+        _capi.check(getattr(_capi.lib(), symbol)(*args, vp(x.data_ptr()), vp(out.data_ptr()),
+                                                 vp(torch.cuda.current_stream(x.device).cuda_stream)))
+        return out
+
+    def gradient(self, x, targets, target_bc=None):
+        """(N,) charges -> (M, 3): g_i = sum_j gamma(t_i, s_j) x_j over ALL panels, gamma that of FMM_plan.execute_gradient, picked by
+        target_bc[i] (None: all 0).  Laplace only: FmmBemError (status 6) on a Stokes kernel.  numpy in, numpy out (host)."""
+        return self._field_host("fmmbem_direct_gradient", x, targets, target_bc, (3,), True)
+
+    def gradient_torch(self, x, targets, target_bc=None, out=None):
+        """The same sum on device tensors, asynchronous on torch's current stream; returns (M, 3)."""
+        return self._field_torch("fmmbem_direct_gradient_device", x, targets, target_bc, out, (3,), True)
+
+    def pressure(self, x, targets):
+        """(N, 3) traction density -> (M,): q_i = sum_j pi(t_i, s_j) . x_j over ALL panels, in the scaling of
+        FMM_plan.execute_pressure (the physical pressure is q / 4 pi).  Stokes only: FmmBemError (status 6) on a Laplace kernel."""
+        return self._field_host("fmmbem_direct_pressure", x, targets, None, (), False)
+
+    def pressure_torch(self, x, targets, out=None):
+        """The same sum on device tensors, asynchronous on torch's current stream; returns (M,)."""
+        return self._field_torch("fmmbem_direct_pressure_device", x, targets, None, out, (), False)
+
+    def velocity_gradient(self, x, targets):
+        """(N, 3) traction density -> (M, 3, 3): G_i[k][m] = d u'_k / d t_m over ALL panels, in the scaling of
+        FMM_plan.execute_velocity_gradient (the 1/(2 mu) included).  Stokes only: FmmBemError (status 6) on a Laplace kernel."""
+        return self._field_host("fmmbem_direct_velocity_gradient", x, targets, None, (3, 3), False)
+
+    def velocity_gradient_torch(self, x, targets, out=None):
+        """The same sum on device tensors, asynchronous on torch's current stream; returns (M, 3, 3)."""
+        return self._field_torch("fmmbem_direct_velocity_gradient_device", x, targets, None, out, (3, 3), False)
+
+    def stress(self, x, targets):
+        """(N, 3) traction density -> (M, 3, 3): sigma_i[k][m] = -q_i delta_km + mu (G_i[k][m] + G_i[m][k]), q of pressure and G of
+        velocity_gradient, composed as FMM_plan.execute_stress composes it (the physical stress is the result / 4 pi)."""
+        q = self.pressure(x, targets)
+        g = self.velocity_gradient(x, targets)
+        return -q[:, None, None] * np.eye(3)[None] + self._K.Mu * (g + g.transpose(0, 2, 1))
 
     def close(self):
         if getattr(self, "_h", None):

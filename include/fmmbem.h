@@ -560,6 +560,48 @@ int fmmbem_direct_apply_device(fmmbem_direct *direct, size_t n_targets, const do
 int fmmbem_direct_chunk(void);
 void fmmbem_direct_destroy(fmmbem_direct *direct);
 
+/* ---- Direct sum: field quantities -- the gradient, the pressure and the velocity gradient at points, over ALL sources ---------
+ * The exact sums the field executes above approximate: on a handle of fmmbem_direct_create, for target point t_i (target_points:
+ * n_targets x 3, required: there is no symmetric form),
+ *   fmmbem_direct_gradient            Laplace handles only.  g_i = sum_j gamma(t_i, s_j) x_j, three doubles per target; gamma is that
+ *                                     of fmmbem_plan_execute_gradient, picked by target_bc[i] (NULL: all 0).
+ *   fmmbem_direct_pressure            Stokes handles only, no flags.  q_i = sum_j pi(t_i, s_j) . x_j, one double per target; pi and
+ *                                     the scaling are those of fmmbem_plan_execute_pressure.
+ *   fmmbem_direct_velocity_gradient   Stokes handles only, no flags.  G_i[k][m], nine doubles per target, row-major; the tensor and
+ *                                     the scaling (the 1/(2 mu) included) are those of fmmbem_plan_execute_velocity_gradient.
+ * Every pair's value is the one the field executes' near kernels and fmmbem_kernel_{gradient,pressure,velocity_gradient}_entries
+ * compute, in every regime (self, the fine rule on the vertices, the K stored points).  x: n_sources x dof, as for apply; the
+ * outputs are OVERWRITTEN.  The host forms take HOST pointers and return when the result is written; the _device forms take
+ * device pointers and are asynchronous on `stream`.
+ * Order of addition, fixed: the chunks of fmmbem_direct_chunk() consecutive sources, ascending j within a chunk from zero sums, the
+ * chunks' partial sums added in ascending chunk order, as for apply.  Within a chunk
+ *   gradient            acc_c = fma(gamma_c, x_j, acc_c), c = 0, 1, 2;
+ *   pressure            acc = fma(pi_x, x_j0, acc), then pi_y x_j1, then pi_z x_j2;
+ *   velocity gradient   every pair is added straight into the chunk's nine sums, each quadrature point's tensor contracted with
+ *                       f = x_j in place and unscaled, points in order; the nine sums are multiplied by 1/2/mu once, where the
+ *                       chunk's partial sum is stored.  With one source and x = e_e these are the operations of
+ *                       fmmbem_kernel_velocity_gradient_entries: the result is its column e, bit for bit.
+ * A result's bits therefore depend on the inputs only -- not on n_targets, on how a set of targets is split over calls, or on the
+ * run.
+ * Checked in this order: a null handle, points, x or output -> FMMBEM_ERR_INVALID; n_targets == 0 -> _INVALID; the wrong kind of
+ * handle (gradient on a Stokes handle; pressure or velocity gradient on a Laplace handle) -> FMMBEM_ERR_UNSUPPORTED, the message
+ * naming the quantity and the kernel it needs; host forms only: a target point that is not finite -> _INVALID.  On every refusal
+ * the output is untouched and the handle stays usable.  The partial sums live in the handle's buffer, as for apply (width 3, 1 or
+ * 9 doubles per chunk and target; at most 256 MB, more targets are served in slabs); if growing it fails: FMMBEM_ERR_ALLOC, the
+ * buffer is left empty and the handle stays usable. */
+int fmmbem_direct_gradient(fmmbem_direct *direct, size_t n_targets, const double *target_points, const uint8_t *target_bc,
+                           const double *x, double *g /* n_targets x 3 */);
+int fmmbem_direct_gradient_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const uint8_t *d_target_bc,
+                                  const double *d_x, double *d_g, void *stream);
+int fmmbem_direct_pressure(fmmbem_direct *direct, size_t n_targets, const double *target_points, const double *x /* n x 3 */,
+                           double *q /* n_targets */);
+int fmmbem_direct_pressure_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const double *d_x,
+                                  double *d_q, void *stream);
+int fmmbem_direct_velocity_gradient(fmmbem_direct *direct, size_t n_targets, const double *target_points, const double *x /* n x 3 */,
+                                    double *G /* n_targets x 9 */);
+int fmmbem_direct_velocity_gradient_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const double *d_x,
+                                           double *d_G, void *stream);
+
 /* ---- the orthogonalisation step of the callers above the matvec (examples/BEM/GMRES.hpp:203-212: modified Gram-Schmidt of
  * w against V_0 .. V_{ncols-1}, then the normalised next basis vector), device vectors, ONE call per Arnoldi column:
  *   for k < ncols:  h[k] = <w, V_k>;  w -= h[k] V_k;      h[ncols] = |w|;   vnext = w / h[ncols]

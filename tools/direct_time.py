@@ -7,6 +7,11 @@ warm-up); pairs/s = N M / time.  Unless --no-baseline, each case is also timed o
   symmetric form   the CPU oracle's Direct (oracle.direct), what tests and bench.py use from Python;
   exterior points  fmmbem_kernel_entries for all 8 N pairs plus the additions on the host -- the calls and the loop of
                    Direct::matvec in include/fmmbem/compat/Direct.hpp, made from Python.
+--quantity gradient|pressure|velocity_gradient (default matvec: everything above, unchanged) times that field quantity of the Direct
+sum instead (fb.Direct.gradient_torch / pressure_torch / velocity_gradient_torch) at the same sizes -- the sources' own centroids
+moved off the surface by 0.05 of their length as explicit points for N = 8 192 and 32 768 (the quantities have no symmetric form, and
+a point ON a panel is the caller's business), and the 8 exterior points against N = 524 288 -- and, in the same run, apply on the same
+points; ratio_to_apply = the quantity's pairs/s over apply's.  No baseline.
 Prints one JSON document."""
 import argparse
 import json
@@ -41,11 +46,44 @@ def device_ms(fn, repeats):
     return e0.elapsed_time(e1) / repeats
 
 
+def time_quantity(quantity, repeats):
+    """the cases of main() for one field quantity, each beside apply on the same points"""
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(1)
+    kind = "laplace" if quantity == "gradient" else "stokes"
+    dof = 1 if kind == "laplace" else 3
+    tail = {"gradient": (3,), "pressure": (), "velocity_gradient": (3, 3)}[quantity]
+    out = dict(chunk=fb.lib().fmmbem_direct_chunk(), device=torch.cuda.get_device_name(0), quantity=quantity, cases=[])
+    d8 = rng.normal(size=(8, 3))
+    for r in (6, 7, 9):
+        v = fb.unit_sphere(r)
+        n = len(v)
+        c = (v[:, 0] + v[:, 1] + v[:, 2]) / 3
+        pts = np.ascontiguousarray(1.05 * c if r != 9 else 3 * d8 / np.linalg.norm(d8, axis=1)[:, None])
+        m = len(pts)
+        x = rng.normal(size=(n,) if dof == 1 else (n, 3))
+        D = fb.Direct(kernel(kind), v)
+        xd, pd = torch.from_numpy(x).to(dev), torch.from_numpy(pts).to(dev)
+        y = torch.empty((m,) if dof == 1 else (m, 3), dtype=torch.float64, device=dev)
+        o = torch.empty((m,) + tail, dtype=torch.float64, device=dev)
+        ms_apply = device_ms(lambda: D.matvec_torch(xd, pd, out=y), repeats)
+        ms = device_ms(lambda: getattr(D, quantity + "_torch")(xd, pd, out=o), repeats)
+        D.close()
+        out["cases"].append(dict(kernel=kind, form="points off the surface" if r != 9 else "exterior points", n_sources=n, n_targets=m, ms=ms,
+                                 pairs_per_s=n * m / (ms * 1e-3), apply_ms=ms_apply, apply_pairs_per_s=n * m / (ms_apply * 1e-3),
+                                 ratio_to_apply=ms_apply / ms))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--quantity", choices=("matvec", "gradient", "pressure", "velocity_gradient"), default="matvec")
     a = ap.parse_args()
+    if a.quantity != "matvec":
+        print(json.dumps(time_quantity(a.quantity, a.repeats), indent=1))
+        return
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(1)
     out = dict(chunk=fb.lib().fmmbem_direct_chunk(), device=torch.cuda.get_device_name(0), cases=[])

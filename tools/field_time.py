@@ -17,6 +17,9 @@ Per order, with <q> the quantity and <k> its kernels' short name (grad, pressure
                                  ms_near_<k>_kernel and ms_l2p_<k>_kernel;
   stages_execute                 the same for the potential or velocity execute (ms_near: the near-matrix stream, ms_l2p: l2p_kernel
                                  or l2p_stokes_kernel).
+--check M (default 0: off): the Direct quantity (fb.Direct.gradient_torch / pressure_torch / velocity_gradient_torch: all N panels,
+every regime) on M points sampled over the whole target set; per order rel_l2_vs_direct_on_sample, the relative L2 of the field
+execute against it on those points, and under "check" the sample's size and the device time of that sum.
 Prints one JSON document."""
 import argparse
 import json
@@ -79,6 +82,7 @@ def main():
     ap.add_argument("--orders", default=None)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--flag", type=int, default=0)
+    ap.add_argument("--check", type=int, default=0)
     a = ap.parse_args()
     q = a.quantity
     if a.flag and q != "gradient":
@@ -110,6 +114,17 @@ def main():
     od = torch.empty((len(pts),) + tail, dtype=torch.float64, device=dev)
     qd = torch.empty(len(pts), dtype=torch.float64, device=dev) if q == "velocity_gradient" else None
     run = getattr(plan, "execute_%s_torch" % q)
+    direct = None
+    if a.check > 0:
+        # the Direct quantity on a sample spread over the whole target set (tools/stokes_field_time.py does this for the velocity)
+        rows = np.sort(np.random.default_rng(2).choice(len(pts), min(a.check, len(pts)), replace=False))
+        rows_d, sample = torch.from_numpy(rows).to(dev), torch.from_numpy(pts[rows]).to(dev)
+        direct = fb.Direct(K, v)
+        args = (xd, sample, torch.from_numpy(flags[rows]).to(dev)) if q == "gradient" else (xd, sample)
+        sum_on_sample = getattr(direct, q + "_torch")
+        ref = sum_on_sample(*args)
+        out["check"] = dict(sample=len(rows), direct_on_sample_ms=device_ms(lambda: sum_on_sample(*args), 1))
+        out["check"]["direct_on_all_targets_ms_extrapolated"] = out["check"]["direct_on_sample_ms"] * len(pts) / len(rows)
     for p in orders:
         K.set_p(p)
         rec = dict(p=p)
@@ -123,6 +138,9 @@ def main():
         rec["ms_l2p_%s_kernel" % short] = rec["stages_" + q]["ms_l2p"]
         if q == "gradient":
             rec["near_pairs_per_s"] = out["near_nnz"] / (rec["ms_near_grad_kernel"] * 1e-3)
+        if direct is not None:
+            got = run(xd, out=od)[rows_d]
+            rec["rel_l2_vs_direct_on_sample"] = float(torch.linalg.norm(got - ref) / torch.linalg.norm(ref))
         out["orders"].append(rec)
     print(json.dumps(out, indent=1))
 
