@@ -30,6 +30,10 @@ fplan.execute_stress; prints "field velocity gradient (FMM): ..." and "field str
 and, for the unit sphere, the largest deviation of G / 4 pi from the exact velocity gradient of a translating sphere, relative to that
 gradient's largest entry on the points.
 
+With -field_fmm N and -field_pressure and/or -field_stress the field comes from ONE fplan.execute_flow_torch (fmmbem_plan_execute_flow):
+the velocity, the pressure and the gradient on one far chain, each bit for bit what its single execute returns, so every line above
+is what it was.
+
 -field_direct (not a flag of the reference; with -field_fmm N and -field_pressure and/or -field_stress): the same quantities on the same
 N points summed over all panels on the device by fb.Direct (pressure_torch, velocity_gradient_torch); after the "field pressure (FMM):"
 and the "field velocity gradient (FMM):" line prints "... against Direct: relative L2 difference ...", the distance of the FMM's value
@@ -277,10 +281,17 @@ def main(argv):
     if field_fmm > 0:
         fplan = plan.field_plan(sphere_points(field_fmm, 3.0))       # VELOCITY targets: the single layer
         plan.kernel().set_p(p)                             # (the relaxed solve leaves the kernel at its last order)
-        uf = fplan.execute_torch(x).cpu().numpy()
-        q = fplan.execute_pressure_torch(x).cpu().numpy() if field_pressure else None
-        gu = fplan.execute_velocity_gradient_torch(x).cpu().numpy() if field_stress else None
-        sig = fplan.execute_stress(x.cpu().numpy()) if field_stress else None
+        q = gu = sig = None
+        if field_pressure or field_stress:
+            # ONE flow execute (fmmbem_plan_execute_flow): the velocity, the pressure (the stress needs it too) and the gradient on
+            # one far chain, each with the bits of its single execute; the stress by execute_stress's formula
+            uf, q, gu = (a if a is None else a.cpu().numpy() for a in fplan.execute_flow_torch(x, True, True, field_stress))
+            if field_stress:
+                sig = -q[:, None, None] * np.eye(3)[None] + fplan.kernel().Mu * (gu + gu.transpose(0, 2, 1))
+            if not field_pressure:
+                q = None
+        else:
+            uf = fplan.execute_torch(x).cpu().numpy()
         fplan.close()
         q_direct = gu_direct = None
         if field_direct:

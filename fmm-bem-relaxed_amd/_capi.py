@@ -113,6 +113,7 @@ SYMBOLS = (
     "fmmbem_plan_execute_gradient", "fmmbem_plan_execute_gradient_device", "fmmbem_kernel_gradient_entries",
     "fmmbem_plan_execute_pressure", "fmmbem_plan_execute_pressure_device", "fmmbem_kernel_pressure_entries",
     "fmmbem_plan_execute_velocity_gradient", "fmmbem_plan_execute_velocity_gradient_device", "fmmbem_kernel_velocity_gradient_entries",
+    "fmmbem_plan_execute_flow", "fmmbem_plan_execute_flow_device",
 )
 
 
@@ -233,6 +234,8 @@ def lib():
     L.fmmbem_plan_execute_velocity_gradient.argtypes = [vp, i32, vp, vp]
     L.fmmbem_plan_execute_velocity_gradient_device.argtypes = [vp, i32, vp, vp, vp]
     L.fmmbem_kernel_velocity_gradient_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp]
+    L.fmmbem_plan_execute_flow.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.fmmbem_plan_execute_flow_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -87,6 +87,7 @@ hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, h
 // entries: gamma (3 doubles), pi (3) or Gamma (27, [k][m][e]) for pairs laid out as launch_kernel_entries takes them
 enum class FieldQuantity { Gradient, Pressure, VelocityGradient };
 hipError_t launch_near_field(FieldQuantity q, const DevicePlan& d, int64_t n_src, double* tree, hipStream_t s);
+hipError_t launch_near_flow(const DevicePlan& d, int64_t n_src, double* q_tree, double* g_tree, hipStream_t s);   // Pressure and VelocityGradient in one kernel
 hipError_t launch_l2p_field(FieldQuantity q, const DevicePlan& d, int p, int64_t n_src, double* tree, hipStream_t s);
 hipError_t launch_field_scatter(FieldQuantity q, const DevicePlan& d, int64_t n_src, const double* tree, double* out, hipStream_t s);
 hipError_t launch_field_entries(FieldQuantity q, const DevicePlan& d, int m, double* out, hipStream_t s);

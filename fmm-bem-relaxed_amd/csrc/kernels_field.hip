@@ -11,6 +11,8 @@
 //
 //   near_field_kernel<Q>      the near pairs, matrix-free (the stored near matrix holds potentials or velocities): Q's pair function
 //                             of near_entry.hpp; explicitly specialised for the velocity gradient
+//   near_flow_kernel          the pressure's and the velocity gradient's near pairs in one walk (fmmbem_plan_execute_flow), with the
+//                             bits of the two kernels above
 //   l2p_*_kernel<PT>          what a quantity reads of the local expansions the potential execute evaluates, along the spherical
 //                             chain: one kernel per quantity over the shared tables and staging
 //   field_scatter_kernel<W>   tree order -> distinct points, W doubles per row
@@ -242,6 +244,66 @@ __global__ __launch_bounds__(kNearWaves * kWave) void near_field_kernel<Velocity
         }
       }
       if (live) {
+        double* o = gt + 9 * (size_t)(i - n_src);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) o[c] = sc * acc[c];
+      }
+    }
+  }
+}
+
+// The flow execute's near kernel (include/fmmbem.h "Flow execute"): the pressure AND the velocity gradient of a row in one walk
+// over its near lists -- the loop above a third time, the 7 + 3 K doubles of a panel staged once, one regime test per pair, and
+// per quadrature point one t - y_q, r2 and reciprocal square root feeding pressure_point and velgrad_point (stokes_flow_far_from /
+// stokes_flow_near of near_entry.hpp).  q += pi . f per pair in PressureQ::pair's expression, the nine sums scaled by 1 / (2 mu) at
+// the store, two stores: the bits of near_field_kernel<PressureQ> and near_field_kernel<VelocityGradientQ>.
+__global__ __launch_bounds__(kNearWaves * kWave) void near_flow_kernel(DevicePlan d, const int64_t n_src, const int PB, double* __restrict__ qt,
+                                                                       double* __restrict__ gt) {
+  extern __shared__ double field_near_lds[];            // [wave][field][PB]
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int nq = d.nq, nf = 7 + 3 * nq;
+  const int64_t N = d.n;
+  const double sc = 1. / 2 / d.mu;
+  double* rec = field_near_lds + (size_t)wave * PB * nf;
+  const int nleaf = d.leaf_end - d.leaf_begin;
+  for (int li = blockIdx.x * kNearWaves + wave; li < nleaf; li += gridDim.x * kNearWaves) {
+    const int leaf = __builtin_amdgcn_readfirstlane(d.leaf_begin + li);
+    const int row0 = d.leaf_row0[leaf], nrows = d.leaf_nrows[leaf], ncols = d.near_ncols[leaf];
+    const int64_t k0 = d.near_ptr[leaf], k1 = d.near_ptr[leaf + 1];
+    for (int chunk = 0; chunk < nrows; chunk += kWave) {
+      const bool live = chunk + lane < nrows;
+      const int64_t i = row0 + (live ? chunk + lane : 0);   // idle lanes take the leaf's first row and store nothing
+      const V3 t = {d.cx[i], d.cy[i], d.cz[i]};
+      double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      double q = 0;
+      for (int64_t k = k0; k < k1; ++k) {
+        const int j0 = d.near_run_row0[k], off = d.near_run_off[k];
+        const int len = (k + 1 < k1 ? d.near_run_off[k + 1] : ncols) - off;
+        for (int jb = j0; jb < j0 + len; jb += PB) {
+          const int nb = j0 + len - jb < PB ? j0 + len - jb : PB;
+          wave_lds_sync();                                // the previous batch's reads are done
+          if (lane < nb) {                                // (PB <= 64: one panel per lane)
+            const int64_t j = jb + lane;
+            rec[0 * PB + lane] = d.cx[j]; rec[1 * PB + lane] = d.cy[j]; rec[2 * PB + lane] = d.cz[j]; rec[3 * PB + lane] = d.area[j];
+            rec[4 * PB + lane] = d.xt[3 * j]; rec[5 * PB + lane] = d.xt[3 * j + 1]; rec[6 * PB + lane] = d.xt[3 * j + 2];
+            for (int qq = 0; qq < 3 * nq; ++qq) rec[(7 + qq) * PB + lane] = d.quad[qq * N + j];
+          }
+          wave_lds_sync();
+          for (int e = 0; e < nb; ++e) {
+            const double A = rec[3 * PB + e];
+            const V3 f = {rec[4 * PB + e], rec[5 * PB + e], rec[6 * PB + e]};
+            V3 pi;
+            if (stokes_flow_far_from(d, t, V3{rec[0 * PB + e], rec[1 * PB + e], rec[2 * PB + e]}, A,
+                                     [&](int p) { return V3{rec[(7 + 3 * p) * PB + e], rec[(8 + 3 * p) * PB + e], rec[(9 + 3 * p) * PB + e]}; }, f, pi, acc))
+              stokes_flow_near(d, t, (int64_t)jb + e, A, f, pi, acc);
+            // pi . f as near_field_kernel<PressureQ> is compiled: of PressureQ::pair's sum of three products the y product is the
+            // plain one and x, then z, are fused onto it.  Written out, because here the compiler starts from the x product.
+            q += fma(pi.z, f.z, fma(pi.x, f.x, pi.y * f.y));
+          }
+        }
+      }
+      if (live) {
+        qt[i - n_src] = q;
         double* o = gt + 9 * (size_t)(i - n_src);
 #pragma unroll
         for (int c = 0; c < 9; ++c) o[c] = sc * acc[c];
@@ -728,6 +790,18 @@ hipError_t launch_near_field(FieldQuantity q, const DevicePlan& d, int64_t n_src
     hipLaunchKernelGGL(near_field_kernel<QT>, dim3(nblk < 256 * 16 ? nblk : 256 * 16), dim3(kNearWaves * kWave), lds, s, d, n_src, pb, tree);
     return hipGetLastError();
   });
+}
+
+// the pressure's and the velocity gradient's near pairs in one kernel (near_flow_kernel): the grid, the batch and the LDS of the
+// velocity gradient's own launch
+hipError_t launch_near_flow(const DevicePlan& d, int64_t n_src, double* q_tree, double* g_tree, hipStream_t s) {
+  const int nleaf = d.leaf_end - d.leaf_begin;
+  if (nleaf <= 0) return hipSuccess;
+  const int nblk = (nleaf + kNearWaves - 1) / kNearWaves, nf = VelocityGradientQ::kRec + 3 * d.nq;
+  const int pb = near_batch(nf);
+  const size_t lds = sizeof(double) * (size_t)kNearWaves * pb * nf;
+  hipLaunchKernelGGL(near_flow_kernel, dim3(nblk < 256 * 16 ? nblk : 256 * 16), dim3(kNearWaves * kWave), lds, s, d, n_src, pb, q_tree, g_tree);
+  return hipGetLastError();
 }
 
 hipError_t launch_l2p_field(FieldQuantity q, const DevicePlan& d, int p, int64_t n_src, double* tree, hipStream_t s) {

@@ -489,6 +489,46 @@ __device__ inline void stokes_velgrad_entry(const DevicePlan& d, V3 t, int64_t j
   for (int c = 0; c < 9; ++c) G[c] *= sc;
 }
 
+// The pressure and the velocity gradient of one pair TOGETHER (include/fmmbem.h, "Flow execute"): the regime test once -- the two
+// quantities' tests are the same expressions -- and per point pressure_point's update of the pair's pi and velgrad_point's update of
+// the nine sums, one after the other on the same t, point and weight.  Both are inlined here, so their common subexpressions --
+// t - y_q, r2, the reciprocal square root, wA / r^3 -- are computed once; each keeps its own text above, and with it its bits.
+// flow_far_from sets pi and adds to G for a pair in the far regime (pi = 0 and nothing added for a self pair) or says `deferred`;
+// flow_near the K_fine rule on the vertices of panel j.
+template <class Quad>
+__device__ __forceinline__ bool stokes_flow_far_from(const DevicePlan& d, V3 t, V3 c, double A, Quad&& quad, V3 f, V3& pi, double (&G)[9]) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  pi = {0, 0, 0};
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {
+    const double dist = sqrt(d2);
+    if (dist < 1e-8) return false;
+    if (sqrt(2 * A) / dist >= 0.5) return true;
+  }
+  for (int q = 0; q < d.nq; ++q) {
+    const double wA = d.qw[q] * A;
+    const V3 pt = quad(q);
+    pressure_point(pi, wA, t, pt);
+    velgrad_point(G, wA, t, pt, f);
+  }
+  return false;
+}
+__device__ __forceinline__ void stokes_flow_near(const DevicePlan& d, V3 t, int64_t j, double A, V3 f, V3& pi, double (&G)[9]) {
+  const int64_t N = d.n;
+  const V3 v0 = {d.vert[0 * N + j], d.vert[1 * N + j], d.vert[2 * N + j]};
+  const V3 v1 = {d.vert[3 * N + j], d.vert[4 * N + j], d.vert[5 * N + j]};
+  const V3 v2 = {d.vert[6 * N + j], d.vert[7 * N + j], d.vert[8 * N + j]};
+  pi = {0, 0, 0};
+  for (int q = 0; q < d.nqf; ++q) {
+    const V3 pt = {v0.x * d.qf[4 * q + 0] + v1.x * d.qf[4 * q + 1] + v2.x * d.qf[4 * q + 2],
+                   v0.y * d.qf[4 * q + 0] + v1.y * d.qf[4 * q + 1] + v2.y * d.qf[4 * q + 2],
+                   v0.z * d.qf[4 * q + 0] + v1.z * d.qf[4 * q + 1] + v2.z * d.qf[4 * q + 2]};
+    const double wA = d.qf[4 * q + 3] * A;
+    pressure_point(pi, wA, t, pt);
+    velgrad_point(G, wA, t, pt, f);
+  }
+}
+
 }  // namespace
 
 }  // namespace fmmbem

@@ -270,6 +270,12 @@ struct fmmbem_plan {
   int field_refusal(FieldQuantity q, int p) const;
   int field_alloc(FieldQuantity q);
   int run_field(FieldQuantity q, int p, const double* d_x, double* d_out, hipStream_t s);
+  // The flow execute (fmmbem_plan_execute_flow): velocity, pressure and velocity gradient on one far chain
+  int flow_refusal(int p) const;
+  int near_potential(bool near_f32, hipStream_t s);
+  int deliver_field(FieldQuantity q, double* d_out, hipStream_t s) const;
+  int run_flow(int p, const double* d_x, double* d_u, double* d_q, double* d_G, hipStream_t s);
+  enum : int { kFlowNearNone = 0, kFlowNearFused = 2, kFlowNearSingle = 3 };       // fmmbem_stats.last_near_f32 after a flow execute
 
   template <class V, class T>
   int upload(const V& v, const T** out) { return mem->upload(v, out); }
@@ -942,6 +948,18 @@ int fmmbem_plan::deliver(const DevicePlan& dv, double* d_y, bool fold, hipStream
   return FMMBEM_OK;
 }
 
+// The near field of the potential into y_tree, by the kernel the plan's options pick: what run() and the flow execute launch
+int fmmbem_plan::near_potential(bool near_f32, hipStream_t ns) {
+  // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
+  // only added to by L2P -- they start from zero
+  if (targets && zero_target_rows)
+    HIP_TRY(hipMemsetAsync(d.yt + hp.n_src * d.dof, 0, sizeof(double) * (size_t)(hp.n - hp.n_src) * d.dof, ns));
+  if (g.hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
+  else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
+  else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
+  return FMMBEM_OK;
+}
+
 int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool near_only, Phase phase, double* xbuf) {
   if (!on_device && targets) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
   if (!on_device) return fail(FMMBEM_ERR_NO_DEVICE, "plan was built host-only; there is no CPU execution path");
@@ -1008,13 +1026,7 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
   const bool near_f32 = d.near_f32 && p <= opts.near_f32_max_p;
   auto near_field = [&](hipStream_t ns) -> int {
     HIP_TRY(tm.begin(Stage::Spmv, ns));
-    // a target plan: rows of target leaves without a near pair (targets away from the surface) are not written by the near field,
-    // only added to by L2P -- they start from zero
-    if (targets && zero_target_rows)
-      HIP_TRY(hipMemsetAsync(d.yt + hp.n_src * d.dof, 0, sizeof(double) * (size_t)(hp.n - hp.n_src) * d.dof, ns));
-    if (g.hybrid) HIP_TRY(launch_near_hybrid(d, ns, hyb));
-    else if (near_f32) HIP_TRY(launch_near_spmv_f32(d, ns));        // the float copy at the low orders (near_f32_max_p)
-    else if (opts.sparse_local) HIP_TRY(launch_near_spmv(d, ns)); else HIP_TRY(launch_near_matfree(d, ns));
+    TRY(near_potential(near_f32, ns));
     HIP_TRY(tm.end(Stage::Spmv, ns));
     return FMMBEM_OK;
   };
@@ -1110,7 +1122,6 @@ int fmmbem_plan::run_field(FieldQuantity q, int p, const double* d_x, double* d_
   TRY(field_refusal(q, p));
   DEVICE_SCOPE(opts.device);
   TRY(field_alloc(q));
-  const int width = kField[(int)q].width;
   const FieldBuffers& b = field[(int)q];
   const int64_t ring = ev_count % kRing;
   StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
@@ -1128,14 +1139,77 @@ int fmmbem_plan::run_field(FieldQuantity q, int p, const double* d_x, double* d_
   HIP_TRY(launch_l2p_field(q, d, p, hp.n_src, b.tree, s));
   HIP_TRY(tm.end(Stage::L2P, s));
   HIP_TRY(tm.begin(Stage::Scatter, s));
+  TRY(deliver_field(q, d_out, s));
+  HIP_TRY(tm.end(Stage::Scatter, s));
+  last_p = p;
+  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
+  return FMMBEM_OK;
+}
+
+// a quantity's tree buffer -> the distinct points -> the targets as given
+int fmmbem_plan::deliver_field(FieldQuantity q, double* d_out, hipStream_t s) const {
+  const int width = kField[(int)q].width;
+  const FieldBuffers& b = field[(int)q];
   HIP_TRY(launch_field_scatter(q, d, hp.n_src, b.tree, d_target_point ? b.points : d_out, s));
   if (d_target_point) {
     const int64_t nu = width * (int64_t)hp.n_targets;  // unknowns, one thread each
     hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, b.points, d_out, nu, width);
     HIP_TRY(hipGetLastError());
   }
+  return FMMBEM_OK;
+}
+
+// ======================================= flow execute =======================================
+// fmmbem_plan_execute_flow: what the velocity execute and the pressure's and the velocity gradient's field executes write, on ONE
+// gather, P2M and far chain.  Every kernel that touches an output is the one the single execute launches, on the same L, in the
+// same order per buffer -- near kernel, then L2P, then the delivery -- so each output has the single execute's bits; the one new
+// kernel, near_flow_kernel (kernels_field.hip), writes the pressure's and the gradient's tree buffers with their own kernels' bits.
+// Launched plainly like a field execute; the velocity's near field goes into y_tree as run() puts it there (near_potential).
+int fmmbem_plan::flow_refusal(int p) const {
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the flow execute: on a plan over separate targets only (fmmbem_plan_create_field)");
+  if (opts.kernel != FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the flow execute: Stokes plans only");
+  if (has_bc[1]) return fail(FMMBEM_ERR_UNSUPPORTED, "the flow execute: VELOCITY targets only (the pressure and the gradient of the double layer are not built)");
+  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan::run_flow(int p, const double* d_x, double* d_u, double* d_q, double* d_G, hipStream_t s) {
+  if (!d_x || (!d_u && !d_q && !d_G)) return fail(FMMBEM_ERR_INVALID, "null vector, or no output asked");
+  TRY(flow_refusal(p));
+  DEVICE_SCOPE(opts.device);
+  if (d_q) TRY(field_alloc(FieldQuantity::Pressure));
+  if (d_G) TRY(field_alloc(FieldQuantity::VelocityGradient));
+  double* const qt = field[(int)FieldQuantity::Pressure].tree;
+  double* const gt = field[(int)FieldQuantity::VelocityGradient].tree;
+  const int64_t ring = ev_count % kRing;
+  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
+  HIP_TRY(tm.begin(Stage::Gather, s));
+  DevicePlan dg = d;
+  dg.n = hp.n_src;                                     // x: the source panels only (the target rows of x_tree stay 0)
+  HIP_TRY(launch_gather_x(dg, d_x, s));
+  HIP_TRY(tm.end(Stage::Gather, s));
+  TRY(p2m(d, p, tm, s));
+  TRY(far_chain(d, d_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));      // (Caller: no L2P in there)
+  const bool near_f32 = d.near_f32 && p <= opts.near_f32_max_p;                   // as run() picks the velocity's near kernel
+  HIP_TRY(tm.begin(Stage::Spmv, s));
+  if (d_u) TRY(near_potential(near_f32, s));
+  if (d_q && d_G) HIP_TRY(launch_near_flow(d, hp.n_src, qt, gt, s));
+  else if (d_q) HIP_TRY(launch_near_field(FieldQuantity::Pressure, d, hp.n_src, qt, s));
+  else if (d_G) HIP_TRY(launch_near_field(FieldQuantity::VelocityGradient, d, hp.n_src, gt, s));
+  HIP_TRY(tm.end(Stage::Spmv, s));
+  HIP_TRY(tm.begin(Stage::L2P, s));
+  if (d_u) TRY(l2p(d, p, nullptr, s));
+  if (d_q) HIP_TRY(launch_l2p_field(FieldQuantity::Pressure, d, p, hp.n_src, qt, s));
+  if (d_G) HIP_TRY(launch_l2p_field(FieldQuantity::VelocityGradient, d, p, hp.n_src, gt, s));
+  HIP_TRY(tm.end(Stage::L2P, s));
+  HIP_TRY(tm.begin(Stage::Scatter, s));
+  if (d_u) TRY(deliver(d, d_u, false, s));
+  if (d_q) TRY(deliver_field(FieldQuantity::Pressure, d_q, s));
+  if (d_G) TRY(deliver_field(FieldQuantity::VelocityGradient, d_G, s));
   HIP_TRY(tm.end(Stage::Scatter, s));
   last_p = p;
+  last_near_f32 = d_q && d_G ? kFlowNearFused : d_q || d_G ? kFlowNearSingle : kFlowNearNone;
   if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
   return FMMBEM_OK;
 }
@@ -2021,6 +2095,31 @@ int fmmbem_plan_execute_velocity_gradient_device(fmmbem_plan* plan, int p, const
 }
 int fmmbem_plan_execute_velocity_gradient(fmmbem_plan* plan, int p, const double* x, double* G) {
   return field_execute(plan, FieldQuantity::VelocityGradient, p, x, G);
+}
+
+// ---- flow execute (include/fmmbem.h) ----
+int fmmbem_plan_execute_flow_device(fmmbem_plan* plan, int p, const double* d_x, double* d_u, double* d_q, double* d_G, void* stream) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  return plan->run_flow(p, d_x, d_u, d_q, d_G, static_cast<hipStream_t>(stream));
+}
+int fmmbem_plan_execute_flow(fmmbem_plan* plan, int p, const double* x, double* u, double* q, double* G) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if (!x || (!u && !q && !G)) return fail(FMMBEM_ERR_INVALID, "null vector, or no output asked");
+  TRY(plan->flow_refusal(p));                          // a refusal touches no pointer
+  DEVICE_SCOPE(plan->opts.device);
+  if (q) TRY(plan->field_alloc(FieldQuantity::Pressure));
+  if (G) TRY(plan->field_alloc(FieldQuantity::VelocityGradient));
+  double* const sq = plan->field[(int)FieldQuantity::Pressure].stage;
+  double* const sG = plan->field[(int)FieldQuantity::VelocityGradient].stage;
+  const size_t nt = (size_t)plan->hp.n_targets;
+  hipStream_t s = plan->own_stream;
+  HIP_TRY(hipMemcpyAsync(plan->stage_x, x, sizeof(double) * plan->x_doubles(), hipMemcpyHostToDevice, s));
+  TRY(plan->run_flow(p, plan->stage_x, u ? plan->stage_y_targets : nullptr, q ? sq : nullptr, G ? sG : nullptr, s));
+  if (u) HIP_TRY(hipMemcpyAsync(u, plan->stage_y_targets, sizeof(double) * plan->y_doubles(), hipMemcpyDeviceToHost, s));
+  if (q) HIP_TRY(hipMemcpyAsync(q, sq, sizeof(double) * nt, hipMemcpyDeviceToHost, s));
+  if (G) HIP_TRY(hipMemcpyAsync(G, sG, sizeof(double) * 9 * nt, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
 }
 
 // ---- batched execute (include/fmmbem.h) ----

@@ -848,13 +848,56 @@ class FMM_plan:
         current stream."""
         return self._field_torch(self.execute_velocity_gradient_device, x, out, p, (3, 3), "dof values")
 
+    # ---- the flow execute: velocity, pressure and velocity gradient on one far chain (include/fmmbem.h, "Flow execute") ----
+    def execute_flow(self, traction, velocity=True, pressure=True, velocity_gradient=True):
+        """(N, 3) or (3N,) traction density -> (u, q, G) at the kernel's current p: u (M, 3) what execute returns, q (M,) what
+        execute_pressure returns, G (M, 3, 3) what execute_velocity_gradient returns, bit for bit, from ONE gather, P2M and far
+        chain; None for what was not asked.  numpy in, numpy out (host).  FmmBemError (status 6) on a plan that is not over
+        separate targets, on a Laplace plan, on a plan with a TRACTION target and on a host-only plan."""
+        x = np.ascontiguousarray(traction, dtype=np.float64)
+        if x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
+            raise ValueError("traction must have dof values per panel")
+        if not (velocity or pressure or velocity_gradient):
+            raise ValueError("no output asked")
+        rows = self._field_rows()
+        u = np.empty((rows, 3)) if velocity else None
+        q = np.empty((rows,)) if pressure else None
+        g = np.empty((rows, 3, 3)) if velocity_gradient else None
+        ptr = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in (u, q, g)]
+        _capi.check(_capi.lib().fmmbem_plan_execute_flow(self._h, self._K.P, x.ctypes.data_as(C.c_void_p), *ptr))
+        return u, q, g
+
+    def execute_flow_device(self, x_ptr, u_ptr, q_ptr, g_ptr, stream=0, p=None):
+        """raw device pointers; 0 for an output that is not asked"""
+        _capi.check(_capi.lib().fmmbem_plan_execute_flow_device(
+            self._h, self._K.P if p is None else int(p), C.c_void_p(x_ptr), C.c_void_p(u_ptr or None), C.c_void_p(q_ptr or None),
+            C.c_void_p(g_ptr or None), C.c_void_p(stream)))
+
+    def execute_flow_torch(self, x, velocity=True, pressure=True, velocity_gradient=True, p=None):
+        """x: contiguous float64 CUDA tensor with 3 values per panel, ORIGINAL panel order; returns (u, q, G) of shapes (M, 3), (M,),
+        (M, 3, 3), None for what was not asked.  Runs on torch's current stream."""
+        tails = ((3,) if velocity else None, () if pressure else None, (3, 3) if velocity_gradient else None)
+        if all(t is None for t in tails):
+            raise ValueError("no output asked")
+        first = next(k for k, t in enumerate(tails) if t is not None)
+        outs = [None, None, None]
+
+        def run(x_ptr, first_ptr, stream, p):                     # x is checked and the first output asked allocated by now
+            for k, t in enumerate(tails):
+                if t is not None and k != first:
+                    outs[k] = x.new_empty((self._field_rows(),) + t)
+            ptrs = [first_ptr if k == first else 0 if o is None else o.data_ptr() for k, o in enumerate(outs)]
+            self.execute_flow_device(x_ptr, *ptrs, stream=stream, p=p)
+
+        outs[first] = self._field_torch(run, x, None, p, tails[first], "dof values")
+        return tuple(outs)
+
     def execute_stress(self, traction):
         """(N, 3) or (3N,) traction density -> (M, 3, 3): sigma_i[k][m] = -q_i delta_km + mu (G_i[k][m] + G_i[m][k]), q of
-        execute_pressure and G of execute_velocity_gradient, in their scaling: the physical stress is the result / 4 pi.  TWO
-        executes, one pressure and one gradient, and each runs the far chain (gather, P2M, M2M, M2L, L2L); an execute that fuses
-        them is not built."""
-        q = self.execute_pressure(traction)
-        g = self.execute_velocity_gradient(traction)
+        execute_pressure and G of execute_velocity_gradient, in their scaling: the physical stress is the result / 4 pi.  ONE
+        execute_flow(velocity=False): the pressure and the gradient on one far chain and one walk over the near lists, with the
+        bits of the two single executes."""
+        _, q, g = self.execute_flow(traction, velocity=False)
         return -q[:, None, None] * np.eye(3)[None] + self._K.Mu * (g + g.transpose(0, 2, 1))
 
     # ---- batched execute: k vectors, one near-field pass per batch_width() of them (fmmbem_plan_execute_batch) ----

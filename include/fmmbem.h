@@ -203,7 +203,7 @@ typedef struct {
                                  * instead of stored (near_nnz counts all of the shard's entries, near_bytes what is stored)         */
   int64_t near_f32_bytes;       /* HBM bytes of the float copy of the near matrix (fmmbem_options.near_f32_max_p); 0: the float near
                                  * field is not active on this plan                                                                */
-  int32_t last_near_f32;        /* 1: the last execute streamed the float copy                                                      */
+  int32_t last_near_f32;        /* 1: the last execute streamed the float copy; after fmmbem_plan_execute_flow: 2 or 3, see there   */
 } fmmbem_stats;
 
 typedef struct fmmbem_plan fmmbem_plan;
@@ -415,6 +415,38 @@ int fmmbem_plan_execute_pressure_device(fmmbem_plan *plan, int p, const double *
  * The host form takes HOST pointers and returns when G is written; the device form is asynchronous on `stream`. */
 int fmmbem_plan_execute_velocity_gradient(fmmbem_plan *plan, int p, const double *x /* n x 3 */, double *G /* n_targets x 9 */);
 int fmmbem_plan_execute_velocity_gradient_device(fmmbem_plan *plan, int p, const double *d_x, double *d_G, void *stream);
+
+/* ---- Flow execute: velocity, pressure and velocity gradient at the points of a field plan in one pass ------------------------
+ * (no reference counterpart).  On a Stokes plan of fmmbem_plan_create_field whose targets are all VELOCITY targets, each non-null
+ * output is BIT FOR BIT what fmmbem_plan_execute (u), fmmbem_plan_execute_pressure (q) and fmmbem_plan_execute_velocity_gradient
+ * (G) write for the same plan, p and x -- the caller's order and coincident targets included.  A null output is not computed.
+ * One call is one gather, one P2M and one far chain through L2L, where the single executes run one each; then, per output asked,
+ * the kernels its single execute launches, on the same L:
+ *   u       the stored near matrix by the plan's near SpMV into the tree-order result (target rows zero-filled first, as
+ *           execute does it), the velocity's L2P, the delivery;
+ *   q or G  alone: that quantity's matrix-free near kernel and its L2P kernel;
+ *   q and G ONE near kernel for both -- one walk over a row's near lists, a panel's record staged once, one regime test per
+ *           pair, one t - y_q, |d_q|^2 and reciprocal square root per quadrature point feeding both quantities' updates, a row's
+ *           ten sums in the list order of the single kernels -- then the pressure's and the gradient's L2P kernels as they stand.
+ * The pressure's and the gradient's buffers are those of their single executes, allocated at first use (FMMBEM_ERR_ALLOC if that
+ * fails; the plan stays usable).  Launched plainly, kernel by kernel, whatever fmmbem_plan_set_graphs says; the captured graphs
+ * of execute are left as they are, and execute, execute_batch and the single field executes return the same bits before and
+ * after a flow execute.
+ * Checked in this order: a null plan -> FMMBEM_ERR_INVALID; a null x, or u, q and G all null -> _INVALID; p outside 1..p_max ->
+ * _INVALID; a plan that is not over separate targets -> _UNSUPPORTED; a Laplace plan -> _UNSUPPORTED; a plan with any TRACTION
+ * target -> _UNSUPPORTED, whichever outputs are asked; a host-only plan -> _UNSUPPORTED.  A refusal touches no pointer and leaves
+ * the handle usable.
+ * With stage timing on a flow execute is recorded as ONE execute: ms_near brackets all its near work (the SpMV of u and the near
+ * kernel(s) of q and G), ms_l2p all its L2P kernels, the other stages as in a field execute.  fmmbem_stats.last_near_f32 after a
+ * flow execute says which near path q and G took: 2 the one kernel for both, 3 a single quantity's kernel, 0 neither was asked
+ * (an execute sets it back to 0 or 1).  No TRACTION targets, no batches, no graphs, no shards.
+ * x: n_panels x 3 doubles; u: n_targets x 3, q: n_targets, G: n_targets x 9 doubles, in the caller's order.  The host form takes
+ * HOST pointers and returns when the outputs are written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_flow(fmmbem_plan *plan, int p, const double *x /* n x 3 */,
+                             double *u /* n_targets x 3 or NULL */, double *q /* n_targets or NULL */,
+                             double *G /* n_targets x 9 or NULL */);
+int fmmbem_plan_execute_flow_device(fmmbem_plan *plan, int p, const double *d_x,
+                                    double *d_u, double *d_q, double *d_G, void *stream);
 
 /* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
  * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES

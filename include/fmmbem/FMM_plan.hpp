@@ -622,11 +622,32 @@ class PlanAdapter {
     check(fmmbem_plan_execute_velocity_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
     return results;
   }
-  // Not in the reference: the stress sigma[k][m] = -q delta_km + mu (G[k][m] + G[m][k]) from one execute_pressure and one
-  // execute_velocity_gradient, in their scaling (the physical stress is the result / 4 pi).  Two executes: each runs the far chain.
+  // Not in the reference: velocity, pressure and velocity gradient at the points of a field plan whose points are all VELOCITY
+  // targets in ONE execute (fmmbem_plan_execute_flow): one gather, P2M and far chain for all that is asked.  u, q, G: where each
+  // result goes, or null for a quantity that is not asked; each is resized and receives bit for bit what execute(),
+  // execute_pressure() and execute_velocity_gradient() return.  The refusals are execute_pressure's; all three null:
+  // Error(FMMBEM_ERR_INVALID).
+  void execute_flow(const std::vector<charge_type>& charges, std::vector<result_type>* u, std::vector<double>* q,
+                    std::vector<std::array<double, 9>>* G) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
+    const size_t m = has_targets_ ? target_bc_.size() : charges.size();
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    // (results of their own: a refusal leaves the caller's vectors as they were)
+    std::vector<result_type> ru(u ? m : 0);
+    std::vector<double> rq(q ? m : 0);
+    std::vector<std::array<double, 9>> rg(G ? m : 0);
+    check(fmmbem_plan_execute_flow(plan_, K.p(), KernelBinding<Kernel>::in(charges), u ? KernelBinding<Kernel>::out(ru) : nullptr,
+                                   q ? rq.data() : nullptr, G ? rg.data()->data() : nullptr));
+    if (u) u->swap(ru);
+    if (q) q->swap(rq);
+    if (G) G->swap(rg);
+  }
+  // Not in the reference: the stress sigma[k][m] = -q delta_km + mu (G[k][m] + G[m][k]) from the pressure and the velocity
+  // gradient of ONE execute_flow, in their scaling (the physical stress is the result / 4 pi).
   std::vector<std::array<double, 9>> execute_stress(const std::vector<charge_type>& charges) {
-    const std::vector<double> q = execute_pressure(charges);
-    std::vector<std::array<double, 9>> g = execute_velocity_gradient(charges);
+    std::vector<double> q;
+    std::vector<std::array<double, 9>> g;
+    execute_flow(charges, nullptr, &q, &g);
     for (size_t i = 0; i < g.size(); ++i) {
       std::array<double, 9> s;
       for (int k = 0; k < 3; ++k)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time a field-quantity execute (FMM_plan.execute_gradient_torch, execute_pressure_torch or execute_velocity_gradient_torch,
 csrc/kernels_field.hip) beside the potential or velocity execute of the same plan.
-  python tools/field_time.py --quantity gradient|pressure|velocity_gradient [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
+  python tools/field_time.py --quantity gradient|pressure|velocity_gradient|flow [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
 Workloads:
   gradient            the target plan of tools/target_field_time.py -- 2 x UnitSphere(recursions) (N = 1 048 576 panels by default)
                       and a regular grid of 1 048 576 points over the bounding box of both spheres, theta = 0.5, ncrit 64;
@@ -17,6 +17,16 @@ Per order, with <q> the quantity and <k> its kernels' short name (grad, pressure
                                  ms_near_<k>_kernel and ms_l2p_<k>_kernel;
   stages_execute                 the same for the potential or velocity execute (ms_near: the near-matrix stream, ms_l2p: l2p_kernel
                                  or l2p_stokes_kernel).
+--quantity flow: the flow execute (FMM_plan.execute_flow_device: velocity, pressure and velocity gradient on one far chain) on the
+Stokes workload, beside the three single executes in the same process.  Per order, --rounds (default 3) alternating rounds of
+{pressure, velocity_gradient, velocity, flow asking q and G, flow asking u, q and G}, each timed as above:
+  ms_execute, ms_execute_pressure, ms_execute_velocity_gradient, ms_execute_flow_qg, ms_execute_flow   the means over the rounds;
+  rounds                         every round's five figures; spread_ms: the largest (max - min) over the rounds of any of them;
+  ms_singles_qg, ms_singles      pressure + velocity_gradient, and that + velocity: what the two flow figures stand against;
+  stages_flow, stages_flow_qg, stages_pressure, stages_velocity_gradient, stages_execute    the stage means;
+  ms_near_flow_kernel            the one near kernel for q and G alone (stage timing 2: events around the near stage only) and
+  ms_near_pressure_kernel, ms_near_velgrad_kernel   the two single near kernels the same way; their sum is what it stands against;
+  bits_equal                     every output of both flow forms against the single executes' results (torch.equal).
 --check M (default 0: off): the Direct quantity (fb.Direct.gradient_torch / pressure_torch / velocity_gradient_torch: all N panels,
 every regime) on M points sampled over the whole target set; per order rel_l2_vs_direct_on_sample, the relative L2 of the field
 execute against it on those points, and under "check" the sample's size and the device time of that sum.
@@ -34,7 +44,8 @@ import fmm_bem_relaxed_amd as fb  # noqa: E402
 
 STAGES = ("ms_gather", "ms_near", "ms_p2m", "ms_m2m", "ms_mh", "ms_m2l", "ms_l2l", "ms_l2p", "ms_scatter", "ms_total")
 # quantity -> (its kernels' short name, the trailing shape of its result, the default orders)
-QUANTITIES = {"gradient": ("grad", (3,), "4,10"), "pressure": ("pressure", (), "8,4"), "velocity_gradient": ("velgrad", (3, 3), "8,4")}
+QUANTITIES = {"gradient": ("grad", (3,), "4,10"), "pressure": ("pressure", (), "8,4"), "velocity_gradient": ("velgrad", (3, 3), "8,4"),
+              "flow": ("flow", (3, 3), "8")}
 
 
 def sphere_grid():
@@ -75,6 +86,62 @@ def staged(plan, fn, repeats):
     return {k: round(s[k], 4) for k in STAGES}
 
 
+def near_ms(plan, fn, repeats):
+    """ms_near with events around the near stage only (stage timing 2)"""
+    plan.set_timing(2)
+    for _ in range(repeats):
+        fn()
+    torch.cuda.synchronize()
+    ms = plan.stats()["ms_near"]
+    plan.set_timing(False)
+    return round(ms, 4)
+
+
+def flow_orders(plan, K, orders, xd, n_targets, repeats, rounds):
+    """the records of --quantity flow, one per order"""
+    dev = xd.device
+    ud, u1 = (torch.empty((n_targets, 3), dtype=torch.float64, device=dev) for _ in range(2))
+    qd, q1 = (torch.empty(n_targets, dtype=torch.float64, device=dev) for _ in range(2))
+    gd, g1 = (torch.empty((n_targets, 3, 3), dtype=torch.float64, device=dev) for _ in range(2))
+    stream = lambda: torch.cuda.current_stream(dev).cuda_stream
+    calls = {
+        "ms_execute_pressure": lambda: plan.execute_pressure_torch(xd, out=q1),
+        "ms_execute_velocity_gradient": lambda: plan.execute_velocity_gradient_torch(xd, out=g1),
+        "ms_execute": lambda: plan.execute_torch(xd, out=u1),
+        "ms_execute_flow_qg": lambda: plan.execute_flow_device(xd.data_ptr(), 0, qd.data_ptr(), gd.data_ptr(), stream()),
+        "ms_execute_flow": lambda: plan.execute_flow_device(xd.data_ptr(), ud.data_ptr(), qd.data_ptr(), gd.data_ptr(), stream()),
+    }
+    recs = []
+    for p in orders:
+        K.set_p(p)
+        rec = dict(p=p, rounds=[])
+        for _ in range(rounds):
+            rec["rounds"].append({k: round(device_ms(fn, repeats), 4) for k, fn in calls.items()})
+        for k in calls:
+            rec[k] = round(sum(r[k] for r in rec["rounds"]) / rounds, 4)
+        rec["spread_ms"] = round(max(max(r[k] for r in rec["rounds"]) - min(r[k] for r in rec["rounds"]) for k in calls), 4)
+        rec["ms_singles_qg"] = round(rec["ms_execute_pressure"] + rec["ms_execute_velocity_gradient"], 4)
+        rec["ms_singles"] = round(rec["ms_singles_qg"] + rec["ms_execute"], 4)
+        for name, key in (("execute", "ms_execute"), ("pressure", "ms_execute_pressure"), ("velocity_gradient", "ms_execute_velocity_gradient"),
+                          ("flow_qg", "ms_execute_flow_qg"), ("flow", "ms_execute_flow")):
+            rec["stages_" + name] = staged(plan, calls[key], repeats)
+        rec["ms_near_flow_kernel"] = near_ms(plan, calls["ms_execute_flow_qg"], repeats)
+        rec["ms_near_pressure_kernel"] = near_ms(plan, calls["ms_execute_pressure"], repeats)
+        rec["ms_near_velgrad_kernel"] = near_ms(plan, calls["ms_execute_velocity_gradient"], repeats)
+        for k in ("ms_execute_pressure", "ms_execute_velocity_gradient", "ms_execute"):
+            calls[k]()
+        equal = True
+        for k, outs in (("ms_execute_flow_qg", ((qd, q1), (gd, g1))), ("ms_execute_flow", ((ud, u1), (qd, q1), (gd, g1)))):
+            for t in (ud, qd, gd):
+                t.fill_(float("nan"))
+            calls[k]()
+            torch.cuda.synchronize()
+            equal = equal and all(torch.equal(a, b) for a, b in outs)
+        rec["bits_equal"] = bool(equal)
+        recs.append(rec)
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quantity", choices=sorted(QUANTITIES), required=True)
@@ -83,6 +150,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--flag", type=int, default=0)
     ap.add_argument("--check", type=int, default=0)
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     q = a.quantity
     if a.flag and q != "gradient":
@@ -111,6 +179,13 @@ def main():
     st = plan.stats()
     out = dict(device=torch.cuda.get_device_name(0), n_panels=len(v), n_targets=len(pts), theta=0.5, ncrit=64, **extra, repeats=a.repeats,
                near_nnz=int(st["near_nnz"]), m2l_pairs=int(st["m2l_pairs"]), target_info=plan.target_info(), orders=[])
+    if q == "flow":
+        if a.check > 0:
+            ap.error("--check belongs to the single quantities: the flow execute is held to them bit for bit (bits_equal)")
+        out["rounds"] = a.rounds
+        out["orders"] = flow_orders(plan, K, orders, xd, len(pts), a.repeats, a.rounds)
+        print(json.dumps(out, indent=1))
+        return
     od = torch.empty((len(pts),) + tail, dtype=torch.float64, device=dev)
     qd = torch.empty(len(pts), dtype=torch.float64, device=dev) if q == "velocity_gradient" else None
     run = getattr(plan, "execute_%s_torch" % q)
