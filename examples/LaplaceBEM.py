@@ -14,6 +14,10 @@ one more report line with its largest error against the exact exterior solution 
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
 -field_grad (not a flag of the reference): with -field N, one more line: the gradient of that formula at the same points
 (FMM_plan.execute_gradient on the two plans over them), its largest error against the exact -x/|x|^3 relative to 1/9.
+-field_one_pass (not a flag of the reference): with -field N, the field line -- and with -field_grad the gradient line -- from ONE
+plan over the points and ONE FMM_plan.execute_representation (fmmbem_plan_execute_representation: both layers folded into one
+multipole set, one far chain, one kernel over the near pairs) where the lines otherwise take two plans and two or four executes;
+the same lines, the same numbers to rounding.
 -block_inverse (not a flag of the reference): GMRES with the exact block-Jacobi preconditioner -- the leaf blocks of the
 block-diagonal operator inverted once on the device (solver.BlockInverse) where -fgmres -diagonal iterates on them; the same
 report lines as the other modes.
@@ -108,6 +112,16 @@ def exterior_fmm_gradient(fb_, v, g_density, dgdn_density, points, p, k=3, opts=
     return out
 
 
+def exterior_fmm_one_pass(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None, gradient=False):
+    """The formula, and with `gradient` its gradient, at the points from ONE plan over them and ONE representation execute (the
+    points' flags do not enter): (phi, grad or None), each / 4 pi"""
+    K = fb_.LaplaceSphericalBEM(p, k)
+    plan = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.zeros(len(points), dtype=np.uint8))
+    phi, grad = plan.execute_representation(g_density, dgdn_density, value=True, gradient=gradient)
+    plan.close()
+    return phi / 4 / math.pi, None if grad is None else grad / 4 / math.pi
+
+
 def sphere_points(m, radius):
     """m points spread over a sphere (golden-angle spiral)"""
     i = np.arange(m) + 0.5
@@ -123,7 +137,7 @@ def main(argv):
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
     second_kind, mesh, field, near_f32, evaluator = False, None, 0, 0, "FMM"
-    field_grad = False
+    field_grad = field_one_pass = False
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -172,6 +186,8 @@ def main(argv):
             i += 1; field = int(argv[i])
         elif a == "-field_grad":                           # not in the reference: FMM_plan.execute_gradient
             field_grad = True
+        elif a == "-field_one_pass":                       # not in the reference: FMM_plan.execute_representation
+            field_one_pass = True
         elif a == "-block_inverse":                        # not in the reference: solver.BlockInverse
             solver, pc = "gmres", "block_inverse"
         elif a == "-near_f32":                             # not in the reference: fmmbem_options.near_f32_max_p
@@ -180,6 +196,9 @@ def main(argv):
             print('[W]: Unknown command line arg: "%s"' % a)
             print_help_and_exit()
         i += 1
+    if field_one_pass and field <= 0:
+        print("[E]: -field_one_pass needs -field <N>: it chooses how the lines of -field are computed", file=sys.stderr)
+        sys.exit(2)
     print("============")
     so.max_iters = so.restart = max_iterations
     so.max_p = p
@@ -257,11 +276,16 @@ def main(argv):
     if field > 0:
         pts = sphere_points(field, 3.0)
         opts.evaluator = "FMM"                             # plans over target points: the FMM evaluator only
-        phi = exterior_fmm(fb, v, xs, np.ones(n), pts, p, k, opts)
+        grad = None
+        if field_one_pass:
+            phi, grad = exterior_fmm_one_pass(fb, v, xs, np.ones(n), pts, p, k, opts, gradient=field_grad)
+        else:
+            phi = exterior_fmm(fb, v, xs, np.ones(n), pts, p, k, opts)
         err = np.abs(phi - 1.0 / 3.0) / (1.0 / 3.0)
         print("field: %d points at r = 3, max error: %.4e, rms error: %.4e" % (field, float(err.max()), float(np.sqrt((err ** 2).mean()))))
         if field_grad:
-            grad = exterior_fmm_gradient(fb, v, xs, np.ones(n), pts, p, k, opts)
+            if grad is None:
+                grad = exterior_fmm_gradient(fb, v, xs, np.ones(n), pts, p, k, opts)
             exact_grad = -pts / np.linalg.norm(pts, axis=1)[:, None] ** 3
             gerr = np.linalg.norm(grad - exact_grad, axis=1) / (1.0 / 9.0)
             print("field gradient: %d points at r = 3, max error: %.4e, rms error: %.4e"

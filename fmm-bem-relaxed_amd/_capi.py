@@ -114,6 +114,7 @@ SYMBOLS = (
     "fmmbem_plan_execute_pressure", "fmmbem_plan_execute_pressure_device", "fmmbem_kernel_pressure_entries",
     "fmmbem_plan_execute_velocity_gradient", "fmmbem_plan_execute_velocity_gradient_device", "fmmbem_kernel_velocity_gradient_entries",
     "fmmbem_plan_execute_flow", "fmmbem_plan_execute_flow_device",
+    "fmmbem_plan_execute_representation", "fmmbem_plan_execute_representation_device",
 )
 
 
@@ -236,6 +237,8 @@ def lib():
     L.fmmbem_kernel_velocity_gradient_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp]
     L.fmmbem_plan_execute_flow.argtypes = [vp, i32, vp, vp, vp, vp]
     L.fmmbem_plan_execute_flow_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.fmmbem_plan_execute_representation.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.fmmbem_plan_execute_representation_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

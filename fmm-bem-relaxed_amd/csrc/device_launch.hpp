@@ -88,6 +88,12 @@ hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, h
 enum class FieldQuantity { Gradient, Pressure, VelocityGradient };
 hipError_t launch_near_field(FieldQuantity q, const DevicePlan& d, int64_t n_src, double* tree, hipStream_t s);
 hipError_t launch_near_flow(const DevicePlan& d, int64_t n_src, double* q_tree, double* g_tree, hipStream_t s);   // Pressure and VelocityGradient in one kernel
+// the representation execute (Laplace): both layers' near pairs in one kernel, sigma in d.xt and mu in mu_tree, phi_tree (1 double
+// per target row) and g_tree (3) as above, either null: not computed; M slot 0 += (set: =) M slot 1 at the P2M leaves; the scatter
+// of one double per row
+hipError_t launch_near_representation(const DevicePlan& d, int64_t n_src, const double* mu_tree, double* phi_tree, double* g_tree, hipStream_t s);
+hipError_t launch_fold_slots(const DevicePlan& d, int p, bool set, hipStream_t s);
+hipError_t launch_value_scatter(const DevicePlan& d, int64_t n_src, const double* tree, double* out, hipStream_t s);
 hipError_t launch_l2p_field(FieldQuantity q, const DevicePlan& d, int p, int64_t n_src, double* tree, hipStream_t s);
 hipError_t launch_field_scatter(FieldQuantity q, const DevicePlan& d, int64_t n_src, const double* tree, double* out, hipStream_t s);
 hipError_t launch_field_entries(FieldQuantity q, const DevicePlan& d, int m, double* out, hipStream_t s);

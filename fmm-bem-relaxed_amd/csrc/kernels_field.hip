@@ -13,6 +13,8 @@
 //                             of near_entry.hpp; explicitly specialised for the velocity gradient
 //   near_flow_kernel          the pressure's and the velocity gradient's near pairs in one walk (fmmbem_plan_execute_flow), with the
 //                             bits of the two kernels above
+//   near_representation_kernel<VALUE, GRAD>   both Laplace layers' near pairs, value and gradient, in one walk
+//                             (fmmbem_plan_execute_representation); fold_slots_kernel adds its two multipole sets at the leaves
 //   l2p_*_kernel<PT>          what a quantity reads of the local expansions the potential execute evaluates, along the spherical
 //                             chain: one kernel per quantity over the shared tables and staging
 //   field_scatter_kernel<W>   tree order -> distinct points, W doubles per row
@@ -310,6 +312,81 @@ __global__ __launch_bounds__(kNearWaves * kWave) void near_flow_kernel(DevicePla
       }
     }
   }
+}
+
+// The representation execute's near kernel (include/fmmbem.h "Representation execute"): the single layer of sigma minus the double
+// layer of mu at a row's point, value and gradient, in one walk over its near lists -- near_field_kernel's loop with a record of
+// 9 + 3 K doubles per panel (centroid, area, normal, sigma_j, mu_j, the K points) staged once, and laplace_representation_from
+// (near_entry.hpp) per pair: one regime test, one dx, |dx|^2 and reciprocal square root per quadrature point for all four
+// integrands.  The row's flag is not read.  A row's four sums in registers, stored once: phi to pt, the gradient to gt (VALUE /
+// GRAD: the outputs asked; the other pointer is not touched).  The batch is this kernel's own (kRepRecDoubles: 64 panels at K = 3,
+// where near_batch gives 61); four workgroups' slices fit a CU's LDS, as the other near kernels' do.
+constexpr int kRepRec = 9;
+constexpr int kRepRecDoubles = 64 * (kRepRec + 9);
+inline int representation_batch(int nf) { const int pb = kRepRecDoubles / nf; return pb < 1 ? 1 : pb > kWave ? kWave : pb; }
+
+template <bool VALUE, bool GRAD>
+__global__ __launch_bounds__(kNearWaves * kWave) __attribute__((amdgpu_waves_per_eu(VALUE ? 2 : 4))) void near_representation_kernel(DevicePlan d, const int64_t n_src, const int PB, const double* __restrict__ mu_tree,
+                                                                                 double* __restrict__ pt, double* __restrict__ gt) {
+  extern __shared__ double field_near_lds[];            // [wave][field][PB]
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int nq = d.nq, nf = kRepRec + 3 * nq;
+  const int64_t N = d.n;
+  double* rec = field_near_lds + (size_t)wave * PB * nf;
+  const int nleaf = d.leaf_end - d.leaf_begin;
+  for (int li = blockIdx.x * kNearWaves + wave; li < nleaf; li += gridDim.x * kNearWaves) {
+    const int leaf = __builtin_amdgcn_readfirstlane(d.leaf_begin + li);
+    const int row0 = d.leaf_row0[leaf], nrows = d.leaf_nrows[leaf], ncols = d.near_ncols[leaf];
+    const int64_t k0 = d.near_ptr[leaf], k1 = d.near_ptr[leaf + 1];
+    for (int chunk = 0; chunk < nrows; chunk += kWave) {
+      const bool live = chunk + lane < nrows;
+      const int64_t i = row0 + (live ? chunk + lane : 0);   // idle lanes take the leaf's first row and store nothing
+      const V3 t = {d.cx[i], d.cy[i], d.cz[i]};
+      double phi = 0;
+      V3 g = {0, 0, 0};
+      for (int64_t k = k0; k < k1; ++k) {
+        const int j0 = d.near_run_row0[k], off = d.near_run_off[k];
+        const int len = (k + 1 < k1 ? d.near_run_off[k + 1] : ncols) - off;
+        for (int jb = j0; jb < j0 + len; jb += PB) {
+          const int nb = j0 + len - jb < PB ? j0 + len - jb : PB;
+          wave_lds_sync();                                // the previous batch's reads are done
+          if (lane < nb) {                                // (PB <= 64: one panel per lane)
+            const int64_t j = jb + lane;
+            rec[0 * PB + lane] = d.cx[j]; rec[1 * PB + lane] = d.cy[j]; rec[2 * PB + lane] = d.cz[j]; rec[3 * PB + lane] = d.area[j];
+            rec[4 * PB + lane] = d.nx[j]; rec[5 * PB + lane] = d.ny[j]; rec[6 * PB + lane] = d.nz[j];
+            rec[7 * PB + lane] = d.xt[j]; rec[8 * PB + lane] = mu_tree[j];
+            for (int q = 0; q < 3 * nq; ++q) rec[(kRepRec + q) * PB + lane] = d.quad[q * N + j];
+          }
+          wave_lds_sync();
+          for (int e = 0; e < nb; ++e) {
+            const int64_t j = (int64_t)jb + e;
+            auto field = [&](int f) FMMBEM_INLINE { return rec[f * PB + e]; };
+            laplace_representation_from<VALUE, GRAD>(t, point(field, 0), field(3), point(field, 4), field(7), field(8), nq, d.qw,
+                                                     [&](int q) FMMBEM_INLINE { return point(field, kRepRec + 3 * q); },
+                                                     [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; },
+                                                     phi, g);
+          }
+        }
+      }
+      if (live) {
+        if (VALUE) pt[i - n_src] = phi;
+        if (GRAD) { double* o = gt + 3 * (size_t)(i - n_src); o[0] = g.x; o[1] = g.y; o[2] = g.z; }
+      }
+    }
+  }
+}
+
+// M of slot 0 += (or, `set`, =) M of slot 1 at the P2M leaves, the first S coefficients: the representation execute folds the two
+// layers into one multipole set before the tree passes.  One thread per coefficient.
+__global__ void fold_slots_kernel(DevicePlan d, const int S, const int set) {
+  const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (u >= (int64_t)d.n_p2m * S) return;
+  const int li = (int)(u / S), idx = (int)(u - (int64_t)li * S);
+  const int box = d.leaf_box[d.p2m_leaf[li]];
+  double2* m0 = d.M + ((size_t)box * d.nslots + 0) * d.s_max + idx;
+  const double2 m1 = d.M[((size_t)box * d.nslots + 1) * d.s_max + idx];
+  if (set) *m0 = m1;
+  else { const double2 a = *m0; *m0 = double2{a.x + m1.x, a.y + m1.y}; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -801,6 +878,40 @@ hipError_t launch_near_flow(const DevicePlan& d, int64_t n_src, double* q_tree, 
   const int pb = near_batch(nf);
   const size_t lds = sizeof(double) * (size_t)kNearWaves * pb * nf;
   hipLaunchKernelGGL(near_flow_kernel, dim3(nblk < 256 * 16 ? nblk : 256 * 16), dim3(kNearWaves * kWave), lds, s, d, n_src, pb, q_tree, g_tree);
+  return hipGetLastError();
+}
+
+// both Laplace layers' near pairs, value and gradient, in one kernel (near_representation_kernel): sigma in d.xt, mu in mu_tree;
+// a null tree buffer: that output is not computed
+hipError_t launch_near_representation(const DevicePlan& d, int64_t n_src, const double* mu_tree, double* phi_tree, double* g_tree, hipStream_t s) {
+  const int nleaf = d.leaf_end - d.leaf_begin;
+  if (nleaf <= 0) return hipSuccess;
+  if (!mu_tree || (!phi_tree && !g_tree)) return hipErrorInvalidValue;
+  const int nblk = (nleaf + kNearWaves - 1) / kNearWaves, nf = kRepRec + 3 * d.nq;
+  const int pb = representation_batch(nf);
+  const size_t lds = sizeof(double) * (size_t)kNearWaves * pb * nf;
+  const dim3 grid(nblk < 256 * 16 ? nblk : 256 * 16), block(kNearWaves * kWave);
+  if (phi_tree && g_tree) hipLaunchKernelGGL((near_representation_kernel<true, true>), grid, block, lds, s, d, n_src, pb, mu_tree, phi_tree, g_tree);
+  else if (phi_tree) hipLaunchKernelGGL((near_representation_kernel<true, false>), grid, block, lds, s, d, n_src, pb, mu_tree, phi_tree, g_tree);
+  else hipLaunchKernelGGL((near_representation_kernel<false, true>), grid, block, lds, s, d, n_src, pb, mu_tree, phi_tree, g_tree);
+  return hipGetLastError();
+}
+
+// M slot 0 += M slot 1 (set: =) at the P2M leaves, the coefficients of order p (fold_slots_kernel)
+hipError_t launch_fold_slots(const DevicePlan& d, int p, bool set, hipStream_t s) {
+  if (d.n_p2m <= 0) return hipSuccess;
+  if (p < 1 || p > kPmaxDev || d.nslots != 2) return hipErrorInvalidValue;
+  const int S = p * (p + 1) / 2;
+  const int64_t n = (int64_t)d.n_p2m * S;
+  hipLaunchKernelGGL(fold_slots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, S, set ? 1 : 0);
+  return hipGetLastError();
+}
+
+// tree order -> distinct points for one double per row: the value of the representation execute
+hipError_t launch_value_scatter(const DevicePlan& d, int64_t n_src, const double* tree, double* out, hipStream_t s) {
+  const int64_t rows = d.n - n_src;
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(field_scatter_kernel<1>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, d.perm, tree, out, n_src, rows);
   return hipGetLastError();
 }
 

@@ -208,6 +208,64 @@ __device__ inline V3 laplace_grad_entry(const DevicePlan& d, V3 t, int tbc, int6
                            [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; });
 }
 
+// Both layers of one pair TOGETHER, value and gradient (include/fmmbem.h, "Representation execute"): what panel j with density
+// sigma and surface potential mu adds to   phi = sum E0 sigma - E1 mu   and   grad = sum gamma0 sigma - gamma1 mu   at the point t,
+// E0 / E1 the entries of a flag-0 / flag-1 target above and gamma0 / gamma1 the two gradients of laplace_grad_from.  ONE regime test
+// -- laplace_grad_from's expressions, which are laplace_far_from's -- and per quadrature point one dx = y_q - t, |dx|^2 and
+// reciprocal square root feeding all four integrands, the densities folded in at the point:
+//   phi  += wA ri sigma  -  wA ri^3 (dx . n) mu
+//   grad += wA ri^3 dx sigma  -  wA ri^3 (h dx - n) mu  =  wA ri^3 ((sigma - h mu) dx + mu n),      h = 3 (dx . n) ri^2
+// The regimes: self (dist < 1e-8): E0 semi-analytic (a flag-0 target has no self test and is nearby there), E1 = 2 pi,
+// gamma0 = 2 pi n, gamma1 = 0; nearby: the 16-point rule on the vertices for E1, gamma0 and gamma1 in one loop and semi_analytic_G
+// beside it for E0; else the K stored points for all four.  VALUE / GRAD: which of the two sums are kept (the other's
+// arithmetic is compiled out).  Points in order, one running sum each: the same bits every run.
+template <bool VALUE, bool GRAD, class Quad, class Vert>
+__device__ __forceinline__ void laplace_representation_from(V3 t, V3 c, double A, V3 nrm, double sigma, double mu, int nq, const double* qw,
+                                                            Quad&& quad, Vert&& vert, double& phi, V3& g) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  bool nearby = false, self = false;
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {              // (see laplace_grad_from: far from the regime boundary, no square root)
+    const double dist = sqrt(d2);
+    self = dist < 1e-8;
+    nearby = self || sqrt(2 * A) / dist >= 0.5;
+  }
+  const V3 mn = {mu * nrm.x, mu * nrm.y, mu * nrm.z};
+  auto point = [&](V3 y, double wA, bool with_e0) {
+    const V3 dx = sub(y, t);
+    const double r2 = dx.x * dx.x + dx.y * dx.y + dx.z * dx.z;
+    const double ri = rsqrt(r2), ri2 = ri * ri;
+    const double f = wA * (ri * ri2);
+    const double dn = dx.x * nrm.x + dx.y * nrm.y + dx.z * nrm.z;
+    if (VALUE) {
+      phi -= f * dn * mu;
+      if (with_e0) phi += wA * ri * sigma;
+    }
+    if (GRAD) {
+      const double a = sigma - 3 * dn * ri2 * mu;
+      g.x += f * (a * dx.x + mn.x); g.y += f * (a * dx.y + mn.y); g.z += f * (a * dx.z + mn.z);
+    }
+  };
+  if (nearby) {
+    const V3 v0 = vert(0), v1 = vert(1), v2 = vert(2);
+    if (self) {
+      if (VALUE) phi -= 2 * M_PI * mu;
+      if (GRAD) {
+        const double s = 2 * M_PI * sigma;
+        g.x += s * nrm.x; g.y += s * nrm.y; g.z += s * nrm.z;
+      }
+    } else {
+      for (int q = 0; q < 16; ++q)
+        point(V3{v0.x * kFine[q][0] + v1.x * kFine[q][1] + v2.x * kFine[q][2], v0.y * kFine[q][0] + v1.y * kFine[q][1] + v2.y * kFine[q][2],
+                 v0.z * kFine[q][0] + v1.z * kFine[q][1] + v2.z * kFine[q][2]}, kFine[q][3] * A, false);
+    }
+    // (one call for both regimes, and last: while it runs the pair's normal, area and weights are dead)
+    if (VALUE) phi += semi_analytic_G(v0, v1, v2, t) * sigma;
+  } else {
+    for (int q = 0; q < nq; ++q) point(quad(q), qw[q] * A, true);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Stokes (velocity boundary condition): one near-matrix entry is the 3x3 block
 //   (1/2mu) int_source ( I/r + d d^T / r^3 ) dS,  d = target centroid - y

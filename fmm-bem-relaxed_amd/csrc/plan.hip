@@ -276,6 +276,21 @@ struct fmmbem_plan {
   int deliver_field(FieldQuantity q, double* d_out, hipStream_t s) const;
   int run_flow(int p, const double* d_x, double* d_u, double* d_q, double* d_G, hipStream_t s);
   enum : int { kFlowNearNone = 0, kFlowNearFused = 2, kFlowNearSingle = 3 };       // fmmbem_stats.last_near_f32 after a flow execute
+  // The representation execute (fmmbem_plan_execute_representation): both Laplace layers, value and gradient, on one far chain.
+  // Its own buffers, allocated at first use: mu in tree order beside x_tree; the value's tree buffer -- hp.n doubles, the target
+  // rows at n_src as l2p_kernel indexes y --, its distinct points and its staging (the gradient's are field[Gradient]'s); the
+  // device copy of the one-slot view the far chain runs on (M2L above the rotation orders reads the plan from device memory)
+  struct Representation {
+    double *mu_tree = nullptr, *phi_tree = nullptr, *phi_points = nullptr, *phi_stage = nullptr, *stage_mu = nullptr;
+    const DevicePlan* view_dev = nullptr;
+  };
+  Representation rep;
+  size_t p2m_tab_doubles = 0;                                  // double2s of one P2M moment table (0: P2M runs without tables)
+  int p2m_table(const uint8_t* bc, const double2** out);
+  DevicePlan representation_view() const;
+  int representation_refusal(int p) const;
+  int representation_alloc(bool value, bool gradient);
+  int run_representation(int p, const double* d_sigma, const double* d_mu, double* d_phi, double* d_grad, hipStream_t s);
 
   template <class V, class T>
   int upload(const V& v, const T** out) { return mem->upload(v, out); }
@@ -751,16 +766,10 @@ int fmmbem_plan::to_device_bc_end() {
     const bool want = !stokes || fd.stokes_velocity_targets;
     if (want && table_on && hp.opt.evaluator == 0 && d.n_p2m > 0 && count * sizeof(double2) <= ((size_t)16 << 30)) {
       const bool per_slot = p2m_per_slot();
+      p2m_tab_doubles = count;
       for (int f = 0; f < 2; ++f) {                    // (a Laplace dual plan: the table of every live slot, all sources; else one table)
         if (per_slot && !has_bc[f]) continue;
-        DevicePlan dt = d;
-        if (per_slot) dt.bc = bc_all[f];
-        double2* tab = nullptr;
-        TRY(alloc(count, &tab, true));
-        HIP_TRY(hipDeviceSynchronize());               // the zero-fill ran on the NULL stream
-        HIP_TRY(launch_p2m_table(dt, tab, own_stream));
-        HIP_TRY(hipStreamSynchronize(own_stream));
-        p2m_tab_slot[f] = tab;
+        TRY(p2m_table(per_slot ? bc_all[f] : d.bc, &p2m_tab_slot[f]));
         if (!per_slot) break;
       }
       fd.p2m_tab = p2m_tab_slot[0] ? p2m_tab_slot[0] : p2m_tab_slot[1];
@@ -854,6 +863,20 @@ int fmmbem_plan::shift_pass(const DevicePlan& dv, int p, ShiftDir dir, hipStream
       HIP_TRY(m2m ? launch_m2m_rot(dv, w, p, s) : launch_l2l_rot(dv, w, p, s));
     } else HIP_TRY(m2m ? launch_m2m_level(dv, sd.ops[p - 1], p, first, count, s) : launch_l2l_level(dv, sd.ops[p - 1], p, first, count, s));
   }
+  return FMMBEM_OK;
+}
+
+// One P2M moment table of p2m_tab_doubles records (kernels_far.hip, launch_p2m_table) with the panels' flags read from bc: the
+// plan's own tables at creation, and the table of a slot the plan's targets do not make live at the first representation execute
+int fmmbem_plan::p2m_table(const uint8_t* bc, const double2** out) {
+  DevicePlan dt = d;
+  dt.bc = bc;
+  double2* tab = nullptr;
+  TRY(alloc(p2m_tab_doubles, &tab, true));
+  HIP_TRY(hipDeviceSynchronize());                     // the zero-fill ran on the NULL stream
+  HIP_TRY(launch_p2m_table(dt, tab, own_stream));
+  HIP_TRY(hipStreamSynchronize(own_stream));
+  *out = tab;
   return FMMBEM_OK;
 }
 
@@ -1156,6 +1179,117 @@ int fmmbem_plan::deliver_field(FieldQuantity q, double* d_out, hipStream_t s) co
     hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, b.points, d_out, nu, width);
     HIP_TRY(hipGetLastError());
   }
+  return FMMBEM_OK;
+}
+
+// ======================================= representation execute =======================================
+// fmmbem_plan_execute_representation: phi = S[sigma] - D[mu] and its gradient at the points of a Laplace target plan, the targets'
+// own flags ignored.  Both layers are Laplace expansions about the same centres moved by the same operators, so they are FOLDED
+// into one multipole set at the leaves: P2M per layer into its own slot of M (the per-slot views of p2m_targets: every source taken
+// with the slot's flag, the slot's table, the layer's vector), then M_slot0 += M_slot1 at the P2M leaves, and ONE far chain on a
+// one-slot view (n_act = 1, act[0] = 0, every row's flag 0).  The signs: l2p_kernel adds +r0 at a flag-0 target and -r1 at a
+// flag-1 target, so S - D has the far field r0 + r1 -- the value and the gradient of the expansion L0 + L1, which is the L of
+// M0 + M1.  M is addressed by the slot's NUMBER (act[a]), not by its position among the live slots, and both slots of a Laplace
+// plan exist whatever its targets' flags: the second P2M lands beside the first, never on it.
+// Launched plainly like a field execute.  It writes x_tree, both slots of M at the leaves, and slot 0 of M, Mh and L above them;
+// every potential execute writes what it reads of these afresh, and y_tree is left alone.
+int fmmbem_plan::representation_refusal(int p) const {
+  if (p < 1 || p > hp.opt.p_max) return fail(FMMBEM_ERR_INVALID, "p outside [1, p_max]");
+  if (!targets) return fail(FMMBEM_ERR_UNSUPPORTED, "the representation execute: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)");
+  if (opts.kernel == FMMBEM_KERNEL_STOKES_BEM) return fail(FMMBEM_ERR_UNSUPPORTED, "the representation execute: Laplace plans only");
+  if (!on_device) return fail(FMMBEM_ERR_UNSUPPORTED, "target plan built host-only: no execute");
+  if (treecode()) return fail(FMMBEM_ERR_UNSUPPORTED, "the representation execute: FMM plans only (the treecode has no local expansions)");
+  return FMMBEM_OK;
+}
+
+// the plan with slot 0 alone live and every row a flag-0 row: what the far chain, L2P and the gradient's L2P run on
+DevicePlan fmmbem_plan::representation_view() const {
+  DevicePlan v = d;
+  v.n_act = 1; v.act[0] = 0;
+  v.bc = bc_all[0];
+  if (d.p2m_tab) v.p2m_tab = p2m_tab_slot[0];
+  return v;
+}
+
+// Buffers of the representation execute, each at its first use; a failure leaves what was allocated in place for the next call
+int fmmbem_plan::representation_alloc(bool value, bool gradient) {
+  const size_t rows = (size_t)(hp.n - hp.n_src);
+  bool zeroed = false;
+  if (!rep.mu_tree) { TRY(alloc((size_t)hp.n, &rep.mu_tree, true)); zeroed = true; }
+  if (!rep.stage_mu) TRY(alloc((size_t)hp.n_src, &rep.stage_mu, false));
+  if (value) {
+    if (!rep.phi_tree) { TRY(alloc((size_t)hp.n, &rep.phi_tree, true)); zeroed = true; }
+    if (d_target_point && !rep.phi_points) TRY(alloc(rows, &rep.phi_points, false));
+    if (!rep.phi_stage) TRY(alloc((size_t)hp.n_targets, &rep.phi_stage, false));
+  }
+  if (gradient) TRY(field_alloc(FieldQuantity::Gradient));
+  // the moment table of a slot the plan's own targets do not make live (the plan's own P2M without tables: this one too)
+  for (int f = 0; d.p2m_tab && f < 2; ++f)
+    if (!p2m_tab_slot[f]) TRY(p2m_table(bc_all[f], &p2m_tab_slot[f]));
+  if (!rep.view_dev) {
+    const DevicePlan v = representation_view();
+    TRY(allocs.upload(&v, 1, &rep.view_dev));
+  }
+  if (zeroed) HIP_TRY(hipDeviceSynchronize());         // the zero-fills ran on the NULL stream
+  return FMMBEM_OK;
+}
+
+int fmmbem_plan::run_representation(int p, const double* d_sigma, const double* d_mu, double* d_phi, double* d_grad, hipStream_t s) {
+  if ((!d_sigma && !d_mu) || (!d_phi && !d_grad)) return fail(FMMBEM_ERR_INVALID, "no layer given, or no output asked");
+  TRY(representation_refusal(p));
+  DEVICE_SCOPE(opts.device);
+  TRY(representation_alloc(d_phi != nullptr, d_grad != nullptr));
+  const DevicePlan v = representation_view();
+  double* const pt = d_phi ? rep.phi_tree + hp.n_src : nullptr;                   // the target rows of the value's tree buffer
+  double* const gt = d_grad ? field[(int)FieldQuantity::Gradient].tree : nullptr;
+  const int64_t ring = ev_count % kRing;
+  StageMarks tm{timing, timing ? &ev[(size_t)ring * 2 * kStages] : nullptr, 0};
+  // sigma into x_tree, mu into the second buffer, source rows only; a layer that is not given is a zero vector to the near kernel
+  HIP_TRY(tm.begin(Stage::Gather, s));
+  const double* const layer[2] = {d_sigma, d_mu};
+  double* const layer_tree[2] = {d.xt, rep.mu_tree};
+  for (int f = 0; f < 2; ++f) {
+    DevicePlan dg = d;
+    dg.n = hp.n_src;
+    dg.xt = layer_tree[f];
+    if (layer[f]) HIP_TRY(launch_gather_x(dg, layer[f], s));
+    else HIP_TRY(hipMemsetAsync(layer_tree[f], 0, sizeof(double) * (size_t)hp.n_src, s));
+  }
+  HIP_TRY(tm.end(Stage::Gather, s));
+  // P2M per layer given (p2m_targets' views), then the fold; a layer that is not given has no P2M
+  HIP_TRY(tm.begin(Stage::P2M, s));
+  for (int f = 0; f < 2; ++f) {
+    if (!layer[f]) continue;
+    DevicePlan dp = d;
+    dp.bc = bc_all[f];
+    dp.n_act = 1; dp.act[0] = f;
+    dp.xt = layer_tree[f];
+    if (d.p2m_tab) dp.p2m_tab = p2m_tab_slot[f];
+    HIP_TRY(launch_p2m(dp, p, s));
+  }
+  if (d_mu) HIP_TRY(launch_fold_slots(d, p, /*set=*/!d_sigma, s));
+  HIP_TRY(tm.end(Stage::P2M, s));
+  TRY(far_chain(v, rep.view_dev, p, true, nullptr, L2PTo::Caller, nullptr, tm, s));          // (Caller: no L2P in there)
+  HIP_TRY(tm.begin(Stage::Spmv, s));
+  HIP_TRY(launch_near_representation(d, hp.n_src, rep.mu_tree, pt, gt, s));
+  HIP_TRY(tm.end(Stage::Spmv, s));
+  HIP_TRY(tm.begin(Stage::L2P, s));
+  if (d_phi) HIP_TRY(launch_l2p(v, p, rep.phi_tree, s));
+  if (d_grad) HIP_TRY(launch_l2p_field(FieldQuantity::Gradient, v, p, hp.n_src, gt, s));
+  HIP_TRY(tm.end(Stage::L2P, s));
+  HIP_TRY(tm.begin(Stage::Scatter, s));
+  if (d_phi) {
+    HIP_TRY(launch_value_scatter(d, hp.n_src, pt, d_target_point ? rep.phi_points : d_phi, s));
+    if (d_target_point) {
+      const int64_t nu = hp.n_targets;
+      hipLaunchKernelGGL(expand_targets_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, s, d_target_point, rep.phi_points, d_phi, nu, 1);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (d_grad) TRY(deliver_field(FieldQuantity::Gradient, d_grad, s));
+  HIP_TRY(tm.end(Stage::Scatter, s));
+  last_p = p;
+  if (timing) { ev_mask[ring] = tm.mask; ++ev_count; }
   return FMMBEM_OK;
 }
 
@@ -2118,6 +2252,31 @@ int fmmbem_plan_execute_flow(fmmbem_plan* plan, int p, const double* x, double* 
   if (u) HIP_TRY(hipMemcpyAsync(u, plan->stage_y_targets, sizeof(double) * plan->y_doubles(), hipMemcpyDeviceToHost, s));
   if (q) HIP_TRY(hipMemcpyAsync(q, sq, sizeof(double) * nt, hipMemcpyDeviceToHost, s));
   if (G) HIP_TRY(hipMemcpyAsync(G, sG, sizeof(double) * 9 * nt, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return FMMBEM_OK;
+}
+
+// ---- representation execute (include/fmmbem.h) ----
+int fmmbem_plan_execute_representation_device(fmmbem_plan* plan, int p, const double* d_density, const double* d_potential, double* d_phi,
+                                              double* d_grad, void* stream) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  return plan->run_representation(p, d_density, d_potential, d_phi, d_grad, static_cast<hipStream_t>(stream));
+}
+int fmmbem_plan_execute_representation(fmmbem_plan* plan, int p, const double* density, const double* potential, double* phi, double* grad) {
+  if (!plan) return fail(FMMBEM_ERR_INVALID, "null plan");
+  if ((!density && !potential) || (!phi && !grad)) return fail(FMMBEM_ERR_INVALID, "no layer given, or no output asked");
+  TRY(plan->representation_refusal(p));                // a refusal touches no pointer
+  DEVICE_SCOPE(plan->opts.device);
+  TRY(plan->representation_alloc(phi != nullptr, grad != nullptr));
+  double* const sg = plan->field[(int)FieldQuantity::Gradient].stage;
+  const size_t nt = (size_t)plan->hp.n_targets, bytes_x = sizeof(double) * plan->x_doubles();
+  hipStream_t s = plan->own_stream;
+  if (density) HIP_TRY(hipMemcpyAsync(plan->stage_x, density, bytes_x, hipMemcpyHostToDevice, s));
+  if (potential) HIP_TRY(hipMemcpyAsync(plan->rep.stage_mu, potential, bytes_x, hipMemcpyHostToDevice, s));
+  TRY(plan->run_representation(p, density ? plan->stage_x : nullptr, potential ? plan->rep.stage_mu : nullptr, phi ? plan->rep.phi_stage : nullptr,
+                               grad ? sg : nullptr, s));
+  if (phi) HIP_TRY(hipMemcpyAsync(phi, plan->rep.phi_stage, sizeof(double) * nt, hipMemcpyDeviceToHost, s));
+  if (grad) HIP_TRY(hipMemcpyAsync(grad, sg, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return FMMBEM_OK;
 }

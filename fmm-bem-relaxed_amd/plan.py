@@ -892,6 +892,64 @@ class FMM_plan:
         outs[first] = self._field_torch(run, x, None, p, tails[first], "dof values")
         return tuple(outs)
 
+    # ---- the representation execute: both Laplace layers, value and gradient, on one far chain (include/fmmbem.h,
+    # "Representation execute") ----
+    def execute_representation(self, density, potential, value=True, gradient=True):
+        """(N,) density sigma and (N,) surface potential mu -> (phi, grad) at the kernel's current p: phi (M,) = S[sigma] - D[mu] at
+        the plan's points, grad (M, 3) its gradient, in execute's scaling (the physical values are the results / 4 pi); None for an
+        output that was not asked.  density or potential None: that layer is left out.  The targets' own flags do not enter.  ONE
+        gather, P2M per layer, far chain and near kernel where the four single executes on an all-0 and an all-1 plan run four.
+        numpy in, numpy out (host).  FmmBemError (status 6) on a plan that is not over separate targets, on a Stokes plan and on a
+        host-only plan."""
+        if density is None and potential is None:
+            raise ValueError("no layer given")
+        if not (value or gradient):
+            raise ValueError("no output asked")
+        layers = []
+        for name, a in (("density", density), ("potential", potential)):
+            x = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            if x is not None and x.shape != (self.n * self.dof,) and x.shape != (self.n, self.dof):
+                raise ValueError("%s must have one value per panel" % name)
+            layers.append(x)
+        rows = self._field_rows()
+        phi = np.empty((rows,)) if value else None
+        grad = np.empty((rows, 3)) if gradient else None
+        ptr = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in (*layers, phi, grad)]
+        _capi.check(_capi.lib().fmmbem_plan_execute_representation(self._h, self._K.P, *ptr))
+        return phi, grad
+
+    def execute_representation_device(self, density_ptr, potential_ptr, phi_ptr, grad_ptr, stream=0, p=None):
+        """raw device pointers; 0 for a layer that is left out and for an output that is not asked"""
+        _capi.check(_capi.lib().fmmbem_plan_execute_representation_device(
+            self._h, self._K.P if p is None else int(p), C.c_void_p(density_ptr or None), C.c_void_p(potential_ptr or None),
+            C.c_void_p(phi_ptr or None), C.c_void_p(grad_ptr or None), C.c_void_p(stream)))
+
+    def execute_representation_torch(self, density, potential, value=True, gradient=True, p=None):
+        """density, potential: contiguous float64 CUDA tensors (N,), ORIGINAL panel order, or None for a layer that is left out;
+        returns (phi, grad) of shapes (M,), (M, 3), None for what was not asked.  Runs on torch's current stream."""
+        if density is None and potential is None:
+            raise ValueError("no layer given")
+        if not (value or gradient):
+            raise ValueError("no output asked")
+        tails = (() if value else None, (3,) if gradient else None)
+        first = 0 if value else 1
+        outs = [None, None]
+        lead = density if density is not None else potential    # checked by _field_torch; the other layer against it, below
+        other = potential if density is not None else None
+
+        def run(lead_ptr, first_ptr, stream, p):
+            if other is not None and (other.dtype != lead.dtype or other.device != lead.device or not other.is_contiguous()
+                                      or other.numel() != lead.numel()):
+                raise ValueError("potential must be a contiguous float64 CUDA tensor with one value per panel on density's device")
+            if value and gradient:
+                outs[1] = lead.new_empty((self._field_rows(), 3))
+            ptrs = [first_ptr if k == first else 0 if o is None else o.data_ptr() for k, o in enumerate(outs)]
+            layer_ptrs = (lead_ptr, 0 if other is None else other.data_ptr()) if density is not None else (0, lead_ptr)
+            self.execute_representation_device(*layer_ptrs, *ptrs, stream=stream, p=p)
+
+        outs[first] = self._field_torch(run, lead, None, p, tails[first], "one value")
+        return tuple(outs)
+
     def execute_stress(self, traction):
         """(N, 3) or (3N,) traction density -> (M, 3, 3): sigma_i[k][m] = -q_i delta_km + mu (G_i[k][m] + G_i[m][k]), q of
         execute_pressure and G of execute_velocity_gradient, in their scaling: the physical stress is the result / 4 pi.  ONE

@@ -448,6 +448,45 @@ int fmmbem_plan_execute_flow(fmmbem_plan *plan, int p, const double *x /* n x 3 
 int fmmbem_plan_execute_flow_device(fmmbem_plan *plan, int p, const double *d_x,
                                     double *d_u, double *d_q, double *d_G, void *stream);
 
+/* ---- Representation execute: both Laplace layers at the points of a target plan, value and gradient, in one pass --------------
+ * (no reference counterpart).  The representation formula of a Laplace BEM solution off the surface is
+ * phi(t) = (S[sigma](t) - D[mu](t)) / 4 pi, S the single layer of the density sigma and D the double layer of the surface
+ * potential mu; its gradient is the physical field.  On a Laplace plan over separate targets (fmmbem_plan_create_targets,
+ * fmmbem_plan_create_field), for target i at the point t_i:
+ *   phi_i  = sum_j E0(t_i, s_j) sigma_j - sum_j E1(t_i, s_j) mu_j
+ *   grad_i = sum_j gamma0(t_i, s_j) sigma_j - sum_j gamma1(t_i, s_j) mu_j          (three doubles: d/dt_x, d/dt_y, d/dt_z)
+ * E0 / E1: the entries fmmbem_kernel_entries gives for a flag-0 / flag-1 target in every regime (the K stored points; semi-analytic
+ * G and the 16-point rule on the vertices; the 2 pi self value of dG/dn); gamma0 / gamma1: those of fmmbem_plan_execute_gradient.
+ * Put differently: phi is fmmbem_plan_execute(sigma) on the all-flag-0 plan over the points minus fmmbem_plan_execute(mu) on the
+ * all-flag-1 plan, grad the same with fmmbem_plan_execute_gradient -- to rounding (1e-12 relative to the two layers' norms), not
+ * bit for bit: the near sums are accumulated in another association and the far field is one expansion instead of two.  The
+ * scaling is execute's: the physical values are the results / 4 pi.
+ * THE TARGETS' OWN FLAGS DO NOT ENTER: every target gets both layers at its point; copies of a point that differ only in flag
+ * receive identical bits.  A null density or potential leaves that layer out; a null output is not computed.
+ * One call is: one gather per layer, P2M per layer given into that layer's slot of M, the two slots FOLDED into one multipole set
+ * at the leaves (M0 += M1), ONE far chain through L2L on slot 0 alone -- the cost of one potential execute's far field for both
+ * layers, value and gradient --, ONE kernel over the near pairs (a panel's record staged once, one regime test per pair, one
+ * y_q - t, |d_q|^2 and reciprocal square root per quadrature point feeding all four integrands, a row's four sums in list order),
+ * the value's and the gradient's L2P kernels on L0, the delivery.  Its buffers are allocated at first use: mu in tree order, the
+ * value's tree / points / staging buffers, the gradient's (those of fmmbem_plan_execute_gradient), and the P2M moment table of a
+ * slot the plan's own targets do not make live -- FMMBEM_ERR_ALLOC if that fails, the plan stays usable; where the plan's own
+ * P2M runs without a table, so does this one.  Launched plainly, kernel by kernel, whatever fmmbem_plan_set_graphs says; the
+ * captured graphs of execute are left as they are, and execute, execute_batch and execute_gradient return the same bits before
+ * and after it.  The same bits on every run.
+ * Checked in this order: a null plan -> FMMBEM_ERR_INVALID; density and potential both null, or phi and grad both null ->
+ * _INVALID; p outside 1..p_max -> _INVALID; a plan that is not over separate targets -> _UNSUPPORTED; a Stokes plan ->
+ * _UNSUPPORTED; a host-only plan -> _UNSUPPORTED; a treecode plan (it has no local expansions) -> _UNSUPPORTED.  A refusal touches
+ * no pointer and leaves the handle usable.
+ * With stage timing on it is recorded as ONE execute: ms_p2m covers the P2M launches and the fold, ms_near the near kernel,
+ * ms_l2p the L2P kernels, the other stages as in a field execute.  No batches, no graphs, no shards, no device lists.
+ * density, potential: n_panels doubles; phi: n_targets, grad: n_targets x 3 doubles, in the caller's order.  The host form takes
+ * HOST pointers and returns when the outputs are written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_representation(fmmbem_plan *plan, int p,
+                                       const double *density /* n_panels or NULL */, const double *potential /* n_panels or NULL */,
+                                       double *phi /* n_targets or NULL */, double *grad /* n_targets x 3 or NULL */);
+int fmmbem_plan_execute_representation_device(fmmbem_plan *plan, int p, const double *d_density, const double *d_potential,
+                                              double *d_phi, double *d_grad, void *stream);
+
 /* ---- exact block-Jacobi preconditioner: z = M v with M = the inverse of the block-diagonal operator ----------------------
  * (no reference counterpart: Preconditioners::BlockDiagonal, examples/BEM/BlockDiagonalPC.hpp:16-60, runs ONE inner GMRES
  * iteration on that operator instead).  A BLOCK_DIAGONAL plan holds every leaf's self block assembled in HBM; build inverts

@@ -601,6 +601,27 @@ class PlanAdapter {
     check(fmmbem_plan_execute_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
     return results;
   }
+  // Not in the reference: the representation formula at the targets of a Laplace plan over separate targets in ONE execute
+  // (fmmbem_plan_execute_representation): phi = S[density] - D[potential] and its gradient, in execute()'s scaling, the targets'
+  // own BCs ignored -- what execute() on an all-POTENTIAL plan minus execute() on an all-NORMAL_DERIV plan over the same points
+  // returns, and the same with execute_gradient(), to rounding.  density, potential: a null pointer leaves that layer out; phi,
+  // grad: where each result goes, or null for an output that is not asked; each is resized.  Both layers null or both outputs
+  // null: Error(FMMBEM_ERR_INVALID); Error(FMMBEM_ERR_UNSUPPORTED) on a Stokes plan and on a plan over its own panels.
+  void execute_representation(const std::vector<charge_type>* density, const std::vector<charge_type>* potential, std::vector<double>* phi,
+                              std::vector<Vec<3, double>>* grad) {
+    if ((density && density->size() != n_) || (potential && potential->size() != n_))
+      throw Error(FMMBEM_ERR_INVALID, "density / potential: size() != number of panels");
+    const size_t m = has_targets_ ? target_bc_.size() : n_;
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    // (results of their own: a refusal leaves the caller's vectors as they were)
+    std::vector<double> rp(phi ? m : 0);
+    std::vector<Vec<3, double>> rg(grad ? m : 0);
+    check(fmmbem_plan_execute_representation(plan_, K.p(), density ? KernelBinding<Kernel>::in(*density) : nullptr,
+                                             potential ? KernelBinding<Kernel>::in(*potential) : nullptr, phi ? rp.data() : nullptr,
+                                             grad ? rg.data()->data() : nullptr));
+    if (phi) phi->swap(rp);
+    if (grad) grad->swap(rg);
+  }
   // Not in the reference: the pressure of the Stokes single layer at the points of a field plan whose points are all VELOCITY
   // targets (field_plan; fmmbem_plan_execute_pressure): result i = sum_j pi(points[i], sources[j]) . charges[j], in the scaling of
   // execute() -- q = 4 pi p, as execute() returns 4 pi u.  Error(FMMBEM_ERR_UNSUPPORTED) on a Laplace plan, on a plan over its own

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time a field-quantity execute (FMM_plan.execute_gradient_torch, execute_pressure_torch or execute_velocity_gradient_torch,
 csrc/kernels_field.hip) beside the potential or velocity execute of the same plan.
-  python tools/field_time.py --quantity gradient|pressure|velocity_gradient|flow [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
+  python tools/field_time.py --quantity gradient|pressure|velocity_gradient|flow|representation [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
 Workloads:
   gradient            the target plan of tools/target_field_time.py -- 2 x UnitSphere(recursions) (N = 1 048 576 panels by default)
                       and a regular grid of 1 048 576 points over the bounding box of both spheres, theta = 0.5, ncrit 64;
@@ -27,6 +27,18 @@ Stokes workload, beside the three single executes in the same process.  Per orde
   ms_near_flow_kernel            the one near kernel for q and G alone (stage timing 2: events around the near stage only) and
   ms_near_pressure_kernel, ms_near_velgrad_kernel   the two single near kernels the same way; their sum is what it stands against;
   bits_equal                     every output of both flow forms against the single executes' results (torch.equal).
+--quantity representation: the representation execute (FMM_plan.execute_representation_device: both Laplace layers, value and
+gradient, on one far chain) on the gradient's workload, beside the four single executes it replaces -- execute and execute_gradient
+on an all-0 and an all-1 plan over the same points -- in the same process.  Per order, --rounds alternating rounds of {value of the
+single layer, value of the double layer, the two gradients, the representation execute asking both outputs, the value alone, the
+gradient alone}, each timed as above:
+  ms_execute_single, ms_execute_double, ms_gradient_single, ms_gradient_double, ms_representation, ms_representation_value,
+  ms_representation_gradient     the means over the rounds; rounds: every round's figures; spread_ms as for flow;
+  ms_four, ms_two_values, ms_two_gradients   the sums the three representation figures stand against;
+  stages_representation, stages_gradient_single, stages_gradient_double, stages_execute_single    the stage means;
+  ms_near_representation_kernel  the one near kernel (stage timing 2) and ms_near_grad_single_kernel, ms_near_grad_double_kernel the
+                                 two gradient passes the same way: their sum is what it stands against;
+  rel_l2_value, rel_l2_gradient  the representation execute against the four executes' S - D, relative to |S| + |D|.
 --check M (default 0: off): the Direct quantity (fb.Direct.gradient_torch / pressure_torch / velocity_gradient_torch: all N panels,
 every regime) on M points sampled over the whole target set; per order rel_l2_vs_direct_on_sample, the relative L2 of the field
 execute against it on those points, and under "check" the sample's size and the device time of that sum.
@@ -45,7 +57,7 @@ import fmm_bem_relaxed_amd as fb  # noqa: E402
 STAGES = ("ms_gather", "ms_near", "ms_p2m", "ms_m2m", "ms_mh", "ms_m2l", "ms_l2l", "ms_l2p", "ms_scatter", "ms_total")
 # quantity -> (its kernels' short name, the trailing shape of its result, the default orders)
 QUANTITIES = {"gradient": ("grad", (3,), "4,10"), "pressure": ("pressure", (), "8,4"), "velocity_gradient": ("velgrad", (3, 3), "8,4"),
-              "flow": ("flow", (3, 3), "8")}
+              "flow": ("flow", (3, 3), "8"), "representation": ("representation", (3,), "4,10")}
 
 
 def sphere_grid():
@@ -142,6 +154,53 @@ def flow_orders(plan, K, orders, xd, n_targets, repeats, rounds):
     return recs
 
 
+def representation_orders(plans, K, orders, sd, md, n_targets, repeats, rounds):
+    """the records of --quantity representation, one per order; plans: the all-0 and the all-1 plan over the points"""
+    zero, one = plans
+    dev = sd.device
+    new = lambda *tail: torch.empty((n_targets,) + tail, dtype=torch.float64, device=dev)
+    S, D, gS, gD, phi, grad = new(), new(), new(3), new(3), new(), new(3)
+    stream = lambda: torch.cuda.current_stream(dev).cuda_stream
+    rep = lambda f, g: zero.execute_representation_device(sd.data_ptr(), md.data_ptr(), f, g, stream())
+    calls = {
+        "ms_execute_single": lambda: zero.execute_torch(sd, out=S),
+        "ms_execute_double": lambda: one.execute_torch(md, out=D),
+        "ms_gradient_single": lambda: zero.execute_gradient_torch(sd, out=gS),
+        "ms_gradient_double": lambda: one.execute_gradient_torch(md, out=gD),
+        "ms_representation": lambda: rep(phi.data_ptr(), grad.data_ptr()),
+        "ms_representation_value": lambda: rep(phi.data_ptr(), 0),
+        "ms_representation_gradient": lambda: rep(0, grad.data_ptr()),
+    }
+    recs = []
+    for p in orders:
+        K.set_p(p)
+        rec = dict(p=p, rounds=[])
+        for _ in range(rounds):
+            rec["rounds"].append({k: round(device_ms(fn, repeats), 4) for k, fn in calls.items()})
+        for k in calls:
+            rec[k] = round(sum(r[k] for r in rec["rounds"]) / rounds, 4)
+        rec["spread_ms"] = round(max(max(r[k] for r in rec["rounds"]) - min(r[k] for r in rec["rounds"]) for k in calls), 4)
+        rec["ms_two_values"] = round(rec["ms_execute_single"] + rec["ms_execute_double"], 4)
+        rec["ms_two_gradients"] = round(rec["ms_gradient_single"] + rec["ms_gradient_double"], 4)
+        rec["ms_four"] = round(rec["ms_two_values"] + rec["ms_two_gradients"], 4)
+        for name, plan, key in (("execute_single", zero, "ms_execute_single"), ("gradient_single", zero, "ms_gradient_single"),
+                                ("gradient_double", one, "ms_gradient_double"), ("representation", zero, "ms_representation")):
+            rec["stages_" + name] = staged(plan, calls[key], repeats)
+        rec["ms_near_representation_kernel"] = near_ms(zero, calls["ms_representation"], repeats)
+        rec["ms_near_representation_gradient_kernel"] = near_ms(zero, calls["ms_representation_gradient"], repeats)
+        rec["ms_near_grad_single_kernel"] = near_ms(zero, calls["ms_gradient_single"], repeats)
+        rec["ms_near_grad_double_kernel"] = near_ms(one, calls["ms_gradient_double"], repeats)
+        for fn in calls.values():
+            fn()
+        calls["ms_representation"]()
+        torch.cuda.synchronize()
+        norm = torch.linalg.norm
+        rec["rel_l2_value"] = float(norm(phi - (S - D)) / (norm(S) + norm(D)))
+        rec["rel_l2_gradient"] = float(norm(grad - (gS - gD)) / (norm(gS) + norm(gD)))
+        recs.append(rec)
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quantity", choices=sorted(QUANTITIES), required=True)
@@ -159,6 +218,20 @@ def main():
     orders = [int(p) for p in (a.orders or default_orders).split(",")]
     dev = torch.device("cuda", 0)
     extra = {}
+    if q == "representation":
+        if a.check > 0:
+            ap.error("--check belongs to the single quantities: the representation execute is held to the four executes (rel_l2_*)")
+        v = np.concatenate([fb.unit_sphere(a.recursions), fb.unit_sphere(a.recursions, center=(3.0, 0.0, 0.0))])
+        pts = sphere_grid()
+        K = fb.LaplaceSphericalBEM(max(orders), 3)
+        plans = [fb.FMM_plan(K, v, p_max=max(orders), targets=pts, target_bc=np.full(len(pts), f, np.uint8)) for f in (0, 1)]
+        sd, md = (torch.rand(len(v), dtype=torch.float64, generator=torch.Generator().manual_seed(seed)).to(dev) for seed in (1, 2))
+        st = plans[0].stats()
+        out = dict(device=torch.cuda.get_device_name(0), n_panels=len(v), n_targets=len(pts), theta=0.5, ncrit=64, repeats=a.repeats,
+                   rounds=a.rounds, near_nnz=int(st["near_nnz"]), m2l_pairs=int(st["m2l_pairs"]), target_info=plans[0].target_info())
+        out["orders"] = representation_orders(plans, K, orders, sd, md, len(pts), a.repeats, a.rounds)
+        print(json.dumps(out, indent=1))
+        return
     if q == "gradient":
         v = np.concatenate([fb.unit_sphere(a.recursions), fb.unit_sphere(a.recursions, center=(3.0, 0.0, 0.0))])
         pts = sphere_grid()
