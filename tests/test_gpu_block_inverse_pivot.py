@@ -307,6 +307,7 @@ def test_nine_value_stokes_rows(fb, monkeypatch):
     monkeypatch.setenv("FMMBEM_PLAN_SHARE", "0")
     monkeypatch.setenv("FMMBEM_STOKES_SYM", "0")
     d = _case(fb, "stokes-86-vel", key="stokes-86-vel/nine")
+    assert d["plan"].stats()["geometry_shared"] == 1
     monkeypatch.undo()
     m = 258
     b9, b6 = d["plan"].stats()["near_bytes"], sym["plan"].stats()["near_bytes"]

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import field_plan_reference as R
+import own_geometry
 from test_gpu_direct import stokes_oracle_at
 from test_target_plan_oracle_host import CASES, HOST_CASES, case
 
@@ -294,9 +295,8 @@ def test_nine_value_rows(fb, oracle_mod, sphere4, monkeypatch):
     the same numbers added in another order (1e-12: far above m 2^-53 for rows of a few hundred entries)."""
     v, pts, flags = sphere4
     sym = Composed(fb, v, pts, flags, 0.5, 20, p_max=6)
-    monkeypatch.setenv("FMMBEM_STOKES_SYM", "0")
-    rows9 = Composed(fb, v, pts, flags, 0.5, 20, p_max=6)
-    monkeypatch.delenv("FMMBEM_STOKES_SYM")
+    rows9 = own_geometry.under(monkeypatch, {"FMMBEM_STOKES_SYM": "0"}, lambda: Composed(fb, v, pts, flags, 0.5, 20, p_max=6),
+                               plan_of=lambda c: c.plan)         # sym is alive: the storage form is the geometry's
     assert rows9.plan.stats()["near_bytes"] > 1.4 * sym.plan.stats()["near_bytes"]
     y9, ys = rows9.run(6), sym.run(6)
     check(y9, rows9.ref(6), flags == 0, "9-value rows, VELOCITY against the composed reference")

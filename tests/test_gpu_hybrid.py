@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import drand48, rel_l2
+from own_geometry import plan_under
 
 pytestmark = pytest.mark.gpu
 
@@ -97,8 +98,8 @@ def test_hybrid_is_ignored_where_it_does_not_apply(fb, oracle_mod, monkeypatch):
     o2 = _opts(fb, 0.3)
     o2.sparse_local = False                                                            # matrix-free: nothing stored anyway
     assert fb.FMM_plan(K, v, o2).stats()["near_recomputed_pairs"] == 0
-    monkeypatch.setenv("FMMBEM_STOKES_SYM", "0")                                       # the 9-value rows: streamed only
-    assert fb.FMM_plan(K, v, _opts(fb, 0.3)).stats()["near_recomputed_pairs"] == 0
+    # the 9-value rows: streamed only.  On a geometry of its own: the storage form is the geometry's
+    assert plan_under(fb, monkeypatch, {"FMMBEM_STOKES_SYM": "0"}, K, v, _opts(fb, 0.3)).stats()["near_recomputed_pairs"] == 0
     # Laplace with a rule of more than three points: the fully streamed plan
     KL = fb.LaplaceSphericalBEM(6, 4)
     assert fb.FMM_plan(KL, v, _opts(fb, 0.3)).stats()["near_recomputed_pairs"] == 0

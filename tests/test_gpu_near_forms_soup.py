@@ -132,6 +132,7 @@ def test_streamed_stokes_nine_value_rows(fb, oracle_mod, monkeypatch, case, mixe
     monkeypatch.setenv("FMMBEM_STOKES_SYM", "0")
     monkeypatch.setenv("FMMBEM_PLAN_SHARE", "0")       # a live plan of the same panels would lend its geometry, symmetric blocks included
     plan = nfc.make_plan(fb, case, mixed)
+    assert plan.stats()["geometry_shared"] == 1
     assert plan.stats()["near_bytes"] > 1.4 * sym_bytes
     _assert_rows(plan, R, "streamed, 9-value rows " + _tag(case, mixed))
     if not mixed:

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import drand48, rel_l2
+from own_geometry import GEOMETRY_SWITCHES, plan_under
 
 pytestmark = pytest.mark.gpu
 
@@ -259,30 +260,46 @@ def test_matrix_free_near_field(fb, oracle_mod, monkeypatch, bc_val, quad_k):
 def test_alternative_paths_match_oracle(fb, oracle_mod, monkeypatch, env):
     """The switches that select the fallback kernels (recurrence P2M instead of the stored moments -- what a plan whose records
     would pass 16 GB runs --, the L2P kernel that takes the order at run time -- p > 12 --) and other cuts of the M2L pair list
-    into items give the same operator -- cuts and the two L2P kernels bit for bit."""
+    into items give the same operator -- cuts and the two L2P kernels bit for bit.
+
+    Both plans own their geometry (own_geometry.plan_under): the cut is the geometry's, and a second plan of these vertices
+    would otherwise run the first one's.  On this mesh (1 736 M2L pairs) the two cases of FMMBEM_ROT_ITEM_PASSES still cut the
+    list as the default does -- items longer than one pass need 524 288 pairs (HostPlan::build_rot_items), long items of another
+    length more passes than the chip has SIMDs; measured on the host: 17 items in 32 passes under every value -- so these two
+    cases hold the switch to be harmless here, and the stats say so; a cut that does differ is compared bit for bit in
+    test_tree_passes_at_the_default_level_rule[10]."""
+    geometry_env = {k: val for k, val in env.items() if k in GEOMETRY_SWITCHES}
     for k, val in env.items():
-        monkeypatch.setenv(k, val)
+        if k not in geometry_env:
+            monkeypatch.setenv(k, val)
     v = oracle_mod.unit_sphere(5)
     rng = np.random.default_rng(3)
     bc = (rng.random(len(v)) < 0.5).astype(np.uint8)
     x = rng.standard_normal(len(v))
     o = oracle_mod.Oracle(v, bc=bc)
     K = fb.LaplaceSphericalBEM(10, 3)
-    pl = fb.FMM_plan(K, v, bc=bc)
-    res = {}
+    pl = plan_under(fb, monkeypatch, geometry_env, K, v, bc=bc)
+    res, cut = {}, {}
     for p in (10, 3):
         K.set_p(p)
         y, yo = pl.execute(x), o.matvec(x, p)
         assert np.linalg.norm(y - yo) <= 1e-12 * np.linalg.norm(yo)
         res[p] = y
+        st = pl.stats()
+        assert st["m2l_kernel"] == 1
+        cut[p] = (st["m2l_items"], st["m2l_passes"])
     if "FMMBEM_L2P_GENERIC" in env or "FMMBEM_ROT_ITEM_PASSES" in env:   # not other arithmetic: the same bits
         for k in env:
-            monkeypatch.delenv(k)
+            if k not in geometry_env:
+                monkeypatch.delenv(k)
         K2 = fb.LaplaceSphericalBEM(10, 3)
-        pl2 = fb.FMM_plan(K2, v, bc=bc)
+        pl2 = plan_under(fb, monkeypatch, None, K2, v, bc=bc)
         for p in (10, 3):
             K2.set_p(p)
             assert np.array_equal(pl2.execute(x), res[p])
+            st = pl2.stats()
+            print("p = %d: items, passes %r under %r, %r by default" % (p, cut[p], env, (st["m2l_items"], st["m2l_passes"])))
+            assert cut[p] == (st["m2l_items"], st["m2l_passes"]) == (17, 32)      # docstring: one cut on a mesh of this size
 
 
 @pytest.mark.gpu
@@ -331,6 +348,7 @@ def test_stokes_assembly_kernels_give_the_same_bits(fb, monkeypatch, case):
         K = fb.StokesSphericalBEM(4, k, 1e-3)
         K.set_Kfine(kf)
         pl = fb.FMM_plan(K, v, opts, bc=bc)
+        assert pl.stats()["geometry_shared"] == 1          # FMMBEM_STOKES_SYM is the geometry's
         got.append((pl.execute(x), [pl.near_row(int(r)) for r in (0, 7, 3 * n - 1)]))
     assert np.array_equal(got[0][0], got[1][0])
     for (ca, va), (cb, vb) in zip(got[0][1], got[1][1]):
@@ -414,29 +432,40 @@ def test_tree_passes_at_the_default_level_rule(fb, monkeypatch, p):
     levels near the root -- on a mesh big enough to have both kinds of level (UnitSphere(8), 131 072 panels), both
     expansion slots live.  No oracle at this size: the two families are each held to the oracle level by level on small meshes
     (test_tree_passes_by_rotation_match_oracle, test_expansions_and_matvec_vs_oracle); here the mixed pass must give the M and L
-    of the all-sparse pass box by box, and the M2L items (long ones at p = 10, short ones at p = 4) the same bits under another cut."""
+    of the all-sparse pass box by box, and the M2L items (long ones at p = 10, short ones at p = 4) the same bits under another cut.
+
+    Every plan owns its geometry (own_geometry.plan_under): the form of the tree passes and the cut are the geometry's.  The
+    other cut: FMMBEM_ROT_ITEM_PASSES=3 and FMMBEM_ROT_LONG_MAX=5 alone leave this operator's cut as it is (167 480 pairs; measured
+    on the host, 2 072 short and 801 long items either way); FMMBEM_ROT_LONG_ROUNDS=2 beside them cuts the long items (p = 10) for
+    two rounds over the SIMDs, 1 130 items, and the stats must show it.  The short items (p = 4) have one cut below 524 288 pairs
+    (HostPlan::build_rot_items): at p = 4 the third plan repeats the default on a geometry of its own."""
     v = fb.unit_sphere(8)
     rng = np.random.default_rng(5)
     bc = (rng.random(len(v)) < 0.5).astype(np.uint8)
     x = rng.standard_normal(len(v))
     K = fb.LaplaceSphericalBEM(p, 3)
-    pl = fb.FMM_plan(K, v, bc=bc)
+    pl = plan_under(fb, monkeypatch, None, K, v, bc=bc)
     lev = pl.boxes()["level"]
     per_level = np.bincount(lev)
     assert per_level.max() >= 2048 and (per_level[2:] < 2048).any()          # both kernels families run
     y = pl.execute(x)
+    cut = (pl.stats()["m2l_items"], pl.stats()["m2l_passes"])
     M, L = pl.expansions("M", p), pl.expansions("L", p)
-    monkeypatch.setenv("FMMBEM_SHIFT_ROT", "0")
-    pl2 = fb.FMM_plan(K, v, bc=bc)
+    pl2 = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_ROT": "0"}, K, v, bc=bc)
     y2 = pl2.execute(x)
     for got, ref, which in ((M, pl2.expansions("M", p), "M"), (L, pl2.expansions("L", p), "L")):
         scale = np.abs(ref).max(axis=2, keepdims=True) + 1e-300
-        assert np.max(np.abs(got - ref) / scale) <= TOL_EXPANSION, which
+        worst = float(np.max(np.abs(got - ref) / scale))
+        print("p = %d: %s of the mixed pass against the all-sparse pass, worst %.3e of the box's largest" % (p, which, worst))
+        assert worst <= TOL_EXPANSION, which
+    print("p = %d: y, rel L2 %.3e" % (p, rel_l2(y, y2)))
     assert rel_l2(y, y2) <= 1e-13
-    monkeypatch.delenv("FMMBEM_SHIFT_ROT")
-    monkeypatch.setenv("FMMBEM_ROT_ITEM_PASSES", "3")
-    monkeypatch.setenv("FMMBEM_ROT_LONG_MAX", "5")
-    assert np.array_equal(fb.FMM_plan(K, v, bc=bc).execute(x), y)
+    pl2.close()
+    pl3 = plan_under(fb, monkeypatch, {"FMMBEM_ROT_ITEM_PASSES": "3", "FMMBEM_ROT_LONG_MAX": "5", "FMMBEM_ROT_LONG_ROUNDS": "2"}, K, v, bc=bc)
+    assert np.array_equal(pl3.execute(x), y)
+    cut3 = (pl3.stats()["m2l_items"], pl3.stats()["m2l_passes"])
+    print("p = %d: items, passes %r by default, %r under the other cut" % (p, cut, cut3))
+    assert (cut3 != cut) == (p == 10)
 
 
 @pytest.mark.gpu
@@ -445,16 +474,15 @@ def test_tree_passes_by_rotation_match_oracle(fb, oracle_mod, monkeypatch, p):
     """M2M and L2L through the rotation kernels (kernels_m2l_rot.hip compiled with FMMBEM_ROT_OP = 1, 2).  By default only
     levels of 2 048 boxes and more take that path, which no mesh of test size has: FMMBEM_SHIFT_ROT_MIN=0 sends every level
     there (with the one-pair-per-wavefront kernel, which small levels take by default, switched off).  Expansions and result against
-    the oracle; mixed boundary conditions so that both expansion slots are live."""
-    monkeypatch.setenv("FMMBEM_SHIFT_ROT_MIN", "0")
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES", "0")
+    the oracle; mixed boundary conditions so that both expansion slots are live.  Both plans own their geometry
+    (own_geometry.plan_under): the form of the tree passes is the geometry's."""
     v = np.concatenate([oracle_mod.unit_sphere(5), oracle_mod.unit_sphere(4, center=(2.5, 0.3, -0.2))])
     rng = np.random.default_rng(11)
     bc = (rng.random(len(v)) < 0.4).astype(np.uint8)
     x = rng.standard_normal(len(v))
     o = oracle_mod.Oracle(v, bc=bc)
     K = fb.LaplaceSphericalBEM(p, 3)
-    pl = fb.FMM_plan(K, v, bc=bc)
+    pl = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_ROT_MIN": "0", "FMMBEM_SHIFT_LANES": "0"}, K, v, bc=bc)
     y, yo = pl.execute(x), o.matvec(x, p)
     for which in ("M", "L"):
         got, ref = pl.expansions(which, p), o.expansions(p, which)
@@ -462,8 +490,8 @@ def test_tree_passes_by_rotation_match_oracle(fb, oracle_mod, monkeypatch, p):
         assert np.max(np.abs(got - ref) / scale) <= TOL_EXPANSION, which
     assert rel_l2(y, yo) <= TOL_MATVEC
     # the same operator as the sparse-operator kernels, to rounding
-    monkeypatch.setenv("FMMBEM_SHIFT_ROT", "0")
-    y2 = fb.FMM_plan(K, v, bc=bc).execute(x)
+    y2 = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_ROT_MIN": "0", "FMMBEM_SHIFT_LANES": "0", "FMMBEM_SHIFT_ROT": "0"}, K, v, bc=bc).execute(x)
+    print("p = %d: rotation tree passes against the sparse operators, rel L2 %.3e" % (p, rel_l2(y, y2)))
     assert rel_l2(y, y2) <= 1e-14
 
 
@@ -479,16 +507,18 @@ def test_shift_lanes_equal_the_one_pair_kernels_bit_for_bit(fb, oracle_mod, monk
     bc = (rng.random(len(v)) < 0.4).astype(np.uint8)
     x = rng.standard_normal(len(v))
     K = fb.LaplaceSphericalBEM(p, 3)
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES", "1")
-    pl = fb.FMM_plan(K, v, bc=bc)
+    pl = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_LANES": "1"}, K, v, bc=bc)
     y = pl.execute(x)
     M, L = pl.expansions("M", p), pl.expansions("L", p)
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES", "0")
-    monkeypatch.setenv("FMMBEM_SHIFT_ROT_MIN", "0")          # every level through the one-pair-per-lane rotation kernels
-    pl1 = fb.FMM_plan(K, v, bc=bc)
+    # every level through the one-pair-per-lane rotation kernels, on a geometry of its own: the form is the geometry's
+    pl1 = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_LANES": "0", "FMMBEM_SHIFT_ROT_MIN": "0"}, K, v, bc=bc)
     y1 = pl1.execute(x)
-    assert np.array_equal(pl1.expansions("M", p), M)
-    assert np.array_equal(pl1.expansions("L", p), L)
+    M1, L1 = pl1.expansions("M", p), pl1.expansions("L", p)
+    print("p = %d: lanes against one pair per lane: M %d, L %d, y %d values of other bits; largest |dM| %.3e, |dL| %.3e, |dy| %.3e"
+          % (p, np.count_nonzero(M1 != M), np.count_nonzero(L1 != L), np.count_nonzero(y1 != y), float(np.abs(M1 - M).max()),
+             float(np.abs(L1 - L).max()), float(np.abs(y1 - y).max())))
+    assert np.array_equal(M1, M)
+    assert np.array_equal(L1, L)
     assert np.array_equal(y1, y)
     o = oracle_mod.Oracle(v, bc=bc)
     assert rel_l2(y, o.matvec(x, p)) <= TOL_MATVEC
@@ -509,9 +539,8 @@ def test_shift_lanes_wavefront_runs_of_parents_bit_for_bit(fb, monkeypatch, p):
     K = fb.LaplaceSphericalBEM(p, 3)
     fo = fb.FMMOptions()
     fo.set_max_per_box(16)
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES", "1")
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES_MAX", "1000000")          # every level through the wavefront kernel
-    pl = fb.FMM_plan(K, v, fo)
+    lanes = {"FMMBEM_SHIFT_LANES": "1", "FMMBEM_SHIFT_LANES_MAX": "1000000"}          # every level through the wavefront kernel
+    pl = plan_under(fb, monkeypatch, lanes, K, v, fo)
     boxes = pl.boxes()
     parents_per_level = np.bincount(boxes["level"][boxes["leaf"] == 0])
     assert parents_per_level.max() > 1024
@@ -519,10 +548,14 @@ def test_shift_lanes_wavefront_runs_of_parents_bit_for_bit(fb, monkeypatch, p):
     M, L = pl.expansions("M", p), pl.expansions("L", p)
     total = np.zeros_like(y)
     for r in range(2):
-        total += fb.FMM_plan(K, v, fo, shard=(r, 2)).execute(x)
+        total += plan_under(fb, monkeypatch, lanes, K, v, fo, shard=(r, 2)).execute(x)
     assert np.array_equal(total, y)
-    monkeypatch.setenv("FMMBEM_SHIFT_LANES", "0")
-    monkeypatch.setenv("FMMBEM_SHIFT_ROT_MIN", "0")
-    pl1 = fb.FMM_plan(K, v, fo)
-    assert np.array_equal(pl1.execute(x), y)
-    assert np.array_equal(pl1.expansions("M", p), M) and np.array_equal(pl1.expansions("L", p), L)
+    # on a geometry of its own: a plan that recognised pl's would run the wavefront kernel again.  FMMBEM_SHIFT_LANES_MAX stays
+    # set, as it was when this test was written: with FMMBEM_SHIFT_LANES=0 it decides nothing
+    pl1 = plan_under(fb, monkeypatch, {"FMMBEM_SHIFT_LANES": "0", "FMMBEM_SHIFT_LANES_MAX": "1000000", "FMMBEM_SHIFT_ROT_MIN": "0"}, K, v, fo)
+    y1, M1, L1 = pl1.execute(x), pl1.expansions("M", p), pl1.expansions("L", p)
+    print("p = %d: runs of parents against one pair per lane: M %d, L %d, y %d values of other bits; largest |dM| %.3e, |dL| %.3e, |dy| %.3e"
+          % (p, np.count_nonzero(M1 != M), np.count_nonzero(L1 != L), np.count_nonzero(y1 != y), float(np.abs(M1 - M).max()),
+             float(np.abs(L1 - L).max()), float(np.abs(y1 - y).max())))
+    assert np.array_equal(y1, y)
+    assert np.array_equal(M1, M) and np.array_equal(L1, L)

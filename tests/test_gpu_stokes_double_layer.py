@@ -16,6 +16,7 @@ import pytest
 
 import double_layer_reference as D
 import field_plan_reference as R
+import own_geometry
 from test_double_layer_reference_host import DENSITY_SEED, two_spheres
 from test_gpu_field_plan import plan_options
 from test_gpu_parity import TOL_EXPANSION
@@ -175,14 +176,12 @@ def test_every_form_that_carries_the_slots(fb, oracle_mod, monkeypatch, form):
     what, env, orders, with_m = form
     g = spheres(fb)
     flags = sphere_flags(g, "mixed")
-    for k, val in env.items():
-        monkeypatch.setenv(k, val)
-    plan, K = g.plan("mixed", flags, p_max=max(orders), fresh=True)
-    for k in env:
-        monkeypatch.delenv(k)
+    # on a geometry of its own (the M2L and the tree passes' form are the geometry's; two forms here share p_max = 8)
+    plan, K = own_geometry.under(monkeypatch, env, lambda: g.plan("mixed", flags, p_max=max(orders), fresh=True))
     for p in orders:
         K.set_p(p)
         y = plan.execute(g.x)
+        assert plan.stats()["m2l_kernel"] == (2 if "FMMBEM_M2L_ROT" in env or p > 12 else 1), (what, p)
         if with_m:
             check_expansions(plan.expansions("M", p), g.expansions(plan, p)[0], "M", (what, p))
         ref, T = g.rows("mixed", flags, plan, p)

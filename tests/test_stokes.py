@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import drand48, rel_l2
+from own_geometry import plan_under
 
 
 @pytest.fixture(scope="module")
@@ -159,10 +160,12 @@ def test_gpu_stokes_traction_far_field_above_the_rotation_orders(fb, oracle_mod,
     assert errs[16] < errs[14] < errs[13] < errs[12] < errs[10] and errs[16] < 0.3 * errs[12], errs
     K.set_p(12)
     y_rot = pl.execute(x)
-    monkeypatch.setenv("FMMBEM_M2L_ROT", "0")
+    assert pl.stats()["m2l_kernel"] == 1
     K2 = fb.StokesSphericalBEM(12, 4, 1e-3)
     K2.set_Kfine(19)
-    assert rel_l2(fb.FMM_plan(K2, v, bc=bc).execute(x), y_rot) <= 1e-13
+    pl2 = plan_under(fb, monkeypatch, {"FMMBEM_M2L_ROT": "0"}, K2, v, bc=bc)      # which M2L a plan runs is its geometry's
+    assert rel_l2(pl2.execute(x), y_rot) <= 1e-13
+    assert pl2.stats()["m2l_kernel"] == 2
     o.close()
 
 
@@ -216,12 +219,10 @@ def test_gpu_stokes_diagonal_and_rows_from_symmetric_blocks(fb, stokes5):
 @pytest.mark.parametrize("env", [{"FMMBEM_P2M_TABLE": "0"}, {"FMMBEM_STOKES_SYM": "0"}])
 def test_gpu_stokes_alternative_paths(fb, stokes5, monkeypatch, env):
     """Recurrence P2M instead of the stored moments; the 9-value near rows instead of the symmetric blocks."""
-    for k, val in env.items():
-        monkeypatch.setenv(k, val)
     v, o = stokes5
     K = fb.StokesSphericalBEM(8, 4, 1e-3)
     K.set_Kfine(19)
-    pl = fb.FMM_plan(K, v)
+    pl = plan_under(fb, monkeypatch, env, K, v)                # the storage form is the geometry's; the P2M table is the plan's own
     x = drand48(3 * o.n, seed=5).reshape(o.n, 3)
     assert rel_l2(pl.execute(x), o.matvec(x, 8)) <= 1e-12
 
