@@ -14,6 +14,9 @@ one more report line with its largest error against the exact exterior solution 
 (fmmbem_options.near_f32_max_p); the report lines are the same, plus one line that states the threshold.
 -field_grad (not a flag of the reference): with -field N, one more line: the gradient of that formula at the same points
 (FMM_plan.execute_gradient on the two plans over them), its largest error against the exact -x/|x|^3 relative to 1/9.
+-field_hess (not a flag of the reference): with -field N, one more line: the Hessian of that formula at the same points
+(FMM_plan.execute_hessian on the two plans over them, also when -field_one_pass is given), the Frobenius norm of its error against
+the exact 3 x x^T / |x|^5 - I / |x|^3 relative to 2/27.  Like -field_grad it does nothing without -field.
 -field_one_pass (not a flag of the reference): with -field N, the field line -- and with -field_grad the gradient line -- from ONE
 plan over the points and ONE FMM_plan.execute_representation (fmmbem_plan_execute_representation: both layers folded into one
 multipole set, one far chain, one kernel over the near pairs) where the lines otherwise take two plans and two or four executes;
@@ -112,6 +115,19 @@ def exterior_fmm_gradient(fb_, v, g_density, dgdn_density, points, p, k=3, opts=
     return out
 
 
+def exterior_fmm_hessian(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None):
+    """The Hessian of the same formula at the points: (Hessian of the single layer of g_density - Hessian of the double layer of
+    dgdn_density) / 4 pi, by the Hessian executes of the two plans over the points; (M, 3, 3)"""
+    m = len(points)
+    K = fb_.LaplaceSphericalBEM(p, k)
+    g = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.zeros(m, dtype=np.uint8))
+    d = fb_.FMM_plan(K, v, opts, targets=points, target_bc=np.ones(m, dtype=np.uint8))
+    out = (g.execute_hessian(g_density) - d.execute_hessian(dgdn_density)) / 4 / math.pi
+    g.close()
+    d.close()
+    return out
+
+
 def exterior_fmm_one_pass(fb_, v, g_density, dgdn_density, points, p, k=3, opts=None, gradient=False):
     """The formula, and with `gradient` its gradient, at the points from ONE plan over them and ONE representation execute (the
     points' flags do not enter): (phi, grad or None), each / 4 pi"""
@@ -137,7 +153,7 @@ def main(argv):
         print_help_and_exit()
     theta, ncrit, p, k, recursions = 0.5, 64, 5, 3, 4
     second_kind, mesh, field, near_f32, evaluator = False, None, 0, 0, "FMM"
-    field_grad = field_one_pass = False
+    field_grad = field_hess = field_one_pass = False
     so = fb.SolverOptions()
     max_iterations, solver, pc = 500, "gmres", "identity"
     print("parameters : \n============ ")
@@ -186,6 +202,8 @@ def main(argv):
             i += 1; field = int(argv[i])
         elif a == "-field_grad":                           # not in the reference: FMM_plan.execute_gradient
             field_grad = True
+        elif a == "-field_hess":                           # not in the reference: FMM_plan.execute_hessian
+            field_hess = True
         elif a == "-field_one_pass":                       # not in the reference: FMM_plan.execute_representation
             field_one_pass = True
         elif a == "-block_inverse":                        # not in the reference: solver.BlockInverse
@@ -290,6 +308,13 @@ def main(argv):
             gerr = np.linalg.norm(grad - exact_grad, axis=1) / (1.0 / 9.0)
             print("field gradient: %d points at r = 3, max error: %.4e, rms error: %.4e"
                   % (field, float(gerr.max()), float(np.sqrt((gerr ** 2).mean()))))
+        if field_hess:
+            hess = exterior_fmm_hessian(fb, v, xs, np.ones(n), pts, p, k, opts)
+            rr = np.linalg.norm(pts, axis=1)
+            exact_hess = 3 * pts[:, :, None] * pts[:, None, :] / rr[:, None, None] ** 5 - np.eye(3)[None] / rr[:, None, None] ** 3
+            herr = np.linalg.norm((hess - exact_hess).reshape(field, 9), axis=1) / (2.0 / 27.0)
+            print("field Hessian: %d points at r = 3, max error: %.4e, rms error: %.4e"
+                  % (field, float(herr.max()), float(np.sqrt((herr ** 2).mean()))))
     return it, res, math.sqrt(e / n), abs(outside - exact) / abs(exact)
 
 

@@ -5,7 +5,7 @@ and this thin host-side mirror of the reference's operator interface.
 """
 from ._capi import FmmBemError, LIB_PATH, Options, PMAX, SYMBOLS, lib  # noqa: F401
 from .plan import (Direct, FMM_plan, FMMOptions, LaplaceSphericalBEM, StokesSphericalBEM, kernel_entries, kernel_gradient_entries, quadrature,  # noqa: F401
-                   kernel_pressure_entries, kernel_velocity_gradient_entries, read_msh,
+                   kernel_hessian_entries, kernel_pressure_entries, kernel_velocity_gradient_entries, read_msh,
                    read_vert_face, red_blood_cell, red_blood_cells, unit_sphere, write_vert_face)
 
 

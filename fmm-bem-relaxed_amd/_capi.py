@@ -115,6 +115,8 @@ SYMBOLS = (
     "fmmbem_plan_execute_velocity_gradient", "fmmbem_plan_execute_velocity_gradient_device", "fmmbem_kernel_velocity_gradient_entries",
     "fmmbem_plan_execute_flow", "fmmbem_plan_execute_flow_device",
     "fmmbem_plan_execute_representation", "fmmbem_plan_execute_representation_device",
+    "fmmbem_plan_execute_hessian", "fmmbem_plan_execute_hessian_device", "fmmbem_kernel_hessian_entries",
+    "fmmbem_direct_hessian", "fmmbem_direct_hessian_device",
 )
 
 
@@ -229,6 +231,11 @@ def lib():
     L.fmmbem_plan_execute_gradient.argtypes = [vp, i32, vp, vp]
     L.fmmbem_plan_execute_gradient_device.argtypes = [vp, i32, vp, vp, vp]
     L.fmmbem_kernel_gradient_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp, vp]
+    L.fmmbem_plan_execute_hessian.argtypes = [vp, i32, vp, vp]
+    L.fmmbem_plan_execute_hessian_device.argtypes = [vp, i32, vp, vp, vp]
+    L.fmmbem_kernel_hessian_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp, vp]
+    L.fmmbem_direct_hessian.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    L.fmmbem_direct_hessian_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.fmmbem_plan_execute_pressure.argtypes = [vp, i32, vp, vp]
     L.fmmbem_plan_execute_pressure_device.argtypes = [vp, i32, vp, vp, vp]
     L.fmmbem_kernel_pressure_entries.argtypes = [C.POINTER(Options), C.c_size_t, vp, vp, vp]

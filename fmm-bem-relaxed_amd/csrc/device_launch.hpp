@@ -82,10 +82,11 @@ hipError_t launch_m2p(const DevicePlan& d, const M2PWork& w, int p, double* y, h
 // near: tree[row] = the near pairs' sums, every target row written (zeros where the leaf has no near pair);
 // l2p: tree[row] += what the quantity reads of the leaf's local expansions -- + (flag 0) or - (flag 1) the gradient of the row's
 //      slot; - (d_x phi_0 + d_y phi_1 + d_z phi_2) of slots 0..2; (1 / 2 mu) [d_m phi_k - d_k phi_m - x_e d_k d_m phi_e + d_k d_m phi_3]
-//      of slots 0..3 (nothing at p = 1);
+//      of slots 0..3 (nothing at p = 1); Hessian: Laplace plans, 9 doubles per target row ([a][b], symmetric), + or - the Hessian of
+//      the row's slot (nothing at p = 1);
 // scatter: out[width perm[row] ..] = tree[width (row - n_src) ..];
-// entries: gamma (3 doubles), pi (3) or Gamma (27, [k][m][e]) for pairs laid out as launch_kernel_entries takes them
-enum class FieldQuantity { Gradient, Pressure, VelocityGradient };
+// entries: gamma (3 doubles), pi (3), Gamma (27, [k][m][e]) or eta (9, [a][b]) for pairs laid out as launch_kernel_entries takes them
+enum class FieldQuantity { Gradient, Pressure, VelocityGradient, Hessian };
 hipError_t launch_near_field(FieldQuantity q, const DevicePlan& d, int64_t n_src, double* tree, hipStream_t s);
 hipError_t launch_near_flow(const DevicePlan& d, int64_t n_src, double* q_tree, double* g_tree, hipStream_t s);   // Pressure and VelocityGradient in one kernel
 // the representation execute (Laplace): both layers' near pairs in one kernel, sigma in d.xt and mu in mu_tree, phi_tree (1 double
@@ -126,8 +127,8 @@ int64_t direct_chunks(int64_t n_sources);              // partial sums per targe
 hipError_t launch_direct(const DevicePlan& d, int64_t m, const double* tx, const double* ty, const double* tz, int tstride,
                          const uint8_t* tbc, const double* x, double* part, double* y, hipStream_t s);
 // the field quantities at points: out_i = sum_j (q's pair function)(t_i, panel j) x_j, W = direct_field_width(q) doubles per target
-// (3, 1, 9).  pts: m x 3; tbc (Gradient only) null: flags 0; x: d.n * d.dof; part: direct_chunks(d.n) * m * W doubles of scratch;
-// out: m * W.  Gradient takes a Laplace d, the other two a Stokes d (hipErrorInvalidValue otherwise).
+// (3, 1, 9, 9).  pts: m x 3; tbc (Gradient and Hessian only) null: flags 0; x: d.n * d.dof; part: direct_chunks(d.n) * m * W doubles of scratch;
+// out: m * W.  Gradient and Hessian take a Laplace d, the other two a Stokes d (hipErrorInvalidValue otherwise).
 int direct_field_width(FieldQuantity q);
 hipError_t launch_direct_field(FieldQuantity q, const DevicePlan& d, int64_t m, const double* pts, const uint8_t* tbc, const double* x,
                                double* part, double* out, hipStream_t s);

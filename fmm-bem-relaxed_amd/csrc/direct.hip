@@ -127,11 +127,11 @@ int fmmbem_direct::apply(size_t m, int width, const FieldQuantity* q, const doub
 
 namespace {
 
-// fmmbem_direct_{gradient,pressure,velocity_gradient}{,_device}: the checks in the header's order, then the sum.  host: the pointers
+// fmmbem_direct_{gradient,pressure,velocity_gradient,hessian}{,_device}: the checks in the header's order, then the sum.  host: the pointers
 // are the caller's host arrays (the points are read, the result is copied back); else device pointers, asynchronous on s.
 int direct_field(fmmbem_direct* direct, FieldQuantity q, bool host, size_t n_targets, const double* pts, const uint8_t* bc, const double* x,
                  double* out, hipStream_t s) {
-  static const char* const kName[3] = {"gradient", "pressure", "velocity gradient"};
+  static const char* const kName[4] = {"gradient", "pressure", "velocity gradient", "Hessian"};
   const char* name = kName[(int)q];
   if (!direct || !pts || !x || !out) return fail(FMMBEM_ERR_INVALID, "null argument");
   if (n_targets == 0) return fail(FMMBEM_ERR_INVALID, std::string("Direct ") + name + ": no targets");
@@ -139,7 +139,10 @@ int direct_field(fmmbem_direct* direct, FieldQuantity q, bool host, size_t n_tar
   if (q == FieldQuantity::Gradient && !laplace)
     return fail(FMMBEM_ERR_UNSUPPORTED, "Direct gradient: the gradient of the Laplace field needs a handle of the Laplace kernel (this one is Stokes: "
                                         "fmmbem_direct_velocity_gradient is its gradient)");
-  if (q != FieldQuantity::Gradient && laplace)
+  if (q == FieldQuantity::Hessian && !laplace)
+    return fail(FMMBEM_ERR_UNSUPPORTED, "Direct Hessian: the Hessian of the Laplace field needs a handle of the Laplace kernel (this one is Stokes: "
+                                        "fmmbem_direct_velocity_gradient is its second-order quantity)");
+  if (q != FieldQuantity::Gradient && q != FieldQuantity::Hessian && laplace)
     return fail(FMMBEM_ERR_UNSUPPORTED, std::string("Direct ") + name + ": the " + name + " of the single layer needs a handle of the Stokes kernel "
                                         "(this one is Laplace: fmmbem_direct_gradient is its gradient)");
   if (host && !all_finite(pts, 3 * n_targets)) return fail(FMMBEM_ERR_INVALID, std::string("Direct ") + name + ": a target point is not finite");
@@ -172,6 +175,14 @@ int fmmbem_direct_gradient(fmmbem_direct* direct, size_t n_targets, const double
 int fmmbem_direct_gradient_device(fmmbem_direct* direct, size_t n_targets, const double* d_target_points, const uint8_t* d_target_bc,
                                   const double* d_x, double* d_g, void* stream) {
   return direct_field(direct, FieldQuantity::Gradient, false, n_targets, d_target_points, d_target_bc, d_x, d_g, static_cast<hipStream_t>(stream));
+}
+int fmmbem_direct_hessian(fmmbem_direct* direct, size_t n_targets, const double* target_points, const uint8_t* target_bc, const double* x,
+                          double* H) {
+  return direct_field(direct, FieldQuantity::Hessian, true, n_targets, target_points, target_bc, x, H, nullptr);
+}
+int fmmbem_direct_hessian_device(fmmbem_direct* direct, size_t n_targets, const double* d_target_points, const uint8_t* d_target_bc,
+                                 const double* d_x, double* d_H, void* stream) {
+  return direct_field(direct, FieldQuantity::Hessian, false, n_targets, d_target_points, d_target_bc, d_x, d_H, static_cast<hipStream_t>(stream));
 }
 int fmmbem_direct_pressure(fmmbem_direct* direct, size_t n_targets, const double* target_points, const double* x, double* q) {
   return direct_field(direct, FieldQuantity::Pressure, true, n_targets, target_points, nullptr, x, q, nullptr);

@@ -73,12 +73,14 @@ __global__ __launch_bounds__(kDirectBlock) void direct_reduce_kernel(const doubl
 }
 
 // The field quantities at points (include/fmmbem.h, "Direct sum: field quantities"): the shape of direct_partial_kernel over the
-// quantity's pair function of near_entry.hpp, W = 3, 1 or 9 sums per lane.
+// quantity's pair function of near_entry.hpp, W = 3, 1, 9 or 6 sums per lane.
 //   Gradient           g = laplace_grad_entry;  acc_c = fma(g_c, x_j, acc_c), c = 0, 1, 2
 //   Pressure           pi = stokes_pressure_entry;  acc = fma(pi_x, x_j0, acc), then pi_y x_j1, then pi_z x_j2
 //   VelocityGradient   stokes_velgrad_far_from / stokes_velgrad_near add the pair, contracted with f = x_j, straight into the nine
 //                      sums (the 27 numbers are never formed); the chunk's partial is stored times 1 / (2 mu) -- with one source and
 //                      x = e_e the operations of stokes_velgrad_entry
+//   Hessian            laplace_hess_entry: acc_c = fma(eta_c, x_j, acc_c) for the six components of the upper triangle, ascending j from
+//                      zero sums; the chunk's partial is stored mirrored, nine doubles, so [a][b] and [b][a] are reduced to the same bits
 // The K_fine and 16-point rules run in place under the lane mask: a row's order does not depend on a pair's regime.  Points are
 // the caller's (m, 3) array; part is [chunk][target][W].  profiles/r28a_direct_field_resources.md has the compiler's report.
 constexpr int field_width(FieldQuantity q) { return q == FieldQuantity::Gradient ? 3 : q == FieldQuantity::Pressure ? 1 : 9; }
@@ -98,7 +100,12 @@ __global__ __launch_bounds__(kDirectBlock) void direct_field_partial_kernel(Devi
 #pragma unroll
   for (int a = 0; a < W; ++a) acc[a] = 0;
   double* out = part + ((int64_t)blockIdx.y * m + i) * W;
-  if constexpr (Q == FieldQuantity::Gradient) {
+  if constexpr (Q == FieldQuantity::Hessian) {
+    const int flag = tbc ? (tbc[i] ? 1 : 0) : 0;
+    Sym3 h = {0, 0, 0, 0, 0, 0};
+    for (int64_t j = j0; j < j1; ++j) laplace_hess_entry(d, t, flag, j, x[j], h);
+    out[0] = h.xx; out[1] = h.xy; out[2] = h.xz; out[3] = h.xy; out[4] = h.yy; out[5] = h.yz; out[6] = h.xz; out[7] = h.yz; out[8] = h.zz;
+  } else if constexpr (Q == FieldQuantity::Gradient) {
     const int flag = tbc ? (tbc[i] ? 1 : 0) : 0;
     for (int64_t j = j0; j < j1; ++j) {
       const V3 g = laplace_grad_entry(d, t, flag, j);
@@ -175,11 +182,12 @@ hipError_t launch_direct_field_as(const DevicePlan& d, int64_t m, const double* 
 hipError_t launch_direct_field(FieldQuantity q, const DevicePlan& d, int64_t m, const double* pts, const uint8_t* tbc, const double* x,
                                double* part, double* out, hipStream_t s) {
   if (m <= 0 || d.n <= 0) return hipSuccess;
-  if ((q == FieldQuantity::Gradient) != (d.dof == 1)) return hipErrorInvalidValue;    // x holds d.dof values per panel
+  if ((q == FieldQuantity::Gradient || q == FieldQuantity::Hessian) != (d.dof == 1)) return hipErrorInvalidValue;    // x holds d.dof values per panel
   switch (q) {
     case FieldQuantity::Gradient: return launch_direct_field_as<FieldQuantity::Gradient>(d, m, pts, tbc, x, part, out, s);
     case FieldQuantity::Pressure: return launch_direct_field_as<FieldQuantity::Pressure>(d, m, pts, tbc, x, part, out, s);
     case FieldQuantity::VelocityGradient: return launch_direct_field_as<FieldQuantity::VelocityGradient>(d, m, pts, tbc, x, part, out, s);
+    case FieldQuantity::Hessian: return launch_direct_field_as<FieldQuantity::Hessian>(d, m, pts, tbc, x, part, out, s);
   }
   return hipErrorInvalidValue;
 }

@@ -1,9 +1,10 @@
 // kernels_field.hip -- the field quantities at the points of a target plan (include/fmmbem.h "Field gradient", "Field pressure",
-// "Field velocity gradient"), each the sum over the source panels of its own pair function:
+// "Field velocity gradient", "Field Hessian"), each the sum over the source panels of its own pair function:
 //
 //   Gradient           g_i = sum_j gamma(t_i, s_j) x_j, three doubles per target; Laplace plans
 //   Pressure           q_i = sum_j pi(t_i, s_j) . x_j, one double per target; the Stokes single layer
 //   VelocityGradient   G_i[k][m] = d u'_k / d t_m, nine doubles per target, row-major; the Stokes single layer
+//   Hessian            H_i[a][b] = sum_j eta_ab(t_i, s_j) x_j, nine doubles per target, row-major and symmetric; Laplace plans
 //
 // Written once for all of them: wave_lds_sync, cart2sph, the step tables (fill_tables), the group staging (stage_group), the near
 // loop for the gradient and the pressure, the scatter, and one launcher per role.  A quantity's own: its pair step, its L2P chain
@@ -20,7 +21,7 @@
 //   field_scatter_kernel<W>   tree order -> distinct points, W doubles per row
 //   *_entries_kernel          the fmmbem_kernel_*_entries calls: the same pair functions for independent pairs
 //
-// A quantity Q is a plain struct of constants and static __device__ functions (GradientQ, PressureQ, VelocityGradientQ below): the
+// A quantity Q is a plain struct of constants and static __device__ functions (GradientQ, PressureQ, VelocityGradientQ, HessianQ below): the
 // record of a source panel and what a pair adds to a row's sums for the near kernel; the slots of L, the tables, the order of the
 // chain and the kernel for L2P.  Everything is inlined: no call, no pointer in a kernel, no run-time choice.
 //
@@ -67,6 +68,7 @@ __device__ __forceinline__ V3 point(Field&& field, int k) { return V3{field(k), 
 template <int PT> __global__ void l2p_grad_kernel(DevicePlan d, int Prt, int64_t n_src, double* gt);
 template <int PT> __global__ void l2p_pressure_kernel(DevicePlan d, int Prt, int64_t n_src, double* qt);
 template <int PT> __global__ void l2p_velgrad_kernel(DevicePlan d, int Prt, int64_t n_src, double* gt);
+template <int PT> __global__ void l2p_hessian_kernel(DevicePlan d, int Prt, int64_t n_src, double* ht);
 
 // =============================================================================================
 // The quantities.  For the near kernel: kRec doubles of a source panel's record come before its K points (centroid and area, then
@@ -144,6 +146,27 @@ struct VelocityGradientQ : StokesLayerQ<4> {
     ext[S + t] = 0.5 * sqrt((double)((n - m + 1) * (n - m + 2)));
     ext[2 * S + t] = 0.5 * sqrt((double)((n + m + 1) * (n + m + 2)));
   }
+};
+
+// The Hessian of the Laplace field: the gradient's record, flag, slots and grouping; six sums per row, the upper triangle, mirrored at
+// the store; for L2P the velocity gradient's tables and chain of order P - 1 over the derived coefficients.
+struct HessianQ : GradientQ {
+  static constexpr int kWidth = 9;
+  // ---- near: laplace_hess_from ----
+  using Acc = Sym3;
+  template <class Field>
+  static __device__ __forceinline__ void pair(const DevicePlan& d, V3 t, int tb, Field&& field, int64_t j, Acc& acc) {
+    const int64_t N = d.n;
+    laplace_hess_from(t, tb, point(field, 0), field(3), point(field, 4), d.nq, d.qw, [&](int q) FMMBEM_INLINE { return point(field, kRec + 3 * q); },
+                      [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; }, field(7), acc);
+  }
+  static __device__ __forceinline__ void store(const DevicePlan& d, double* o, const Acc& acc) {
+    o[0] = acc.xx; o[1] = acc.xy; o[2] = acc.xz; o[3] = acc.xy; o[4] = acc.yy; o[5] = acc.yz; o[6] = acc.xz; o[7] = acc.yz; o[8] = acc.zz;
+  }
+  // ---- L2P: +- the Hessian of the expansion of the row's slot ----
+  static constexpr int kTables = 6, kDrop = 1;
+  template <int PT> static constexpr auto l2p_kernel() { return l2p_hessian_kernel<PT>; }
+  static __device__ __forceinline__ void fill_extra(double* ext, int S, int t, int n, int m) { VelocityGradientQ::fill_extra(ext, S, t, n, m); }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -782,6 +805,127 @@ __global__ __launch_bounds__(kL2PWaves * kWave) void l2p_velgrad_kernel(DevicePl
   }
 }
 
+// l2p_hessian: the Hessian of the expansion of the row's slot -- the slot its flag picks, as in l2p_grad_kernel, whose grouping and
+// staging this is -- along l2p_velgrad_kernel's chain: the derived coefficients c_x, c_y, c_z of d_x phi, d_y phi, d_z phi (order
+// P - 1; the tables fz, fp / 2, fm / 2), here W_k = c_k(phi_slot) and no antisymmetric part; nine sums, the spherical gradients of the
+// three W_k; one division by sin a per row, then sph2cart.  Of the nine Cartesian numbers the upper triangle is kept, component m of
+// grad d_k phi for k <= m, and h_tree[row] += it (flag 0) or -= (flag 1), mirrored: [a][b] and [b][a] get the same bits.  Order 1
+// has no term and is not launched.
+template <int PT>
+__global__ __launch_bounds__(kL2PWaves * kWave) void l2p_hessian_kernel(DevicePlan d, const int Prt, const int64_t n_src, double* __restrict__ ht) {
+  extern __shared__ double2 field_lds[];                   // six tables (6 S doubles), then [wave][leaf][active slot][S]
+  const int P = PT > 0 ? PT : Prt;
+  const int P1 = P - 1;                                 // the order of the derived expansions
+  const int S = P * (P + 1) / 2, na = d.n_act;
+  double* sPref = reinterpret_cast<double*>(field_lds);
+  double* sC1 = sPref + S;
+  double* sC2 = sC1 + S;
+  double* sFz = sC2 + S;
+  double* sFp = sFz + S;
+  double* sFm = sFp + S;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
+  double2* Lw = field_lds + 3 * S + (size_t)wave * HessianQ::kLeaves * na * S;
+  if (wave == 0) fill_tables<HessianQ>(d, P1, S, lane, sPref);
+  __syncthreads();
+  for (int gi = blockIdx.x * nwaves + wave; gi < d.n_l2p_grp; gi += gridDim.x * nwaves) {
+    const int l0 = d.l2p_grp[gi], nl = d.l2p_grp[gi + 1] - l0;
+    wave_lds_sync();                                    // the previous group's reads are done
+    int g, first, total, my_leaf, my_box, my_nr;
+    const int act0 = d.act[0], act1 = d.act[1];
+    stage_group(d, l0, nl, na, S, lane, Lw, [&](int a) { return a == 0 ? act0 : act1; }, my_leaf, my_box, my_nr, g, first, total);
+    wave_lds_sync();
+    if (nl == 1) { g = 0; first = 0; }                  // single leaf: every lane, chunk by chunk
+    const int leaf = __shfl(my_leaf, g < 0 ? 0 : g, kWave), box = __shfl(my_box, g < 0 ? 0 : g, kWave);
+    const int row0 = d.leaf_row0[leaf], nrows = __shfl(my_nr, g < 0 ? 0 : g, kWave);
+    const double c0 = d.box_center[3 * box], c1 = d.box_center[3 * box + 1], c2 = d.box_center[3 * box + 2];
+    for (int chunk = 0; chunk < total; chunk += kWave) {
+      const int r_in_leaf = chunk + lane - first;
+      if (g < 0 || r_in_leaf >= nrows) continue;
+      const int64_t i = row0 + r_in_leaf;
+      const int tb = d.bc[i] ? 1 : 0;
+      const double2* Ls = Lw + (size_t)(g * na + (na == 2 ? tb : 0)) * S;
+      const Sph s = cart2sph(d.cx[i] - c0, d.cy[i] - c1, d.cz[i] - c2);
+      double gs[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};   // (d/dr, d/dtheta, d/dphi) of d_x phi, d_y phi, d_z phi
+      double pn = 1, rhom = 1, er = 1, ei = 0, fact = 1;
+      const double inv_sa = 1.0 / s.sa, inv_rho = 1.0 / s.rho;
+      auto order = [&](int m, int& step, auto unrolled) FMMBEM_INLINE {
+        double p = pn, p1 = p, rhon = rhom;
+        const double w = m == 0 ? 1.0 : 2.0;
+        auto degree = [&](int n) FMMBEM_INLINE {
+          int tz_ = 0;                                  // unrolled: a coefficient's LDS reads stay with its term (see l2p_kernel)
+          if constexpr (decltype(unrolled)::value)
+            asm volatile("" : "+v"(tz_), "+v"(gs[0][0]), "+v"(gs[0][1]), "+v"(gs[0][2]), "+v"(gs[1][0]), "+v"(gs[1][1]), "+v"(gs[1][2]),
+                         "+v"(gs[2][0]), "+v"(gs[2][1]), "+v"(gs[2][2]));
+          const double *tPref = sPref + tz_, *tC1 = sC1 + tz_, *tC2 = sC2 + tz_, *tFz = sFz + tz_, *tFp = sFp + tz_, *tFm = sFm + tz_;
+          const double2* Lm = Ls + tz_;
+          const double pref = tPref[step];
+          const double mag = rhon * p * pref;
+          const double yr = mag * er, yi = mag * ei;                 // Ynm = mag e^{+i m beta}
+          const double pcur = p;
+          const double pnext = tC1[step] * s.ca * pcur - tC2[step] * p1;
+          double tmag;                                               // YnmTheta (LaplaceSpherical.hpp:471,482)
+          if (n == m) tmag = rhon * (pnext - (m + 1) * s.ca * pcur) * inv_sa * pref;
+          else tmag = rhon * ((n - m + 1) * pnext - (n + 1) * s.ca * pcur) * inv_sa * pref;
+          const double tr = tmag * er, ti = tmag * ei;
+          const double factor = inv_rho * n;
+          const double fz = tFz[step], hp = tFp[step], hm = tFm[step];
+          const int up = (n + 1) * (n + 2) / 2 + m;                  // (n + 1, m) of the order-P expansion
+          const double2 Lz = Lm[up], Lp = Lm[up + 1];
+          double2 Ll;                                                // L_{n+1,m-1}; at m = 0, -conj L_{n+1,1}
+          if (m) Ll = Lm[up - 1];
+          else { Ll.x = -Lp.x; Ll.y = Lp.y; }
+          const double px = hp * Ll.x, py = hp * Ll.y, mx = hm * Lp.x, my = hm * Lp.y;     // D+ / 2 and -D- / 2
+          const double2 W[3] = {{px - mx, py - my},                  // (D+ + D-) / 2
+                                {py + my, -(px + mx)},               // (D+ - D-) / (2 i)
+                                {fz * Lz.x, fz * Lz.y}};
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const double re = W[k].x * yr - W[k].y * yi;             // Re(W Ynm)
+            gs[k][0] += w * re * factor;
+            gs[k][1] += w * (W[k].x * tr - W[k].y * ti);             // Re(W YnmTheta)
+            if (m) gs[k][2] += 2 * (-(W[k].x * yi + W[k].y * yr)) * m;   // Re(W Ynm i) m
+          }
+          p1 = pcur; p = pnext;
+          rhon *= s.rho;
+          ++step;
+        };
+        if constexpr (decltype(unrolled)::value) {
+#pragma unroll
+          for (int n = m; n < PT - 1; ++n) degree(n);
+        } else {
+#pragma nounroll
+          for (int n = m; n < P1; ++n) degree(n);
+        }
+        pn = -pn * fact * s.sa;
+        fact += 2;
+        rhom *= s.rho;
+        const double nr = er * s.cb - ei * s.sb, ni = er * s.sb + ei * s.cb;
+        er = nr; ei = ni;
+      };
+      int step = 0;
+      if constexpr (PT > 0) {
+#pragma unroll
+        for (int m = 0; m < PT - 1; ++m) order(m, step, std::true_type{});
+      } else {
+#pragma nounroll
+        for (int m = 0; m < P1; ++m) order(m, step, std::false_type{});
+      }
+      // sph2cart (kernel/LaplaceSpherical.hpp:546-561): component m of grad d_k phi, k <= m
+      const double r = s.rho, st = s.sa, ct = s.ca, cp = s.cb, sp = s.sb;
+      const double hxx = st * cp * gs[0][0] + ct * cp / r * gs[0][1] - sp / r / st * gs[0][2];
+      const double hxy = st * sp * gs[0][0] + ct * sp / r * gs[0][1] + cp / r / st * gs[0][2];
+      const double hxz = ct * gs[0][0] - st / r * gs[0][1];
+      const double hyy = st * sp * gs[1][0] + ct * sp / r * gs[1][1] + cp / r / st * gs[1][2];
+      const double hyz = ct * gs[1][0] - st / r * gs[1][1];
+      const double hzz = ct * gs[2][0] - st / r * gs[2][1];
+      const double sg = tb ? -1.0 : 1.0;
+      double* o = ht + 9 * (size_t)(i - n_src);
+      const double oxx = o[0] + sg * hxx, oxy = o[1] + sg * hxy, oxz = o[2] + sg * hxz, oyy = o[4] + sg * hyy, oyz = o[5] + sg * hyz, ozz = o[8] + sg * hzz;
+      o[0] = oxx; o[1] = oxy; o[2] = oxz; o[3] = oxy; o[4] = oyy; o[5] = oyz; o[6] = oxz; o[7] = oyz; o[8] = ozz;
+    }
+  }
+}
+
 // out[W perm[row] + a] = tree[W (row - n_src) + a]: the target rows (tree order) -> the distinct points; one thread per double
 template <int W>
 __global__ void field_scatter_kernel(const uint32_t* __restrict__ perm, const double* __restrict__ tree, double* __restrict__ out, int64_t n_src, int64_t rows) {
@@ -821,6 +965,16 @@ __global__ void velgrad_entries_kernel(DevicePlan d, int m, double* __restrict__
   }
 }
 
+// eta(target, source), row-major 3x3: the upper triangle mirrored
+__global__ void hess_entries_kernel(DevicePlan d, int m, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  Sym3 e = {0, 0, 0, 0, 0, 0};
+  laplace_hess_entry(d, V3{d.cx[i], d.cy[i], d.cz[i]}, d.bc[i] ? 1 : 0, (int64_t)m + i, 1.0, e);
+  double* o = out + 9 * (size_t)i;
+  o[0] = e.xx; o[1] = e.xy; o[2] = e.xz; o[3] = e.xy; o[4] = e.yy; o[5] = e.yz; o[6] = e.xz; o[7] = e.yz; o[8] = e.zz;
+}
+
 // f(Q{}) for the quantity q names
 template <class F>
 hipError_t with_quantity(FieldQuantity q, F&& f) {
@@ -828,6 +982,7 @@ hipError_t with_quantity(FieldQuantity q, F&& f) {
     case FieldQuantity::Gradient: return f(GradientQ{});
     case FieldQuantity::Pressure: return f(PressureQ{});
     case FieldQuantity::VelocityGradient: return f(VelocityGradientQ{});
+    case FieldQuantity::Hessian: return f(HessianQ{});
   }
   return hipErrorInvalidValue;
 }
@@ -937,6 +1092,7 @@ hipError_t launch_field_entries(FieldQuantity q, const DevicePlan& d, int m, dou
     case FieldQuantity::Gradient: hipLaunchKernelGGL(grad_entries_kernel, grid, block, 0, s, d, m, out); break;
     case FieldQuantity::Pressure: hipLaunchKernelGGL(pressure_entries_kernel, grid, block, 0, s, d, m, out); break;
     case FieldQuantity::VelocityGradient: hipLaunchKernelGGL(velgrad_entries_kernel, grid, block, 0, s, d, m, out); break;
+    case FieldQuantity::Hessian: hipLaunchKernelGGL(hess_entries_kernel, grid, block, 0, s, d, m, out); break;
   }
   return hipGetLastError();
 }

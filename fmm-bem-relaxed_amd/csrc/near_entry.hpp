@@ -208,6 +208,75 @@ __device__ inline V3 laplace_grad_entry(const DevicePlan& d, V3 t, int tbc, int6
                            [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; });
 }
 
+// The Hessian: the derivative, with respect to the target point t, of the gradient above (include/fmmbem.h, "Field Hessian"): a
+// symmetric, trace-free 3x3 per (target point, source panel j), held as its upper triangle xx, xy, xz, yy, yz, zz.  The regime is
+// decided by laplace_grad_from's expressions, shortcut included, so that a pair is in the same regime there and here; a self pair
+// (dist < 1e-8) gives 0 for both flags.  With dx = y_q - t, r = |dx|, n the panel normal:
+//   flag 0:  sum_q w_q A (3 dx_a dx_b / r^5 - delta_ab / r^3)
+//   flag 1:  sum_q w_q A (15 (dx.n) dx_a dx_b / r^7 - 3 (n_a dx_b + n_b dx_a + (dx.n) delta_ab) / r^5)
+// One reciprocal square root per point, no division; points in order, one running sum per component.  The ONE text of it: the near
+// kernel of the Hessian execute, fmmbem_kernel_hessian_entries and the Direct sum call it: laplace_hess_from adds x times the pair to
+// six sums (x = 1 from zero sums: the entry), laplace_hess_entry is the entry of panel j of d.
+struct Sym3 { double xx, xy, xz, yy, yz, zz; };
+template <class Quad, class Vert>
+__device__ __forceinline__ void laplace_hess_from(V3 t, int tbc, V3 c, double A, V3 nrm, int nq, const double* qw, Quad&& quad, Vert&& vert,
+                                                  double x, Sym3& acc) {
+  const V3 tc = sub(t, c);
+  const double d2 = tc.x * tc.x + tc.y * tc.y + tc.z * tc.z;
+  bool nearby = false;
+  if (!(8 * A < 0.99 * d2 && d2 > 1e-15)) {              // (see laplace_grad_from: far from the regime boundary, no square root)
+    const double dist = sqrt(d2);
+    if (dist < 1e-8) return;
+    nearby = sqrt(2 * A) / dist >= 0.5;
+  }
+  // From here on nothing is left to the compiler's contraction: every fused multiply-add is written, so that the entry has the
+  // same bits in every kernel that asks for it.
+  {
+#pragma clang fp contract(off)
+    Sym3 h = {0, 0, 0, 0, 0, 0};
+    auto point = [&](V3 y, double wA) {
+#pragma clang fp contract(off)
+      const V3 dx = sub(y, t);
+      const double r2 = __builtin_fma(dx.z, dx.z, __builtin_fma(dx.y, dx.y, dx.x * dx.x));
+      const double ri = rsqrt(r2), ri2 = ri * ri;        // 1 / |dx|: one reciprocal square root per point, no division
+      const double f3 = wA * (ri * ri2), f5 = 3 * f3 * ri2;
+      if (tbc == 0) {
+        const V3 u = {f5 * dx.x, f5 * dx.y, f5 * dx.z};
+        h.xx = __builtin_fma(u.x, dx.x, h.xx - f3); h.xy = __builtin_fma(u.x, dx.y, h.xy); h.xz = __builtin_fma(u.x, dx.z, h.xz);
+        h.yy = __builtin_fma(u.y, dx.y, h.yy - f3); h.yz = __builtin_fma(u.y, dx.z, h.yz);
+        h.zz = __builtin_fma(u.z, dx.z, h.zz - f3);
+      } else {
+        const double dn = __builtin_fma(dx.z, nrm.z, __builtin_fma(dx.y, nrm.y, dx.x * nrm.x));
+        const double s = f5 * dn, g = (5 * ri2) * s;     // 3 (dx.n) / r^5 and 15 (dx.n) / r^7, times wA
+        const V3 u = {g * dx.x, g * dx.y, g * dx.z}, v = {-f5 * nrm.x, -f5 * nrm.y, -f5 * nrm.z};
+        h.xx = __builtin_fma(u.x, dx.x, __builtin_fma(v.x + v.x, dx.x, h.xx - s));
+        h.xy = __builtin_fma(u.x, dx.y, __builtin_fma(v.x, dx.y, __builtin_fma(v.y, dx.x, h.xy)));
+        h.xz = __builtin_fma(u.x, dx.z, __builtin_fma(v.x, dx.z, __builtin_fma(v.z, dx.x, h.xz)));
+        h.yy = __builtin_fma(u.y, dx.y, __builtin_fma(v.y + v.y, dx.y, h.yy - s));
+        h.yz = __builtin_fma(u.y, dx.z, __builtin_fma(v.y, dx.z, __builtin_fma(v.z, dx.y, h.yz)));
+        h.zz = __builtin_fma(u.z, dx.z, __builtin_fma(v.z + v.z, dx.z, h.zz - s));
+      }
+    };
+    if (nearby) {
+      const V3 v0 = vert(0), v1 = vert(1), v2 = vert(2);
+      for (int q = 0; q < 16; ++q)
+        point(V3{v0.x * kFine[q][0] + v1.x * kFine[q][1] + v2.x * kFine[q][2], v0.y * kFine[q][0] + v1.y * kFine[q][1] + v2.y * kFine[q][2],
+                 v0.z * kFine[q][0] + v1.z * kFine[q][1] + v2.z * kFine[q][2]}, kFine[q][3] * A);
+    } else {
+      for (int q = 0; q < nq; ++q) point(quad(q), qw[q] * A);
+    }
+    // the pair's eta is rounded before the charge meets it, whoever asks: fma(eta_c, x, acc_c)
+    acc.xx = __builtin_fma(h.xx, x, acc.xx); acc.xy = __builtin_fma(h.xy, x, acc.xy); acc.xz = __builtin_fma(h.xz, x, acc.xz);
+    acc.yy = __builtin_fma(h.yy, x, acc.yy); acc.yz = __builtin_fma(h.yz, x, acc.yz); acc.zz = __builtin_fma(h.zz, x, acc.zz);
+  }
+}
+__device__ inline void laplace_hess_entry(const DevicePlan& d, V3 t, int tbc, int64_t j, double x, Sym3& acc) {
+  const int64_t N = d.n;
+  laplace_hess_from(t, tbc, V3{d.cx[j], d.cy[j], d.cz[j]}, d.area[j], V3{d.nx[j], d.ny[j], d.nz[j]}, d.nq, d.qw,
+                    [&](int q) { return V3{d.quad[(q * 3 + 0) * N + j], d.quad[(q * 3 + 1) * N + j], d.quad[(q * 3 + 2) * N + j]}; },
+                    [&](int a) { return V3{d.vert[(3 * a + 0) * N + j], d.vert[(3 * a + 1) * N + j], d.vert[(3 * a + 2) * N + j]}; }, x, acc);
+}
+
 // Both layers of one pair TOGETHER, value and gradient (include/fmmbem.h, "Representation execute"): what panel j with density
 // sigma and surface potential mu adds to   phi = sum E0 sigma - E1 mu   and   grad = sum gamma0 sigma - gamma1 mu   at the point t,
 // E0 / E1 the entries of a flag-0 / flag-1 target above and gamma0 / gamma1 the two gradients of laplace_grad_from.  ONE regime test

@@ -262,11 +262,11 @@ struct fmmbem_plan {
   const uint32_t* d_target_point = nullptr;                    // given target -> distinct point (only when some coincide)
   double* y_points = nullptr;                                  // the result per distinct point (only when some coincide)
   double* stage_y_targets = nullptr;                           // device staging of y for host-pointer execute
-  // Field quantities (fmmbem_plan_execute_gradient, _pressure, _velocity_gradient; kField below): per quantity its width in doubles
+  // Field quantities (fmmbem_plan_execute_gradient, _pressure, _velocity_gradient, _hessian; kField below): per quantity its width in doubles
   // per target row in tree order, per distinct point (only when some targets coincide) and per given target (the host form's
   // staging); each quantity's buffers are allocated at its first call
   struct FieldBuffers { double *tree = nullptr, *points = nullptr, *stage = nullptr; };
-  FieldBuffers field[3];
+  FieldBuffers field[4];
   int field_refusal(FieldQuantity q, int p) const;
   int field_alloc(FieldQuantity q);
   int run_field(FieldQuantity q, int p, const double* d_x, double* d_out, hipStream_t s);
@@ -1092,7 +1092,8 @@ int fmmbem_plan::run(int p, const double* d_x, double* d_y, hipStream_t s, bool 
 }
 
 // ======================================= field quantities =======================================
-// What the three field executes differ in (include/fmmbem.h "Field gradient", "Field pressure", "Field velocity gradient"): the
+// What the four field executes differ in (include/fmmbem.h "Field gradient", "Field pressure", "Field velocity gradient", "Field
+// Hessian"): the
 // doubles per target, the plans a quantity accepts and the texts of its refusals, the doubles per pair and the most pairs of its
 // fmmbem_kernel_*_entries call.  Indexed by FieldQuantity, as the plan's buffers and the launchers of kernels_field.hip are.
 struct FieldRow {
@@ -1103,8 +1104,9 @@ struct FieldRow {
   int entry_width;
   size_t max_pairs;
   const char* entries_kernel;
+  int l2p_from = 1;                                    // the lowest order at which the quantity's L2P has a term: below it no L2P stage
 };
-static const FieldRow kField[3] = {
+static const FieldRow kField[4] = {
     {3, false, "the field gradient: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)",
      "the field gradient: Laplace plans only", nullptr, 3, (size_t)1 << 30, "the field gradient: the Laplace kernel only"},
     {1, true, "the field pressure: on a plan over separate targets only (fmmbem_plan_create_field)", "the field pressure: Stokes plans only",
@@ -1113,7 +1115,9 @@ static const FieldRow kField[3] = {
     {9, true, "the field velocity gradient: on a plan over separate targets only (fmmbem_plan_create_field)",
      "the field velocity gradient: Stokes plans only",
      "the field velocity gradient: VELOCITY targets only (the gradient of the double layer is not built)", 27, (size_t)1 << 26,
-     "the field velocity gradient: the Stokes kernel only"},
+     "the field velocity gradient: the Stokes kernel only", 2},
+    {9, false, "the field Hessian: on a plan over separate targets only (fmmbem_plan_create_targets, _create_field)",
+     "the field Hessian: Laplace plans only", nullptr, 9, (size_t)1 << 27, "the field Hessian: the Laplace kernel only", 2},
 };
 
 // the refusals of a field execute after the null checks, in the order include/fmmbem.h states them
@@ -1158,9 +1162,13 @@ int fmmbem_plan::run_field(FieldQuantity q, int p, const double* d_x, double* d_
   HIP_TRY(tm.begin(Stage::Spmv, s));
   HIP_TRY(launch_near_field(q, d, hp.n_src, b.tree, s));
   HIP_TRY(tm.end(Stage::Spmv, s));
-  HIP_TRY(tm.begin(Stage::L2P, s));
-  HIP_TRY(launch_l2p_field(q, d, p, hp.n_src, b.tree, s));
-  HIP_TRY(tm.end(Stage::L2P, s));
+  if (p >= kField[(int)q].l2p_from) {
+    HIP_TRY(tm.begin(Stage::L2P, s));
+    HIP_TRY(launch_l2p_field(q, d, p, hp.n_src, b.tree, s));
+    HIP_TRY(tm.end(Stage::L2P, s));
+  } else {
+    tm.mask &= ~(1u << (int)Stage::L2P);               // nothing is launched: far_chain's empty pair does not count, ms_l2p = 0
+  }
   HIP_TRY(tm.begin(Stage::Scatter, s));
   TRY(deliver_field(q, d_out, s));
   HIP_TRY(tm.end(Stage::Scatter, s));
@@ -2218,6 +2226,12 @@ int fmmbem_plan_execute_gradient_device(fmmbem_plan* plan, int p, const double* 
 int fmmbem_plan_execute_gradient(fmmbem_plan* plan, int p, const double* x, double* g) {
   return field_execute(plan, FieldQuantity::Gradient, p, x, g);
 }
+int fmmbem_plan_execute_hessian_device(fmmbem_plan* plan, int p, const double* d_x, double* d_H, void* stream) {
+  return field_execute_device(plan, FieldQuantity::Hessian, p, d_x, d_H, stream);
+}
+int fmmbem_plan_execute_hessian(fmmbem_plan* plan, int p, const double* x, double* H) {
+  return field_execute(plan, FieldQuantity::Hessian, p, x, H);
+}
 int fmmbem_plan_execute_pressure_device(fmmbem_plan* plan, int p, const double* d_x, double* d_q, void* stream) {
   return field_execute_device(plan, FieldQuantity::Pressure, p, d_x, d_q, stream);
 }
@@ -2886,6 +2900,10 @@ static int field_entries(FieldQuantity q, const fmmbem_options* opts, size_t n, 
 int fmmbem_kernel_gradient_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
                                    const double* source_vertices, double* out) {
   return field_entries(FieldQuantity::Gradient, opts, n, target_vertices, target_bc, source_vertices, out);
+}
+int fmmbem_kernel_hessian_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const uint8_t* target_bc,
+                                  const double* source_vertices, double* out) {
+  return field_entries(FieldQuantity::Hessian, opts, n, target_vertices, target_bc, source_vertices, out);
 }
 int fmmbem_kernel_pressure_entries(const fmmbem_options* opts, size_t n, const double* target_vertices, const double* source_vertices,
                                    double* out) {

@@ -269,6 +269,18 @@ def kernel_gradient_entries(K, targets, sources, target_bc=None, device=0):
     the target point, of the panel integral the target's flag picks, by the function FMM_plan.execute_gradient's near kernel calls.
     targets, sources: (n, 3, 3) vertices -- the target POINT is the target panel's centroid; target_bc: n flags.  Laplace only.
     Returns (n, 3)."""
+    return _laplace_pair_entries("fmmbem_kernel_gradient_entries", (3,), K, targets, sources, target_bc, device)
+
+
+def kernel_hessian_entries(K, targets, sources, target_bc=None, device=0):
+    """eta(target_i, source_i) of the field Hessian for n pairs (fmmbem_kernel_hessian_entries): the derivative, with respect to the
+    target point, of kernel_gradient_entries' gamma, by the function FMM_plan.execute_hessian's near kernel calls.  targets, sources:
+    (n, 3, 3) vertices -- the target POINT is the target panel's centroid; target_bc: n flags.  Laplace only.  Returns (n, 3, 3),
+    symmetric bit for bit."""
+    return _laplace_pair_entries("fmmbem_kernel_hessian_entries", (3, 3), K, targets, sources, target_bc, device)
+
+
+def _laplace_pair_entries(symbol, tail, K, targets, sources, target_bc, device):
     t = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 9)
     s = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 9)
     if t.shape != s.shape:
@@ -284,9 +296,9 @@ def kernel_gradient_entries(K, targets, sources, target_bc=None, device=0):
         if target_bc.shape != (len(t),):
             raise ValueError("target_bc must have one flag per pair")
         bcp = target_bc.ctypes.data_as(C.c_void_p)
-    out = np.empty((len(t), 3))
-    _capi.check(_capi.lib().fmmbem_kernel_gradient_entries(C.byref(o), len(t), t.ctypes.data_as(C.c_void_p), bcp,
-                                                           s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    out = np.empty((len(t),) + tail)
+    _capi.check(getattr(_capi.lib(), symbol)(C.byref(o), len(t), t.ctypes.data_as(C.c_void_p), bcp,
+                                             s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -472,6 +484,16 @@ class Direct:
     def gradient_torch(self, x, targets, target_bc=None, out=None):
         """The same sum on device tensors, asynchronous on torch's current stream; returns (M, 3)."""
         return self._field_torch("fmmbem_direct_gradient_device", x, targets, target_bc, out, (3,), True)
+
+    def hessian(self, x, targets, target_bc=None):
+        """(N,) charges -> (M, 3, 3): H_i[a][b] = sum_j eta_ab(t_i, s_j) x_j over ALL panels, eta that of FMM_plan.execute_hessian,
+        picked by target_bc[i] (None: all 0); symmetric bit for bit.  Laplace only: FmmBemError (status 6) on a Stokes kernel.  numpy
+        in, numpy out (host)."""
+        return self._field_host("fmmbem_direct_hessian", x, targets, target_bc, (3, 3), True)
+
+    def hessian_torch(self, x, targets, target_bc=None, out=None):
+        """The same sum on device tensors, asynchronous on torch's current stream; returns (M, 3, 3)."""
+        return self._field_torch("fmmbem_direct_hessian_device", x, targets, target_bc, out, (3, 3), True)
 
     def pressure(self, x, targets):
         """(N, 3) traction density -> (M,): q_i = sum_j pi(t_i, s_j) . x_j over ALL panels, in the scaling of
@@ -817,6 +839,20 @@ class FMM_plan:
     def execute_gradient_torch(self, x, out=None, p=None):
         """x: contiguous float64 CUDA tensor (N,), ORIGINAL panel order; returns (M, 3).  Runs on torch's current stream."""
         return self._field_torch(self.execute_gradient_device, x, out, p, (3,), "one value")
+
+    def execute_hessian(self, charges):
+        """(N,) charges -> (M, 3, 3): H_i[a][b] = sum_j eta_ab(t_i, s_j) x_j at the kernel's current p, the second derivatives with
+        respect to the target point of what execute returns there (include/fmmbem.h, "Field Hessian"); H[a][b] and H[b][a] carry the
+        same bits.  numpy in, numpy out (host).  FmmBemError (status 6) on a plan that is not over separate targets, on a Stokes plan
+        and on a host-only plan."""
+        return self._field_host("fmmbem_plan_execute_hessian", charges, (3, 3), "one value")
+
+    def execute_hessian_device(self, x_ptr, h_ptr, stream=0, p=None):
+        self._field_device("fmmbem_plan_execute_hessian_device", x_ptr, h_ptr, stream, p)
+
+    def execute_hessian_torch(self, x, out=None, p=None):
+        """x: contiguous float64 CUDA tensor (N,), ORIGINAL panel order; returns (M, 3, 3).  Runs on torch's current stream."""
+        return self._field_torch(self.execute_hessian_device, x, out, p, (3, 3), "one value")
 
     def execute_pressure(self, charges):
         """(N, 3) or (3N,) traction density -> (M,): q_i = sum_j pi(t_i, s_j) . x_j at the kernel's current p, the pressure that

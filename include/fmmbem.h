@@ -355,6 +355,40 @@ int fmmbem_plan_batch_width(const fmmbem_plan *plan, int *width);
 int fmmbem_plan_execute_gradient(fmmbem_plan *plan, int p, const double *x, double *g);
 int fmmbem_plan_execute_gradient_device(fmmbem_plan *plan, int p, const double *d_x, double *d_g, void *stream);
 
+/* ---- Field Hessian: the second derivatives of the Laplace field at the points of a plan over separate targets -------------
+ * (no reference counterpart: the strain rate of a potential flow, the field gradient in the force on a dipole, the tidal tensor, a
+ * second-order Taylor step, Newton's method for stagnation points).  On a Laplace plan of fmmbem_plan_create_targets or
+ * fmmbem_plan_create_field, for target i with point t_i,
+ *   H_i[a][b] = sum_j eta_ab(t_i, s_j) x_j,   nine doubles, row-major,
+ * eta_ab = d gamma_a / d t_b, the derivative WITH RESPECT TO THE TARGET POINT of the entry gamma of the field gradient above for the
+ * target's flag: H is the matrix of second derivatives of what fmmbem_plan_execute returns at that point.  The rule is chosen
+ * exactly as for gamma, by the same expressions, so that a pair is in the same regime in both: dist = |t - c_j|;
+ *   dist < 1e-8: eta = 0 for both flags (the second derivative jumps across the layer; a point on it is the caller's business, as
+ *     for the Stokes quantities);
+ *   sqrt(2 A_j) / dist >= 0.5: the 16-point rule on the vertices;  otherwise the K stored points.
+ * With dx = y_q - t, r = |dx| and n the panel normal as the plan holds it:
+ *   flag 0 (single layer):  eta_ab = sum_q w_q A_j ( 3 dx_a dx_b / r^5 - delta_ab / r^3 )
+ *   flag 1 (double layer):  eta_ab = sum_q w_q A_j ( 15 (dx.n) dx_a dx_b / r^7 - 3 (n_a dx_b + n_b dx_a + (dx.n) delta_ab) / r^5 )
+ * Both are symmetric and trace-free point by point.  The far field is +- the Hessian of the local expansion of the slot the
+ * target's flag picks, + for flag 0 and - for flag 1: the exact Hessian of the truncated expansion, evaluated as the Cartesian
+ * gradients of the three expansions of order p - 1 that d_x phi, d_y phi, d_z phi are.  At p = 1 and p = 2 that expansion has no
+ * second derivative and the result is the near half.
+ * The upper triangle is computed and the lower mirrors it: H[a][b] and H[b][a] carry the same bits.  The trace is left as computed,
+ * zero to rounding, not forced.  The physical Hessian of the representation formula is
+ * (H[flag 0 plan, density] - H[flag 1 plan, potential]) / (4 pi).
+ * x: n_panels doubles; H: n_targets x 9, both in the caller's order; coincident targets each get their copy.  The execute is the
+ * gradient execute's with its own two kernels -- the near pairs matrix-free (a row's sums: the leaf's near list in order, panels
+ * ascending, quadrature points in order) and the Hessian of L (terms m-major) --: the same bits every run.  Its buffers are
+ * allocated at the first Hessian call (FMMBEM_ERR_ALLOC if that fails; the plan stays usable).  Checked in the gradient's order:
+ * a null plan or vector -> FMMBEM_ERR_INVALID; p outside 1..p_max -> _INVALID; a plan that is not over separate targets ->
+ * _UNSUPPORTED; a Stokes plan -> _UNSUPPORTED; a host-only plan -> _UNSUPPORTED; the handle stays usable and no pointer is
+ * touched.  Launched plainly, whatever fmmbem_plan_set_graphs says; the captured graphs of the potential execute stay as they are.
+ * Stage timing: ms_near is its near kernel, ms_l2p the Hessian of L (0 at p = 1, where it is not launched).  No batches.  The Hessian
+ * on the plan's own panels is not built.
+ * The host form takes HOST pointers and returns when H is written; the device form is asynchronous on `stream`. */
+int fmmbem_plan_execute_hessian(fmmbem_plan *plan, int p, const double *x, double *H);
+int fmmbem_plan_execute_hessian_device(fmmbem_plan *plan, int p, const double *d_x, double *d_H, void *stream);
+
 /* ---- Field pressure: the pressure of the Stokes single layer at the points of a field plan ----------------------------------
  * (no reference counterpart: the other half of a Stokes field off the surface).  On a Stokes plan of fmmbem_plan_create_field
  * whose targets are all VELOCITY targets, for target i with point t_i,
@@ -561,6 +595,11 @@ int fmmbem_kernel_entries(const fmmbem_options *opts, size_t n, const double *ta
  * all 0).  Laplace only (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, device.  out: n x 3. */
 int fmmbem_kernel_gradient_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
                                    const uint8_t *target_bc, const double *source_vertices, double *out /* n x 3 */);
+/* eta(target, source) of the field Hessian (see fmmbem_plan_execute_hessian) for n independent pairs, by the function the Hessian
+ * execute's near kernel calls: the target POINT is the centroid of target_vertices' panel i, target_bc its flag (NULL: all 0).
+ * Laplace only (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, device.  out: n x 9, [a][b], symmetric bit for bit. */
+int fmmbem_kernel_hessian_entries(const fmmbem_options *opts, size_t n, const double *target_vertices,
+                                  const uint8_t *target_bc, const double *source_vertices, double *out /* n x 9 */);
 /* pi(target, source) of the field pressure (see fmmbem_plan_execute_pressure) for n independent pairs, by the function the
  * pressure execute's near kernel calls: the target POINT is the centroid of target_vertices' panel i.  Stokes only
  * (FMMBEM_ERR_UNSUPPORTED otherwise); reads opts->kernel, quad_k, quad_k_fine, device.  out: n x 3. */
@@ -664,6 +703,17 @@ int fmmbem_direct_gradient(fmmbem_direct *direct, size_t n_targets, const double
                            const double *x, double *g /* n_targets x 3 */);
 int fmmbem_direct_gradient_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const uint8_t *d_target_bc,
                                   const double *d_x, double *d_g, void *stream);
+/* The Hessian of the Laplace field over ALL sources: H_i[a][b] = sum_j eta_ab(t_i, s_j) x_j, nine doubles per target, row-major; eta
+ * is that of fmmbem_plan_execute_hessian, picked by target_bc[i] (NULL: all 0), every pair's value the one
+ * fmmbem_kernel_hessian_entries gives.  Laplace handles only.  The gradient's chunks and order: within a chunk
+ * acc_c = fma(eta_c, x_j, acc_c) for the six components of the upper triangle in ascending j from zero sums, the chunks' partial sums
+ * added in ascending chunk order, mirrored where they are stored: H[a][b] and H[b][a] carry the same bits, and with one source and
+ * x = 1 the result is the entry bit for bit.  The checks, their order and the buffer are those of fmmbem_direct_gradient (a Stokes
+ * handle -> FMMBEM_ERR_UNSUPPORTED naming the Hessian; 9 doubles per chunk and target). */
+int fmmbem_direct_hessian(fmmbem_direct *direct, size_t n_targets, const double *target_points, const uint8_t *target_bc,
+                          const double *x, double *H /* n_targets x 9 */);
+int fmmbem_direct_hessian_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const uint8_t *d_target_bc,
+                                 const double *d_x, double *d_H, void *stream);
 int fmmbem_direct_pressure(fmmbem_direct *direct, size_t n_targets, const double *target_points, const double *x /* n x 3 */,
                            double *q /* n_targets */);
 int fmmbem_direct_pressure_device(fmmbem_direct *direct, size_t n_targets, const double *d_target_points, const double *d_x,

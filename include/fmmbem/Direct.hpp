@@ -5,7 +5,7 @@
 //     results = D.matvec(charges, targets);             // Direct::matvec(K, s, c, t, r) of include/Direct.hpp:236-247, r overwritten
 //     results = D.matvec(charges);                      // the symmetric form (:291-302): targets = sources
 //     fmmbem::direct_matvec(K, sources, charges, targets, results);   // one call, "+=" into results as Direct::matvec does
-//     D.gradient(charges, targets);                     // Laplace: the field gradient;  Stokes: D.pressure, D.velocity_gradient, D.stress
+//     D.gradient(charges, targets);                     // Laplace: the field gradient, D.hessian its derivative;  Stokes: D.pressure, D.velocity_gradient, D.stress
 //
 // A target's centre and BC are what count, as in FMM_plan(K, sources, targets, opts).  The order of addition is the library's fixed
 // one (include/fmmbem.h), not the host loop's of compat/Direct.hpp: the two agree to rounding, not bit for bit, which is why the
@@ -67,8 +67,8 @@ class DirectSum {
     return results;
   }
 
-  // Not in the reference: the field quantities at the targets' centres over ALL sources (fmmbem_direct_gradient / _pressure /
-  // _velocity_gradient) -- the sums that FMM_plan's execute_gradient, execute_pressure, execute_velocity_gradient and execute_stress
+  // Not in the reference: the field quantities at the targets' centres over ALL sources (fmmbem_direct_gradient / _hessian /
+  // _pressure / _velocity_gradient) -- the sums that FMM_plan's execute_gradient, execute_pressure, execute_velocity_gradient and execute_stress
   // approximate, with their return types and scaling.  gradient: Laplace kernels, the target's BC picks gamma; pressure,
   // velocity_gradient, stress: Stokes kernels, the targets' BCs are not read.  The other kernel's methods throw
   // Error(FMMBEM_ERR_UNSUPPORTED), the library's refusal.
@@ -78,6 +78,15 @@ class DirectSum {
     const std::vector<double> pts = points_of(targets, &bc);
     std::vector<Vec<3, double>> results(targets.size());
     check(fmmbem_direct_gradient(h_, targets.size(), pts.data(), bc.data(), KernelBinding<Kernel>::in(charges), results.empty() ? nullptr : results.data()->data()));
+    return results;
+  }
+  // the Hessian of the Laplace field (fmmbem_direct_hessian): H[a][b] row-major, the target's BC picks eta; Laplace kernels
+  std::vector<std::array<double, 9>> hessian(const std::vector<charge_type>& charges, const std::vector<target_type>& targets) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of sources");
+    std::vector<uint8_t> bc;
+    const std::vector<double> pts = points_of(targets, &bc);
+    std::vector<std::array<double, 9>> results(targets.size());
+    check(fmmbem_direct_hessian(h_, targets.size(), pts.data(), bc.data(), KernelBinding<Kernel>::in(charges), results.empty() ? nullptr : results.data()->data()));
     return results;
   }
   std::vector<double> pressure(const std::vector<charge_type>& charges, const std::vector<target_type>& targets) {

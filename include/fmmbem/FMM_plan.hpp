@@ -601,6 +601,17 @@ class PlanAdapter {
     check(fmmbem_plan_execute_gradient(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
     return results;
   }
+  // Not in the reference: the Hessian of the field at the targets of a plan over separate targets (fmmbem_plan_execute_hessian):
+  // result i is H[a][b] = sum_j eta_ab(targets[i], sources[j]) charges[j], nine doubles row-major, the second derivatives with
+  // respect to the target point of what execute() returns there; [a][b] and [b][a] carry the same bits.  The refusals are
+  // execute_gradient's.
+  std::vector<std::array<double, 9>> execute_hessian(const std::vector<charge_type>& charges) {
+    if (charges.size() != n_) throw Error(FMMBEM_ERR_INVALID, "charges.size() != number of panels");
+    std::vector<std::array<double, 9>> results(has_targets_ ? target_bc_.size() : charges.size());
+    if (K.p() > p_max_) create(K.p());                  // set_p above what the plan was sized for: grow, as execute() does
+    check(fmmbem_plan_execute_hessian(plan_, K.p(), KernelBinding<Kernel>::in(charges), results.data()->data()));
+    return results;
+  }
   // Not in the reference: the representation formula at the targets of a Laplace plan over separate targets in ONE execute
   // (fmmbem_plan_execute_representation): phi = S[density] - D[potential] and its gradient, in execute()'s scaling, the targets'
   // own BCs ignored -- what execute() on an all-POTENTIAL plan minus execute() on an all-NORMAL_DERIV plan over the same points

@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
-"""Time a field-quantity execute (FMM_plan.execute_gradient_torch, execute_pressure_torch or execute_velocity_gradient_torch,
-csrc/kernels_field.hip) beside the potential or velocity execute of the same plan.
-  python tools/field_time.py --quantity gradient|pressure|velocity_gradient|flow|representation [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
+"""Time a field-quantity execute (FMM_plan.execute_gradient_torch, execute_hessian_torch, execute_pressure_torch or
+execute_velocity_gradient_torch, csrc/kernels_field.hip) beside the potential or velocity execute of the same plan.
+  python tools/field_time.py --quantity gradient|hessian|pressure|velocity_gradient|flow|representation [--recursions 9] [--orders ...] [--repeats 10] [--flag 0|1|2]
 Workloads:
-  gradient            the target plan of tools/target_field_time.py -- 2 x UnitSphere(recursions) (N = 1 048 576 panels by default)
+  gradient, hessian   the target plan of tools/target_field_time.py -- 2 x UnitSphere(recursions) (N = 1 048 576 panels by default)
                       and a regular grid of 1 048 576 points over the bounding box of both spheres, theta = 0.5, ncrit 64;
                       --flag 2: the points' flags alternate (both expansion slots live).  Orders 4,10.
   pressure,           the field plan of tools/stokes_field_time.py -- RedBloodCell(recursions) (N = 524 288 panels by default) and a
   velocity_gradient   regular grid of 1 048 576 points over the cell's bounding box, all VELOCITY targets, theta = 0.5, ncrit 64,
                       K = 4, K_fine = 19.  Orders 8,4.
-Per order, with <q> the quantity and <k> its kernels' short name (grad, pressure, velgrad):
+Per order, with <q> the quantity and <k> its kernels' short name (grad, hess, pressure, velgrad):
   ms_execute, ms_execute_<q>     device time between two events, the mean of --repeats calls after two warm-ups, stage timing off
                                  (velocity_gradient also times ms_execute_pressure);
   stages_<q>                     fmmbem_plan_stats with stage timing on, in a pass of its own (an event pair per stage lengthens
@@ -39,7 +39,7 @@ gradient alone}, each timed as above:
   ms_near_representation_kernel  the one near kernel (stage timing 2) and ms_near_grad_single_kernel, ms_near_grad_double_kernel the
                                  two gradient passes the same way: their sum is what it stands against;
   rel_l2_value, rel_l2_gradient  the representation execute against the four executes' S - D, relative to |S| + |D|.
---check M (default 0: off): the Direct quantity (fb.Direct.gradient_torch / pressure_torch / velocity_gradient_torch: all N panels,
+--check M (default 0: off): the Direct quantity (fb.Direct.gradient_torch / hessian_torch / pressure_torch / velocity_gradient_torch: all N panels,
 every regime) on M points sampled over the whole target set; per order rel_l2_vs_direct_on_sample, the relative L2 of the field
 execute against it on those points, and under "check" the sample's size and the device time of that sum.
 Prints one JSON document."""
@@ -56,7 +56,7 @@ import fmm_bem_relaxed_amd as fb  # noqa: E402
 
 STAGES = ("ms_gather", "ms_near", "ms_p2m", "ms_m2m", "ms_mh", "ms_m2l", "ms_l2l", "ms_l2p", "ms_scatter", "ms_total")
 # quantity -> (its kernels' short name, the trailing shape of its result, the default orders)
-QUANTITIES = {"gradient": ("grad", (3,), "4,10"), "pressure": ("pressure", (), "8,4"), "velocity_gradient": ("velgrad", (3, 3), "8,4"),
+QUANTITIES = {"gradient": ("grad", (3,), "4,10"), "hessian": ("hess", (3, 3), "4,10"), "pressure": ("pressure", (), "8,4"), "velocity_gradient": ("velgrad", (3, 3), "8,4"),
               "flow": ("flow", (3, 3), "8"), "representation": ("representation", (3,), "4,10")}
 
 
@@ -212,8 +212,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     q = a.quantity
-    if a.flag and q != "gradient":
-        ap.error("--flag belongs to --quantity gradient: the Stokes quantities take VELOCITY targets only")
+    laplace = q in ("gradient", "hessian")
+    if a.flag and not laplace:
+        ap.error("--flag belongs to --quantity gradient and hessian: the Stokes quantities take VELOCITY targets only")
     short, tail, default_orders = QUANTITIES[q]
     orders = [int(p) for p in (a.orders or default_orders).split(",")]
     dev = torch.device("cuda", 0)
@@ -232,7 +233,7 @@ def main():
         out["orders"] = representation_orders(plans, K, orders, sd, md, len(pts), a.repeats, a.rounds)
         print(json.dumps(out, indent=1))
         return
-    if q == "gradient":
+    if laplace:
         v = np.concatenate([fb.unit_sphere(a.recursions), fb.unit_sphere(a.recursions, center=(3.0, 0.0, 0.0))])
         pts = sphere_grid()
         flags = (np.arange(len(pts)) % 2).astype(np.uint8) if a.flag == 2 else np.full(len(pts), a.flag, np.uint8)
@@ -268,7 +269,7 @@ def main():
         rows = np.sort(np.random.default_rng(2).choice(len(pts), min(a.check, len(pts)), replace=False))
         rows_d, sample = torch.from_numpy(rows).to(dev), torch.from_numpy(pts[rows]).to(dev)
         direct = fb.Direct(K, v)
-        args = (xd, sample, torch.from_numpy(flags[rows]).to(dev)) if q == "gradient" else (xd, sample)
+        args = (xd, sample, torch.from_numpy(flags[rows]).to(dev)) if laplace else (xd, sample)
         sum_on_sample = getattr(direct, q + "_torch")
         ref = sum_on_sample(*args)
         out["check"] = dict(sample=len(rows), direct_on_sample_ms=device_ms(lambda: sum_on_sample(*args), 1))
@@ -284,8 +285,8 @@ def main():
         rec["stages_" + q] = staged(plan, lambda: run(xd, out=od), a.repeats)
         rec["ms_near_%s_kernel" % short] = rec["stages_" + q]["ms_near"]
         rec["ms_l2p_%s_kernel" % short] = rec["stages_" + q]["ms_l2p"]
-        if q == "gradient":
-            rec["near_pairs_per_s"] = out["near_nnz"] / (rec["ms_near_grad_kernel"] * 1e-3)
+        if laplace:
+            rec["near_pairs_per_s"] = out["near_nnz"] / (rec["ms_near_%s_kernel" % short] * 1e-3)
         if direct is not None:
             got = run(xd, out=od)[rows_d]
             rec["rel_l2_vs_direct_on_sample"] = float(torch.linalg.norm(got - ref) / torch.linalg.norm(ref))
